@@ -17,9 +17,16 @@ largest configuration, which fits one GPU.  The same command runs at any N:
 So total work is fixed ("scaling": "strong") and value(N=8) / value(N=1) is the 8-GPU speed-up north_star asks for.
 
 `value` is the host-fed rate (cs16 block in page-locked host memory -> all frames of the block delivered):
-the block crosses PCIe inside every timed step, overlapped with compute by the library's copy stream.  The K timed steps
-are run `--repeats` times (default 3); `value` / `ms_per_step` are the MEDIAN repeat, all repeats are listed.  The same is
-then done with the block already resident in HBM (`value_hbm_resident`).  At N = 1 the line also carries
+the block crosses PCIe inside every timed step, overlapped with compute by the library's copy stream.
+
+A plain run does only what that figure needs: it synthesises the block, warms up, times exactly K = `--steps` steps once
+and prints the line (`roofline` then comes from the channeliser launches of that same region).  `--dump-outputs DIR`
+also writes the frames of the last timed step's block as DIR/frame_<field>.npy (see dump_frames()).
+
+`--full` adds everything else: the K timed steps are run `--repeats` times (default 3 there, 1 in a plain run); `value` /
+`ms_per_step` are the MEDIAN repeat, all repeats are listed.  The parity gate against the CPU oracle (whole block, then in
+pieces), the CPU baseline and per-stage kernel times come first and last; the same timed region is then run with the
+block already resident in HBM (`value_hbm_resident`, and the roofline from it).  At N = 1 the full line also carries
   * `projected_scaling`: the rank-sized workload of the 8-GPU split (32 of the 256 channels, three ranks' shards, block
     resident in HBM as an RCCL exchange leaves it) timed on this GPU -> the compute-side ceiling t256 / max t32 of the
     speed-up, with the ingest bounds beside it;
@@ -109,7 +116,7 @@ class Case:
         # every rank synthesises the capture itself (seeded: identical bytes, checked below) - each needs it in its own
         # page-locked memory for the striped ingest, and nothing large has to cross process boundaries
         if iq is None:
-            iq, bursts = synth.synthesize(cfg)
+            iq, bursts = synth.synthesize(cfg, workers=cpus_available())      # (the same bytes whatever the number of workers)
         self.iq, self.bursts = iq, bursts
         self.t_synth = time.time() - t0
         self.nvals = self.iq.size
@@ -145,9 +152,9 @@ class Case:
         n, recs, octs = feeder.step()
         return self.vdl2hip.Receiver.unpack(n, recs, octs)
 
-    def timed(self, feeder, steps, dist, repeats=1):
+    def timed(self, feeder, steps, dist, repeats=1, keep_last=False):
         """`repeats` times exactly `steps` steps in streaming mode (six blocks in flight: VDL2HIP_MAX_DRAIN_LAG + 1); every block fully delivered inside
-        each timed region.  Returns the median repeat plus the list."""
+        each timed region.  Returns the median repeat plus the list; keep_last: with the frames of the last step's block in "last_frames"."""
         # the shader clock idles at ~100 MHz and needs some tens of ms of load to come up (profiles/r03_clocks_under_load.txt): after the CPU-side
         # pauses of this script (oracle gate, set-up of a receiver) a short region would otherwise start on a cold clock.  Untimed steps.
         t0 = time.perf_counter()
@@ -161,9 +168,11 @@ class Case:
                 el = float(t.item())
             if el >= CLOCK_WARMUP_S:
                 break
-        runs = [self._timed_once(feeder, steps, dist) for _ in range(max(1, repeats))]
+        runs = [self._timed_once(feeder, steps, dist, keep_last) for _ in range(max(1, repeats))]
         runs_sorted = sorted(runs, key=lambda r: r["dt"])
         med = dict(runs_sorted[len(runs_sorted) // 2])
+        if keep_last:
+            med["last_frames"] = runs[-1]["last_frames"]
         med["all_ms_per_step"] = [round(r["dt"] / steps * 1e3, 4) for r in runs]
         med["min_ms_per_step"] = round(runs_sorted[0]["dt"] / steps * 1e3, 4)
         med["k1_ms"] = statistics.median(r["k1_ms"] for r in runs)
@@ -171,7 +180,7 @@ class Case:
             med["rank_ms_per_step"] = [round(x / steps * 1e3, 4) for x in med["rank_dt"]]
         return med
 
-    def _timed_once(self, feeder, steps, dist):
+    def _timed_once(self, feeder, steps, dist, keep_last=False):
         torch = self.torch
         self.rx.set_profiling(1)           # start/stop events on the channeliser launch only: its duration is the roofline figure
         self.rx.set_drain_lag(self.vdl2hip.MAX_DRAIN_LAG)
@@ -186,7 +195,8 @@ class Case:
         if self.pair:
             feeder.flush()                  # (an odd K: the last block has no partner)
         self.rx.set_drain_lag(0)
-        nframes += self.rx.drain_packed()[0]
+        last = self.rx.drain_packed()        # (every frame of the last step's block: a feed's frames come out at least one drain after it)
+        nframes += last[0]
         feeder.finish()
         torch.cuda.synchronize()
         t_own = time.perf_counter() - t0
@@ -195,6 +205,11 @@ class Case:
         dt = time.perf_counter() - t0
         s1 = self.rx.stats()
         out = {}
+        if keep_last:
+            # the last block starts `nsamples` input samples before the end of what was fed; frames are stamped in decimated samples
+            first = (s1["input_samples"] - self.nsamples) // self.cfg.oversample
+            out["last_frames"] = [dict(f, sync_sample=f["sync_sample"] - first, end_sample=f["end_sample"] - first)
+                                  for f in self.vdl2hip.Receiver.unpack(*last) if f["sync_sample"] >= first]
         if self.world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=self.device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -621,22 +636,56 @@ def h2d_ms(torch, host_pinned, device, iters=3):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
+DUMP_FIELDS = ("chan", "freq", "idx", "len", "synd_weight", "datalen_octets", "num_fec_corrections", "frame_pwr_dbfs", "nf_pwr_dbfs",
+               "ppm_error", "sync_sample", "end_sample", "avlc_status", "dst_addr", "src_addr")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_frames(frames, out_dir, seed=0):
+    """--dump-outputs: the frames a caller received for the last timed step's block, ordered by (channel, sync sample, index in
+    the burst), one array per field: DIR/frame_<field>.npy (float64, a frame per entry; sync_sample / end_sample counted from
+    the block's first decimated sample) and DIR/frame_octets.npy (float32, every frame's octets one after the other).  Should
+    that exceed 64 MB, a fixed seeded sample of the frames is written.  Returns the number of frames written."""
+    frames = sorted((dict(f, len=len(f["octets"])) for f in frames), key=lambda f: (f["chan"], f["sync_sample"], f["idx"]))
+    nbytes = lambda fs: sum(8 * len(DUMP_FIELDS) + 4 * f["len"] for f in fs)         # noqa: E731
+    if nbytes(frames) > DUMP_MAX_BYTES:
+        keep = np.random.default_rng(seed).permutation(len(frames))
+        n = len(frames)
+        while n > 1 and nbytes(frames[i] for i in keep[:n]) > DUMP_MAX_BYTES:
+            n = n * 3 // 4
+        frames = [frames[i] for i in sorted(keep[:n])]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f"frame_{k}.npy"), np.array([f[k] for f in frames], dtype=np.float64))
+    octets = b"".join(f["octets"] for f in frames)
+    np.save(os.path.join(out_dir, "frame_octets.npy"), np.frombuffer(octets, dtype=np.uint8).astype(np.float32))
+    return len(frames)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="how many times the K timed steps are run (median reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the K timed steps are run (median reported; default 1, with --full 3)")
     ap.add_argument("--duration", type=float, default=16.0, help="seconds of 2.1 MS/s signal per step")
     ap.add_argument("--channels", type=int, default=8, help="channel count of config2 (experiments)")
     ap.add_argument("--workload", default="config4", choices=["config2", "config3", "config4", "config5", "config4_bursty"],
                     help="BASELINE configs[1..4]; default config4 = north_star's 256 channels")
     ap.add_argument("--exchange", default="auto", choices=["auto", "broadcast", "allgather"],
                     help="N>1: how each rank gets the raw IQ block (both are always measured; this picks `value`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="N=1: skip the other configurations and the projected-scaling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: parity gate, CPU baseline, stage times, HBM-resident and steady-state regions, "
+                         "referee cost, measured issue rates, N>1 the other exchange form, N=1 projected scaling and secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the parity gate against the CPU oracle")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, N=1: skip the other configurations and the projected-scaling runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step's block to DIR/frame_<field>.npy (float64; octets float32)")
     args = ap.parse_args()
+    full = args.full
+    if args.repeats is None:
+        args.repeats = 3 if full else 1
 
     import torch
     import torch.distributed as dist
@@ -671,7 +720,7 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         assert int(lo.item()) == int(hi.item()), "ranks synthesised different captures"
 
-    # ---- exchange: both forms measured bare, from both sources ----
+    # ---- exchange: both forms measured bare from host memory (--full: from HBM too) ----
     exchange_info = None
     mode = "broadcast"
     forms = ["broadcast"]
@@ -691,7 +740,7 @@ def main():
         dist.all_gather_object(idents, ident)
         exchange_info["devices_by_rank"] = idents
         exchange_info["distinct_devices"] = len(set(idents))
-        for src_kind in ("host", "hbm"):
+        for src_kind in ("host", "hbm") if full else ("host",):
             for m in forms:
                 secs, ok = vdist.time_exchange(case.host, world, rank, m, src_kind, case.device)
                 exchange_info[f"{m}_{src_kind}_ms"] = round(secs * 1e3, 4) if ok else None
@@ -705,6 +754,7 @@ def main():
         forms = ok_forms
         exchange_info["chosen"] = mode
         exchange_info["chosen_by"] = "fastest bare exchange from host memory (auto)" if args.exchange == "auto" else "--exchange"
+    if world > 1 and full:
         pin = case.host.pin_memory()
         mine = torch.tensor([h2d_ms(torch, pin, case.device)], dtype=torch.float64, device=case.device)
         every = [torch.zeros_like(mine) for _ in range(world)]
@@ -712,14 +762,14 @@ def main():
         exchange_info["h2d_whole_block_ms_by_rank"] = [round(float(x.item()), 4) for x in every]   # [0] = the broadcast form's ingest cost
         del pin
 
-    # ---- warm-up, with the parity gate on the first pass ----
+    # ---- warm-up, with the parity gate on the first pass (--full) ----
     f_host = case.feeder(mode, "host")
     verified = verified_pieces = None
     cpu_baseline = None
     oracle_frames = None
     fr = case.frames_of_step(f_host)
-    allfr = vdist.gather_frames(fr, dst=0) if world > 1 else fr
-    if rank == 0 and not args.no_verify:
+    allfr = (vdist.gather_frames(fr, dst=0) if world > 1 else fr) if full else None
+    if full and rank == 0 and not args.no_verify:
         from oracle import pyoracle as po
         # N > 1: rank 0 holds the merged frames of all ranks - the frame / metadata comparison covers all channels, the counter
         # comparison rank 0's own (the other ranks' counters stay on their GPUs)
@@ -735,12 +785,17 @@ def main():
     case.rx.sync()
 
     # ---- timed region: exactly K steps, host-fed, `repeats` times ----
-    t_host = case.timed(f_host, args.steps, dist, args.repeats)
-    stage_ms = case.stage_times(f_host)
+    t_host = case.timed(f_host, args.steps, dist, args.repeats, keep_last=args.dump_outputs is not None)
+    dumped = None
+    if args.dump_outputs is not None:
+        last = vdist.gather_frames(t_host.pop("last_frames"), dst=0) if world > 1 else t_host.pop("last_frames")
+        if rank == 0:
+            dumped = dump_frames(last, args.dump_outputs)
+    stage_ms = case.stage_times(f_host) if full else None
     # every timed region above pays the pipeline's fill and drain once (first H2D exposed, the last block's back end after the last
     # front): a fixed 2-4 ms, i.e. 0.1-0.2 ms per step at K = 20.  One long region (10 K steps, at least 100) shows the streaming rate.
     steady = None
-    if world == 1 and not args.no_secondary:
+    if full and world == 1 and not args.no_secondary:
         ks = max(100, 10 * args.steps)
         ts = case.timed(f_host, ks, dist, 1)
         steady = {"steps": ks, "value": round(case.nsamples * ks / ts["dt"] / 1e6, 3), "ms_per_step": round(ts["dt"] / ks * 1e3, 4),
@@ -748,22 +803,23 @@ def main():
                   "note": "host-fed, one timed region of this many steps: the fill and drain of the pipeline (six blocks deep) (paid once per "
                           "region, whatever its length) weigh a tenth of what they do in the K-step regions `value` comes from"}
     del f_host
-    # ---- the same with the block resident in HBM ----
-    f_hbm = case.feeder(mode, "hbm")
-    for _ in range(2):
-        f_hbm.step()
-    case.rx.set_drain_lag(0); case.rx.drain_packed()
-    rs0 = case.rx.stats()
-    t_hbm = case.timed(f_hbm, args.steps, dist, args.repeats)
-    rs1 = case.rx.stats()
-    stage_ms_hbm = case.stage_times(f_hbm)
-    t_hbm_steady = None
-    if world == 1 and not args.no_secondary:      # (one long region, as `steady_state` above: what the projection below divides by)
+    # ---- --full: the same with the block resident in HBM ----
+    t_hbm = stage_ms_hbm = t_hbm_steady = None
+    if full:
+        f_hbm = case.feeder(mode, "hbm")
+        for _ in range(2):
+            f_hbm.step()
+        case.rx.set_drain_lag(0); case.rx.drain_packed()
+        rs0 = case.rx.stats()
+        t_hbm = case.timed(f_hbm, args.steps, dist, args.repeats)
+        rs1 = case.rx.stats()
+        stage_ms_hbm = case.stage_times(f_hbm)
+    if full and world == 1 and not args.no_secondary:      # (one long region, as `steady_state` above: what the projection below divides by)
         ks = max(100, 10 * args.steps)
         t_hbm_steady = case.timed(f_hbm, ks, dist, 1)["dt"] / ks * 1e3
     # ---- what the referee costs: the same timed region with it switched off (the answer is then no longer the oracle's on every input) ----
     referee_ab = None
-    if world == 1 and not args.no_secondary:
+    if full and world == 1 and not args.no_secondary:
         nf = max(1, rs1["feeds"] - rs0["feeds"])
         per = lambda k: round((rs1[k] - rs0[k]) / nf, 2)
         case.rx.debug_option("referee", 0)
@@ -780,12 +836,13 @@ def main():
                       "symbol_scans_per_step": per("referee_symbol_scans"), "channels_walked_again_per_step": per("referee_rewalks"), "refused": rs1["referee_refused"] - rs0["referee_refused"],
                       "what": "decisions within the margin of the channeliser's distance from the reference's fp32 scan are taken on the reference's own samples, "
                               "recomputed sequentially from the raw input (DESIGN 5); `value` is measured with it on"}
-    del f_hbm
-    measured = measured_rates(vdl2hip, local) if rank == 0 else (None, None)     # right behind the timed regions: the clock is up
+    if full:
+        del f_hbm
+    measured = measured_rates(vdl2hip, local) if full and rank == 0 else (None, None)     # right behind the timed regions: the clock is up
 
     # ---- N > 1: the other exchange form, demodulating, beside the chosen one ----
     by_exchange = None
-    if world > 1:
+    if full and world > 1:
         by_exchange = {mode: {"value": round(case.nsamples * args.steps / t_host["dt"] / 1e6, 3), "ms_per_step": round(t_host["dt"] / args.steps * 1e3, 4),
                               "ms_per_step_hbm_resident": round(t_hbm["dt"] / args.steps * 1e3, 4)}}
         for m in forms:
@@ -805,12 +862,12 @@ def main():
     # ---- N = 1: what one rank of the 8-GPU split would do on this GPU -> ceiling of the speed-up ----
     projected = None
     secondary = []
-    if world == 1 and not args.no_secondary:
+    if full and world == 1 and not args.no_secondary:
         # one receiver at a time from here on: the HIP streams of an idle second receiver share the few hardware queues with the
         # active one's (its front and walk streams then serialise: measured +0.5 ms per step on the rank-sized workload)
         case.close()
     try:
-      if world == 1 and not args.no_secondary and case.C % 8 == 0 and case.C >= 64:
+      if full and world == 1 and not args.no_secondary and case.C % 8 == 0 and case.C >= 64:
         per = case.C // 8
         shards = []
         for r in (0, 3, 7):
@@ -872,7 +929,7 @@ def main():
     except Exception as e:  # noqa: BLE001 - informational block: a failure here must not take the headline line with it
         projected = {"error": f"{type(e).__name__}: {str(e)[:400]}"}
 
-    if world == 1 and not args.no_secondary and args.workload == "config4":
+    if full and world == 1 and not args.no_secondary and args.workload == "config4":
         from oracle import pyoracle as po
         try:
             secondary.append(dropin_block_rate(case, torch))
@@ -909,20 +966,24 @@ def main():
 
     if rank == 0:
         value = case.nsamples * args.steps / t_host["dt"] / 1e6
-        value_hbm = case.nsamples * args.steps / t_hbm["dt"] / 1e6
+        value_hbm = case.nsamples * args.steps / t_hbm["dt"] / 1e6 if t_hbm else None
+        t_roof = t_hbm if t_hbm else t_host           # (a plain run: the channeliser launches of the headline region itself)
         widx = WORKLOAD_INDEX.get(args.workload)
         out = {
             "metric": "IQ MS/s demodulated end-to-end",
             "value": round(value, 3), "unit": "MS/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(t_host["dt"] / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "repeats": args.repeats, "clock_warmup_s": CLOCK_WARMUP_S, "value_is": f"median of {args.repeats} repeats of the K = {args.steps} timed steps",
+            "full": full, "repeats": args.repeats, "clock_warmup_s": CLOCK_WARMUP_S,
+            "value_is": f"median of {args.repeats} repeats of the K = {args.steps} timed steps" if args.repeats > 1 else f"one region of the K = {args.steps} timed steps",
             "ms_per_step_all_repeats": t_host["all_ms_per_step"], "ms_per_step_min": t_host["min_ms_per_step"],
             "steady_state": steady,
-            "value_hbm_resident": round(value_hbm, 3), "ms_per_step_hbm_resident": round(t_hbm["dt"] / args.steps * 1e3, 4),
-            "ms_per_step_hbm_resident_all_repeats": t_hbm["all_ms_per_step"],
+            "value_hbm_resident": round(value_hbm, 3) if t_hbm else None,
+            "ms_per_step_hbm_resident": round(t_hbm["dt"] / args.steps * 1e3, 4) if t_hbm else None,
+            "ms_per_step_hbm_resident_all_repeats": t_hbm["all_ms_per_step"] if t_hbm else None,
             "parity": ("frames, integer metadata, burst timing and the reference's 18 counters identical to the CPU oracle on the whole block, every "
-                       "channel; float metadata within SURVEY 8.5's tolerances (0.01 ppm, 0.05 dB); no tie allowances (config.verified)") if verified else "not checked (--no-verify)",
+                       "channel; float metadata within SURVEY 8.5's tolerances (0.01 ppm, 0.05 dB); no tie allowances (config.verified)") if verified
+                      else "not checked (--no-verify)" if full else "not checked (a plain run: --full checks it)",
             "config": {"workload": (f"configs[{widx}] " if widx else "") + f"({args.workload}): synthetic 2.1 MS/s cs16 IQ, {cfg.duration_s:g} s per step, {case.C} VDL2 channels "
                                    f"in total, {case.count} per GPU; value = block in page-locked host memory -> frames in host memory "
                                    f"(H2D inside the step, overlapped); six blocks in flight",
@@ -948,8 +1009,10 @@ def main():
                        "verified_in_pieces": verified_pieces,
                        "synth_s": round(case.t_synth, 1),
                        "secondary": secondary},
-            "roofline": roofline_of(t_hbm, pmc_traffic(args.workload, case)),
+            "roofline": roofline_of(t_roof, pmc_traffic(args.workload, case)),
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "frames": dumped}
         # the parity gate's outcome as flat scalars (headline workload, then every secondary one that was checked against the oracle)
         def flat(prefix, v):
             out[prefix + "timing_ties"] = v["timing_ties"]; out[prefix + "nf_update_ties"] = v["nf_update_ties"]
@@ -983,7 +1046,8 @@ def main():
             rl = out["roofline"]
             items = rl["chan_samples_per_launch"] / 64.0 / (4 * measured[1]["compute_units"])          # wavefront-items per SIMD and launch
             rl["co_bound"]["k_chanfir_clocks_per_chan_sample_wave_per_SIMD"] = round(rl["avg_launch_ms"] * 1e-3 * measured[0]["shader_clock_GHz"] * 1e9 / items, 1)
-        out["roofline"]["measured_in"] = "the HBM-resident timed region (HIP start/stop events attached to each k_chanfir launch; median of the repeats)"
+        out["roofline"]["measured_in"] = ("the HBM-resident timed region" if t_hbm else "the host-fed timed region") + \
+            " (HIP start/stop events attached to each k_chanfir launch; median of the repeats)"
         out["roofline"]["avg_launch_ms_host_fed"] = round(t_host["k1_ms"], 5)
         if projected is not None:
             out["projected_scaling"] = projected

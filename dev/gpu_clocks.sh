@@ -12,6 +12,6 @@ echo "idle $(rocm-smi --showclocks --showpower 2>/dev/null | grep -E 'sclk|fclk|
 ( for i in 1 2 3 4 5 6; do /tmp/ub > /tmp/ub.out; done ) & P=$!
 sample ubench $P | tail -12
 head -4 /tmp/ub.out
-python bench.py --no-secondary --no-cpu-baseline --no-verify --steps 200 --repeats 2 > /tmp/b.json 2>/dev/null & P=$!
+python bench.py --full --no-secondary --no-cpu-baseline --no-verify --steps 200 --repeats 2 > /tmp/b.json 2>/dev/null & P=$!
 sample bench $P | tail -24
 python -c "import json; j=json.load(open('/tmp/b.json')); print(j['value'], j['ms_per_step'], j['ms_per_step_hbm_resident'])"

@@ -3,7 +3,7 @@
 R="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/gap
-rocprofv3 --kernel-trace -d /tmp/gap -o g -- python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-verify > /tmp/gap.log 2>&1
+rocprofv3 --kernel-trace -d /tmp/gap -o g -- python $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-verify > /tmp/gap.log 2>&1
 python - <<'PY'
 import sqlite3, glob
 db = glob.glob("/tmp/gap/**/*.db", recursive=True)[0]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The one GPU-box runner: dev/gpu_run.sh <tag> <job> [<job> ...]   (outputs under gpurun_out/<tag>.*; copy what is to be judged to profiles/)
 #   pytest        python -m pytest tests -m gpu
-#   bench         the driver's line: python bench.py --gpus 1 --steps 20 --warmup 5
+#   bench         the driver's line: python bench.py --full --gpus 1 --steps 20 --warmup 5
 #   bench5        config5 (injected errors), no secondary / cpu baseline
 #   benchw:<w>    bench.py --workload <w> without gate / baseline / secondary: value, ms/step, stage times
 #   shard32       dev/gpu_shard32.py: the rank-sized workload (32 of 256 channels), ranks 0,3,7
@@ -38,10 +38,10 @@ for job in "$@"; do
 	env:*) export "${job#env:}" ;;
 	unenv:*) unset "${job#unenv:}" ;;
 	pytest) timeout 1200 python -m pytest tests -m gpu -x -q > $O.pytest.txt 2>&1; echo "pytest rc=$?" >> $O.pytest.txt; tail -3 $O.pytest.txt ;;
-	bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O.bench_default.json 2> $O.bench_default.err; echo "bench rc=$?"; tail -c 400 $O.bench_default.err; cut -c1-600 $O.bench_default.json ;;
-	bench5) timeout 600 python bench.py --workload config5 --no-secondary --no-cpu-baseline > $O.bench_config5.json 2> $O.bench_config5.err; echo "config5 rc=$?"; cut -c1-400 $O.bench_config5.json ;;
-	benchq) timeout 600 python bench.py --no-secondary --no-cpu-baseline --no-verify >> $O.benchq.jsonl 2>> $O.benchq.err; echo "rc=$?"; tail -1 $O.benchq.jsonl | python -c "import json,sys; j=json.loads(sys.stdin.read()); print(j['value'], j['ms_per_step'], j['ms_per_step_hbm_resident'], j['config']['stage_ms_per_step'], j['config'].get('stage_ms_per_step_hbm_resident'), j['roofline']['avg_launch_ms'], j['roofline']['avg_launch_ms_host_fed'])" ;;
-	benchw:*) timeout 600 python bench.py --workload ${job#benchw:} --no-secondary --no-cpu-baseline --no-verify --repeats 2 2>> $O.benchw.err | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$job [$(sfx)]', j['value'], j['ms_per_step'], j['ms_per_step_hbm_resident'], j['config']['stage_ms_per_step'])" | tee -a $O.benchw.txt ;;
+	bench) timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O.bench_default.json 2> $O.bench_default.err; echo "bench rc=$?"; tail -c 400 $O.bench_default.err; cut -c1-600 $O.bench_default.json ;;
+	bench5) timeout 600 python bench.py --full --workload config5 --no-secondary --no-cpu-baseline > $O.bench_config5.json 2> $O.bench_config5.err; echo "config5 rc=$?"; cut -c1-400 $O.bench_config5.json ;;
+	benchq) timeout 600 python bench.py --full --no-secondary --no-cpu-baseline --no-verify >> $O.benchq.jsonl 2>> $O.benchq.err; echo "rc=$?"; tail -1 $O.benchq.jsonl | python -c "import json,sys; j=json.loads(sys.stdin.read()); print(j['value'], j['ms_per_step'], j['ms_per_step_hbm_resident'], j['config']['stage_ms_per_step'], j['config'].get('stage_ms_per_step_hbm_resident'), j['roofline']['avg_launch_ms'], j['roofline']['avg_launch_ms_host_fed'])" ;;
+	benchw:*) timeout 600 python bench.py --full --workload ${job#benchw:} --no-secondary --no-cpu-baseline --no-verify --repeats 2 2>> $O.benchw.err | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$job [$(sfx)]', j['value'], j['ms_per_step'], j['ms_per_step_hbm_resident'], j['config']['stage_ms_per_step'])" | tee -a $O.benchw.txt ;;
 	shard32) timeout 900 python dev/gpu_shard32.py --json $O.shard32.json 2> $O.shard32.err | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
@@ -55,7 +55,7 @@ for r in j['ranks']: print(j['env'], 'rank', r['rank'], r['ms_per_step'], 'K1', 
 	sweep32:*) timeout 900 python dev/gpu_shard32.py --ranks 3 --repeats 2 --sweep "${job#sweep32:}" --json $O.sweep32_$(date +%s).json 2>&1 >/dev/null | grep '^{' | cut -c1-330 | tee -a $O.sweep32.txt ;;
 	trace32) trace shard32 python $R/dev/gpu_shard32.py --ranks 3 --repeats 1 --no-check ;;
 	tracedropin) trace dropin python $R/dev/gpu_dropin_rate.py config4 2 ;;
-	trace256) trace bench_config4 python $R/bench.py --workload config4 --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-secondary ;;
+	trace256) trace bench_config4 python $R/bench.py --full --workload config4 --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-secondary ;;
 	pmc256) timeout 500 bash dev/gpu_pmc_traffic.sh config4 > $O.pmc_hbm_traffic_config4.txt 2>&1; cat $O.pmc_hbm_traffic_config4.txt | cut -c1-160 ;;
 	sq_k1:*) timeout 500 bash dev/gpu_k1_pmc.sh ${job#sq_k1:} > $O.sq_k1_${job#sq_k1:}ch.txt 2>&1; cut -c1-140 $O.sq_k1_${job#sq_k1:}ch.txt ;;
 	sq_k3a:*) KFILTER=sync_screen timeout 500 bash dev/gpu_k1_pmc.sh ${job#sq_k3a:} > $O.sq_k3a_${job#sq_k3a:}ch.txt 2>&1; cut -c1-140 $O.sq_k3a_${job#sq_k3a:}ch.txt ;;

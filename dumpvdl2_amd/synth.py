@@ -8,6 +8,7 @@ of transmitted frames), so a decode can be checked without any oracle.
 """
 from __future__ import annotations
 
+import concurrent.futures
 import dataclasses
 from typing import List, Optional, Sequence
 
@@ -322,58 +323,36 @@ def _random_frames(rng: np.random.Generator, cfg: SynthConfig) -> List[bytes]:
     return frames
 
 
-def synthesize(cfg: SynthConfig, dtype=np.int16):
-    """Return (iq, bursts): iq is interleaved I,Q int16 (2*N values), bursts the ground truth."""
+def synthesize(cfg: SynthConfig, dtype=np.int16, workers: int = 1):
+    """Return (iq, bursts): iq is interleaved I,Q int16 (2*N values), bursts the ground truth.
+
+    workers > 1 computes the channels' bursts on that many threads (numpy's FFTs and array operations release the GIL);
+    they are still added into the capture one channel after the other, so the result is the same bytes as with workers = 1."""
     fs = cfg.sample_rate
     n = int(round(cfg.duration_s * fs))
     n -= n % 2
-    sps = SPS * cfg.oversample
     acc = np.zeros(n, dtype=np.complex64)
     bursts: List[TxBurst] = []
     master = np.random.default_rng(cfg.seed)
-    for k, f in enumerate(cfg.freqs):
-        rng = np.random.default_rng(master.integers(0, 2 ** 63))
-        t = cfg.first_burst_s + float(rng.exponential(cfg.mean_gap_s))
-        while True:
-            frames = _random_frames(rng, cfg)
-            errs = None
-            hflips = 0
-            if cfg.error_injection:
-                probe = build_burst(frames)
-                errs = []
-                for r in range(probe.num_blocks):
-                    last = probe.datalen_octets - (probe.num_blocks - 1) * RS_K
-                    npar = 6 if r < probe.num_blocks - 1 else fec_octets_for(last)
-                    tcap = npar // 2
-                    errs.append(tcap + 1 if (rng.random() < 0.05 and npar > 0) else int(rng.integers(0, tcap + 1)))
-                u = rng.random()
-                hflips = 2 if u < 0.02 else 1 if u < 0.12 else 0
-            bb = build_burst(frames, rng, errs, hflips)
-            wave = None
-            if cfg.tdm_slots > 0:
-                period = cfg.tdm_slots * cfg.tdm_slot_s
-                slot0 = (k % cfg.tdm_slots) * cfg.tdm_slot_s
-                stay = False
-                if cfg.tdm_pack:
-                    wave = modulate(bb.symbols, sps, start_phase=float(rng.uniform(0, 2 * np.pi)))
-                    into = (t - slot0) % period              # position inside the channel's own period
-                    stay = t >= slot0 and 0.002 <= into and into + wave.size / fs + 0.002 <= cfg.tdm_slot_s
-                if not stay:
-                    m = np.ceil((t - slot0) / period)
-                    t = slot0 + max(m, 0) * period + 0.002
-            if wave is None:
-                wave = modulate(bb.symbols, sps, start_phase=float(rng.uniform(0, 2 * np.pi)))
-            start = int(round(t * fs))
-            if start + wave.size >= n:
-                break
-            cfo = float(rng.uniform(-cfg.max_ppm, cfg.max_ppm)) * 1e-6 * f
-            w = 2.0 * np.pi * ((f - cfg.centerfreq) + cfo) / fs
-            idx = np.arange(start, start + wave.size, dtype=np.float64)
-            acc[start:start + wave.size] += (cfg.amplitude * wave * np.exp(1j * (w * idx))).astype(np.complex64)
-            bursts.append(TxBurst(k, start, frames, bb.tl_bits, bb.datalen_octets, bb.injected_byte_errors,
-                                  bb.header_flips,
-                                  bb.decodable and (hflips == 0 or (hflips == 1 and bb.tl_bits <= 0x1FFF)), cfo))
-            t = (start + wave.size) / fs + float(rng.exponential(cfg.mean_gap_s)) + 0.004
+    seeds = [master.integers(0, 2 ** 63) for _ in cfg.freqs]
+
+    def one(k):
+        return _channel_bursts(cfg, k, seeds[k], n)
+
+    def add(results):
+        for parts, chan_bursts in results:
+            for start, part in parts:
+                acc[start:start + part.size] += part
+            bursts.extend(chan_bursts)
+
+    nchan = len(cfg.freqs)
+    if workers > 1 and nchan > 1:
+        with concurrent.futures.ThreadPoolExecutor(workers) as ex:
+            chunk = 4 * workers                 # (a bounded number of channels' bursts held at a time)
+            for k0 in range(0, nchan, chunk):
+                add(ex.map(one, range(k0, min(nchan, k0 + chunk))))
+    else:
+        add(map(one, range(nchan)))
     nrng = np.random.default_rng(cfg.seed ^ 0x5EED)
     iq = np.empty(2 * n, dtype=np.float32)
     iq[0::2] = acc.real
@@ -390,6 +369,58 @@ def synthesize(cfg: SynthConfig, dtype=np.int16):
     else:
         raise ValueError("dtype must be int16 or uint8")
     return out, bursts
+
+
+def _channel_bursts(cfg: SynthConfig, k: int, seed, n: int):
+    """Channel k's bursts in a capture of n samples: ([(start, complex64 samples to add there)], [TxBurst])."""
+    fs = cfg.sample_rate
+    sps = SPS * cfg.oversample
+    f = cfg.freqs[k]
+    parts = []
+    bursts: List[TxBurst] = []
+    rng = np.random.default_rng(seed)
+    t = cfg.first_burst_s + float(rng.exponential(cfg.mean_gap_s))
+    while True:
+        frames = _random_frames(rng, cfg)
+        errs = None
+        hflips = 0
+        if cfg.error_injection:
+            probe = build_burst(frames)
+            errs = []
+            for r in range(probe.num_blocks):
+                last = probe.datalen_octets - (probe.num_blocks - 1) * RS_K
+                npar = 6 if r < probe.num_blocks - 1 else fec_octets_for(last)
+                tcap = npar // 2
+                errs.append(tcap + 1 if (rng.random() < 0.05 and npar > 0) else int(rng.integers(0, tcap + 1)))
+            u = rng.random()
+            hflips = 2 if u < 0.02 else 1 if u < 0.12 else 0
+        bb = build_burst(frames, rng, errs, hflips)
+        wave = None
+        if cfg.tdm_slots > 0:
+            period = cfg.tdm_slots * cfg.tdm_slot_s
+            slot0 = (k % cfg.tdm_slots) * cfg.tdm_slot_s
+            stay = False
+            if cfg.tdm_pack:
+                wave = modulate(bb.symbols, sps, start_phase=float(rng.uniform(0, 2 * np.pi)))
+                into = (t - slot0) % period              # position inside the channel's own period
+                stay = t >= slot0 and 0.002 <= into and into + wave.size / fs + 0.002 <= cfg.tdm_slot_s
+            if not stay:
+                m = np.ceil((t - slot0) / period)
+                t = slot0 + max(m, 0) * period + 0.002
+        if wave is None:
+            wave = modulate(bb.symbols, sps, start_phase=float(rng.uniform(0, 2 * np.pi)))
+        start = int(round(t * fs))
+        if start + wave.size >= n:
+            break
+        cfo = float(rng.uniform(-cfg.max_ppm, cfg.max_ppm)) * 1e-6 * f
+        w = 2.0 * np.pi * ((f - cfg.centerfreq) + cfo) / fs
+        idx = np.arange(start, start + wave.size, dtype=np.float64)
+        parts.append((start, (cfg.amplitude * wave * np.exp(1j * (w * idx))).astype(np.complex64)))
+        bursts.append(TxBurst(k, start, frames, bb.tl_bits, bb.datalen_octets, bb.injected_byte_errors,
+                              bb.header_flips,
+                              bb.decodable and (hflips == 0 or (hflips == 1 and bb.tl_bits <= 0x1FFF)), cfo))
+        t = (start + wave.size) / fs + float(rng.exponential(cfg.mean_gap_s)) + 0.004
+    return parts, bursts
 
 
 def expected_frames(bursts: Sequence[TxBurst]):

@@ -51,3 +51,40 @@ def test_workload_names_are_baseline_configs(bench):
         want = {1: 8, 2: 64, 3: 256, 4: 256}[idx]
         assert len(cfg.freqs) == want and str(want) in base["configs"][idx]
         assert cfg.oversample == 20                    # 2.1 MS/s
+
+
+def _frame(chan, sync, idx, octets):
+    """a frame as vdl2hip.Receiver.unpack() returns it"""
+    return {"chan": chan, "freq": 136975000 + chan, "idx": idx, "octets": octets, "synd_weight": 0, "datalen_octets": len(octets),
+            "num_fec_corrections": 1, "frame_pwr_dbfs": -20.5, "nf_pwr_dbfs": -50.25, "ppm_error": 0.125, "sync_sample": sync,
+            "end_sample": sync + 100, "avlc_status": 0, "dst_addr": 7, "src_addr": 9}
+
+
+def test_dump_frames_layout_and_order(bench, tmp_path):
+    """--dump-outputs: one float64 array per frame field, frames ordered by (channel, sync sample, index), octets one after the other as float32"""
+    import numpy as np
+    frames = [_frame(3, 500, 1, b"\x01\x02"), _frame(1, 900, 0, b"\xff"), _frame(3, 500, 0, b"\x10\x20\x30"), _frame(1, 100, 0, b"")]
+    assert bench.dump_frames(frames, str(tmp_path)) == 4
+    assert {p.name for p in tmp_path.iterdir()} == {f"frame_{k}.npy" for k in bench.DUMP_FIELDS + ("octets",)}
+    chan, sync, idx = (np.load(tmp_path / f"frame_{k}.npy") for k in ("chan", "sync_sample", "idx"))
+    assert chan.dtype == np.float64 and list(chan) == [1, 1, 3, 3] and list(sync) == [100, 900, 500, 500] and list(idx) == [0, 0, 0, 1]
+    oct_ = np.load(tmp_path / "frame_octets.npy")
+    assert oct_.dtype == np.float32 and list(oct_) == [0xff, 0x10, 0x20, 0x30, 1, 2]
+    assert list(np.load(tmp_path / "frame_ppm_error.npy")) == [0.125] * 4
+
+
+def test_dump_frames_sample_is_bounded_and_fixed(bench, tmp_path, monkeypatch):
+    """above the size limit a seeded sample of the frames is written: within the limit, the same frames every time, still in order"""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    frames = [_frame(c, 1000 * s, 0, bytes(range(50))) for c in range(16) for s in range(10)]
+    n1 = bench.dump_frames(frames, str(tmp_path / "a"))
+    n2 = bench.dump_frames(list(reversed(frames)), str(tmp_path / "b"))
+    assert 0 < n1 == n2 < len(frames)
+    size = sum(np.load(p).nbytes for p in (tmp_path / "a").iterdir())
+    assert size <= 20000
+    for k in ("chan", "sync_sample"):
+        a, b = np.load(tmp_path / "a" / f"frame_{k}.npy"), np.load(tmp_path / "b" / f"frame_{k}.npy")
+        assert (a == b).all()
+    key = list(zip(np.load(tmp_path / "a" / "frame_chan.npy"), np.load(tmp_path / "a" / "frame_sync_sample.npy")))
+    assert key == sorted(key)

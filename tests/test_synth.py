@@ -79,3 +79,14 @@ def test_u8_samples(oracle_mod):
     o = oracle_mod.Oracle(CF, [CF], oversample=10, sample_fmt=oracle_mod.FMT_U8)
     o.process(iq)
     assert [f["octets"] for f in o.frames()] == [w[3] for w in synth.expected_frames(bursts)]
+
+
+@pytest.mark.parametrize("name", ["config3", "config5", "config4_bursty"])
+def test_threaded_synthesis_is_the_same_capture(name):
+    """synthesize(workers=N) - what bench.py uses - gives the bytes and the ground truth of the one-thread synthesis"""
+    from dumpvdl2_amd import workloads
+    cfg = getattr(workloads, name)(1.0)
+    iq1, b1 = synth.synthesize(cfg)
+    iq4, b4 = synth.synthesize(cfg, workers=4)
+    assert iq1.dtype == iq4.dtype == np.int16 and np.array_equal(iq1, iq4)
+    assert b1 == b4 and len(b1) > 0
