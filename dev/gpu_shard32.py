@@ -6,7 +6,7 @@ usage: python dev/gpu_shard32.py [--count 32] [--ranks 0,3,7] [--steps 20] [--re
 
 Prints one JSON object: per rank ms/step (min / median of the repeats), the channeliser's own time per launch, per-stage kernel
 times of a profiled pass, and the frames check (every transmitted frame of the shard's channels recovered).  Knobs of the
-library (VDL2HIP_CR, VDL2HIP_K1_TILES, VDL2HIP_SEG_MAX ...) are taken from the environment and echoed."""
+library (VDL2HIP_SEG_MAX, VDL2HIP_REF_PRESCAN ...) are taken from the environment and echoed."""
 import argparse
 import json
 import os
@@ -92,7 +92,7 @@ def main():
     ap.add_argument("--workload", default="config4")
     ap.add_argument("--json", default="")
     ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--sweep", default="", help='e.g. "VDL2HIP_CR=1,2,4;VDL2HIP_K1_TILES=2,4,8": every combination (the library reads its knobs at create)')
+    ap.add_argument("--sweep", default="", help='e.g. "VDL2HIP_SEG_MAX=4,8,16;VDL2HIP_REF_PRESCAN=0,1": every combination (the library reads its knobs at create)')
     a = ap.parse_args()
     cfg = getattr(workloads, a.workload)(a.duration)
     import pickle

@@ -2,7 +2,7 @@
 variant - a library build (VDL2HIP_LIB) plus environment switches - runs in a process of its own over the same captures:
 
   python dev/gpu_variants.py --out gpurun_out/x.jsonl --workloads config4,config4_bursty \
-         --variant base --variant eager:VDL2HIP_BACKEND=eager --variant ph:@/tmp/vdl2hip_ph.so --variant ...
+         --variant base --variant seg4:VDL2HIP_SEG_MAX=4 --variant ph:@/tmp/vdl2hip_ph.so --variant ...
 
 A variant is `name[:@lib.so][:ENV=VALUE]...`.  Per variant and workload, block resident in HBM, three blocks in flight:
 ms per step (all channels and as the 32-channel shard 96..127 - a rank's share at N = 8), the channeliser's own time per

@@ -70,12 +70,11 @@ struct RefChan {
 	const uint8_t *mix;                    // per channel: offset_tuning (src/demod.c:386: centerfreq != freq)
 	const Lut4 *lut;
 	float A0, A1, A2, B1, B2;              // src/demod.c:55
-	int32_t os, fmt, npiece, kinds;        // kinds: bit k set = requests of kind k (REF_CANDIDATE ...) are served
+	int32_t os, fmt, npiece;
 	RefPiece piece[kRefPieces];            // oldest first, contiguous; the last one is this feed's block
 	int64_t warm;                          // input samples the scan starts before the stretch
 	unsigned long long *done;              // [nchan][kRefCache] stretches made exact (see ref_exact_window_dev)
 	uint32_t *done_n;                      // [nchan] entries written so far
-	unsigned long long *dbg; int32_t dbg_chan, dbg_pad;   // development aid (-DVDL2_REF_DEBUG): event log of one channel, dbg[0] = entries written
 	uint32_t *stats;                       // [0] scans run, [1] requests answered from the list, [2] requests refused (input no longer held), [3] scans with a shortened run-up, [4 + kind] scans by who asked, [7] channels walked again
 };
 
@@ -109,17 +108,15 @@ __device__ __forceinline__ float ref_lane(float v, int l) { return __builtin_bit
 // began.  launch = 16 * feed + kind.  Kinds of the walk chain of feed s and when they run (vdl2hip.hip: launch_back / launch_rest):
 //   8 scans ahead of the walk        own stream, after the feed's front: BESIDE the walk chains of the feeds before
 //   1 speculative / single walk, 2 stitch                 walk stream
-//   0 the noted decisions' scans, 3 check                 own stream, after stitch(s): beside the walks of the next one or two feeds
-//   4 walk again (after check(s) AND the walks that went ahead of it), 9 / 10 feed s once more from a corrected start - as the first /
-//     the second feed behind the one whose second walk corrected it: walk stream
-// The walk stream runs (walk ahead by two feeds)  ... S(s) 4(s-2) 9(s-1) 10(s)  S(s+1) 4(s-1) 9(s) 10(s+1)  S(s+2) 4(s) ...  - by one:
-// ... S(s) 4(s-1) 9(s)  S(s+1) 4(s) 9(s+1) ... - with 0/3 of feed s anywhere between S(s) and 4(s).  Kinds of the burst stream of feed
-// s, after 4(s): 5 burst decoder (first pass), 6 its listed scans, 7 second pass; they run beside the walk chains of the feeds after s
-// and beside other feeds' burst kernels.  Hence a reader (feed m, kind mk) believes an entry (feed e, kind ek), d = m - e - rules that
-// hold for either depth:
+//   0 the noted decisions' scans, 3 check                 own stream, after stitch(s): beside the walk of the next feed
+//   4 walk again (after check(s) AND the walk that went ahead of it), 9 feed s once more from a start that the second walk of the
+//     feed before has corrected: walk stream
+// The walk stream runs (S = 1 and 2; the next feed's walk at most one feed ahead)  ... S(s) 4(s-1) 9(s)  S(s+1) 4(s) 9(s+1) ...  - with
+// 0/3 of feed s anywhere between S(s) and 4(s).  Kinds of the burst stream of feed s, after 4(s): 5 burst decoder (first pass), 6 its
+// listed scans, 7 second pass; they run beside the walk chains of the feeds after s and beside other feeds' burst kernels.  Hence a
+// reader (feed m, kind mk) believes an entry (feed e, kind ek), d = m - e:
 //   4, 9: every walk-chain entry of an earlier feed (check(m - 1) has ended by then); of its own feed 4: everything, 9: {8, 1, 2}.
-//   10: d >= 2: yes; d = 1: {8, 1, 2, 9, 10} (check(m - 1) may still run); d = 0: {8, 1, 2}.
-//   1, 2, 0, 3: d >= 3: yes; d = 2: {8, 1, 2, 9, 10}; d = 1: {8, 1, 2}; d = 0: reader 1: {8}; 2: {8, 1}; 0: {8, 1, 2}; 3: {8, 1, 2, 0}.
+//   1, 2, 0, 3: d >= 3: yes; d = 2: {8, 1, 2, 9}; d = 1: {8, 1, 2}; d = 0: reader 1: {8}; 2: {8, 1}; 0: {8, 1, 2}; 3: {8, 1, 2, 0}.
 //   burst kernel: walk-chain entries of its own and earlier feeds, and its own feed's earlier burst kinds.
 //   the scans ahead of the walk (8) believe nobody; nobody believes an entry of his own launch or a burst kernel of another feed.
 // (Round 5 believed every entry of another launch - a burst decoder could pick up the entry of a later feed's scan that was still
@@ -131,15 +128,13 @@ __device__ __forceinline__ bool ref_entry_visible(uint32_t entry, uint32_t mine)
 	if(mine >= 0xfffeu || entry >= 0xfffeu) return true;
 	const uint32_t ek = entry & 15u, mk = mine & 15u, d = ((mine >> 4) - (entry >> 4)) & 0xfffu;
 	if(mk == 8u || d >= 2048u) return false;
-	auto walk_kind = [](uint32_t k) { return k <= 4u || (k >= 8u && k <= 10u); };
+	auto walk_kind = [](uint32_t k) { return k <= 4u || k == 8u || k == 9u; };
 	if(!walk_kind(mk)) return walk_kind(ek) || (d == 0u && ek < mk);       // a burst kernel (5, 6, 7)
 	if(!walk_kind(ek)) return false;
 	const bool early = ek == 8u || ek == 1u || ek == 2u;                        // ends before anything of the next feed's walk begins
-	const bool redone = ek == 9u || ek == 10u;
 	if(mk == 4u || mk == 9u) return d >= 1u || mk == 4u || early;
-	if(mk == 10u) return d >= 2u || early || (d == 1u && redone);
 	if(d >= 3u) return true;
-	if(d == 2u) return early || redone;
+	if(d == 2u) return early || ek == 9u;
 	if(d == 1u) return early;
 	switch(mk) {                                                                 // d == 0
 		case 1: return ek == 8u;
@@ -176,7 +171,7 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 	RefChan *rp = v.ref;
 	if(!rp) return false;
 	const int lane = threadIdx.x & 63, c = v.ref_chan;
-	// the hook's scalars, once (wave-uniform: they live in SGPRs from here on; nothing below reads the hook again)
+	// the hook's scalars, once (wave-uniform: they live in SGPRs from here on; below, the hook is read again only for the statistics' pointer, where something is counted - one pointer less to keep across the recursion)
 	const int os = rp->os, fmt = rp->fmt, npiece = rp->npiece;
 	const uint32_t mask = rp->mask, cap = rp->cap;
 	const int64_t warm = rp->warm;
@@ -189,7 +184,7 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 	const bool mix = rp->mix[c] != 0;
 	ref_gf4 *lut = (ref_gf4 *)rp->lut;
 	unsigned long long *done = rp->done + (size_t)c * kRefCache;
-	uint32_t *done_n = rp->done_n + c, *stats = rp->stats;
+	uint32_t *done_n = rp->done_n + c;
 	__attribute__((address_space(1))) float *yout = (__attribute__((address_space(1))) float *)(rp->y + (size_t)c * cap);
 	if(n_lo < 0) n_lo = 0;
 	if(n_hi < n_lo) return true;
@@ -201,16 +196,16 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 		if((n_hi | 255) <= last) n_hi |= 255; else if(n_hi < last) n_hi = last;
 	}
 	// done before?
-	if(ref_done_lookup(done, *done_n, n_lo, n_hi, v.ref_launch, lane)) { if(lane == 0) atomicAdd(stats + 1, 1u); return true; }
+	if(ref_done_lookup(done, *done_n, n_lo, n_hi, v.ref_launch, lane)) { if(lane == 0) atomicAdd(rp->stats + 1, 1u); return true; }
 	const int64_t s_end = (int64_t)os * (n_hi + 1);            // decimated sample k is the filter's output after input sample os (k + 1) - 1
 	int64_t s_beg = (int64_t)os * n_lo - warm;
 	bool shortened = false;
 	if(s_beg < 0) s_beg = 0;                                     // the stream's own start: the reference's state there is zero, exactly
 	else {
 		if(ps0[0] > s_beg) { shortened = true; s_beg = (ps0[0] + os - 1) / os * os; }      // (the oldest sample held, on the next decimation boundary: nothing that is not held is read)
-		if(s_beg > 0 && (int64_t)os * n_lo - s_beg < warm / 4) { if(lane == 0) atomicAdd(stats + 2, 1u); return false; }
+		if(s_beg > 0 && (int64_t)os * n_lo - s_beg < warm / 4) { if(lane == 0) atomicAdd(rp->stats + 2, 1u); return false; }
 	}
-	if(npiece <= 0 || in_end < s_end) { if(lane == 0) atomicAdd(stats + 2, 1u); return false; }
+	if(npiece <= 0 || in_end < s_end) { if(lane == 0) atomicAdd(rp->stats + 2, 1u); return false; }
 	__builtin_amdgcn_s_setprio(VDL2_REF_PRIO);
 
 	const int G = 64 / os, blk = G * os;                        // decimated outputs / input samples per block (os <= kMaxOversample = 32)
@@ -318,23 +313,14 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 		int64_t len = (n_hi - n_lo) >> 8; if(len > 0xffff) len = 0xffff;     // (whole blocks of 256: n_lo is aligned, n_hi ends a block or the input)
 		if(((n_hi + 1) & 255) != 0) len -= 1;                                 // a last, partial block is not promised
 		if(len >= 0) __hip_atomic_store(done + (i % (uint32_t)kRefCache), ((unsigned long long)(n_lo >> 8) << 32) | ((unsigned long long)len << 16) | (unsigned long long)(v.ref_launch & 0xffffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		atomicAdd(stats + 0, 1u); atomicAdd(stats + 4 + kind, 1u);
-		if(shortened) atomicAdd(stats + 3, 1u);
+		atomicAdd(rp->stats + 0, 1u); atomicAdd(rp->stats + 4 + kind, 1u);
+		if(shortened) atomicAdd(rp->stats + 3, 1u);
 	}
 	return true;
 }
 #endif
 
-VDL2_HD void ref_debug_log(const ChanView &v, int tag, int64_t a, float b, float c, float d) {
-#if VDL2_DEVICE_PASS && defined(VDL2_REF_DEBUG)
-	RefChan *r = v.ref;
-	if(!r || !r->dbg || v.ref_chan != r->dbg_chan) return;
-	const unsigned long long i = atomicAdd(r->dbg, 1ull);
-	if(i < 1000) { unsigned long long *e = r->dbg + 1 + 4 * i; e[0] = ((unsigned long long)tag << 56) | (unsigned long long)(a & 0xffffffffffffffll); e[1] = __float_as_uint(b); e[2] = __float_as_uint(c); e[3] = __float_as_uint(d); }
-#else
-	(void)v; (void)tag; (void)a; (void)b; (void)c; (void)d;
-#endif
-}
+VDL2_HD void ref_debug_log(const ChanView &v, int tag, int64_t a, float b, float c, float d) { (void)v; (void)tag; (void)a; (void)b; (void)c; (void)d; }
 
 // the referee's raw-input history: `n` samples (sb bytes each) from src go to the ring at sample position pos (modulo cap samples)
 __global__ void k_ref_hist(const uint8_t *src, uint64_t n, uint8_t *ring, uint64_t pos, uint64_t cap, int sb) {
@@ -367,7 +353,6 @@ VDL2_HD bool ref_window_done(const ChanView &v, int64_t n_lo, int64_t n_hi) {
 }
 VDL2_HD __attribute__((always_inline)) bool ref_exact_window(const ChanView &v, int64_t n_lo, int64_t n_hi, void *scratch, int kind) {
 #if VDL2_DEVICE_PASS
-	if(v.ref && !((v.ref->kinds >> kind) & 1)) return false;
 	(void)scratch;
 	return ref_exact_window_dev(v, n_lo, n_hi, kind);
 #else
@@ -1270,7 +1255,6 @@ struct K4Args {
 	// the next feed's walk stands; else the snapshot is corrected, rq_flag2_next[c] set, and the next feed is stitched once more for
 	// that channel from the corrected snapshot (again = 3, its own rq_flag2).
 	WalkState *ws_tmp; unsigned long long *cnt_tmp; WalkState *ws_snap_next; unsigned long long *cnt_snap_next; uint32_t *rq_flag2, *rq_flag2_next;
-	uint32_t *rq_flag2_next2;  // walk ahead by two feeds: the feed after the next has been walked as well and is stitched once more too (again = 4 for the next feed: into the snapshot the feed after it starts from; 3 for that one)
 	int32_t force_mismatch;    // test hook: every channel walked again is taken to have ended differently (the next feed is redone for it)
 };
 
@@ -1353,20 +1337,17 @@ __global__ __launch_bounds__(256, 4) void k_walk_stitch(K4sArgs s) {
 	// again: 0 the feed's walk; 1 a flagged channel once more, nothing walked after this feed yet (state and counters: the live rows);
 	// 2 the same when the next feed HAS been walked (K4Args: ws_tmp ...); 3 this feed once more for a channel whose start state the
 	// previous feed's second walk has corrected
-	// 4: as 3 when the feed AFTER this one has been walked too (walk ahead by two): the end state and counters go where that feed starts
-	// from (its snapshot: ws_snap_next), and it is stitched once more itself (3; its flag was set together with this feed's); 5: as 3,
-	// as the second feed behind the corrected one (launch kind 10: ref_entry_visible())
 	const int mode = s.again;
 	if((mode == 1 || mode == 2) && !a.rq_flag[c]) return;
-	if(mode >= 3 && !a.rq_flag2[c]) return;
+	if(mode == 3 && !a.rq_flag2[c]) return;
 	StitchLds &lds = reinterpret_cast<StitchLds *>(k4_lds)[wave];
-	// (launch kinds, ref_entry_visible(): a.ref_launch is kind 1; stitch 2, walk again 4, the corrected feed's second walk 9 / 10)
-	ChanView v{ a.y + (size_t)c * a.cap, a.pf + (size_t)c * a.cap, a.cand + (size_t)c * (a.cap >> 6), a.mask, a.ref, c, a.ref_launch + (mode == 0 ? 1u : mode == 5 ? 9u : mode >= 3 ? 8u : 3u), mode ? nullptr : a.rq, a.rq_n, a.rq_cap, a.rq_flag,
-	            // (mode 3, 4, 5: this feed's check may not have run yet - no speculative walk that noted decisions is adopted: spec_requests_stand() without a list)
+	// (launch kinds, ref_entry_visible(): a.ref_launch is kind 1; stitch 2, walk again 4, the corrected feed's second walk 9)
+	ChanView v{ a.y + (size_t)c * a.cap, a.pf + (size_t)c * a.cap, a.cand + (size_t)c * (a.cap >> 6), a.mask, a.ref, c, a.ref_launch + (mode == 0 ? 1u : mode == 3 ? 8u : 3u), mode ? nullptr : a.rq, a.rq_n, a.rq_cap, a.rq_flag,
+	            // (mode 3: this feed's check may not have run yet - no speculative walk that noted decisions is adopted: spec_requests_stand() without a list)
 	            (a.rq_bad && mode < 3) ? a.rq_bad + c : nullptr, a.ref_pre != 0 };
 	EvalLog lg{ a.log + (size_t)c * a.cap_log, a.nlog + c };
-	WalkState *gstate = mode == 2 ? &a.ws_tmp[c] : mode == 4 ? &a.ws_snap_next[c] : &a.ws[c];
-	unsigned long long *cnt = (mode == 2 ? a.cnt_tmp : mode == 4 ? a.cnt_snap_next : a.cnt) + (size_t)c * kNumCounters;
+	WalkState *gstate = mode == 2 ? &a.ws_tmp[c] : &a.ws[c];
+	unsigned long long *cnt = (mode == 2 ? a.cnt_tmp : a.cnt) + (size_t)c * kNumCounters;
 	stitch_channel(c, a.freq[c], a.max_ppm, a.ppm_thr[c], s.k0, s.seglen, s.nseg, a.k_end, *a.tab, v, gstate, cnt,
 	               a.bursts + (size_t)c * a.cap_bursts_chan, a.cap_bursts_chan, a.nb_chan + c, a.ctl, lg,
 	               s.spec + (size_t)c * s.spec_stride, lds.sh, lds.ss, s.seg_stats + 2 * c, WalkSnap{ (a.rq || mode) ? a.ws_snap : nullptr, a.cnt_snap }, mode != 0);
@@ -1379,11 +1360,11 @@ __global__ __launch_bounds__(256, 4) void k_walk_stitch(K4sArgs s) {
 		if(lane == 0) same = walk_state_equal(a.ws_tmp[c], a.ws_snap_next[c]) && !a.force_mismatch;
 		if(lane < kNumCounters) same = same && cnt[lane] == a.cnt_snap_next[(size_t)c * kNumCounters + lane];
 		if(__any(!same)) {
-			if(lane == 0) { a.ws_snap_next[c] = a.ws_tmp[c]; a.rq_flag2_next[c] = 1u; if(a.rq_flag2_next2) a.rq_flag2_next2[c] = 1u; atomicAdd(a.ref->stats + 8, 1u); }
+			if(lane == 0) { a.ws_snap_next[c] = a.ws_tmp[c]; a.rq_flag2_next[c] = 1u; atomicAdd(a.ref->stats + 8, 1u); }
 			if(lane < kNumCounters) a.cnt_snap_next[(size_t)c * kNumCounters + lane] = cnt[lane];
 		}
 	}
-	if(mode >= 3 && (threadIdx.x & 63) == 0) a.rq_flag2[c] = 0u;
+	if(mode == 3 && (threadIdx.x & 63) == 0) a.rq_flag2[c] = 0u;
 }
 
 struct K4bArgs {
@@ -1527,7 +1508,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 			const int64_t in_end = ps0[npiece - 1] + pn[npiece - 1];
 			if(n_lo < 0) n_lo = 0;
 			if(kind == REF_STALE) kind = REF_CANDIDATE;                  // (asked for by the candidate search: counted and switched with it)
-			bool go = n_hi >= n_lo && ((rp->kinds >> kind) & 1);
+			bool go = n_hi >= n_lo;
 			if(go) {
 				const int64_t last = in_end / os - 1;
 				n_lo &= ~255ll;

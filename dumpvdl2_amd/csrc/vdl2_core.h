@@ -584,7 +584,7 @@ constexpr int   kRefPre = 156, kRefPost = 96;   // a marginal candidate at n: ev
 // the stretch [n_lo, n_hi] of the channel's decimated stream becomes the reference's own; wave-uniform call, `scratch`: >= 2 KiB of
 // LDS the caller can spare.  false: not possible (no referee, or the raw input is no longer held) - the caller keeps its decision.
 VDL2_HD void ref_debug_log(const ChanView &v, int tag, int64_t a, float b, float c, float d);   // development aid (a no-op unless the build provides one)
-enum { REF_CANDIDATE = 0, REF_HEADER = 1, REF_SYMBOLS = 2, REF_STALE = 3 };   // who asks (statistics; a test hook can switch a kind off)
+enum { REF_CANDIDATE = 0, REF_HEADER = 1, REF_SYMBOLS = 2, REF_STALE = 3 };   // who asks (statistics)
 // a decision taken on the channeliser's samples although it lies within the margin (optimistic mode)
 struct RefReq {
 	int32_t  chan, kind;               // REF_CANDIDATE / REF_HEADER

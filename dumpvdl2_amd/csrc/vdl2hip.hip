@@ -64,10 +64,7 @@ static uint32_t defer_scans_for(int64_t D, int C) {
 // The streams of a receiver that is destroyed go to a pool (per device) and the next receiver takes them over: the runtime's mapping
 // of streams to queues depends on every stream the process has created so far, and a receiver made after a hundred others had come
 // and gone ran 30-60 % slower than the same receiver in a fresh process (bench.py's secondary workloads, round 6).
-#ifndef VDL2_SIDE_PRE
-#define VDL2_SIDE_PRE 3
-#endif
-constexpr int kSidePre = VDL2_SIDE_PRE, kSideBurst = 2;
+constexpr int kSidePre = 3, kSideBurst = 2;
 constexpr int kSlots = VDL2HIP_MAX_DRAIN_LAG + 1;   // feeds in flight (vdl2hip_set_drain_lag: at most kSlots - 1 undelivered).  Six: a feed's way through the device of a receiver of few channels - front 1 ms, the scans ahead of the walk 1.5, walk, the next feed's walk (the second walks are queued behind it), burst decoder and its scans 1.5-2.5 - is four to six fronts long (rank-sized receivers, walk ahead: 2.22 / 1.46 / 1.56 ms per step with four slots, 1.76 / 1.29 / 1.45 with six; with 256 channels it is three fronts and four slots were enough)
 
 }  // namespace
@@ -81,13 +78,12 @@ struct OutSlot {
 	uint32_t *d_dq = nullptr; ScanReq *d_sq = nullptr;      // referee, long feeds: the bursts that wait for a scan, the stretches they wait for (counts: d_rqn[1], d_rqn[2])
 	RefReq *d_rq = nullptr; uint32_t *d_rqn = nullptr, *d_rqflag = nullptr; RefBad *d_rqbad = nullptr;
 	ScanReq *d_retry = nullptr;            // [3][kRetryScans]: the unmet scans of the scans ahead of the walk / of the check / of the burst decoder (counts: d_rqn[4..6])
-	ScanReq *d_pq = nullptr; hipEvent_t ev_pre = nullptr;      // referee: the stretches around marked candidates, made exact between the front and the walk (count: d_rqn[3])   // referee, optimistic mode: this feed's decisions to check, its "walk again" flags
+	ScanReq *d_pq = nullptr; hipEvent_t ev_pre = nullptr;      // referee: the stretches around marked candidates, made exact between the front and the walk (count: d_rqn[3])
 	OutMail *h_mail = nullptr;             // pinned
-	hipEvent_t done = nullptr, ev_front = nullptr, ev_chan = nullptr, ev_walk = nullptr, ev_nf = nullptr, ev[kNumEv] = {};
+	hipEvent_t done = nullptr, ev_front = nullptr, ev_walk = nullptr, ev_nf = nullptr, ev[kNumEv] = {};
 	bool pending = false, ev_valid = false, fused = false; int ev_level = 0;
 	uint64_t seq = 0;
-	// the burst-rate back end of this feed (K4, K4b, K5, frame finish) still has to be queued: launch_back()
-	bool back_queued = false; int64_t back_D = 0, back_k0 = 0; hipEvent_t ev_k1 = nullptr;
+	int64_t back_D = 0, back_k0 = 0;        // the burst-rate back end of this feed (launch_back, launch_rest): its decimated samples, the first one's number
 	bool k1_timed = false;                 // the channeliser launch of this feed carries start/stop events (not on a cold-start feed: its pieces wait for copies in between)
 	bool prescan = false;                  // referee: the stretches around this feed's marked candidates are scanned ahead of its walk
 	// launch_back() / launch_rest(): the walk and check of this feed are queued, what follows them is not yet (rest_pending); what the
@@ -133,16 +129,11 @@ struct vdl2hip_ctx {
 	NfState *d_nf = nullptr; int64_t *d_scfirst = nullptr, *d_sccum = nullptr;
 	float *d_nfring = nullptr, *d_lpbuf = nullptr; NfFeed *d_nffeed = nullptr; uint32_t cap_log = 0, cap_comb = 0, cap_hist = 0, nf_ring = 0;
 	uint32_t cap_bursts_chan = 0;
-	SpecOut *d_spec[3] = {}; uint32_t *d_segstats = nullptr; int seg_max = 1; int64_t seg_min = 16384;   // segmented walk
+	SpecOut *d_spec[2] = {}; uint32_t *d_segstats = nullptr; int seg_max = 1; int64_t seg_min = 16384;   // segmented walk
 	OutSlot slot[kSlots];                  // per-feed output buffers: the fronts of feeds i+1, i+2 run while feed i's back still fills slot i%kSlots
 	uint64_t feed_no = 0; int drain_lag = 0;
 	hipStream_t stream_pre[kSidePre] = {};        // referee, VDL2HIP_REF_PRESCAN=1: the scans ahead of the walk, a stream per feed in flight (one stream would put them in a row: 4.4 ms each)
 	hipStream_t stream_back = nullptr, stream_nf = nullptr, stream_burst[kSideBurst] = {};   // (a burst stream per feed in flight: a burst decoder that waits for the referee - a scan over a whole burst takes milliseconds - does not hold up the next feed's)
-	// Experiment switches (only read in builds with -DVDL2_EXPERIMENTS, dev/gpu_run.sh; the measured outcomes are in DESIGN 6).
-	// sync_on: 0 = both sync kernels on the front stream (the product); 1 = the exact tier in front of the walk on the walk stream;
-	// 2 = both on a stream of their own (stream_sync), beside the channeliser of the next feed.  tiles_force / k3b_wpl: K1 tiles per
-	// workgroup segment / K3b words per lane instead of the values chosen from the channel count.
-	int sync_on = 0; hipStream_t stream_sync = nullptr; int k3b_wpl = 0, tiles_force = 0; bool show_gaps = false; int ablate = 0;
 	OutCtl ctl_template{};                 // the capacities of a feed's output buffers (the counters are reset on the device: reset_out_ctl)
 	bool pooled = false;                   // its streams are complete and of the product's priorities: they go to the pool when the receiver is destroyed
 	bool avlc_filter = false, failed = false; int debug_force_timeout = 0, debug_force_again = 0;
@@ -151,14 +142,12 @@ struct vdl2hip_ctx {
 	// buffer) while its back end runs; what lies before it - up to ref_T samples: the run-up of the scan + the longest burst - is kept
 	// in a ring (ref_hist), appended to by every feed (its last min(n, ref_T) samples).  ref_pieces: what of the stream the ring holds,
 	// contiguously, newest last: {first absolute sample, count, ring position of the first}.
-	bool referee = true; int ref_kinds = 7; bool ref_prescan = false;   /* VDL2HIP_REF_PRESCAN=1: the stretches around marked candidates are made exact ahead of the walk - a rank-sized shard 4.05 -> 2.88 ms per step, 256 channels 7.2 -> 7.85: for receivers of few channels */ int64_t ref_warm = 3 << 16 /* 196 608: kernels.h */, ref_T = 0; uint8_t *d_refhist = nullptr; uint64_t ref_cap = 0, ref_wp = 0;
+	bool referee = true; bool ref_prescan = false;   /* VDL2HIP_REF_PRESCAN=1: the stretches around marked candidates are made exact ahead of the walk - a rank-sized shard 4.05 -> 2.88 ms per step, 256 channels 7.2 -> 7.85: for receivers of few channels */ int64_t ref_warm = 3 << 16 /* 196 608: kernels.h */, ref_T = 0; uint8_t *d_refhist = nullptr; uint64_t ref_cap = 0, ref_wp = 0;
 	struct HistPiece { int64_t s0, n; uint64_t pos; }; std::vector<HistPiece> ref_pieces;
-	unsigned long long *d_refdbg = nullptr; int ref_dbg_chan = -1;
-	WalkState *d_ws_snap[3] = {}, *d_ws_tmp = nullptr; unsigned long long *d_cnt_snap[3] = {}, *d_cnt_tmp = nullptr; uint32_t rq_cap = 8192; uint32_t sq_alloc = 8192; bool ref_optimistic = true;
-	int walk_ahead = 1; bool walk_ahead_auto = true; double walk_ahead_below = 1.1e8; int debug_force_mismatch = 0;   // launch_back(): the walks of the next feed (1) or the next two (2) do not wait for this feed's check
+	WalkState *d_ws_snap[2] = {}, *d_ws_tmp = nullptr; unsigned long long *d_cnt_snap[2] = {}, *d_cnt_tmp = nullptr; uint32_t rq_cap = 8192; uint32_t sq_alloc = 8192;
+	int walk_ahead = 1; bool walk_ahead_auto = true; double walk_ahead_below = 1.1e8; int debug_force_mismatch = 0;   // launch_back(): the walk of the next feed does not (1) / does (0) wait for this feed's check
 	int ref_retry_mul = 2;                 // a scan that has not met its witness is run again from this many times further back (0: not at all; VDL2HIP_REF_RETRY)
 	RefChan *d_ref[kSlots] = {}; unsigned long long *d_refdone = nullptr; uint32_t *d_refdonen = nullptr, *d_refstats = nullptr; uint8_t *d_mix = nullptr;
-	bool defer_back = false;               // VDL2HIP_BACKEND=deferred: the back end of feed i is queued behind the channeliser of feed i+1 (launch_back)
 	std::vector<uint64_t> statsd_prev;
 	std::vector<HostFrame> queue;
 	int64_t k_total = 0; uint64_t n_total = 0;
@@ -204,16 +193,15 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 	}
 }
 
-static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate);
-static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, struct OutSlot *succ, struct OutSlot *succ2);
+static int launch_back(vdl2hip_ctx *c, OutSlot &sl);
+static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, struct OutSlot *succ);
 static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto);
 // A short feed (fewer than two walk segments' worth of samples; the reference's own 320 000-byte blocks are 4 000): launch_back()
 static bool feed_is_small(const vdl2hip_ctx *c, int64_t D);
 
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
-	if(sl.back_queued) { int r = launch_back(c, sl, nullptr); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: its back end goes now
-	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // ... nor did the walks that its second walks could have been queued behind (it and what is older, oldest first)
+	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
 	HIPCHK(hipEventSynchronize(sl.done));
 	sl.pending = false;
 	if(c->profiling && sl.ev_valid) {
@@ -229,18 +217,6 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 		} else {
 			if(hipEventElapsedTime(&ms, ev[8], ev[9]) == hipSuccess) c->stats.nf_ms += ms;
 			if(hipEventElapsedTime(&ms, ev[10], ev[11]) == hipSuccess) c->stats.burst_ms += ms;
-		}
-		if(c->show_gaps) {   // development: idle time of the front stream between its kernels
-			float g12 = 0, g23 = 0, g31 = -1;
-			if(!sl.fused) { (void)hipEventElapsedTime(&g12, ev[1], ev[2]); (void)hipEventElapsedTime(&g23, ev[3], ev[4]); } else (void)hipEventElapsedTime(&g23, ev[1], ev[4]);
-			OutSlot &pv = c->slot[(sl.seq + kSlots - 1) % kSlots];
-			if(sl.seq > 0 && pv.ev_level >= 2) (void)hipEventElapsedTime(&g31, pv.ev_front, ev[0]);
-			float lat = -1, per = -1, fr = -1, wk = -1, w2d = -1, w2b = -1, bb = -1, b2d = -1, w2n = -1;
-			(void)hipEventElapsedTime(&w2b, ev[7], ev[10]); (void)hipEventElapsedTime(&bb, ev[10], ev[11]); (void)hipEventElapsedTime(&b2d, ev[11], sl.done); (void)hipEventElapsedTime(&w2n, ev[7], ev[8]);
-			fprintf(stderr, "tail feed %llu: walk end -> burst start %.3f (nf start %.3f), burst %.3f, burst end -> done %.3f\n", (unsigned long long)sl.seq, w2b, w2n, bb, b2d);
-			(void)hipEventElapsedTime(&lat, ev[0], sl.done); (void)hipEventElapsedTime(&fr, ev[0], sl.ev_front); (void)hipEventElapsedTime(&wk, sl.ev_front, ev[6]); (void)hipEventElapsedTime(&w2d, ev[7], sl.done);
-			if(sl.seq > 0 && pv.ev_level >= 2) (void)hipEventElapsedTime(&per, pv.ev[0], ev[0]);
-			fprintf(stderr, "gaps feed %llu: K1->K2 %.1f us, K2->K3 %.1f us, K3(prev)->K1 %.1f us | K1 start -> done %.3f ms, front %.3f, front end -> walk start %.3f, walk end -> done %.3f, K1 start (prev) -> K1 start %.3f\n", (unsigned long long)sl.seq, g12 * 1e3, g23 * 1e3, g31 * 1e3, lat, fr, wk, w2d, per);
 		}
 		}
 	}
@@ -309,7 +285,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	OutSlot &sl = c->slot[c->feed_no % kSlots];
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // its buffers are about to be reused
-	hipStream_t st = c->stream, sb_ = c->stream_back;
+	hipStream_t st = c->stream;
 	hipEvent_t *ev = sl.ev;
 	const bool prof = c->profiling != 0, prof_all = c->profiling >= 2;
 
@@ -329,7 +305,6 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		const int64_t ntile = (D + seglen - 1) / seglen;
 		const int groups = (c->C + c->cr - 1) / c->cr, gy = (groups + 3) / 4;
 		int64_t tiles = ntile * gy / 6144; if(tiles < 1) tiles = 1; if(tiles > 8) tiles = 8;
-		if(c->tiles_force) tiles = c->tiles_force;
 		a.tiles = (int)tiles;
 		a.nseg = (int)((ntile + tiles - 1) / tiles);
 	}
@@ -385,8 +360,8 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		ref_dst = c->d_ref[c->feed_no % kSlots];
 		refv.y = c->d_y; refv.cap = c->cap; refv.mask = c->cap - 1; refv.dphi = c->d_dphi; refv.mix = c->d_mix; refv.lut = c->d_lut;
 		refv.A0 = c->lpf.A[0]; refv.A1 = c->lpf.A[1]; refv.A2 = c->lpf.A[2]; refv.B1 = c->lpf.B[1]; refv.B2 = c->lpf.B[2];
-		refv.os = c->os; refv.fmt = c->fmt; refv.warm = c->ref_warm; refv.kinds = c->ref_kinds;
-		refv.done = c->d_refdone; refv.done_n = c->d_refdonen; refv.stats = c->d_refstats; refv.dbg = c->d_refdbg; refv.dbg_chan = c->ref_dbg_chan;
+		refv.os = c->os; refv.fmt = c->fmt; refv.warm = c->ref_warm;
+		refv.done = c->d_refdone; refv.done_n = c->d_refdonen; refv.stats = c->d_refstats;
 		int np = 0;
 		const int64_t blk_s0 = (int64_t)c->n_total, want0 = blk_s0 - c->ref_T;
 		// (at most the two newest pieces matter - an older one ends more than ref_T samples back - and each may wrap once)
@@ -417,16 +392,6 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 			while(c->ref_pieces.size() > 2) c->ref_pieces.erase(c->ref_pieces.begin());
 		}
 	}
-	// deferred mode: the back end of the feed before this one is queued now, behind this feed's channeliser
-	if(c->feed_no > 0) {
-		OutSlot &pv = c->slot[(c->feed_no - 1) % kSlots];
-		if(pv.pending && pv.back_queued) {
-			hipEvent_t gate = nullptr;
-			if(D > 0) { HIPCHK(hipEventRecord(sl.ev_k1, st)); gate = sl.ev_k1; }
-			int r = launch_back(c, pv, gate);
-			if(r != VDL2HIP_OK) return r;
-		}
-	}
 	if(D > 0) {
 		const int64_t k1 = c->k_total + D, nbase = c->k_total & ~63ll;
 		// wavefronts of this feed's burst decoder: each owns kResSlots frame records of the output from the start, so a short block gets few
@@ -436,34 +401,26 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		sl.prescan = c->referee && c->ref_prescan && !feed_is_small(c, D);
 		K3Args k3{ c->d_y, c->d_pf, c->d_cand, c->d_flag, c->d_tab, nbase, k1, c->cap, c->cap - 1, 1, sl.d_ctl, sl.k5_waves, ref_dst, refv, c->cfg.max_ppm, c->d_ppmthr, c->referee ? 1 : 0, sl.d_rqn, sl.d_rqflag, sl.d_rqbad, sl.prescan ? sl.d_pq : nullptr, kPreScans, sl.d_rqflag2 };
 		// The exact tier's stop event doubles as "front of this feed done" (what the walk stream waits for): one queue entry less
-		// on the front stream than a separate hipEventRecord.  (VDL2HIP_SYNC_ON=walk puts the exact tier in front of the walk on
-		// the walk stream, VDL2HIP_SYNC_ON=own both sync kernels on a stream of their own, so that the front stream goes on
-		// with the next feed's channeliser: measured, profiles/r02_sync_kernel_streams.txt.)
-		hipStream_t s3 = c->sync_on == 2 ? c->stream_sync : st;
-		if(c->sync_on == 2) { HIPCHK(hipEventRecord(sl.ev_chan, st)); HIPCHK(hipStreamWaitEvent(s3, sl.ev_chan, 0)); }
-		LAUNCH_EV(k_sync_screen, dim3((unsigned)((k1 - nbase + kK3Tile - 1) / kK3Tile), (unsigned)c->C), dim3(kK3Threads), s3, EV(4), c->sync_on == 1 ? sl.ev_chan : (hipEvent_t) nullptr, k3);
-		hipStream_t sx = c->sync_on == 1 ? sb_ : s3;
-		if(c->sync_on == 1) HIPCHK(hipStreamWaitEvent(sb_, sl.ev_chan, 0));
+		// on the front stream than a separate hipEventRecord.
+		LAUNCH_EV(k_sync_screen, dim3((unsigned)((k1 - nbase + kK3Tile - 1) / kK3Tile), (unsigned)c->C), dim3(kK3Threads), st, EV(4), (hipEvent_t) nullptr, k3);
 		const int64_t nwords = ((k1 + 63) >> 6) - (nbase >> 6);
 		// words per lane of the exact tier: as many as keep >= 8 workgroups per CU (a wavefront with more words amortises its scan,
 		// but the kernel is latency-bound: at 32 channels 1 word per lane - 3 296 workgroups - beat 4 - 832 - by 0.02 ms of a 0.85 ms step,
 		// at 256 channels 4 is as good as any; profiles/r03_k3b_forms.txt)
 		for(int wpl = kK3bWordsPerLane; wpl >= 1; wpl >>= 1) { k3.wpl = wpl; if(((nwords + 256 * wpl - 1) / (256 * wpl)) * c->C >= 2048 || wpl == 1) break; }
-		if(c->k3b_wpl) k3.wpl = c->k3b_wpl;                                   // experiments only (VDL2HIP_K3B_WPL)
 		const int64_t wpb = 256 * k3.wpl;                                      // words per block
 		// (receivers that scan ahead of the walk work out the windows with one or two unwrap decisions within the margin: sync_metric_ref)
-		if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_exact4<true>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), sx, (hipEvent_t) nullptr, sl.ev_front, k3);
-		else LAUNCH_EV(k_sync_exact4<false>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), sx, (hipEvent_t) nullptr, sl.ev_front, k3);
+		if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_exact4<true>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+		else LAUNCH_EV(k_sync_exact4<false>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
 	}
 	if(D <= 0) HIPCHK(hipEventRecord(sl.ev_front, st));
 	if(D > 0) { sl.ev_valid = prof; sl.ev_level = c->profiling; sl.fused = a.fuse != 0; if(sl.k1_timed) c->stats.chan_samples += (uint64_t)D * c->os * c->C; } else sl.k1_timed = false;
-	sl.back_queued = true; sl.back_D = D; sl.back_k0 = c->k_total;
+	sl.back_D = D; sl.back_k0 = c->k_total;
 	sl.pending = true; sl.seq = c->feed_no++;
 	c->k_total += D; c->n_total += nnew;
 	c->stats.feeds++; c->stats.input_samples += nnew;
-	// Eager mode queues this feed's back end right away (it then runs beside the NEXT feed's channeliser); deferred mode leaves it
-	// to the next feed call, which queues it behind its own channeliser (above), or to whoever collects this feed first.
-	if(!c->defer_back) { int r = launch_back(c, sl, nullptr); if(r != VDL2HIP_OK) return r; }
+	// this feed's back end is queued right away: it then runs beside the NEXT feed's channeliser
+	{ int r = launch_back(c, sl); if(r != VDL2HIP_OK) return r; }
 	HIPCHK(hipGetLastError());
 	return VDL2HIP_OK;
 }
@@ -473,18 +430,26 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 //   stream_back   K4   walk(i) -> walk(i+1) -> ...             (each needs the previous one's FSM state)
 //   stream_nf     K4b  noise floor of feed i, after walk(i)    (each needs the previous one's NfState)
 //   stream_burst  K5   bursts of feed i, after walk(i); the frames get their noise-floor figure when K4b(i) is done
-// `gate` (deferred mode): an event of the FOLLOWING feed's front stream - the end of its channeliser - that the walk waits for as
-// well, so that these latency-bound kernels run beside the sync screening (few registers: they fit in beside it) instead of taking
-// workgroup slots from a channeliser (whose four waves per SIMD own the whole register file: every back-end workgroup keeps one
-// channeliser workgroup off its CU for as long as it lives).
 // (the kernel is compiled per sample format)
 static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 	const int nseg = (int)std::min<int64_t>(c->seg_max, D / c->seg_min);
-	return D > 0 && D < 2 * c->seg_min && nseg < 2 && !c->defer_back && c->sync_on == 0;
+	return D > 0 && D < 2 * c->seg_min && nseg < 2;
 }
 #define LAUNCH_SCAN_MULTI(how, ...) do { \
 	if(c->fmt == 1) { if(c->os == 20) how((k_ref_scan_multi<1, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<1, 10>), __VA_ARGS__); else how((k_ref_scan_multi<1, 0>), __VA_ARGS__); } \
 	else { if(c->os == 20) how((k_ref_scan_multi<0, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<0, 10>), __VA_ARGS__); else how((k_ref_scan_multi<0, 0>), __VA_ARGS__); } } while(0)
+// Referee: the listed stretches (`sq`, or the decisions `rq` whose stretches they are; *n of them, at most cap) are made the reference's own,
+// many side by side, and those of them that had not met their witness - a few in ten thousand - are listed in `retry` and scanned again
+// from ref_retry_mul times further back (no list, or ref_retry_mul 0: they are published as they are, counted).  e0 / e1: the first
+// kernel's start and the last one's stop (the test hook's timing).
+static void launch_scans(vdl2hip_ctx *c, hipStream_t st, RefChan *ref, uint32_t launch, const ScanReq *sq, const RefReq *rq, const uint32_t *n, uint32_t cap, int64_t k_end,
+                         ScanReq *retry, uint32_t *retry_n, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+	const int rty = retry ? c->ref_retry_mul : 0;
+	LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3((cap + kScanLanes - 1) / kScanLanes), dim3(64 * kScanWaves), 0, st, e0, rty ? (hipEvent_t) nullptr : e1, 0, ref, launch,
+	                  sq, rq, n, cap, k_end, rty ? retry : (ScanReq *) nullptr, retry_n, kRetryScans, 1);
+	if(rty) LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, st, (hipEvent_t) nullptr, e1, 0, ref, launch,
+	                  (const ScanReq *)retry, (const RefReq *) nullptr, (const uint32_t *)retry_n, kRetryScans, k_end, (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty);
+}
 // The walk of feed i + 1 does not wait for the check of feed i ("walk ahead").  walk(i + 1) needs the state walk(i) leaves, and that
 // state is final only when the decisions walk(i) noted have been checked - behind a scan of 1.5 ms that no hardware shortens; with a
 // front of 1 ms (a rank's 32 channels) that chain was the step.  But the check confirms the walk all but always.  So:
@@ -496,23 +461,28 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 //   redo(i+1): the flagged channels are stitched once more over feed i+1 from the corrected snapshot, into the live rows.
 // stitch(i+2) follows on the same stream: it starts from a state in which feeds <= i are checked - the check of feed i overlaps one
 // walk and one front.  launch_back() queues the walk and the check; launch_rest() - called when the NEXT feed's walk has been queued,
-// or, if nothing follows (a drain, a short feed, the old schedule with VDL2HIP_WALK_AHEAD=0), at once with `succ` = nullptr: again(i)
+// or, if nothing follows (a drain, a short feed, the old schedule: walk_ahead_of() 0), at once with `succ` = nullptr: again(i)
 // then works on the live rows as it always did - queues the second walks and everything behind them: noise floor, burst decoder,
 // frame finish, the copy of the control block.
-static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ, OutSlot *succ2);
+static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ);
+// k_walk_stitch over a feed's segments and speculative walks (`again`: the kernel's modes), a channel per wavefront
+static void launch_stitch(vdl2hip_ctx *c, hipStream_t st, const OutSlot &sl, const K4Args &k4, int again, hipEvent_t e1 = nullptr) {
+	K4sArgs k4s{ k4, sl.d_spec_of, (uint32_t)(3 * (c->seg_max - 1)), sl.nseg, sl.back_k0, sl.seglen, c->d_segstats, again };
+	hipExtLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((c->C + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), st, (hipEvent_t) nullptr, e1, 0, k4s);
+}
 
 // Does the walk of the feed after this one go ahead of this feed's check?  It pays when a feed's front is shorter than a check (a scan:
 // 2.3 ms) - a front is 6.2 ms for 1.68 M decimated samples of 256 channels, 1.45e-8 ms per channel-sample: receivers of 16-64 channels
 // on the bench's 16 s blocks (rounds 6a/b), and ANY receiver of >= 16 channels on feeds of a second or so - the drop-in adapter's
 // sixteen collected 320 000-byte blocks at 256 channels: 0.155 -> 0.10 ms per block (profiles/r06_block_batch.txt).  With fewer than
 // 16 channels the walk itself is longer than the front and the second walks' extra launches cost more than they save (1.22 against
-// 1.11 ms at 8).  VDL2HIP_WALK_AHEAD / the debug option fix the depth for every feed.
+// 1.11 ms at 8).  The debug option "walk_ahead" fixes the choice for every feed.
 static int walk_ahead_of(const vdl2hip_ctx *c, int64_t D) {
 	if(!c->walk_ahead_auto) return c->walk_ahead;
 	return c->C >= 16 && (double)D * (double)c->C < c->walk_ahead_below ? 1 : 0;
 }
 
-static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
+static int launch_back(vdl2hip_ctx *c, OutSlot &sl) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const int wa = walk_ahead_of(c, D);
 	// long feeds: the walk runs in speculative segments (vdl2_core.h), one wavefront per (channel, segment, grid phase)
@@ -520,33 +490,29 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
 	// A short feed (fewer than two walk segments' worth of samples; the reference's own 320 000-byte blocks are 4 000) is a chain of kernels that each run for
 	// microseconds: its whole back end goes onto the FRONT stream, behind its own sync kernels - no event hand-offs between streams -
 	// with the three noise-floor passes as one kernel.  Whoever follows on the front stream is then behind it anyway.
-	// (... and only when both sync kernels ARE on the front stream - sync_on 0, the product; the experiment builds' other placements hand the
-	// candidate bitmap over with an event the short cut does not wait for)
 	const bool small = feed_is_small(c, D);
 	hipStream_t sb_ = small ? c->stream : c->stream_back;
 	hipEvent_t *ev = sl.ev;
 	const bool prof_all = sl.ev_valid && sl.ev_level >= 2;
-	sl.back_queued = false; sl.small = small; sl.has_chk = false; sl.nseg = 1; sl.seglen = D;
+	sl.small = small; sl.has_chk = false; sl.nseg = 1; sl.seglen = D;
 	OutSlot &pv = c->slot[(sl.seq + kSlots - 1) % kSlots];
 	// (short feeds too, since round 6: a block with a decision within the margin - one in three of the reference's own 320 000-byte
 	// blocks at 256 channels - used to wait for a scan by the walker's own wavefront, 3.1 ms; noted, scanned side by side (1.5 ms for all
 	// of them) and checked, on the front stream like the rest of a short feed's back end, it is 1.34 -> 0.8 ms per block on average)
-	const bool opt = c->referee && c->ref_optimistic && D > 0;
+	const bool opt = c->referee && D > 0;
 	const uint32_t rq_cap = small ? std::min<uint32_t>(c->rq_cap, 16u * kScanLanes) : c->rq_cap;      // (a short feed: few requests, small grids - it queues these kernels whether or not it notes anything)
-	// does this feed's walk go ahead of the check of the feed(s) before?  (long feeds with a check, segmented walks)  If not, what is
+	// does this feed's walk go ahead of the check of the feed before?  (long feeds with a check, segmented walks)  If not, what is
 	// still waiting for a successor's walk is queued now, oldest first
-	const bool ahead = wa && opt && nseg >= 2 && !gate && sl.seq > 0 && pv.pending && pv.rest_pending && pv.has_chk && pv.nseg >= 2;
+	const bool ahead = wa && opt && nseg >= 2 && sl.seq > 0 && pv.pending && pv.rest_pending && pv.has_chk && pv.nseg >= 2;
 	if(!ahead) { int r = flush_rest(c, nullptr); if(r != VDL2HIP_OK) return r; }
 	if(small) {
 		// the walker, the noise floor and the burst list carry state from feed to feed: wait for a predecessor whose back end is on the other streams
-		if(sl.seq > 0 && pv.pending && !pv.small && !pv.back_queued) HIPCHK(hipStreamWaitEvent(sb_, pv.done, 0));
+		if(sl.seq > 0 && pv.pending && !pv.small) HIPCHK(hipStreamWaitEvent(sb_, pv.done, 0));
 	} else {
 		HIPCHK(hipStreamWaitEvent(sb_, sl.ev_front, 0));
-		if(gate) HIPCHK(hipStreamWaitEvent(sb_, gate, 0));
 	}
 	if(D <= 0) hipLaunchKernelGGL(k_reset_ctl, dim3(1), dim3(1), 0, sb_, sl.d_ctl, 0u);     // (a feed with a front has had it reset by its last sync kernel)
 	hipStream_t sp_ = small ? c->stream : c->stream_pre[sl.seq % kSidePre];
-	const int rty = c->ref_retry_mul;
 	if(D > 0 && sl.prescan) {
 		// Referee: the stretches the exact sync tier has listed (around its marked candidates) are made the reference's own NOW, beside
 		// the next feed's front and off the walk stream - the walk of this feed waits for them, the walk of the next one does not
@@ -554,20 +520,20 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
 		// (on a stream of its own: behind this feed's noise floor - which waits for the walk - the next feed's scans would wait for this
 		// feed's whole walk chain)
 		if(!small) HIPCHK(hipStreamWaitEvent(sp_, sl.ev_front, 0));
-		LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(kPreScans / kScanLanes), dim3(64 * kScanWaves), 0, sp_, c->d_ref[sl.seq % kSlots], (uint32_t)(16 * sl.seq + 8),
-		                  (const ScanReq *)sl.d_pq, (const RefReq *) nullptr, (const uint32_t *)(sl.d_rqn + 3), kPreScans, (int64_t)(k0 + D), rty ? sl.d_retry : (ScanReq *) nullptr, sl.d_rqn + 4, kRetryScans, 1);
-		// (... and those of them that had not met their witness - a few in ten thousand - again, from further back)
-		if(rty) LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, sp_, c->d_ref[sl.seq % kSlots], (uint32_t)(16 * sl.seq + 8),
-		                  (const ScanReq *)sl.d_retry, (const RefReq *) nullptr, (const uint32_t *)(sl.d_rqn + 4), kRetryScans, (int64_t)(k0 + D), (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty);
+		launch_scans(c, sp_, c->d_ref[sl.seq % kSlots], (uint32_t)(16 * sl.seq + 8), sl.d_pq, nullptr, sl.d_rqn + 3, kPreScans, k0 + D, sl.d_retry, sl.d_rqn + 4);
 		if(!small) { HIPCHK(hipEventRecord(sl.ev_pre, sp_)); HIPCHK(hipStreamWaitEvent(sb_, sl.ev_pre, 0)); }
 	}
 	if(D > 0) {
 		const int64_t k1 = k0 + D;
-		const int par = (int)(sl.seq % 3);        // feed i's snapshot and speculative walks are still needed when feeds i + 1 and i + 2 are walked: three of each
+		// Two sets of snapshots and speculative walks.  With the next feed's walk at most ONE feed ahead the walk stream runs
+		// ... S(i+1) again(i) redo(i+1) S(i+2) again(i+1) redo(i+2) ... (S is queued below, then the feed before is flushed): S(i+2) is the
+		// first writer of set i mod 2 after S(i), and the last reader of that set, again(i), is ahead of it on the same stream; check(i) on
+		// the scan stream reads neither snapshots nor speculative walks (k_ref_verify -> ref_verify() is handed none).
+		const int par = (int)(sl.seq % 2);
 		sl.k4 = K4Args{ c->d_y, c->d_pf, c->d_cand, c->d_tab, c->d_ws, c->d_wcnt, sl.d_bursts, sl.d_nbchan, c->cap_bursts_chan, sl.d_ctl, c->d_freq,
 		           sl.d_log, sl.d_nlog, c->cap_log, k1, c->cfg.max_ppm, c->cap, c->cap - 1, c->chan_first, c->C, c->d_ppmthr, c->referee ? c->d_ref[sl.seq % kSlots] : nullptr, (uint32_t)(16 * sl.seq + 1),
 		           opt ? sl.d_rq : nullptr, sl.d_rqn, rq_cap, sl.d_rqflag, c->d_ws_snap[par], c->d_cnt_snap[par], sl.d_rqbad, sl.prescan ? 1 : 0, c->debug_force_again,
-		           c->d_ws_tmp, c->d_cnt_tmp, nullptr, nullptr, sl.d_rqflag2, nullptr, nullptr, c->debug_force_mismatch };   // (a short feed's walk notes and is checked like a long one's since round 6a: `opt`)
+		           c->d_ws_tmp, c->d_cnt_tmp, nullptr, nullptr, sl.d_rqflag2, nullptr, c->debug_force_mismatch };   // (a short feed's walk notes and is checked like a long one's since round 6a: `opt`)
 		const K4Args &k4 = sl.k4;
 		sl.d_spec_of = c->d_spec[par];
 		if(nseg >= 2) {
@@ -575,10 +541,8 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
 			nseg = (int)((D + sl.seglen - 1) / sl.seglen);
 			sl.nseg = nseg;
 			K4sArgs k4s{ k4, sl.d_spec_of, (uint32_t)(3 * (c->seg_max - 1)), nseg, k0, sl.seglen, c->d_segstats, 0 };
-			if(!(c->ablate & 1))
 			LAUNCH_EV(k_walk_spec, dim3((unsigned)((1 + 3 * (nseg - 1) + kWalkWaves - 1) / kWalkWaves), (unsigned)c->C), dim3(64 * kWalkWaves), sb_, EV(6), (hipEvent_t) nullptr, k4s);
-			if(!(c->ablate & 1))
-			hipExtLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((c->C + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), sb_, (hipEvent_t) nullptr, EV(7), 0, k4s);
+			launch_stitch(c, sb_, sl, k4, 0, EV(7));
 		} else {
 			LAUNCH_EV(k_walk, dim3((unsigned)c->C), dim3(64), sb_, EV(6), EV(7), k4);
 		}
@@ -591,16 +555,13 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
 			sl.has_chk = true;
 			hipStream_t sc_ = wa ? sp_ : sb_;
 			if(sc_ != sb_) { HIPCHK(hipEventRecord(sl.ev_stitch, sb_)); HIPCHK(hipStreamWaitEvent(sc_, sl.ev_stitch, 0)); }
-			LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(rq_cap / kScanLanes), dim3(64 * kScanWaves), 0, sc_, k4.ref, k4.ref_launch - 1u, (const ScanReq *) nullptr, (const RefReq *)k4.rq, (const uint32_t *)k4.rq_n, rq_cap, k1,
-			                  rty ? sl.d_retry + kRetryScans : (ScanReq *) nullptr, sl.d_rqn + 5, kRetryScans, 1);
-			if(rty) LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, sc_, k4.ref, k4.ref_launch - 1u, (const ScanReq *)(sl.d_retry + kRetryScans), (const RefReq *) nullptr, (const uint32_t *)(sl.d_rqn + 5), kRetryScans, k1,
-			                  (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty);
+			launch_scans(c, sc_, k4.ref, k4.ref_launch - 1u, nullptr, k4.rq, k4.rq_n, rq_cap, k1, sl.d_retry + kRetryScans, sl.d_rqn + 5);
 			hipLaunchKernelGGL(k_ref_verify, dim3(small ? 64 : 1024), dim3(64), 0, sc_, k4);
 			HIPCHK(hipEventRecord(sl.ev_chk, sc_));
 		}
 	}
 	sl.rest_pending = true;
-	// the feeds whose second walks have now waited for as many successors' walks as they may (walk_ahead: 1 or 2) ...
+	// the feeds whose second walks have now waited for the one successor's walk that they may (walk ahead), or for none ...
 	for(;;) {
 		OutSlot *old = nullptr;
 		for(auto &x : c->slot) if(x.pending && x.rest_pending && (!old || x.seq < old->seq)) old = &x;
@@ -608,26 +569,25 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl, hipEvent_t gate) {
 		int r = flush_rest(c, old); if(r != VDL2HIP_OK) return r;
 	}
 	// does the NEXT feed's walk get the chance to go ahead of this feed's check?  Not if there is nothing to check, nor in the old schedule
-	if(!(wa && sl.has_chk && sl.nseg >= 2 && !gate && !c->defer_back)) return flush_rest(c, nullptr);
+	if(!(wa && sl.has_chk && sl.nseg >= 2)) return flush_rest(c, nullptr);
 	HIPCHK(hipGetLastError());
 	return VDL2HIP_OK;
 }
 
 // The feeds whose walk and check are queued and the rest is not (rest_pending), oldest first, up to and including `upto` (nullptr: all
-// of them): each with the one or two feeds behind it whose walks are queued as its successors (their walks went ahead of its check).
+// of them): each with the feed behind it, if that one's walk is queued, as its successor (its walk went ahead of this feed's check).
 static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto) {
 	for(;;) {
 		OutSlot *old = nullptr;
 		for(auto &x : c->slot) if(x.pending && x.rest_pending && (!old || x.seq < old->seq)) old = &x;
 		if(!old || (upto && old->seq > upto->seq)) return VDL2HIP_OK;
-		OutSlot *s1 = &c->slot[(old->seq + 1) % kSlots], *s2 = &c->slot[(old->seq + 2) % kSlots];
+		OutSlot *s1 = &c->slot[(old->seq + 1) % kSlots];
 		if(!(s1->pending && s1->rest_pending && s1->seq == old->seq + 1)) s1 = nullptr;
-		if(!(s1 && s2->pending && s2->rest_pending && s2->seq == old->seq + 2)) s2 = nullptr;
-		int r = launch_rest(c, *old, s1, s2); if(r != VDL2HIP_OK) return r;
+		int r = launch_rest(c, *old, s1); if(r != VDL2HIP_OK) return r;
 	}
 }
 
-static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ, OutSlot *succ2) {
+static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const bool small = sl.small;
 	hipStream_t sb_ = small ? c->stream : c->stream_back, sn_ = small ? c->stream : c->stream_nf, s5_ = small ? c->stream : c->stream_burst[sl.seq % kSideBurst];
@@ -635,33 +595,21 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ, OutSlot *succ
 	hipEvent_t *ev = sl.ev;
 	const bool prof_all = sl.ev_valid && sl.ev_level >= 2;
 	sl.rest_pending = false;
-	const int rty = c->ref_retry_mul;
 	if(D > 0 && sl.has_chk) {
 		// the (rare) channel one of whose decisions did not stand is stitched again
 		HIPCHK(hipStreamWaitEvent(sb_, sl.ev_chk, 0));
 		K4Args k4 = sl.k4;
-		if(succ) { k4.ws_snap_next = succ->k4.ws_snap; k4.cnt_snap_next = succ->k4.cnt_snap; k4.rq_flag2_next = succ->d_rqflag2; k4.rq_flag2_next2 = succ2 ? succ2->d_rqflag2 : nullptr; }
-		if(sl.nseg >= 2) {
-			K4sArgs k4a{ k4, sl.d_spec_of, (uint32_t)(3 * (c->seg_max - 1)), sl.nseg, k0, sl.seglen, c->d_segstats, succ ? 2 : 1 };
-			hipExtLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((c->C + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), sb_, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0, k4a);
-		} else hipLaunchKernelGGL(k_walk_again, dim3((unsigned)c->C), dim3(64), 0, sb_, k4);      // (never with a successor: launch_back)
+		if(succ) { k4.ws_snap_next = succ->k4.ws_snap; k4.cnt_snap_next = succ->k4.cnt_snap; k4.rq_flag2_next = succ->d_rqflag2; }
+		if(sl.nseg >= 2) launch_stitch(c, sb_, sl, k4, succ ? 2 : 1);
+		else hipLaunchKernelGGL(k_walk_again, dim3((unsigned)c->C), dim3(64), 0, sb_, k4);      // (never with a successor: launch_back)
 	}
 	if(!small) {
 		HIPCHK(hipEventRecord(sl.ev_walk, sb_));
 		HIPCHK(hipStreamWaitEvent(sn_, sl.ev_walk, 0));
 		HIPCHK(hipStreamWaitEvent(s5_, sl.ev_walk, 0));
 	}
-	if(succ) {
-		// ... and the next feed once more for the channels whose start state that has corrected (none, all but always: the kernel looks at the flags and ends)
-		// (walk ahead by two: the feed after it has been walked as well - the next feed's end state then goes into THAT feed's snapshot, and it is stitched once more too)
-		K4sArgs k4r{ succ->k4, succ->d_spec_of, (uint32_t)(3 * (c->seg_max - 1)), succ->nseg, succ->back_k0, succ->seglen, c->d_segstats, succ2 ? 4 : 3 };
-		if(succ2) { k4r.k.ws_snap_next = succ2->k4.ws_snap; k4r.k.cnt_snap_next = succ2->k4.cnt_snap; }
-		hipExtLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((c->C + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), sb_, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0, k4r);
-		if(succ2) {
-			K4sArgs k4q{ succ2->k4, succ2->d_spec_of, (uint32_t)(3 * (c->seg_max - 1)), succ2->nseg, succ2->back_k0, succ2->seglen, c->d_segstats, 5 };
-			hipExtLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((c->C + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), sb_, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0, k4q);
-		}
-	}
+	// ... and the next feed once more for the channels whose start state that has corrected (none, all but always: the kernel looks at the flags and ends)
+	if(succ) launch_stitch(c, sb_, *succ, succ->k4, 3);
 	if(D > 0) {
 		K4bArgs k4b{ c->d_y, c->d_nf, sl.d_log, sl.d_nlog, c->d_scfirst, c->d_sccum, c->d_nffeed, c->d_lpbuf, c->d_nfring, c->nf_ring - 1,
 		             c->cap, c->cap - 1, c->cap_log, c->cap_comb, c->cap_hist, c->C };
@@ -671,7 +619,6 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ, OutSlot *succ
 		} else {
 			hipExtLaunchKernelGGL(k_nf_prepare, dim3(nf_grid), dim3(64 * kNfWaves), nf_lds, sn_, EV(8), (hipEvent_t) nullptr, 0, k4b);
 			const unsigned ngrp = (unsigned)std::min<uint64_t>(64, (c->cap_hist + kNfGroup * kNfWaves - 1) / (kNfGroup * kNfWaves));   // workgroups per channel
-			if(!(c->ablate & 2))      // (experiment builds: what does a stage cost the front by running beside it?)
 			hipLaunchKernelGGL(k_nf_replay, dim3(ngrp, (unsigned)c->C), dim3(64 * kNfWaves), nf_lds, sn_, k4b);
 			hipExtLaunchKernelGGL(k_nf_finish, dim3(nf_grid), dim3(64 * kNfWaves), nf_lds, sn_, (hipEvent_t) nullptr, EV(9), 0, k4b);
 			HIPCHK(hipEventRecord(sl.ev_nf, sn_));
@@ -681,18 +628,15 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ, OutSlot *succ
 		// referee: a burst that needs a scan is listed by the first pass, the scans run side by side, a second pass decodes the listed bursts.
 		// (Short feeds too, since round 6c: their burst wavefronts used to scan on the spot - a weak burst with ten marked symbols held its
 		// block for 22 ms, profiles/r06_weak_bursts.txt; their lists and the grids that serve them are a sixteenth of a long feed's.)
-		const bool defer5 = c->referee && c->ref_optimistic && ((c->ref_kinds >> REF_SYMBOLS) & 1);
+		const bool defer5 = c->referee;
 		const uint32_t sq_cap = small ? kDeferScans / 16 : std::min(c->sq_alloc, defer_scans_for(D, c->C)), dq_cap = sq_cap / 2;
 		if(defer5) k5.df = BurstDefer{ sl.d_dq, sl.d_rqn + 1, dq_cap, sl.d_sq, sl.d_rqn + 2, sq_cap, 1 };
-		if(c->ablate & 4) k5.nchan = 0;      // (experiment builds: no bursts to decode)
 		const unsigned k5_lds = (unsigned)((sizeof(BurstShared) + 4 * (kK5MaxChan + 1)) * kBurstWaves);
 		hipEvent_t ev_last5 = defer5 ? (hipEvent_t) nullptr : EV(11);
 		if(small) hipExtLaunchKernelGGL(k_nf_burst, dim3(nf_grid + sl.k5_waves / kBurstWaves), dim3(64 * kNfWaves), std::max(nf_lds, k5_lds), s5_, EV(8), ev_last5, 0, k4b, k5, (uint32_t)nf_grid);
 		else hipExtLaunchKernelGGL(k_burst, dim3(sl.k5_waves / kBurstWaves), dim3(64 * kBurstWaves), k5_lds, s5_, EV(10), ev_last5, 0, k5);
 		if(defer5) {
-			LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(sq_cap / kScanLanes), dim3(64 * kScanWaves), 0, s5_, k5.ref, (uint32_t)(16 * sl.seq + 6), (const ScanReq *)sl.d_sq, (const RefReq *) nullptr, (const uint32_t *)(sl.d_rqn + 2), sq_cap, (int64_t)(k0 + D), rty ? sl.d_retry + 2 * kRetryScans : (ScanReq *) nullptr, sl.d_rqn + 6, kRetryScans, 1);
-			if(rty) LAUNCH_SCAN_MULTI(hipLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, s5_, k5.ref, (uint32_t)(16 * sl.seq + 6), (const ScanReq *)(sl.d_retry + 2 * kRetryScans), (const RefReq *) nullptr, (const uint32_t *)(sl.d_rqn + 6), kRetryScans, (int64_t)(k0 + D),
-			                  (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty);
+			launch_scans(c, s5_, k5.ref, (uint32_t)(16 * sl.seq + 6), sl.d_sq, nullptr, sl.d_rqn + 2, sq_cap, k0 + D, sl.d_retry + 2 * kRetryScans, sl.d_rqn + 6);
 			K5Args k5b = k5; k5b.df.pass = 2; k5b.ref_launch = (uint32_t)(16 * sl.seq + 7);
 			hipExtLaunchKernelGGL(k_burst, dim3(std::max(1u, dq_cap / kBurstWaves / 4)), dim3(64 * kBurstWaves), k5_lds, s5_, (hipEvent_t) nullptr, EV(11), 0, k5b);
 		}
@@ -754,7 +698,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	OnDevice dev_guard(c);
 	if(c->stream) (void)hipStreamSynchronize(c->stream);
 	void *ptrs[] = { c->d_bf, c->d_lut, c->d_tab, c->d_dphi, c->d_freq, c->d_ppmthr, c->d_carry[0], c->d_carry[1], c->d_y, c->d_pf,
-	                 c->d_cand, c->d_flag, c->d_segend, c->d_qpow, c->d_tcarry[0], c->d_tcarry[1], c->d_ws, c->d_cnt, c->d_nf, c->d_scfirst, c->d_sccum, c->d_nfring, c->d_lpbuf, c->d_nffeed, c->d_spec[0], c->d_spec[1], c->d_spec[2], c->d_segstats, c->d_acnt, c->d_segpub, c->d_synctmo };
+	                 c->d_cand, c->d_flag, c->d_segend, c->d_qpow, c->d_tcarry[0], c->d_tcarry[1], c->d_ws, c->d_cnt, c->d_nf, c->d_scfirst, c->d_sccum, c->d_nfring, c->d_lpbuf, c->d_nffeed, c->d_spec[0], c->d_spec[1], c->d_segstats, c->d_acnt, c->d_segpub, c->d_synctmo };
 	for(auto &sl : c->slot) {
 		void *q[] = { sl.d_bursts, sl.d_nbchan, sl.d_frames, sl.d_pool, sl.d_frames_out, sl.d_pool_out, sl.d_mail, sl.d_log, sl.d_nlog, sl.d_rq, sl.d_rqn, sl.d_rqflag, sl.d_dq, sl.d_sq, sl.d_rqbad, sl.d_pq, sl.d_rqflag2, sl.d_retry };
 		for(void *p : q) if(p) (void)hipFree(p);
@@ -765,21 +709,18 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
 		if(sl.ev_front) (void)hipEventDestroy(sl.ev_front);
 		if(sl.ev_pre) (void)hipEventDestroy(sl.ev_pre);
-		if(sl.ev_chan) (void)hipEventDestroy(sl.ev_chan);
 		if(sl.ev_nf) (void)hipEventDestroy(sl.ev_nf);
-		if(sl.ev_k1) (void)hipEventDestroy(sl.ev_k1);
 		for(int i = 0; i < kNumEv; i++) if(sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
 	}
 	if(c->h_stage) (void)hipHostFree(c->h_stage);
 	for(auto &p : c->d_in) if(p) (void)hipFree(p);
 	for(auto &p : c->d_ref) if(p) (void)hipFree(p);
-	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_refdbg, c->d_ws_snap[0], c->d_ws_snap[1], c->d_ws_snap[2], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_cnt_snap[2], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
+	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
 	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
 	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
-	for(hipStream_t st_ : { c->stream_copy, c->stream_out, c->stream_sync, c->stream_back, c->stream_nf }) if(st_) (void)hipStreamSynchronize(st_);
+	for(hipStream_t st_ : { c->stream_copy, c->stream_out, c->stream_back, c->stream_nf }) if(st_) (void)hipStreamSynchronize(st_);
 	for(auto &sp : c->stream_pre) if(sp) (void)hipStreamSynchronize(sp);
 	for(auto &sb5 : c->stream_burst) if(sb5) (void)hipStreamSynchronize(sb5);
-	if(c->stream_sync) (void)hipStreamDestroy(c->stream_sync);
 	for(void *p : ptrs) if(p) (void)hipFree(p);
 	if(c->stream && c->pooled) {
 		StreamSet ss; ss.device = c->cfg.device; ss.front = c->stream; ss.copy = c->stream_copy; ss.out = c->stream_out; ss.back = c->stream_back; ss.nf = c->stream_nf;
@@ -820,9 +761,6 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	c->specialised = (c->os == 10 || c->os == 13 || c->os == 20);
 	c->run = c->specialised ? kRun : kRunGeneric;
 	c->cr = c->C >= 16 ? 4 : c->C >= 8 ? 2 : 1;                   // channels per wave: keep >= 4 channel groups where possible
-#ifdef VDL2_EXPERIMENTS
-	if(const char *e = getenv("VDL2HIP_CR")) { int v = atoi(e); if(v == 1 || v == 2 || v == 4) c->cr = v; }
-#endif
 	c->bf = derive_block_form(c->lpf, c->os, c->run);
 	c->dphi.resize(count);
 	for(uint32_t i = 0; i < count; i++) c->dphi[i] = nco_step(cfg->centerfreq, c->freqs[i], fs) & 0xffffffu;
@@ -841,23 +779,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	{
 		int prio_low = 0, prio_high = 0;
 		DEV_CHK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-		const char *lowp = "nf,burst";
-#ifdef VDL2_EXPERIMENTS
-		if(getenv("VDL2HIP_NO_PRIO")) prio_low = prio_high = 0;
-		if(getenv("VDL2HIP_LOW_PRIO")) lowp = getenv("VDL2HIP_LOW_PRIO");          // list of nf,burst,walk
-		if(const char *e = getenv("VDL2HIP_SYNC_ON")) c->sync_on = strcmp(e, "walk") == 0 ? 1 : strncmp(e, "own", 3) == 0 ? 2 : 0;   // front | walk | own | own-high
-		if(const char *e = getenv("VDL2HIP_K3B_WPL")) { int v = atoi(e); if(v == 1 || v == 2 || v == 4) c->k3b_wpl = v; }
-		if(const char *e = getenv("VDL2HIP_K1_TILES")) { long v = atol(e); if(v >= 1 && v <= 64) c->tiles_force = (int)v; }
-		if(const char *e = getenv("VDL2HIP_ABLATE")) c->ablate = (strstr(e, "walk") ? 1 : 0) | (strstr(e, "nf") ? 2 : 0) | (strstr(e, "burst") ? 4 : 0);
-		c->show_gaps = getenv("VDL2HIP_GAPS") != nullptr;
-#endif
-		int prio_front = prio_low;
-#ifdef VDL2_EXPERIMENTS
-		if(const char *e = getenv("VDL2HIP_FRONT_PRIO")) { if(strcmp(e, "mid") == 0) prio_front = (prio_low + prio_high) / 2; else if(strcmp(e, "high") == 0) prio_front = prio_high; }
-		if(getenv("VDL2HIP_GAPS")) fprintf(stderr, "vdl2hip: stream priority range low %d .. high %d, front %d\n", prio_low, prio_high, prio_front);
-#endif
 		bool from_pool = false;
-#ifndef VDL2_EXPERIMENTS
 		{
 			std::lock_guard<std::mutex> lk(g_pool_mutex);
 			for(size_t i = 0; i < g_pool.size(); i++) if(g_pool[i].device == cfg->device) {
@@ -869,33 +791,26 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 				break;
 			}
 		}
-#endif
 		if(!from_pool) {
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_front));
+		DEV_CHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_low));
 		// The walk goes first whenever it competes with the channeliser of a later feed (every later stage waits for it).  The
 		// noise-floor and burst streams do not: their many single-wave workgroups, dispatched with priority, each take the
 		// register slot of one of the four waves a channeliser workgroup needs on a CU and so keep whole workgroups out; at
 		// the front's priority they fill in while the sync kernels (few registers) run.  Measured at 256 channels
 		// (profiles/r02_stream_priorities.txt): all three high 7.10 ms/step, walk only 6.91, none 6.93; no difference at 8.
-		auto prio_of = [&](const char *name) { return strstr(lowp, name) ? prio_low : prio_high; };
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream_back, hipStreamNonBlocking, prio_of("walk")));
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream_nf, hipStreamNonBlocking, prio_of("nf")));
+		DEV_CHK(hipStreamCreateWithPriority(&c->stream_back, hipStreamNonBlocking, prio_high));
+		DEV_CHK(hipStreamCreateWithPriority(&c->stream_nf, hipStreamNonBlocking, prio_low));
 		for(auto &sp : c->stream_pre) DEV_CHK(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, prio_high));
-		for(auto &sb5 : c->stream_burst) DEV_CHK(hipStreamCreateWithPriority(&sb5, hipStreamNonBlocking, prio_of("burst")));
+		for(auto &sb5 : c->stream_burst) DEV_CHK(hipStreamCreateWithPriority(&sb5, hipStreamNonBlocking, prio_low));
 		DEV_CHK(hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
 		DEV_CHK(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
 		}
-#ifndef VDL2_EXPERIMENTS
 		c->pooled = true;
-#endif
-#ifdef VDL2_EXPERIMENTS
-		if(c->sync_on == 2) DEV_CHK(hipStreamCreateWithPriority(&c->stream_sync, hipStreamNonBlocking, strcmp(getenv("VDL2HIP_SYNC_ON"), "own-high") == 0 ? prio_high : prio_low));
-#endif
 	}
 	for(auto &sl : c->slot) {
 		DEV_CHK(hipEventCreate(&sl.done)); for(int i = 0; i < kNumEv; i++) DEV_CHK(hipEventCreate(&sl.ev[i]));
 		DEV_CHK(hipEventCreateWithFlags(&sl.ev_walk, hipEventDisableTiming)); DEV_CHK(hipEventCreateWithFlags(&sl.ev_nf, hipEventDisableTiming));
-		DEV_CHK(hipEventCreate(&sl.ev_front)); DEV_CHK(hipEventCreate(&sl.ev_chan)); DEV_CHK(hipEventCreateWithFlags(&sl.ev_k1, hipEventDisableTiming));
+		DEV_CHK(hipEventCreate(&sl.ev_front));
 	}
 	DEV_ALLOC(c->d_bf, sizeof(BlockForm)); DEV_ALLOC(c->d_lut, sizeof(Lut4) * 256); DEV_ALLOC(c->d_tab, sizeof(Tables));
 	DEV_ALLOC(c->d_dphi, 4 * count); DEV_ALLOC(c->d_freq, 4 * count); DEV_ALLOC(c->d_ppmthr, 4 * count);
@@ -916,7 +831,6 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	// VDL2HIP_NO_FUSE=1 selects the separate fix-up kernel k_fixup instead (no inter-workgroup wait at all, bit-identical results,
 	// ~3 % slower): worth setting where the GPU is permanently shared, so that no time is spent waiting.
 	c->fuse_k2 = getenv("VDL2HIP_NO_FUSE") == nullptr;
-	if(const char *e = getenv("VDL2HIP_BACKEND")) c->defer_back = strcmp(e, "deferred") == 0;   // eager (default) | deferred
 	DEV_ALLOC(c->d_ws, count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt, 2 * (size_t)count * kNumCounters * 8); c->d_wcnt = c->d_cnt + (size_t)count * kNumCounters;
 	DEV_ALLOC(c->d_acnt, (size_t)count * kNumAvlcCounters * 8);
 	// a decodable burst occupies >= 22 symbols = 220 decimated samples (header + 3 data + 2 FEC octets)
@@ -980,14 +894,11 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 		std::vector<uint8_t> mix(count);
 		for(uint32_t i = 0; i < count; i++) mix[i] = cfg->centerfreq != c->freqs[i];       // v->offset_tuning, demod.c:386
 		DEV_CHK(hipMemcpy(c->d_mix, mix.data(), count, hipMemcpyHostToDevice));
-		if(const char *e = getenv("VDL2HIP_REF_MODE")) c->ref_optimistic = strcmp(e, "sync") != 0;        // optimistic (default) | sync
-		if(const char *e = getenv("VDL2HIP_REF_KINDS")) c->ref_kinds = atoi(e) & 7;                          // (development: 1 candidates, 2 headers, 4 symbols)
-		for(int k = 0; k < 3; k++) { DEV_ALLOC(c->d_ws_snap[k], count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt_snap[k], (size_t)count * kNumCounters * 8); }
+		for(int k = 0; k < 2; k++) { DEV_ALLOC(c->d_ws_snap[k], count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt_snap[k], (size_t)count * kNumCounters * 8); }
 		DEV_ALLOC(c->d_ws_tmp, count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt_tmp, (size_t)count * kNumCounters * 8);
 		// Walk ahead (launch_back): for receivers whose front does not hide the chain walk - scans - check (a feed's results then come a
 		// feed later: with 256 channels, where the front hides the chain anyway, that extra depth cost 10 % and more)
 		c->walk_ahead = (count >= 16 && count <= 64) ? 1 : 0;   // (8 channels: the walk itself is longer than the front, the second walks' extra launches cost more than they save: 1.22 against 1.11 ms)
-		if(const char *e = getenv("VDL2HIP_WALK_AHEAD")) { const int v = atoi(e); c->walk_ahead = v < 0 ? 0 : v > 2 ? 2 : v; c->walk_ahead_auto = false; }      // 0: a feed's walk waits for the check of the feed before (round 5's schedule)
 		c->sq_alloc = defer_scans_for((int64_t)dmax, (int)count);
 		for(auto &sl : c->slot) {
 			DEV_ALLOC(sl.d_rq, (size_t)c->rq_cap * sizeof(RefReq)); DEV_ALLOC(sl.d_rqn, 32); DEV_ALLOC(sl.d_retry, 3 * (size_t)kRetryScans * sizeof(ScanReq)); DEV_ALLOC(sl.d_rqflag, (size_t)count * 4);
@@ -1333,15 +1244,9 @@ int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
 	if(strcmp(name, "force_timeout") == 0) { c->debug_force_timeout = value != 0; return VDL2HIP_OK; }
 	if(strcmp(name, "force_mismatch") == 0) { c->debug_force_mismatch = value != 0; return VDL2HIP_OK; }   // every channel walked again with the next feed's walk already done is taken to have ended differently: the next feed is redone for it
 	if(strcmp(name, "walk_ahead_below") == 0) { c->walk_ahead_below = (double)value; c->walk_ahead_auto = true; return VDL2HIP_OK; }   // (tests: feeds of fewer channel-samples than this let the next walk go ahead)
-	if(strcmp(name, "walk_ahead") == 0) { c->walk_ahead = value < 0 ? 0 : value > 2 ? 2 : (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // feeds whose walks may go ahead of a feed's check: 0, 1, 2
+	if(strcmp(name, "walk_ahead") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->walk_ahead = (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // 1: the next feed's walk goes ahead of a feed's check, for every feed; 0: a feed's walk waits for the check of the feed before (round 5's schedule)
 	if(strcmp(name, "force_again") == 0) { c->debug_force_again = value != 0; return VDL2HIP_OK; }   // every channel of every long feed is stitched a second time (the referee's walk-again path)
 	if(strcmp(name, "referee") == 0) { if(value && !c->d_refhist) return VDL2HIP_E_INVAL; c->referee = value != 0; return VDL2HIP_OK; }   // (on only where it was on at create: the history ring)
-	if(strcmp(name, "ref_debug_chan") == 0) {
-		if(!c->d_refdbg) { if(hipMalloc((void **)&c->d_refdbg, 8 * 4001) != hipSuccess) return VDL2HIP_E_NOMEM; }
-		if(hipMemset(c->d_refdbg, 0, 8 * 4001) != hipSuccess) return VDL2HIP_E_DEVICE;
-		c->ref_dbg_chan = (int)value; return VDL2HIP_OK;
-	}
-	if(strcmp(name, "ref_kinds") == 0) { c->ref_kinds = (int)value & 7; return VDL2HIP_OK; }
 	if(strcmp(name, "ref_warm") == 0) { if(value < 0 || value > c->ref_T - 4096) return VDL2HIP_E_INVAL; c->ref_warm = value; return VDL2HIP_OK; }
 	return VDL2HIP_E_INVAL;
 }
@@ -1378,7 +1283,6 @@ int vdl2hip_debug_scan_multi2(vdl2hip_ctx *c, const int32_t *chan, const int64_t
 	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
 	std::vector<ScanReq> h(count);
 	for(uint32_t i = 0; i < count; i++) { if(chan[i] < 0 || chan[i] >= c->C) return VDL2HIP_E_INVAL; h[i] = ScanReq{ chan[i], REF_CANDIDATE, lo[i], hi[i] }; }
-	const bool rty = with_retry && c->ref_retry_mul > 0;
 	ScanReq *d_sq = nullptr, *d_rt = nullptr; uint32_t *d_n = nullptr;
 	if(hipMalloc((void **)&d_sq, sizeof(ScanReq) * (size_t)count) != hipSuccess || hipMalloc((void **)&d_n, 8) != hipSuccess || hipMalloc((void **)&d_rt, sizeof(ScanReq) * (size_t)kRetryScans) != hipSuccess) {
 		if(d_sq) (void)hipFree(d_sq);
@@ -1392,10 +1296,7 @@ int vdl2hip_debug_scan_multi2(vdl2hip_ctx *c, const int32_t *chan, const int64_t
 		&& hipMemcpy(d_sq, h.data(), sizeof(ScanReq) * (size_t)count, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_n, nn, 8, hipMemcpyHostToDevice) == hipSuccess
 		&& hipMemcpy(before, c->d_refstats, sizeof before, hipMemcpyDeviceToHost) == hipSuccess;
 	RefChan *ref = c->d_ref[(c->feed_no - 1) % kSlots];
-	if(ok) LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3((count + kScanLanes - 1) / kScanLanes), dim3(64 * kScanWaves), 0, c->stream, e0, rty ? (hipEvent_t) nullptr : e1, 0, ref, 0xfffeu,
-	                             (const ScanReq *)d_sq, (const RefReq *) nullptr, (const uint32_t *)d_n, count, (int64_t)c->k_total, rty ? d_rt : (ScanReq *) nullptr, d_n + 1, kRetryScans, 1);
-	if(ok && rty) LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, c->stream, (hipEvent_t) nullptr, e1, 0, ref, 0xfffeu,
-	                             (const ScanReq *)d_rt, (const RefReq *) nullptr, (const uint32_t *)(d_n + 1), kRetryScans, (int64_t)c->k_total, (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, c->ref_retry_mul);
+	if(ok) launch_scans(c, c->stream, ref, 0xfffeu, d_sq, nullptr, d_n, count, c->k_total, with_retry ? d_rt : nullptr, d_n + 1, e0, e1);
 	ok = ok && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(after, c->d_refstats, sizeof after, hipMemcpyDeviceToHost) == hipSuccess;
 	float t = 0.f;
 	if(ok && ms) { (void)hipEventElapsedTime(&t, e0, e1); *ms = t; }
@@ -1404,7 +1305,6 @@ int vdl2hip_debug_scan_multi2(vdl2hip_ctx *c, const int32_t *chan, const int64_t
 	(void)hipFree(d_sq); (void)hipFree(d_n); (void)hipFree(d_rt);
 	return ok ? (int)(after[0] - before[0]) : VDL2HIP_E_DEVICE;
 }
-int vdl2hip_debug_scan_multi(vdl2hip_ctx *c, const int32_t *chan, const int64_t *lo, const int64_t *hi, uint32_t count, float *ms) { return vdl2hip_debug_scan_multi2(c, chan, lo, hi, count, 0, ms); }
 int vdl2hip_debug_exact_window(vdl2hip_ctx *c, uint32_t chan, int64_t n_lo, int64_t n_hi) { return vdl2hip_debug_exact_window_many(c, chan, n_lo, n_hi, 1, 0, nullptr); }
 
 // test hook (not declared in vdl2hip.h): what the DPP controls the channeliser's scan relies on do on this device
@@ -1491,37 +1391,6 @@ int vdl2hip_read_decimated(vdl2hip_ctx *c, uint32_t chan, int64_t first, float *
 		HIPCHK(hipMemcpy(dst + 2 * done, base + slot, m * sizeof(cf32), hipMemcpyDeviceToHost));
 		done += m;
 	}
-	return (int)n;
-}
-
-// development aid: the referee's event log (ref_debug_log) of the channel chosen with debug option "ref_debug_chan": out[4 * i ..] per entry
-int vdl2hip_debug_ref_log(vdl2hip_ctx *c, unsigned long long *out, size_t cap_entries) {
-	if(!c || !c->d_refdbg) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	(void)collect_pending(c);
-	unsigned long long n = 0;
-	HIPCHK(hipMemcpy(&n, c->d_refdbg, 8, hipMemcpyDeviceToHost));
-	if(n > 1000) n = 1000;
-	if(n > cap_entries) n = cap_entries;
-	if(n) HIPCHK(hipMemcpy(out, c->d_refdbg + 1, 32 * n, hipMemcpyDeviceToHost));
-	return (int)n;
-}
-
-// test hook (not declared in vdl2hip.h): the decisions the walk of the LAST feed has asked the referee to check (optimistic mode), as
-// (chan, kind, n, k0 of the feed) quadruples of int64; returns how many there were
-int vdl2hip_debug_read_requests(vdl2hip_ctx *c, int64_t *out, size_t cap) {
-	if(!c || !out) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	if(c->feed_no == 0 || !c->referee) return 0;
-	OutSlot &sl = c->slot[(c->feed_no - 1) % kSlots];
-	uint32_t n = 0;
-	HIPCHK(hipMemcpy(&n, sl.d_rqn, 4, hipMemcpyDeviceToHost));
-	const uint32_t m = std::min<uint32_t>(n, c->rq_cap);
-	std::vector<RefReq> rq(m);
-	if(m) HIPCHK(hipMemcpy(rq.data(), sl.d_rq, (size_t)m * sizeof(RefReq), hipMemcpyDeviceToHost));
-	for(uint32_t i = 0; i < m && i < cap; i++) { out[4 * i] = rq[i].chan; out[4 * i + 1] = rq[i].kind; out[4 * i + 2] = rq[i].n; out[4 * i + 3] = sl.back_k0; }
 	return (int)n;
 }
 
