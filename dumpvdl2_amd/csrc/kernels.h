@@ -1009,6 +1009,7 @@ struct K3Args {
 	int64_t nbase, k1;        // first sample to (re)compute (multiple of 64); one past the last valid sample
 	uint32_t cap, mask;
 	int32_t wpl;              // exact tier: flag words scanned per lane (1..kK3bWordsPerLane)
+	int32_t screen_all;       // test hook (vdl2hip_debug_option "screen_all"): every sample is flagged, as if the screening threshold were infinite
 	OutCtl *ctl; uint32_t k5_waves;   // the feed's output control block, reset here (the last kernel of the front, so that no copy has to do it)
 	// referee (nullptr: off): the feed's hook - written here from `refv`, for the same reason - and what the candidate verdict needs
 	RefChan *ref; RefChan refv; float max_ppm; const float *ppm_thr; int32_t ref_on; uint32_t *rq_n, *rq_flag; RefBad *rq_bad; ScanReq *pq; uint32_t pq_cap; uint32_t *rq_flag2;      // rq_n, rq_flag, rq_bad: the feed's list of decisions to check / its "walk again" flags / the decisions that fell, reset here;      // (ref != nullptr, ref_on == 0: the hook is written, the verdicts are the plain ones)
@@ -1024,7 +1025,7 @@ struct K3Args {
 // Ten consecutive lanes cover 10 S consecutive samples; 320 threads cover the tile.  Verdicts go through LDS to be regrouped into words of 64 consecutive samples.  Output: one flag
 // bit per sample - "the exact value may be under the threshold".
 //
-// k_sync_exact4 (and its older form k_sync_exact) - only where a flag is set (on noise 3e-5 of the samples): the reference's arithmetic - atan2 in double on the
+// k_sync_dense (and the form it replaces, k_sync_exact4) - only where a flag is set (on noise 3e-5 of the samples): the reference's arithmetic - atan2 in double on the
 // 16 taps, the double-precision unwrap, the centred regression - for the flagged samples and 3 samples either side (those are
 // y1/y3 of calc_para_vertex and the right-hand side of the candidate test), stored in pf, and the candidate bit
 // pherr(n-3) < 4 && pherr(n) > pherr(n-3) of every sample.  The walker reads the metric nowhere else.  A sample whose right
@@ -1091,12 +1092,30 @@ __global__ __launch_bounds__(kK3Threads) void k_sync_screen(K3Args a) {
 	for(int j = 0; j < (kK3Tile / 64) / (kK3Threads / 64); j++) {
 		const int word = (tid >> 6) * ((kK3Tile / 64) / (kK3Threads / 64)) + j;
 		const int64_t n = nblk + 64 * word + (tid & 63);
-		const unsigned long long bits = __ballot(n < a.k1 && verdict[64 * word + (tid & 63)] != 0);
+		const unsigned long long bits = __ballot(n < a.k1 && (verdict[64 * word + (tid & 63)] != 0 || a.screen_all != 0));
 		if((tid & 63) == 0 && n < a.k1) a.flag[(size_t)c * (a.cap >> 6) + ((uint32_t)(n >> 6) & (a.mask >> 6))] = bits;
 	}
 }
 
 constexpr int kK3bWordsPerLane = 4;      // at most; fewer when that leaves the chip short of wavefronts (few channels)
+// optional per-phase cycle probe of the exact tier (development aid, -DVDL2_K3B_PROF; compiled out by default), in the style of
+// VDL2_K1_PROF: wave 0 of every workgroup adds the shader clocks it spends in each phase to vdl2_k3b_prof[slot][phase] -
+// 0 flag scan, 1 y loads + staging (dense form: tile set-up), 2 error bounds, 3 metric round 0 (dense form: all evaluations),
+// 4 metric round 1, 5 verdict + stores - and [8] workgroups, [9] busy words, [10] evaluations, [11] wavefront passes / tiles
+#ifdef VDL2_K3B_PROF
+__device__ unsigned long long vdl2_k3b_prof[64][16];
+#define K3B_BEGIN() unsigned k3b_t0_ = (unsigned)__builtin_readcyclecounter(), k3b_acc_[6] = {0, 0, 0, 0, 0, 0}, k3b_cnt_[3] = {0, 0, 0}
+#define K3B_MARK(k) do { if(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0) { const unsigned t_ = (unsigned)__builtin_readcyclecounter(); \
+	k3b_acc_[k] += t_ - k3b_t0_; k3b_t0_ = t_; } } while(0)
+#define K3B_COUNT(k, v) do { k3b_cnt_[k] += (unsigned)__builtin_amdgcn_readfirstlane((int)(v)); } while(0)
+#define K3B_END() do { if(threadIdx.x == 0) { const int s_ = (blockIdx.x + blockIdx.y) & 63; for(int k_ = 0; k_ < 6; k_++) atomicAdd(&vdl2_k3b_prof[s_][k_], (unsigned long long)k3b_acc_[k_]); \
+	atomicAdd(&vdl2_k3b_prof[s_][8], 1ull); for(int k_ = 0; k_ < 3; k_++) atomicAdd(&vdl2_k3b_prof[s_][9 + k_], (unsigned long long)k3b_cnt_[k_]); } } while(0)
+#else
+#define K3B_BEGIN() do {} while(0)
+#define K3B_MARK(k) do {} while(0)
+#define K3B_COUNT(k, v) do {} while(0)
+#define K3B_END() do {} while(0)
+#endif
 // The exact tier, a word at a time.  A word with work is taken by the whole wavefront: the 224 samples its evaluations can read (the
 // word and 160 before it) are loaded once, coalesced, and turned into exact phases (atan2 in double, four per lane) - and, for the
 // referee, into the bounds on their errors (ref_eps2_of: a sample and its three predecessors) - in LDS; then every sample that has
@@ -1127,6 +1146,7 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 	const int64_t w0 = a.nbase >> 6, w1 = (a.k1 + 63) >> 6;
 	const int64_t wb = w0 + ((int64_t)blockIdx.x * 4 + wave) * (64 * a.wpl);   // first word of this wavefront
 	int nwork = 0;
+	K3B_BEGIN();
 	for(int g = 0; g < a.wpl; g++) {
 		const int64_t w = wb + 64 * g + lane;
 		uint64_t need = 0, fprev = 0, fpp = 0, f0 = 0;
@@ -1152,6 +1172,7 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 		nwork += __builtin_popcountll(busy);
 	}
 	WAVE_SYNC();
+	K3B_MARK(0); if(wave == 0) K3B_COUNT(0, nwork);
 	float *ps = psh[wave], *fs = fsh[wave], *es = esh[wave], *as = ash[wave], *bs = bsh[wave], *ph = phs[wave], *e2 = e2s[wave];
 	#pragma unroll 1
 	for(int it = 0; it < nwork; it++) {
@@ -1176,6 +1197,7 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 		}
 		ps[6 + lane] = kPherrBig; if(lane < 6) ps[lane] = kPherrBig;
 		WAVE_SYNC();
+		K3B_MARK(1); if(wave == 0) { K3B_COUNT(1, __builtin_popcountll(needj) + __builtin_popcount(fprevj)); K3B_COUNT(2, 1 + (fprevj != 0)); }
 		if(ref_on) {
 			// |y|^2 -> the squared bound on the phase error (ref_eps2_of), in place: every lane reads its four and their predecessors first
 			float ev[4];
@@ -1193,6 +1215,7 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 			for(int k = 0; k < 4; k++) if(64 * k + lane < kSpan) e2[64 * k + lane] = ev[k];
 			WAVE_SYNC();
 		}
+		K3B_MARK(2);
 		// ---- one lane per sample with work: the word's own (bit = lane), then the six before it (lanes 0..5) ----
 		#pragma unroll 1
 		for(int round = 0; round < 2; round++) {
@@ -1208,6 +1231,7 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 				else { sync_metric(p, T, pv, fv); pa = pb = pv; }
 				ps[6 + bit] = pv; fs[6 + bit] = fv; es[6 + bit] = E; as[6 + bit] = pa; bs[6 + bit] = pb;
 			}
+			K3B_MARK(3 + round);
 		}
 		WAVE_SYNC();
 		// the verdict of every sample of the word as a candidate: got_sync() may fire there (bitmap) / some decision of the fire is
@@ -1234,7 +1258,250 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 			}
 		}
 		WAVE_SYNC();
+		K3B_MARK(5);
 	}
+	K3B_END();
+}
+
+// The exact tier in its dense form.  The form above gives a word with work to a whole wavefront, and its metric - some 450 dependent
+// float instructions - then runs with the 7 lanes of 64 that have a sample to evaluate, word after word, in wavefronts that mostly
+// wait: 0.68 ms for what is 0.1 ms of issue (profiles/exact_tier_before.txt).  Here a workgroup does the same work on its
+// 256 * wpl words (wpl up to kK3dRounds: thousands of words, so that its evaluations fill wavefronts) in three steps:
+//   list      256 flag words at a time, a lane each, as above (cand = 0 where there is nothing to do); the busy words go on a list
+//             in LDS - the word, its work mask `need`, which of the six samples before it are tabulated - together with the running
+//             count of samples to evaluate: one LDS atomic per wavefront and pass, none in global memory.  Once kK3dFlush
+//             evaluations are waiting (and at the end) the list is worked off:
+//   evaluate  in tiles of whole words with at most kK3dEvals evaluations.  ONE LANE PER EVALUATION, 256 at a time, whichever word
+//             it belongs to: the lane loads its sixteen taps (and, for the referee, the three predecessors of each) and runs the
+//             reference's metric on them in the same operation order as above;
+//   decide    again a lane per evaluation: the verdict of sample n is worked out by the lane that holds n-3 (no verdict without it:
+//             is_candidate / ref_candidate_verdict), from the evaluations of n, n-3, n-6 (kPherrBig where there was none); the
+//             candidate bits are gathered per word in LDS; then pf at the samples with work, the candidate word, the referee's
+//             stretch request - one per word with a marked candidate.
+// A tile is the unit whatever the density: 0.05 % of the samples flagged or all of them (seven words a tile), there is one code path.
+// Every value is the one the word-at-a-time form computes, bit for bit: the arithmetic of an evaluation depends on its sample
+// alone, and the six samples before a word are evaluated for that word again, as there.
+constexpr int kK3dEvals = 320;           // evaluations per tile; a word has at most 64 + 6
+constexpr int kK3dFlush = kK3dEvals - 64;      // evaluations waiting before the list is worked off: the tile is then all but full
+constexpr int kK3dList = kK3dFlush + 256;      // words on the list at most: fewer than kK3dFlush waiting (a word has an evaluation at least) + a pass
+constexpr int kK3dMinGroups = 2048;       // workgroups the chip should have at least: 256 channels x 16 s then take 8 passes (3 328 workgroups), which beat 4, 16 and 32 (profiles/exact_tier_ab.txt)
+constexpr int kK3dGroup = 4;             // passes whose flag words are fetched at once
+constexpr int kK3dRounds = 32;           // passes of 256 words per workgroup at most (vdl2hip.hip: fewer when that leaves the chip short of workgroups)
+static_assert(kK3dEvals >= 70 && kK3dEvals <= 512 && kK3dList * 70 < (1 << 20) && kK3dList < (1 << 11) && kK3dRounds * 256 <= (1 << 16),
+              "tile map: 9 bits of word, 7 of position; list head: 11 bits of words, 21 of evaluations; 16 bits of word index");
+// (a workgroup barrier that orders LDS alone: the kernel's threads hand nothing to each other through global memory, and a barrier
+// that waited for the cand / pf stores in flight would cost every pass of the list a trip to memory - 7 600 clocks a pass, measured)
+#define K3D_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while(0)
+template<bool FULL>
+__global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
+	if(blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { reset_out_ctl(a.ctl, a.k5_waves); if(a.ref) *a.ref = a.refv; if(a.rq_n) { a.rq_n[0] = 0u; a.rq_n[1] = 0u; a.rq_n[2] = 0u; a.rq_n[4] = 0u; a.rq_n[5] = 0u; a.rq_n[6] = 0u; } }   // (rq_n[1], [2]: the burst decoder's lists, BurstDefer)
+	if(blockIdx.x == 0 && threadIdx.x == 0 && a.rq_flag) { a.rq_flag[blockIdx.y] = 0u; a.rq_bad[blockIdx.y].n = 0u; if(a.rq_flag2) a.rq_flag2[blockIdx.y] = 0u; }
+	// the list: word (index within the workgroup), work mask, the six before it, the number of evaluations up to and including the
+	// word, and what the decide step gathers for it: candidate bits, marked candidates
+	__shared__ uint64_t s_need[kK3dList], s_cbits[kK3dList], s_mbits[kK3dList];
+	__shared__ uint32_t s_end[kK3dList];
+	__shared__ uint16_t s_word[kK3dList];
+	__shared__ uint8_t s_fprev[kK3dList];
+	// the tile: evaluation -> (word of the tile, position 0..69: 6 + bit, or 0..5 for the six before the word), its five results,
+	// and whether its sample is a marked candidate
+	__shared__ uint16_t s_map[kK3dEvals];
+	__shared__ float s_res[5][kK3dEvals];
+	__shared__ uint8_t s_neg[kK3dEvals];
+	__shared__ uint32_t s_head, s_r1;
+	// the flag words of kK3dGroup passes, and the two before and the one after them: one trip to memory for the group
+	__shared__ uint64_t s_flag[256 * kK3dGroup + 3];
+	const int c = blockIdx.y, tid = threadIdx.x, lane = threadIdx.x & 63;
+	const cf32 *y = a.y + (size_t)c * a.cap;
+	const uint64_t *flag = a.flag + (size_t)c * (a.cap >> 6);
+	uint64_t *cand = a.cand + (size_t)c * (a.cap >> 6);
+	const uint32_t wmask = a.mask >> 6;
+	const Tables &T = *a.tab;
+	const bool ref_on = a.ref != nullptr && a.ref_on != 0;
+	const float ppm_thr = ref_on ? a.ppm_thr[c] : 0.f;
+	const int64_t w0 = a.nbase >> 6, w1 = (a.k1 + 63) >> 6;
+	const int64_t wb = w0 + (int64_t)blockIdx.x * (256 * a.wpl);      // first word of this workgroup
+	K3B_BEGIN();
+	if(tid == 0) s_head = 0u;
+	K3D_BARRIER();
+	#pragma unroll 1
+	for(int g = 0; g < a.wpl; g++) {
+		// ---- list ----
+		if(g % kK3dGroup == 0) {
+			// (words before nbase hold the previous feed's flags; none before the stream's first word or after the feed's last)
+			const int ng = a.wpl - g < kK3dGroup ? a.wpl - g : kK3dGroup;
+			for(int i = tid; i < 256 * ng + 3; i += 256) {
+				const int64_t w = wb + 256 * g - 2 + i;
+				s_flag[i] = w >= 0 && w < w1 ? flag[(uint32_t)w & wmask] : 0ull;
+			}
+			K3D_BARRIER();
+		}
+		{
+			const int64_t w = wb + 256 * g + tid;
+			const int fi = 256 * (g % kK3dGroup) + tid;                  // s_flag[fi]: word w - 2
+			uint64_t need = 0, fprev = 0, fpp = 0, f0 = 0;
+			if(w < w1) {
+				f0 = s_flag[fi + 2]; fprev = s_flag[fi + 1]; fpp = s_flag[fi];
+				const uint64_t fnext = s_flag[fi + 3];
+				need = f0 | (f0 << 3) | (f0 >> 3) | (fprev >> 61) | (fnext << 61);
+				const int64_t base = w << 6;
+				if(a.k1 - 3 < base + 64) {                                      // right neighbour n+3 not there yet
+					const int64_t lo = a.k1 - 3 - base;
+					need |= lo <= 0 ? ~0ull : (~0ull << lo);
+				}
+				if(a.k1 < base + 64) need &= (a.k1 - base <= 0) ? 0ull : (~0ull >> (64 - (a.k1 - base)));   // samples that exist
+				if(need == 0) cand[(uint32_t)w & wmask] = 0;
+			}
+			// which of the six samples before the word have a tabulated metric: the last six bits of the previous word's work mask
+			// (none before the stream's first sample)
+			const uint64_t need_prev = fprev | (fprev << 3) | (fprev >> 3) | (fpp >> 61) | (f0 << 61);
+			const uint32_t fp6 = w > 0 ? (uint32_t)(need_prev >> 58) : 0u;
+			const uint32_t cnt = need != 0 ? (uint32_t)__builtin_popcountll(need) + (uint32_t)__builtin_popcount(fp6) : 0u;
+			// one head word for both counts, so that a word's place in the list and its place among the evaluations go together
+			const uint32_t inc = cnt << 11 | (need != 0 ? 1u : 0u);
+			uint32_t incl = inc;
+			#pragma unroll
+			for(int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)incl, d); if(lane >= d) incl += o; }
+			const uint32_t tot = (uint32_t)__shfl((int)incl, 63);
+			uint32_t at = 0;
+			if(lane == 0 && tot != 0) at = atomicAdd(&s_head, tot);
+			at = (uint32_t)__shfl((int)at, 0) + incl - inc;
+			if(need != 0) {
+				const uint32_t r = at & 2047u;
+				s_need[r] = need; s_fprev[r] = (uint8_t)fp6; s_word[r] = (uint16_t)(256 * g + tid); s_end[r] = (at >> 11) + cnt;
+				s_cbits[r] = 0ull; s_mbits[r] = 0ull;
+			}
+		}
+		K3D_BARRIER();
+		const uint32_t head = s_head;
+		K3D_BARRIER();                                                 // (everyone has read the head before the next pass adds to it)
+		const int nrec = (int)(head & 2047u);
+		K3B_MARK(0);
+		if((int)(head >> 11) < kK3dFlush && g + 1 < a.wpl) continue;
+		K3B_COUNT(0, nrec); K3B_COUNT(1, head >> 11);
+		// ---- tiles ----
+		#pragma unroll 1
+		for(int r0 = 0; r0 < nrec; ) {
+			const uint32_t e0 = r0 ? s_end[r0 - 1] : 0u;
+			if(tid == 0) s_r1 = (uint32_t)r0 + 1u;                        // (a word alone always fits)
+			K3D_BARRIER();
+			{	// the words of the tile: as many whole ones as fit (s_end rises along the list; a word has at least one evaluation)
+				uint32_t best = 0;
+				for(int r = r0 + 1 + tid; r < nrec && r < r0 + kK3dEvals; r += 256) if(s_end[r] - e0 <= (uint32_t)kK3dEvals) best = (uint32_t)r + 1u;
+				if(best) atomicMax(&s_r1, best);
+			}
+			K3D_BARRIER();
+			const int r1 = (int)s_r1, nev = (int)(s_end[r1 - 1] - e0);
+			for(int r = r0 + tid; r < r1; r += 256) {
+				uint32_t at = (r ? s_end[r - 1] : 0u) - e0;
+				const uint32_t code = (uint32_t)(r - r0) << 7;
+				for(uint32_t m = s_fprev[r]; m; m &= m - 1u) s_map[at++] = (uint16_t)(code | (uint32_t)__builtin_ctz(m));
+				for(uint64_t m = s_need[r]; m; m &= m - 1ull) s_map[at++] = (uint16_t)(code | (6u + (uint32_t)__builtin_ctzll(m)));
+			}
+			K3D_BARRIER();
+			K3B_MARK(1); K3B_COUNT(2, 1);
+			// ---- evaluate: one lane per evaluation ----
+			#pragma unroll 1
+			for(int s = tid; s < nev; s += 256) {
+				const uint32_t code = s_map[s];
+				const int64_t n = ((wb + s_word[r0 + (int)(code >> 7)]) << 6) + (int)(code & 127u) - 6;
+				// (a sample with work exists, and so do the samples before it: a tap is outside the stream only before its first sample)
+				float p[kPreamble], e2[kPreamble];
+				cf32 yt[kPreamble];
+				#pragma unroll
+				for(int i = 0; i < kPreamble; i++) { const int64_t t = n - 150 + 10 * i; yt[i] = t >= 0 ? y[(uint32_t)t & a.mask] : cf32{0.f, 0.f}; }
+				if(ref_on) {
+					// the three predecessors of each tap, four taps at a time (registers): |y|^2 -> the squared bound on the phase error
+					#pragma unroll
+					for(int h = 0; h < kPreamble; h += 4) {
+						cf32 yv[4][3];
+						#pragma unroll
+						for(int i = 0; i < 4; i++) {
+							#pragma unroll
+							for(int k = 0; k < 3; k++) { const int64_t t = n - 150 + 10 * (h + i) - 1 - k; yv[i][k] = t >= 0 ? y[(uint32_t)t & a.mask] : cf32{0.f, 0.f}; }
+						}
+						#pragma unroll
+						for(int i = 0; i < 4; i++) {
+							const int64_t t = n - 150 + 10 * (h + i);
+							float m[4];
+							m[0] = t >= 0 ? yt[h + i].re * yt[h + i].re + yt[h + i].im * yt[h + i].im : -1.f;      // (-1: outside the stream - its phase is exactly the reference's)
+							#pragma unroll
+							for(int k = 0; k < 3; k++) m[1 + k] = t - 1 - k >= 0 ? yv[i][k].re * yv[i][k].re + yv[i][k].im * yv[i][k].im : -1.f;
+							e2[h + i] = m[0] < 0.f ? 0.f : ref_eps2_of(m[0], fmaxf(m[1], 0.f), fmaxf(m[2], 0.f), fmaxf(m[3], 0.f));
+						}
+					}
+				}
+				#pragma unroll
+				for(int i = 0; i < kPreamble; i++) { const int64_t t = n - 150 + 10 * i; p[i] = t >= 0 ? phase_of(yt[i]) : 0.f; }
+				float pv, fv, E = 0.f, pa, pb;
+				if(ref_on) sync_metric_ref(p, e2, 1, T, pv, fv, E, pa, pb, FULL);
+				else { sync_metric(p, T, pv, fv); pa = pb = pv; }
+				s_res[0][s] = pv; s_res[1][s] = fv; s_res[2][s] = E; s_res[3][s] = pa; s_res[4][s] = pb; s_neg[s] = 0;
+			}
+			K3D_BARRIER();
+			K3B_MARK(3);
+			// ---- decide, first half: the lane of evaluation n-3 works out the verdict of sample n as a candidate - got_sync() may
+			// fire there (bitmap) / some decision of the fire is within the margin of the stream's error (sign of the tabulated metric:
+			// the walker has it checked on the reference's samples) ----
+			#pragma unroll 1
+			for(int s = tid; s < nev; s += 256) {
+				const uint32_t code = s_map[s];
+				const int r = r0 + (int)(code >> 7), pos = (int)(code & 127u) + 3;      // position of n in the word: its bit + 6
+				if(pos < 6 || pos > 69) continue;
+				const uint64_t needj = s_need[r];
+				const uint64_t mlo = (uint64_t)s_fprev[r] | (needj << 6), mhi = needj >> 58;      // positions 0..63 / 64..69
+				const int at = (int)((r ? s_end[r - 1] : 0u) - e0);
+				const int64_t n = ((wb + s_word[r]) << 6) + pos - 6;
+				if(!(n >= 3 && n < a.k1)) continue;
+				// the evaluations of n and of n-6: -1 where there was none
+				int sl[2];
+				#pragma unroll
+				for(int k = 0; k < 2; k++) {
+					const int q = pos - 6 * k;
+					const bool has = q < 64 ? ((mlo >> q) & 1ull) != 0 : ((mhi >> (q - 64)) & 1ull) != 0;
+					const int below = q < 64 ? __builtin_popcountll(mlo & ((1ull << q) - 1ull)) : __builtin_popcountll(mlo) + __builtin_popcountll(mhi & ((1ull << (q - 64)) - 1ull));
+					sl[k] = has ? at + below : -1;
+				}
+				const int i0 = sl[0] < 0 ? 0 : sl[0], i6 = sl[1] < 0 ? 0 : sl[1];
+				const bool h0 = sl[0] >= 0, h6 = sl[1] >= 0;
+				const float p0 = h0 ? s_res[0][i0] : kPherrBig, p3 = s_res[0][s], p6 = h6 ? s_res[0][i6] : kPherrBig;
+				int vd;
+				if(!ref_on) vd = is_candidate(p3, p0) ? 1 : 0;
+				else vd = ref_candidate_verdict(ref_pherr_range(p0, h0 ? s_res[3][i0] : 0.f, h0 ? s_res[4][i0] : 0.f, h0 ? s_res[2][i0] : 0.f), ref_pherr_range(p3, s_res[3][s], s_res[4][s], s_res[2][s]), s_res[1][s], s_res[2][s],
+				                                ref_pherr_range(p6, h6 ? s_res[3][i6] : 0.f, h6 ? s_res[4][i6] : 0.f, h6 ? s_res[2][i6] : 0.f), a.max_ppm, ppm_thr);
+				if(vd & 1) atomicOr((unsigned long long *)&s_cbits[r], 1ull << (pos - 6));
+				if((vd & 2) && h0) { atomicOr((unsigned long long *)&s_mbits[r], 1ull << (pos - 6)); s_neg[i0] = 1; }
+			}
+			K3D_BARRIER();
+			// ---- decide, second half: pf at the samples with work, the candidate word, the stretch request ----
+			#pragma unroll 1
+			for(int s = tid; s < nev; s += 256) {
+				const uint32_t code = s_map[s];
+				const int pos = (int)(code & 127u);
+				if(pos < 6) continue;
+				const int64_t n = ((wb + s_word[r0 + (int)(code >> 7)]) << 6) + pos - 6;
+				const float p0 = s_res[0][s];
+				a.pf[(size_t)c * a.cap + ((uint32_t)n & a.mask)] = cf32{ s_neg[s] ? -p0 : p0, s_res[1][s] };
+			}
+			for(int r = r0 + tid; r < r1; r += 256) {
+				const int64_t wj = wb + s_word[r];
+				cand[(uint32_t)wj & wmask] = s_cbits[r];
+				const uint64_t mk = s_mbits[r];
+				if(a.pq && mk) {
+					// the marked candidates of the word: the stretch their decisions read goes on the list of those made exact before the walk
+					const int64_t nf = (wj << 6) + __builtin_ctzll(mk), nl = (wj << 6) + 63 - __builtin_clzll(mk);
+					int64_t lo = (nf - kRefPre) & ~255ll, hi = (nl + kRefPost) | 255; if(lo < 0) lo = 0; if(hi > a.k1 - 1) hi = a.k1 - 1;
+					const uint32_t i = atomicAdd(a.rq_n + 3, 1u);
+					if(i < a.pq_cap) a.pq[i] = ScanReq{ c, REF_CANDIDATE, lo, hi };
+				}
+			}
+			K3D_BARRIER();                                              // (the next tile overwrites the map and the results)
+			K3B_MARK(5);
+			r0 = r1;
+		}
+		if(tid == 0) s_head = 0u;
+		K3D_BARRIER();
+	}
+	K3B_END();
 }
 
 struct K4Args {

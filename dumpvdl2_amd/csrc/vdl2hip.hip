@@ -136,7 +136,7 @@ struct vdl2hip_ctx {
 	hipStream_t stream_back = nullptr, stream_nf = nullptr, stream_burst[kSideBurst] = {};   // (a burst stream per feed in flight: a burst decoder that waits for the referee - a scan over a whole burst takes milliseconds - does not hold up the next feed's)
 	OutCtl ctl_template{};                 // the capacities of a feed's output buffers (the counters are reset on the device: reset_out_ctl)
 	bool pooled = false;                   // its streams are complete and of the product's priorities: they go to the pool when the receiver is destroyed
-	bool avlc_filter = false, failed = false; int debug_force_timeout = 0, debug_force_again = 0;
+	bool avlc_filter = false, failed = false; int debug_force_timeout = 0, debug_force_again = 0, debug_exact_tier = 1, debug_screen_all = 0;
 	// Referee (kernels.h): decisions within the margin of the channeliser's distance from the reference's fp32 scan are taken on the
 	// reference's own samples, recomputed from the raw input.  The input of a feed stays where it is (d_in / the caller's device
 	// buffer) while its back end runs; what lies before it - up to ref_T samples: the run-up of the scan + the longest burst - is kept
@@ -399,7 +399,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		sl.k5_waves = (sl.k5_waves + kBurstWaves - 1) / kBurstWaves * kBurstWaves;
 		// (a short feed - launch_back: `small` - has no scans ahead of its walk: its one walk notes, the noted stretches are scanned side by side and checked on the front stream)
 		sl.prescan = c->referee && c->ref_prescan && !feed_is_small(c, D);
-		K3Args k3{ c->d_y, c->d_pf, c->d_cand, c->d_flag, c->d_tab, nbase, k1, c->cap, c->cap - 1, 1, sl.d_ctl, sl.k5_waves, ref_dst, refv, c->cfg.max_ppm, c->d_ppmthr, c->referee ? 1 : 0, sl.d_rqn, sl.d_rqflag, sl.d_rqbad, sl.prescan ? sl.d_pq : nullptr, kPreScans, sl.d_rqflag2 };
+		K3Args k3{ c->d_y, c->d_pf, c->d_cand, c->d_flag, c->d_tab, nbase, k1, c->cap, c->cap - 1, 1, c->debug_screen_all, sl.d_ctl, sl.k5_waves, ref_dst, refv, c->cfg.max_ppm, c->d_ppmthr, c->referee ? 1 : 0, sl.d_rqn, sl.d_rqflag, sl.d_rqbad, sl.prescan ? sl.d_pq : nullptr, kPreScans, sl.d_rqflag2 };
 		// The exact tier's stop event doubles as "front of this feed done" (what the walk stream waits for): one queue entry less
 		// on the front stream than a separate hipEventRecord.
 		LAUNCH_EV(k_sync_screen, dim3((unsigned)((k1 - nbase + kK3Tile - 1) / kK3Tile), (unsigned)c->C), dim3(kK3Threads), st, EV(4), (hipEvent_t) nullptr, k3);
@@ -408,10 +408,22 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		// but the kernel is latency-bound: at 32 channels 1 word per lane - 3 296 workgroups - beat 4 - 832 - by 0.02 ms of a 0.85 ms step,
 		// at 256 channels 4 is as good as any; profiles/r03_k3b_forms.txt)
 		for(int wpl = kK3bWordsPerLane; wpl >= 1; wpl >>= 1) { k3.wpl = wpl; if(((nwords + 256 * wpl - 1) / (256 * wpl)) * c->C >= 2048 || wpl == 1) break; }
+		// (the dense form: a workgroup's evaluations should fill its wavefronts - a word in a hundred has work, seven evaluations each -
+		// so it takes as many passes of 256 words as leave the chip kK3dMinGroups workgroups)
+		if(c->debug_exact_tier) {
+			for(int wpl = kK3dRounds; wpl >= 1; wpl >>= 1) { k3.wpl = wpl; if(((nwords + 256 * wpl - 1) / (256 * wpl)) * c->C >= kK3dMinGroups || wpl == 1) break; }
+		}
 		const int64_t wpb = 256 * k3.wpl;                                      // words per block
 		// (receivers that scan ahead of the walk work out the windows with one or two unwrap decisions within the margin: sync_metric_ref)
-		if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_exact4<true>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
-		else LAUNCH_EV(k_sync_exact4<false>, dim3((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C), dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+		// (debug_exact_tier 0: the word-at-a-time form the dense one replaced, kept as its yardstick - same grid, same arguments)
+		const dim3 k3b_grid((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C);
+		if(c->debug_exact_tier) {
+			if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_dense<true>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+			else LAUNCH_EV(k_sync_dense<false>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+		} else {
+			if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_exact4<true>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+			else LAUNCH_EV(k_sync_exact4<false>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
+		}
 	}
 	if(D <= 0) HIPCHK(hipEventRecord(sl.ev_front, st));
 	if(D > 0) { sl.ev_valid = prof; sl.ev_level = c->profiling; sl.fused = a.fuse != 0; if(sl.k1_timed) c->stats.chan_samples += (uint64_t)D * c->os * c->C; } else sl.k1_timed = false;
@@ -1245,6 +1257,8 @@ int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
 	if(strcmp(name, "force_mismatch") == 0) { c->debug_force_mismatch = value != 0; return VDL2HIP_OK; }   // every channel walked again with the next feed's walk already done is taken to have ended differently: the next feed is redone for it
 	if(strcmp(name, "walk_ahead_below") == 0) { c->walk_ahead_below = (double)value; c->walk_ahead_auto = true; return VDL2HIP_OK; }   // (tests: feeds of fewer channel-samples than this let the next walk go ahead)
 	if(strcmp(name, "walk_ahead") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->walk_ahead = (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // 1: the next feed's walk goes ahead of a feed's check, for every feed; 0: a feed's walk waits for the check of the feed before (round 5's schedule)
+	if(strcmp(name, "exact_tier") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->debug_exact_tier = (int)value; return VDL2HIP_OK; }   // 1 (default): the exact sync tier's dense form, k_sync_dense; 0: the word-at-a-time form it replaced, k_sync_exact4 (bit-identical results)
+	if(strcmp(name, "screen_all") == 0) { c->debug_screen_all = value != 0; return VDL2HIP_OK; }   // the screening tier flags every sample (flags are only ever conservative: same frames), so that the exact tier runs at its worst-case density
 	if(strcmp(name, "force_again") == 0) { c->debug_force_again = value != 0; return VDL2HIP_OK; }   // every channel of every long feed is stitched a second time (the referee's walk-again path)
 	if(strcmp(name, "referee") == 0) { if(value && !c->d_refhist) return VDL2HIP_E_INVAL; c->referee = value != 0; return VDL2HIP_OK; }   // (on only where it was on at create: the history ring)
 	if(strcmp(name, "ref_warm") == 0) { if(value < 0 || value > c->ref_T - 4096) return VDL2HIP_E_INVAL; c->ref_warm = value; return VDL2HIP_OK; }
@@ -1336,6 +1350,16 @@ int vdl2hip_debug_k1_prof(unsigned long long out[16], int reset) {
 	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k1_prof), sizeof h) != hipSuccess) return -3;
 	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
 	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k1_prof), h, sizeof h) != hipSuccess) return -3; }
+	return 0;
+}
+#endif
+
+#ifdef VDL2_K3B_PROF
+int vdl2hip_debug_k3b_prof(unsigned long long out[16], int reset) {
+	static unsigned long long h[64][16];
+	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k3b_prof), sizeof h) != hipSuccess) return -3;
+	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
+	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k3b_prof), h, sizeof h) != hipSuccess) return -3; }
 	return 0;
 }
 #endif
