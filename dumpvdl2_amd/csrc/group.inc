@@ -186,8 +186,9 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 	const bool gather = g->exchange == GX_ALLGATHER && n > 1;
 	if(gather) {
 		// ---- all-gather: stripe i crosses member i's own PCIe link, the rest comes from the peers ----
-		const size_t unit = 256;                                        // stripe boundaries on 256 bytes (whole samples in either format)
+		const size_t unit = 256;                                        // stripe boundaries on 256 bytes: whole samples in every format (2, 4 or 8 bytes), and the broadcast sends the block whole
 		const size_t per = ((nbytes + n - 1) / n + unit - 1) / unit * unit;
+		static_assert(unit % 8 == 0, "a stripe ends on a sample boundary");
 		std::vector<size_t> off(n + 1);
 		for(int i = 0; i <= n; i++) off[i] = std::min(nbytes, per * (size_t)i);
 		for(int i = 0; i < n; i++) {

@@ -78,12 +78,21 @@ struct RefChan {
 	uint32_t *stats;                       // [0] scans run, [1] requests answered from the list, [2] requests refused (input no longer held), [3] scans with a shortened run-up, [4 + kind] scans by who asked, [7] channels walked again
 };
 
+// CF32 input (VDL2HIP_FMT_CF32: interleaved I, Q as float32, 8 bytes per complex sample): process_buf_short() / process_buf_uchar() do
+// nothing but fill the float array sbuf[] (src/demod.c:349-365) that every later stage reads, so a CF32 sample IS the reference's
+// sbuf[] value - unscaled, unclipped.  This is the one conversion of the format, and every reader of raw input calls it: a negative
+// zero is read as a positive one.  The integer conversions never produce -0; the scan's shortcut for channels that are not mixed
+// (k_ref_scan_multi: q_dphi) multiplies by (sin, cos) = (0, 1) and would turn (+0, -0) into (+0, +0) where the reference leaves it,
+// and atan2 of a silent sample would land on the other side of its branch cut.
+__device__ __forceinline__ float cf32_level(float x) { return x + 0.0f; }
+
 // one raw sample as process_buf_short() / process_buf_uchar() convert it (src/demod.c:349-365)
 __device__ __forceinline__ bool ref_raw_sample(const RefChan &r, int64_t s, float &re, float &im) {
 	for(int j = r.npiece - 1; j >= 0; j--) {
 		const RefPiece &pc = r.piece[j];
 		if(s >= pc.s0 && s < pc.s0 + pc.n) {
-			if(r.fmt == 1) { const uint32_t w = ((const uint32_t *)pc.p)[s - pc.s0]; re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
+			if(r.fmt == 2) { const float2 w = ((const float2 *)pc.p)[s - pc.s0]; re = cf32_level(w.x); im = cf32_level(w.y); }
+			else if(r.fmt == 1) { const uint32_t w = ((const uint32_t *)pc.p)[s - pc.s0]; re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
 			else { const uint16_t w = ((const uint16_t *)pc.p)[s - pc.s0]; re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)(w >> 8) - 127.5f) / 127.5f; }
 			return true;
 		}
@@ -100,6 +109,8 @@ __device__ __forceinline__ float dpp_wave_shr1_keep(float lane0, float v);
 // The raw samples and NCO table entries of block k + 1 are fetched while block k's recursion runs.)
 typedef __attribute__((address_space(1))) const uint32_t ref_gu32;
 typedef __attribute__((address_space(1))) const uint16_t ref_gu16;
+typedef uint32_t ref_v2u __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) const ref_v2u ref_gu64;       // a CF32 sample: the bits of I and of Q
 typedef __attribute__((address_space(1))) const v4f ref_gf4;
 __device__ __forceinline__ float ref_lane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 // the list of stretches of a channel made exact: (lo / 256 : 32 bits, length / 256 : 16, launch : 16).
@@ -209,15 +220,16 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 	__builtin_amdgcn_s_setprio(VDL2_REF_PRIO);
 
 	const int G = 64 / os, blk = G * os;                        // decimated outputs / input samples per block (os <= kMaxOversample = 32)
-	// raw sample s (this lane's of a block) as a 32-bit word, and its NCO table entry
+	// raw sample s (this lane's of a block) as a 32-bit word (CF32: as two, the bits of I in w and of Q in w2), and its NCO table entry
 	// (a uniform search for the one stretch a whole block lies in, with a single load behind it, was tried: 23.5 against 22.6 ns per sample)
-	auto fetch = [&](int64_t s0, uint32_t &w, v4f &e) {
+	auto fetch = [&](int64_t s0, uint32_t &w, uint32_t &w2, v4f &e) {
 		const int64_t s = s0 + (lane < blk ? lane : 0);
-		w = 0u;
+		w = 0u; w2 = 0u;
 		#pragma unroll
 		for(int j = 0; j < kRefPieces; j++) {
 			if(j < npiece && s >= ps0[j] && s < ps0[j] + pn[j] && s < s_end) {
-				if(fmt == 1) w = ((ref_gu32 *)pp[j])[s - ps0[j]];
+				if(fmt == 2) { const ref_v2u v = ((ref_gu64 *)pp[j])[s - ps0[j]]; w = v.x; w2 = v.y; }
+				else if(fmt == 1) w = ((ref_gu32 *)pp[j])[s - ps0[j]];
 				else w = ((ref_gu16 *)pp[j])[s - ps0[j]];
 			}
 		}
@@ -237,16 +249,17 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 	// its own, so that the slots stay in the registers they were loaded into; the stretch is padded to whole groups of blocks (the
 	// padding reads nothing - fetch() stops at s_end - and stores nothing).
 	constexpr int kRefAhead = 3;
-	uint32_t w_q[kRefAhead]; v4f e_q[kRefAhead];
+	uint32_t w_q[kRefAhead], w2_q[kRefAhead]; v4f e_q[kRefAhead];
 	#pragma unroll
-	for(int k = 0; k < kRefAhead; k++) fetch(s_beg + (int64_t)k * blk, w_q[k], e_q[k]);
+	for(int k = 0; k < kRefAhead; k++) fetch(s_beg + (int64_t)k * blk, w_q[k], w2_q[k], e_q[k]);
 	auto do_block = [&](int64_t sb, auto SLOTC) {
 		constexpr int SLOT = decltype(SLOTC)::value;
-		const uint32_t w = w_q[SLOT]; const v4f e = e_q[SLOT];
-		fetch(sb + (int64_t)kRefAhead * blk, w_q[SLOT], e_q[SLOT]);    // in flight during the next blocks' recursions
+		const uint32_t w = w_q[SLOT], w2 = w2_q[SLOT]; const v4f e = e_q[SLOT];
+		fetch(sb + (int64_t)kRefAhead * blk, w_q[SLOT], w2_q[SLOT], e_q[SLOT]);    // in flight during the next blocks' recursions
 		// ---- this lane's sample: conversion (demod.c:349-365), NCO (:58-72), mixer (:200-203) ----
 		float re, im;
-		if(fmt == 1) { re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
+		if(fmt == 2) { re = cf32_level(__builtin_bit_cast(float, w)); im = cf32_level(__builtin_bit_cast(float, w2)); }
+		else if(fmt == 1) { re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
 		else { re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
 		if(mix) {
 			const uint32_t phi = ((uint32_t)(sb + lane) * dphi) & 0xffffffu;
@@ -327,7 +340,8 @@ __global__ void k_ref_hist(const uint8_t *src, uint64_t n, uint8_t *ring, uint64
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n) return;
 	const uint64_t d = (pos + i) % cap;
-	if(sb == 4) reinterpret_cast<uint32_t *>(ring)[d] = reinterpret_cast<const uint32_t *>(src)[i];
+	if(sb == 8) reinterpret_cast<uint2 *>(ring)[d] = reinterpret_cast<const uint2 *>(src)[i];
+	else if(sb == 4) reinterpret_cast<uint32_t *>(ring)[d] = reinterpret_cast<const uint32_t *>(src)[i];
 	else reinterpret_cast<uint16_t *>(ring)[d] = reinterpret_cast<const uint16_t *>(src)[i];
 }
 
@@ -383,7 +397,7 @@ inline K1Consts make_k1_consts(const BlockForm &bf) {
 }
 
 struct K1Args {
-	const void *in;            // raw IQ block of this feed (cs16 or cu8), device memory
+	const void *in;            // raw IQ block of this feed (cs16, cu8 or cf32), device memory
 	const void *carry;         // raw samples left over from the previous feed
 	uint32_t ncarry;           // number of complex samples in carry
 	uint64_t nlogical;         // ncarry + samples in `in`
@@ -412,8 +426,15 @@ struct K1Args {
 	uint32_t cap, mask, nseg_cap;
 };
 
+// (CF32: the float32 builds of the channeliser - they see no other format, and the other builds never see this one: vdl2hip.hip, launch_chanfir)
+template<bool CF32 = false>
 __device__ __forceinline__ void load_sample(const K1Args &a, int64_t s, float &re, float &im) {
-	if(a.fmt == 1) {   // S16_LE: (float)v / 32768.0f  (demod.c:362-363)
+	if(CF32) {         // the value itself (cf32_level)
+		const float2 *p = (s < (int64_t)a.ncarry) ? (const float2 *)a.carry + s : (const float2 *)a.in + (s - a.ncarry);
+		const float2 w = *p;
+		re = cf32_level(w.x);
+		im = cf32_level(w.y);
+	} else if(a.fmt == 1) {   // S16_LE: (float)v / 32768.0f  (demod.c:362-363)
 		const uint32_t *p = (s < (int64_t)a.ncarry) ? (const uint32_t *)a.carry + s : (const uint32_t *)a.in + (s - a.ncarry);
 		uint32_t w = *p;
 		re = (float)(int16_t)(w & 0xffff) / 32768.0f;
@@ -503,7 +524,16 @@ __global__ void k_u8_level_probe(float *out) { const uint32_t i = threadIdx.x; o
 // ahead and converted without per-sample range checks or divisions, as the s16 tiles of the other build are (round 6c: the generic
 // staging path cost a 256-channel receiver 18 % of its channeliser: 4.46 against 3.77 ms per 16 s).  Only instantiated where the tile
 // prefetch is (kPrefetch below); U8 = false is the code as it was.
-template<int OS, int R, int CR, bool U8 = false>
+// CF32: the builds for complex-float32 input, beside the ones above - a build of its own for every shape, so that the other formats'
+// builds are the code they were, register for register.  Where the tile prefetch exists its tiles too are fetched a tile ahead and staged
+// without per-sample range checks - and without arithmetic but cf32_level(): the staging is data movement; elsewhere it is the generic
+// staging path (load_sample).  A sample is two words, so at oversample 20 the look-ahead is 20 registers where the s16 build's is 10, and
+// that build already sits at the 128-register cap of four resident workgroups.  Measured at 256 channels x 16 s (profiles/cf32_rate.txt;
+// the s16 build: 3.78 ms per launch): the whole tile ahead under the same cap, at the price of 37 spilled registers (the s16 build: 28), 3.89 ms; the
+// first half of the tile ahead and the second asked for at the top of the staging (3 spills) 3.97; the generic path 4.02; the whole
+// tile ahead with three resident workgroups (148 registers, no spills) 4.08.  Hence the first, which is also the other builds' scheme.
+// After the staging the code is the shared code: the tile is float2 whatever the format.
+template<int OS, int R, int CR, bool U8 = false, bool CF32 = false>
 __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MIN_BLOCKS)) void k_chanfir(K1Args a) {
 	static_assert(64 * R == kFixW || R == 1, "the fused fix-up assumes the fix window is the segment's first tile");
 	static_assert(R >= 1 && R <= 2, "the run's outputs are held in two register pairs");
@@ -535,16 +565,25 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 	// and the tile is a whole number of 256-sample rows.
 	constexpr bool kPrefetch = OS != 0 && CR >= 4 && (64 * R * OS + 255) / 256 <= 10 && (64 * R * OS) % 256 == 0;
 	static_assert(!U8 || kPrefetch, "the unsigned-byte build exists where the tile prefetch does");
+	static_assert(!CF32 || !U8, "one format per build");
+	constexpr int kFmt = CF32 ? 2 : U8 ? 0 : 1;               // the sample format this build stages without range checks
 	constexpr int kPre = kPrefetch ? (64 * R * OS) / 256 : 1;
 	constexpr bool kPipeGather = kPrefetch;
 	uint32_t pre[kPre]; bool have_pre = false;
+	float2 pre2[CF32 ? kPre : 1];                            // (the float32 build's look-ahead: two words per sample)
 	#pragma unroll
 	for(int k = 0; k < kPre; k++) pre[k] = 0u;
+	#pragma unroll
+	for(int k = 0; k < (CF32 ? kPre : 1); k++) pre2[k] = make_float2(0.f, 0.f);
 	if(kPrefetch) {
 		const int64_t s0 = (int64_t)seg * a.tiles * (64 * R * (OS ? OS : 1));      // first sample of the segment's first tile
-		have_pre = a.fmt == (U8 ? 0 : 1) && s0 >= (int64_t)a.ncarry && s0 + 64 * R * (OS ? OS : 1) <= (int64_t)a.nlogical && (int64_t)seg * a.tiles * (64 * R) < a.D;
+		have_pre = a.fmt == kFmt && s0 >= (int64_t)a.ncarry && s0 + 64 * R * (OS ? OS : 1) <= (int64_t)a.nlogical && (int64_t)seg * a.tiles * (64 * R) < a.D;
 		if(have_pre) {
-			if constexpr(U8) {
+			if constexpr(CF32) {
+				const float2 *sn = (const float2 *)a.in + (s0 - a.ncarry);
+				#pragma unroll
+				for(int k = 0; k < kPre; k++) pre2[k] = sn[tid + 256 * k];
+			} else if constexpr(U8) {
 				const uint16_t *sn = (const uint16_t *)a.in + (s0 - a.ncarry);
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre[k] = sn[tid + 256 * k];
@@ -598,8 +637,25 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		K1_MARK(ts ? 4 : 0);                                     // 0: prologue (tables, first prefetch); 4: scan, outputs, carry of the previous tile
 		if(ts) __syncthreads();                                  // everyone is done with the previous tile
 		K1_MARK(5);                                              // 5: waiting for the workgroup's other waves before the tile is overwritten
-		const bool fast_now = a.fmt == (U8 ? 0 : 1) && sbase >= (int64_t)a.ncarry && sbase + tile_n <= (int64_t)a.nlogical;
-		if(kPrefetch && U8 && fast_now) {
+		const bool fast_now = a.fmt == kFmt && sbase >= (int64_t)a.ncarry && sbase + tile_n <= (int64_t)a.nlogical;
+		if(CF32 && kPrefetch && fast_now) {
+			// (the float32 build: the same, eight bytes per sample and nothing to convert)
+			const float2 *src = (const float2 *)a.in + (sbase - a.ncarry);
+			#pragma unroll
+			for(int k = 0; k < kPre; k++) {
+				const int t = tid + 256 * k;
+				const float2 w = have_pre ? pre2[CF32 ? k : 0] : src[t];
+				const int l = t / run, m = t - l * run;
+				tile[m * 65 + l] = make_float2(cf32_level(w.x), cf32_level(w.y));
+			}
+			const int64_t snext = sbase + tile_n;
+			have_pre = ts + 1 < a.tiles && (tix + 1) * L < a.D && snext + tile_n <= (int64_t)a.nlogical;
+			if(have_pre) {
+				const float2 *sn = (const float2 *)a.in + (snext - a.ncarry);
+				#pragma unroll
+				for(int k = 0; k < kPre; k++) pre2[CF32 ? k : 0] = sn[tid + 256 * k];
+			}
+		} else if(!CF32 && kPrefetch && U8 && fast_now) {
 			// (the unsigned-byte build: the same, two bytes per sample)
 			const uint16_t *src = (const uint16_t *)a.in + (sbase - a.ncarry);
 			#pragma unroll
@@ -616,7 +672,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre[k] = sn[tid + 256 * k];
 			}
-		} else if(kPrefetch && fast_now) {
+		} else if(!CF32 && kPrefetch && fast_now) {
 			// the usual case - a cs16 tile that lies entirely inside this feed's block: no per-sample range or carry checks
 			const uint32_t *src = (const uint32_t *)a.in + (sbase - a.ncarry);
 			#pragma unroll
@@ -633,7 +689,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre[k] = sn[tid + 256 * k];
 			}
-		} else if(fast_now) {
+		} else if(!CF32 && fast_now) {
 			// (builds without the prefetch) a cs16 tile that lies entirely inside this feed's block: no per-sample range or carry checks
 			const uint32_t *src = (const uint32_t *)a.in + (sbase - a.ncarry);
 			for(int t = tid; t < tile_n; t += 256) {
@@ -645,7 +701,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 			for(int t = tid; t < tile_n; t += 256) {
 				const int64_t sidx = sbase + t;
 				float re = 0.f, im = 0.f;
-				if(sidx < (int64_t)a.nlogical) load_sample(a, sidx, re, im);
+				if(sidx < (int64_t)a.nlogical) load_sample<CF32>(a, sidx, re, im);
 				const int l = t / run, m = t - l * run;
 				tile[m * 65 + l] = make_float2(re, im);
 			}
@@ -863,7 +919,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		for(int t = tid; t < tile_n; t += 256) {
 			const int64_t sidx = sbase + t;
 			float re = 0.f, im = 0.f;
-			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample(a, sidx, re, im);
+			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample<CF32>(a, sidx, re, im);
 			const int l = t / run, m = t - l * run;
 			tile[m * 65 + l] = make_float2(re, im);
 		}
@@ -987,7 +1043,10 @@ __global__ void k_carry(K1Args a, void *carry_out, uint32_t nrem) {
 	const uint32_t i = threadIdx.x;
 	if(i >= nrem) return;
 	const int64_t s = (int64_t)(a.nlogical - nrem) + i;
-	if(a.fmt == 1) {
+	if(a.fmt == 2) {
+		const uint2 *p = (s < (int64_t)a.ncarry) ? (const uint2 *)a.carry + s : (const uint2 *)a.in + (s - a.ncarry);
+		((uint2 *)carry_out)[i] = *p;                                  // (the bits as they are: every reader converts)
+	} else if(a.fmt == 1) {
 		const uint32_t *p = (s < (int64_t)a.ncarry) ? (const uint32_t *)a.carry + s : (const uint32_t *)a.in + (s - a.ncarry);
 		((uint32_t *)carry_out)[i] = *p;
 	} else {
@@ -1863,8 +1922,9 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		// the raw samples of the next PF blocks are in flight at any time (block b's in wq[b % PF]): a block lasts the consumer ~0.6 us,
 		// a load that misses the L2 takes longer - with one block of look-ahead the producers waited for memory, and the consumer for them
 		constexpr int PF = 4;
-		uint32_t wq[PF][NQ];
-		constexpr int SB = FMT == 1 ? 4 : 2;                          // bytes per raw sample
+		// (a CF32 sample is two words - the bits of I in wq, of Q in wq2; the other formats leave wq2 alone and it costs them nothing)
+		uint32_t wq[PF][NQ], wq2[PF][NQ];
+		constexpr int SB = FMT == 2 ? 8 : FMT == 1 ? 4 : 2;           // bytes per raw sample
 		#pragma unroll
 		for(int q = 0; q < NQ; q++) {
 			const int r = pidx + q * kScanProd;
@@ -1872,7 +1932,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 			q_ph0[q] = (uint32_t)q_beg[q];
 			q_len[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sh.len[r]);
 			// a channel that is not mixed (src/demod.c:312: offset_tuning == 0) gets the phase step 0: table entry 0 with fraction 0 is
-			// (sin, cos) = (0, 1) exactly, and multiplying by it leaves a sample exactly as it is (the conversions never produce a negative zero)
+			// (sin, cos) = (0, 1) exactly, and multiplying by it leaves a sample exactly as it is (the integer conversions never produce a negative zero, cf32_level() reads one as a positive zero)
 			q_dphi[q] = (__builtin_amdgcn_readfirstlane((int)sh.flags[r]) & 1) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sh.dphi[r]) : 0u;
 			pre[q] = 0.f; pim[q] = 0.f; q_ptr[q] = nullptr; q_pend[q] = 0u;
 		}
@@ -1889,9 +1949,16 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 				}
 			}
 		};
+		// sample p of request q out of the stretch it lies in
+		auto raw = [&](int q, uint32_t p, uint32_t &w, uint32_t &w2) {
+			const uint8_t *at = q_ptr[q] + (size_t)p * SB;
+			if constexpr(FMT == 2) { const ref_v2u v = *(ref_gu64 *)at; w = v.x; w2 = v.y; }
+			else w = FMT == 1 ? *(ref_gu32 *)at : (uint32_t)*(ref_gu16 *)at;
+		};
 		// the raw sample of request q and block b for this lane (0 past the request's end)
-		auto fetch = [&](int q, uint32_t b) -> uint32_t {
+		auto fetch = [&](int q, uint32_t b, uint32_t &w2) -> uint32_t {
 			const uint32_t p0 = b * (uint32_t)BLK;
+			w2 = 0u;
 			if(p0 >= q_len[q]) return 0u;                                // (uniform)
 			const uint32_t n = q_len[q] - p0 < (uint32_t)BLK ? q_len[q] - p0 : (uint32_t)BLK;
 			if(p0 + n > q_pend[q]) {
@@ -1899,13 +1966,13 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 				uint32_t w = 0u;
 				for(uint32_t i = 0; i < n; i++) {
 					if(p0 + i >= q_pend[q]) locate(q, p0 + i);
-					if(q_ptr[q] && (uint32_t)lane == i) w = FMT == 1 ? *(ref_gu32 *)(q_ptr[q] + (size_t)(p0 + i) * SB) : (uint32_t)*(ref_gu16 *)(q_ptr[q] + (size_t)(p0 + i) * SB);
+					if(q_ptr[q] && (uint32_t)lane == i) raw(q, p0 + i, w, w2);
 					if(!q_ptr[q]) q_pend[q] = p0 + i + 1;
 				}
 				return w;
 			}
 			uint32_t w = 0u;
-			if((uint32_t)lane < n) w = FMT == 1 ? *(ref_gu32 *)(q_ptr[q] + (size_t)(p0 + (uint32_t)lane) * SB) : (uint32_t)*(ref_gu16 *)(q_ptr[q] + (size_t)(p0 + (uint32_t)lane) * SB);
+			if((uint32_t)lane < n) raw(q, p0 + (uint32_t)lane, w, w2);
 			return w;
 		};
 		// block b of all its requests (the raw samples are in wq[SLOT]): the NCO table entries first, all of them, then the arithmetic;
@@ -1915,9 +1982,9 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 #if defined(VDL2_SCAN_EXP) && VDL2_SCAN_EXP == 1
 			return;
 #endif
-			uint32_t wc[NQ]; v4f eq[NQ]; uint32_t phq[NQ];
+			uint32_t wc[NQ], wc2[NQ]; v4f eq[NQ]; uint32_t phq[NQ];
 			#pragma unroll
-			for(int q = 0; q < NQ; q++) { wc[q] = wq[SLOT][q]; wq[SLOT][q] = fetch(q, b + PF); }
+			for(int q = 0; q < NQ; q++) { wc[q] = wq[SLOT][q]; wc2[q] = wq2[SLOT][q]; wq[SLOT][q] = fetch(q, b + PF, wq2[SLOT][q]); }
 			#pragma unroll
 			for(int q = 0; q < NQ; q++) {
 				phq[q] = ((q_ph0[q] + b * (uint32_t)BLK + (uint32_t)lane) * q_dphi[q]) & 0xffffffu;
@@ -1929,7 +1996,8 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 			#pragma unroll
 			for(int q = 0; q < NQ; q++) {
 				const uint32_t w = wc[q];
-				if(FMT == 1) { re[q] = (float)(int16_t)(w & 0xffff) / 32768.0f; im[q] = (float)(int16_t)(w >> 16) / 32768.0f; }
+				if(FMT == 2) { re[q] = cf32_level(__builtin_bit_cast(float, w)); im[q] = cf32_level(__builtin_bit_cast(float, wc2[q])); }
+				else if(FMT == 1) { re[q] = (float)(int16_t)(w & 0xffff) / 32768.0f; im[q] = (float)(int16_t)(w >> 16) / 32768.0f; }
 				else { re[q] = ((float)(w & 0xff) - 127.5f) / 127.5f; im[q] = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
 				const float F = (float)(phq[q] & 0xffffu);
 				const float sn = eq[q].x + eq[q].z * F, cs = eq[q].y + eq[q].w * F;
@@ -1951,7 +2019,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		#pragma unroll
 		for(int k = 0; k < PF; k++) {
 			#pragma unroll
-			for(int q = 0; q < NQ; q++) wq[k][q] = fetch(q, (uint32_t)k);
+			for(int q = 0; q < NQ; q++) wq[k][q] = fetch(q, (uint32_t)k, wq2[k][q]);
 		}
 		produce(0u, std::integral_constant<int, 0>());
 		lds_barrier();

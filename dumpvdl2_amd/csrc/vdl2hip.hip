@@ -159,7 +159,7 @@ struct vdl2hip_ctx {
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) { \
 	fprintf(stderr, "vdl2hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return VDL2HIP_E_DEVICE; } } while(0)
 
-static size_t sample_bytes(int fmt) { return fmt == VDL2HIP_FMT_S16LE ? 4 : 2; }
+static size_t sample_bytes(int fmt) { return fmt == VDL2HIP_FMT_CF32 ? 8 : fmt == VDL2HIP_FMT_S16LE ? 4 : 2; }
 
 // Every entry point works on the context's own device whatever the calling thread's current device is (a process may hold
 // receivers on several GPUs), and leaves the thread's device as it found it.
@@ -183,6 +183,16 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 	dim3 grid((unsigned)(nseg8 * b.gy)), block(256);
 	// e0/e1 (profiling only, else null): the runtime stamps them with the kernel's own start and stop, so the roofline figure is
 	// the kernel's duration and not the time the launch spent queued behind other streams' work
+	// (float32 input: builds of its own, so that the integer formats' builds stay the code they were; with four channels per wavefront at
+	// oversample 20 and 10 the one that fetches its tiles ahead and stages them as they are)
+	if(c->fmt == VDL2HIP_FMT_CF32) {
+		switch(cr) {
+			case 4: hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
+			case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
+			default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
+		}
+		return;
+	}
 	switch(cr) {
 		case 4:
 			// (unsigned-byte input where the tile prefetch exists: the build that fetches and converts its tiles the way the s16 build does)
@@ -448,7 +458,8 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 	return D > 0 && D < 2 * c->seg_min && nseg < 2;
 }
 #define LAUNCH_SCAN_MULTI(how, ...) do { \
-	if(c->fmt == 1) { if(c->os == 20) how((k_ref_scan_multi<1, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<1, 10>), __VA_ARGS__); else how((k_ref_scan_multi<1, 0>), __VA_ARGS__); } \
+	if(c->fmt == 2) { if(c->os == 20) how((k_ref_scan_multi<2, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<2, 10>), __VA_ARGS__); else how((k_ref_scan_multi<2, 0>), __VA_ARGS__); } \
+	else if(c->fmt == 1) { if(c->os == 20) how((k_ref_scan_multi<1, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<1, 10>), __VA_ARGS__); else how((k_ref_scan_multi<1, 0>), __VA_ARGS__); } \
 	else { if(c->os == 20) how((k_ref_scan_multi<0, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<0, 10>), __VA_ARGS__); else how((k_ref_scan_multi<0, 0>), __VA_ARGS__); } } while(0)
 // Referee: the listed stretches (`sq`, or the decisions `rq` whose stretches they are; *n of them, at most cap) are made the reference's own,
 // many side by side, and those of them that had not met their witness - a few in ten thousand - are listed in `retry` and scanned again
@@ -751,7 +762,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	if(!cfg || !out || cfg->struct_size < sizeof(vdl2hip_cfg) || !cfg->freqs || cfg->nchan == 0) return VDL2HIP_E_INVAL;
 	if(cfg->oversample == 0 || cfg->oversample > (uint32_t)kMaxOversample) return VDL2HIP_E_INVAL;
-	if(cfg->sample_fmt != VDL2HIP_FMT_U8 && cfg->sample_fmt != VDL2HIP_FMT_S16LE) return VDL2HIP_E_INVAL;
+	if(cfg->sample_fmt != VDL2HIP_FMT_U8 && cfg->sample_fmt != VDL2HIP_FMT_S16LE && cfg->sample_fmt != VDL2HIP_FMT_CF32) return VDL2HIP_E_INVAL;
 	uint32_t first = cfg->chan_first, count = cfg->chan_count ? cfg->chan_count : cfg->nchan - first;
 	if(first >= cfg->nchan || first + count > cfg->nchan || count > (uint32_t)kK5MaxChan) return VDL2HIP_E_INVAL;
 	*out = nullptr;
@@ -826,7 +837,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	}
 	DEV_ALLOC(c->d_bf, sizeof(BlockForm)); DEV_ALLOC(c->d_lut, sizeof(Lut4) * 256); DEV_ALLOC(c->d_tab, sizeof(Tables));
 	DEV_ALLOC(c->d_dphi, 4 * count); DEV_ALLOC(c->d_freq, 4 * count); DEV_ALLOC(c->d_ppmthr, 4 * count);
-	DEV_ALLOC(c->d_carry[0], 4 * kMaxOversample); DEV_ALLOC(c->d_carry[1], 4 * kMaxOversample);
+	DEV_ALLOC(c->d_carry[0], sb * kMaxOversample); DEV_ALLOC(c->d_carry[1], sb * kMaxOversample);       // fewer than `oversample` samples left over
 	const size_t nring = (size_t)count * cap;
 	DEV_ALLOC(c->d_y, nring * sizeof(cf32)); DEV_ALLOC(c->d_pf, nring * sizeof(cf32));
 	DEV_ALLOC(c->d_cand, nring / 8); DEV_ALLOC(c->d_flag, nring / 8);
@@ -990,6 +1001,8 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	c->cold.n = 0;
 	if(parts) {
 		const size_t piece = (nbytes / kColdParts) & ~(size_t)4095;
+		static_assert(4096 % 8 == 0 && 4096 % 4 == 0, "a piece of a cold-start block ends on a sample boundary in every format");
+		if(piece % sample_bytes(c->fmt)) return VDL2HIP_E_INVAL;
 		size_t off = 0;
 		for(int p = 0; p < kColdParts; p++) {
 			const size_t len = p == kColdParts - 1 ? nbytes - off : piece;

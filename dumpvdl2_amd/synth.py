@@ -324,7 +324,7 @@ def _random_frames(rng: np.random.Generator, cfg: SynthConfig) -> List[bytes]:
 
 
 def synthesize(cfg: SynthConfig, dtype=np.int16, workers: int = 1):
-    """Return (iq, bursts): iq is interleaved I,Q int16 (2*N values), bursts the ground truth.
+    """Return (iq, bursts): iq is interleaved I,Q (2*N values) as int16, uint8 or - unquantised - float32; bursts the ground truth.
 
     workers > 1 computes the channels' bursts on that many threads (numpy's FFTs and array operations release the GIL);
     they are still added into the capture one channel after the other, so the result is the same bytes as with workers = 1."""
@@ -366,8 +366,10 @@ def synthesize(cfg: SynthConfig, dtype=np.int16, workers: int = 1):
         out = np.clip(np.rint(iq * 32768.0), -32768, 32767).astype(np.int16)
     elif dtype == np.uint8:
         out = np.clip(np.rint(iq * 127.5 + 127.5), 0, 255).astype(np.uint8)
+    elif dtype == np.float32:
+        out = iq                        # the waveform unquantised (full scale 1.0): what a FMT_CF32 receiver takes
     else:
-        raise ValueError("dtype must be int16 or uint8")
+        raise ValueError("dtype must be int16, uint8 or float32")
     return out, bursts
 
 

@@ -16,7 +16,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvdl2hip.so")
 
-FMT_U8, FMT_S16LE = 0, 1
+FMT_U8, FMT_S16LE, FMT_CF32 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_FMT_* (CF32: np.complex64 / interleaved float32, full scale 1.0)
 COUNTER_NAMES = [
     "demod.sync.good", "decoder.crc.good", "decoder.crc.bad", "decoder.errors.no_header",
     "decoder.errors.too_long", "decoder.errors.no_fec", "decoder.errors.data_truncated",
@@ -201,7 +201,8 @@ class Receiver:
             pass
 
     def feed(self, raw) -> None:
-        """process_buf_uchar()/process_buf_short(): one block of raw IQ bytes from host memory."""
+        """process_buf_uchar()/process_buf_short(): one block of raw IQ from host memory - any array, taken as its bytes (FMT_CF32: np.complex64
+        or interleaved np.float32)."""
         a = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
         self._chk(self.L.vdl2hip_feed(self.h, a.ctypes.data, a.size), "vdl2hip_feed")
 
@@ -213,7 +214,7 @@ class Receiver:
         self._chk(self.L.vdl2hip_feed_device(self.h, C.c_void_p(dev_ptr), nbytes), "vdl2hip_feed_device")
 
     def feed_tensor(self, t) -> None:
-        """a block resident on this receiver's device (torch tensor of raw bytes / int16 values)"""
+        """a block resident on this receiver's device (torch tensor of raw bytes / int16 values / float32 or complex64 values)"""
         self.feed_device(t.data_ptr(), t.numel() * t.element_size())
 
     def feed_pinned_tensor(self, t) -> None:

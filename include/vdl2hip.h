@@ -33,11 +33,24 @@ extern "C" {
                                  *    taken on the reference's own samples): vdl2hip_stats grew by referee_*; vdl2hip_get_stats_sized() for callers
                                  *    built against an older vdl2hip_stats.  (Since ABI 4 chanfir_ms / chanfir_launches / chan_samples cover only
                                  *    the TIMED channeliser launches - profiling on, cold-start feeds excluded - not every launch.)
-                                 * 6: vdl2hip_stats.referee_redone_next (a feed's walk no longer waits for the check of the feed before) */
+                                 * 6: vdl2hip_stats.referee_redone_next (a feed's walk no longer waits for the check of the feed before)
+                                 *    VDL2HIP_FMT_CF32: one more accepted value of vdl2hip_cfg.sample_fmt - no structure, no entry point and no
+                                 *    result for the other formats changed, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
 #define VDL2HIP_FMT_S16LE  1
+/* Not in the reference's enum: complex float32 - interleaved I, Q as IEEE float32 in host byte order, 8 bytes per complex sample (GNU
+ * Radio file sinks, SoapySDR's default stream format).  process_buf_uchar() / process_buf_short() do nothing but fill the float array
+ * sbuf[] that every later stage reads (src/demod.c:309-310,349-365): a CF32 sample IS that sbuf[] value, taken as it is.
+ *  - Full scale is 1.0.  Values are used unscaled and unclipped; beyond +-1 is legal, frame_pwr_dbfs simply goes above 0.
+ *    k / 32768.0f gives exactly what the int16 k gives, (b - 127.5f) / 127.5f computed in float32 what the byte b gives.
+ *  - A negative zero is read as a positive zero (x + 0.0f at the load), as the integer conversions never produce one.
+ *  - Non-finite samples (NaN, infinities) are the caller's error and are not looked for: they poison that channel's filter state
+ *    for good, as they would the reference's.
+ *  - A feed is truncated to whole samples (8 bytes), as it is to 4 or 2 in the other formats; vdl2hip_feed_device() wants an 8-byte
+ *    aligned pointer; max_block_bytes stays in bytes (default 320000 = 40000 samples). */
+#define VDL2HIP_FMT_CF32   2
 
 #define VDL2HIP_OK            0
 #define VDL2HIP_E_INVAL      -1   /* bad argument / configuration */
@@ -181,7 +194,8 @@ const char *vdl2hip_strerror(int err);
 int  vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out);
 void vdl2hip_destroy(vdl2hip_ctx *ctx);
 
-/* = process_buf_uchar()/process_buf_short(): one block of raw IQ from host memory.
+/* = process_buf_uchar()/process_buf_short(): one block of raw IQ from host memory (cfg.sample_fmt says what the bytes are;
+ * a trailing part of a sample is dropped).
  * Returns after the block has been queued on the device (the copy out of `buf` is complete).  The copy runs on a
  * stream of its own into one of six device buffers (one per block in flight), so it overlaps the kernels of the blocks fed before. */
 int  vdl2hip_feed(vdl2hip_ctx *ctx, const void *buf, size_t nbytes);
@@ -192,7 +206,7 @@ int  vdl2hip_feed(vdl2hip_ctx *ctx, const void *buf, size_t nbytes);
  * for its whole transfer; results do not depend on it.) */
 int  vdl2hip_feed_pinned(vdl2hip_ctx *ctx, const void *buf, size_t nbytes);
 /* Same, for a block that already lives in this device's memory (e.g. the
- * destination of an RCCL broadcast).  The block must stay valid until it has been drained
+ * destination of an RCCL broadcast).  `dev_buf` must be aligned to a sample (2, 4 or 8 bytes), else VDL2HIP_E_INVAL.  The block must stay valid until it has been drained
  * (vdl2hip_sync(), or a drain that covers it - see vdl2hip_set_drain_lag). */
 int  vdl2hip_feed_device(vdl2hip_ctx *ctx, const void *dev_buf, size_t nbytes);
 

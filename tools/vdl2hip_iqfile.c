@@ -8,7 +8,8 @@
  *                                 samples - 16 s16 blocks at oversample 20, 4 u8 blocks at 10; 1 = the reference's block by block).
  *                                 A block is microseconds of GPU work behind a fixed chain of launches (and, now and then, a 2 ms
  *                                 scan of the referee's): collected blocks give the same frames at 5-7x the rate
- *   --sample-format U8|S16_LE     (the reference's token is S16_LE, src/dumpvdl2.c:849)
+ *   --sample-format U8|S16_LE|CF32  (the reference's token is S16_LE, src/dumpvdl2.c:849; CF32 - interleaved float32 I, Q, full scale 1.0,
+ *                                 what GNU Radio file sinks and SoapySDR write - is this library's own, VDL2HIP_FMT_CF32)
  *   --oversample <n>  --centerfreq <Hz>  --max-ppm <x>  --station-id <s>
  *   --avlc-filter                 deliver only frames that pass avlc_parse()'s first checks (length, FCS) - src/avlc.c:168-187
  *   --statsd-out <path>           at exit, write the per-channel counters in the reference's statsd names
@@ -67,6 +68,7 @@ int main(int argc, char **argv) {
 			NEEDARG(); i++; fmt_set = 1;
 			if(!strcmp(argv[i], "U8")) fmt = VDL2HIP_FMT_U8;
 			else if(!strcmp(argv[i], "S16_LE")) fmt = VDL2HIP_FMT_S16LE;
+			else if(!strcmp(argv[i], "CF32")) fmt = VDL2HIP_FMT_CF32;
 			else { fprintf(stderr, "Unknown sample format\n"); return 1; }
 		}
 		else if(!strcmp(a, "--oversample")) { NEEDARG(); oversample = (uint32_t)strtoul(argv[++i], NULL, 10); }
@@ -81,7 +83,7 @@ int main(int argc, char **argv) {
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
 	}
 	(void)fmt_set;
-	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE] [--oversample n] [--centerfreq Hz] "
+	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
@@ -103,7 +105,7 @@ int main(int argc, char **argv) {
 	memset(&cfg, 0, sizeof cfg);
 	cfg.struct_size = sizeof cfg; cfg.centerfreq = centerfreq; cfg.oversample = oversample; cfg.sample_fmt = fmt;
 	if(per_feed == 0) {
-		const uint32_t dec = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_S16LE ? 4u : 2u) / oversample;      /* decimated samples per block */
+		const uint32_t dec = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_CF32 ? 8u : fmt == VDL2HIP_FMT_S16LE ? 4u : 2u) / oversample;      /* decimated samples per block */
 		per_feed = dec ? (64000u + dec - 1) / dec : 1;
 	}
 	if(per_feed > 64) per_feed = 64;
