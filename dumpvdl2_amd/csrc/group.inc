@@ -100,8 +100,11 @@ void vdl2hip_group_destroy(vdl2hip_group *g) {
 	delete g;
 }
 
-int vdl2hip_group_create(const vdl2hip_cfg *cfg, const int32_t *devices, uint32_t ndev, vdl2hip_group **out) {
-	if(!cfg || !out || !devices || ndev == 0 || ndev > 64 || cfg->struct_size < sizeof(vdl2hip_cfg) || !cfg->freqs || cfg->nchan < ndev) return VDL2HIP_E_INVAL;
+int vdl2hip_group_create(const vdl2hip_cfg *cfg_in, const int32_t *devices, uint32_t ndev, vdl2hip_group **out) {
+	vdl2hip_cfg cfg_v;
+	if(cfg_read(cfg_in, cfg_v) != VDL2HIP_OK) return VDL2HIP_E_INVAL;      // (a 56-byte structure, from before input_rate, included)
+	const vdl2hip_cfg *cfg = &cfg_v;
+	if(!out || !devices || ndev == 0 || ndev > 64 || !cfg->freqs || cfg->nchan < ndev) return VDL2HIP_E_INVAL;
 	if(cfg->chan_first != 0 || cfg->chan_count != 0) return VDL2HIP_E_INVAL;      // the group does the sharding
 	*out = nullptr;
 	DeviceGuard guard;
@@ -280,7 +283,7 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 	int rc = VDL2HIP_OK;
 	for(int i = 0; i < n; i++) {
 		GRPCHK(hipSetDevice(g->dev[i]));
-		int r = feed_common(g->ctx[i], g->blk[k][i], nbytes);
+		int r = feed_block(g->ctx[i], g->blk[k][i], nbytes);      // (every member resamples the whole block itself, where the receiver resamples)
 		if(r != VDL2HIP_OK) { g->failed = true; rc = r; break; }
 	}
 	g->feed_no++;

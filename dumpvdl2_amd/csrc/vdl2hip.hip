@@ -15,6 +15,8 @@
 #include <vector>
 #include "../../include/vdl2hip.h"
 #include "kernels.h"
+#include "resample.h"
+#include "resample_design.h"
 #include "tables.h"
 
 using namespace vdl2;
@@ -90,12 +92,24 @@ struct OutSlot {
 	// second walks need of the first: its arguments, segmentation and speculative walks; has_chk: the walk noted decisions to a list that is checked
 	bool rest_pending = false, has_chk = false; int nseg = 1; int64_t seglen = 0; K4Args k4{}; SpecOut *d_spec_of = nullptr;
 	hipEvent_t ev_stitch = nullptr, ev_chk = nullptr; uint32_t *d_rqflag2 = nullptr;
+	hipEvent_t ev_rs[2] = {}; bool rs_timed = false;   // resampling receivers: start / stop of this feed's k_resample (profiling level 2)
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
 struct vdl2hip_ctx {
 	vdl2hip_cfg cfg{};
 	int C = 0, chan_first = 0, os = 0, fmt = 0, run = kRun, cr = 1;
+	// fmt: what the channeliser and the referee read; in_fmt: what the caller feeds.  They differ only for a receiver that resamples
+	// (cfg.input_rate): its blocks go through k_resample into a buffer of the feed's slot, and the rest of the receiver is a
+	// VDL2HIP_FMT_CF32 receiver fed that buffer.
+	int in_fmt = 0;
+	struct {
+		bool on = false; uint32_t L = 0, M = 0, T = 0, span_cap = 0; size_t lds = 0; bool taps_lds = false;
+		float *d_taps = nullptr; float2 *d_tail[2] = {nullptr, nullptr}; int tail_sel = 0;
+		float2 *d_out[kSlots] = {}; uint64_t cap = 0;                 // per slot: a feed's resampled block (samples)
+		uint64_t first[kSlots] = {}, count[kSlots] = {};              // ... and which part of r[] it holds
+		uint64_t n_in = 0, n_out = 0;                                 // samples taken / made so far
+	} rs;
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi;
 	LpfCoeffs lpf{};
@@ -214,6 +228,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
 	HIPCHK(hipEventSynchronize(sl.done));
 	sl.pending = false;
+	if(sl.rs_timed) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->stats.resample_ms += ms; else (void)hipGetLastError(); sl.rs_timed = false; }
 	if(c->profiling && sl.ev_valid) {
 		hipEvent_t *ev = sl.ev;
 		float ms = 0.f;
@@ -445,6 +460,46 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	{ int r = launch_back(c, sl); if(r != VDL2HIP_OK) return r; }
 	HIPCHK(hipGetLastError());
 	return VDL2HIP_OK;
+}
+
+// One block of the caller's IQ, in device memory and ordered ahead of the front stream's next work.  A receiver that resamples
+// (cfg.input_rate) turns it into this feed's block of r[] first - K0, k_resample, on the front stream into the buffer of the feed's
+// slot, which stays as it is until the slot comes round again: the referee reads it as it reads any block - and is a CF32 receiver
+// fed that block from there on.
+template<int FMT>
+static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
+	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
+}
+static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
+	if(!c->rs.on) return feed_common(c, dev_in, nbytes, in_parts);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	auto &rs = c->rs;
+	const int k = (int)(c->feed_no % kSlots);
+	OutSlot &sl = c->slot[k];
+	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // the slot's block of r[] is about to be overwritten
+	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
+	// outputs n with b_n = floor(n M / L) <= N - 1 exist after N input samples: ceil(N L / M) of them (64 bits: 2^50 samples)
+	const uint64_t N0 = rs.n_in, N1 = N0 + nin, n0 = rs.n_out, n1 = (N1 * rs.L + rs.M - 1) / rs.M, nout = n1 - n0;
+	if(nout > rs.cap) return VDL2HIP_E_TOOBIG;
+	K0Args a{};
+	a.in = dev_in; a.tail_in = rs.d_tail[rs.tail_sel]; a.tail_out = rs.d_tail[rs.tail_sel ^ 1]; a.taps = rs.d_taps; a.out = rs.d_out[k];
+	a.q0 = n0 % rs.L; a.t0 = n0 * rs.M - N0 * rs.L;                  // b_{n0} >= N0: output n0 is the first that needed a sample of this block
+	a.nin = (uint32_t)nin; a.nout = (uint32_t)nout; a.L = rs.L; a.M = rs.M; a.T = rs.T; a.span_cap = rs.span_cap;
+	const uint64_t per = (uint64_t)kResTile * kResTiles;
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nout + per - 1) / per);       // (no output: workgroup 0 still moves the tail on)
+	const bool timed = c->profiling >= 2;
+	hipEvent_t e0 = timed ? sl.ev_rs[0] : nullptr, e1 = timed ? sl.ev_rs[1] : nullptr;
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, e0, e1);
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, e0, e1);
+	else launch_resample<0>(c, a, grid, e0, e1);
+	HIPCHK(hipGetLastError());
+	sl.rs_timed = timed;
+	rs.tail_sel ^= 1; rs.first[k] = n0; rs.count[k] = nout; rs.n_in = N1; rs.n_out = n1;
+	int r = feed_common(c, rs.d_out[k], (size_t)nout * sizeof(float2));
+	c->stats.input_samples += nin - nout;                           // (feed_common counted the block it saw) the caller's samples
+	c->stats.resampled_samples += nout;
+	return r;
 }
 
 // The burst-rate back end of one feed (K4 walk, K4b noise floor, K5 burst decoder, frame finish), on three streams of its own so
@@ -727,6 +782,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 		for(void *p : q) if(p) (void)hipFree(p);
 		if(sl.ev_stitch) (void)hipEventDestroy(sl.ev_stitch);
 		if(sl.ev_chk) (void)hipEventDestroy(sl.ev_chk);
+		for(auto &e : sl.ev_rs) if(e) (void)hipEventDestroy(e);
 		if(sl.h_mail) (void)hipHostFree(sl.h_mail);
 		if(sl.done) (void)hipEventDestroy(sl.done);
 		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
@@ -738,6 +794,8 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	if(c->h_stage) (void)hipHostFree(c->h_stage);
 	for(auto &p : c->d_in) if(p) (void)hipFree(p);
 	for(auto &p : c->d_ref) if(p) (void)hipFree(p);
+	for(auto &p : c->rs.d_out) if(p) (void)hipFree(p);
+	{ void *q[] = { c->rs.d_taps, c->rs.d_tail[0], c->rs.d_tail[1] }; for(void *p : q) if(p) (void)hipFree(p); }
 	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
 	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
 	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
@@ -759,12 +817,35 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	delete c;
 }
 
-int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
-	if(!cfg || !out || cfg->struct_size < sizeof(vdl2hip_cfg) || !cfg->freqs || cfg->nchan == 0) return VDL2HIP_E_INVAL;
+// The caller's configuration as this build's structure: one that ends before input_rate (struct_size 56, built against the header
+// before it) is taken with input_rate 0.
+static int cfg_read(const vdl2hip_cfg *in, vdl2hip_cfg &cfg) {
+	if(!in || in->struct_size < VDL2HIP_CFG_SIZE_V1) return VDL2HIP_E_INVAL;
+	memset(&cfg, 0, sizeof cfg);
+	memcpy(&cfg, in, in->struct_size >= sizeof(vdl2hip_cfg) ? sizeof(vdl2hip_cfg) : (size_t)VDL2HIP_CFG_SIZE_V1);
+	cfg.struct_size = sizeof(vdl2hip_cfg); cfg.reserved0 = 0;
+	return cfg.reserved1 ? VDL2HIP_E_INVAL : VDL2HIP_OK;
+}
+
+int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
+	vdl2hip_cfg cfg_v;
+	if(!out || cfg_read(cfg_in, cfg_v) != VDL2HIP_OK) return VDL2HIP_E_INVAL;
+	const vdl2hip_cfg *cfg = &cfg_v;
+	if(!cfg->freqs || cfg->nchan == 0) return VDL2HIP_E_INVAL;
 	if(cfg->oversample == 0 || cfg->oversample > (uint32_t)kMaxOversample) return VDL2HIP_E_INVAL;
 	if(cfg->sample_fmt != VDL2HIP_FMT_U8 && cfg->sample_fmt != VDL2HIP_FMT_S16LE && cfg->sample_fmt != VDL2HIP_FMT_CF32) return VDL2HIP_E_INVAL;
 	uint32_t first = cfg->chan_first, count = cfg->chan_count ? cfg->chan_count : cfg->nchan - first;
 	if(first >= cfg->nchan || first + count > cfg->nchan || count > (uint32_t)kK5MaxChan) return VDL2HIP_E_INVAL;
+	// a receiver that resamples: the ratio must be one the resampler takes, and a block must stay a block
+	const bool resample = cfg->input_rate != 0 && cfg->input_rate != (uint32_t)kSymbolRate * kSps * cfg->oversample;
+	ResamplerDesign rd;
+	uint64_t rs_max_out = 0;
+	if(resample) {
+		if(!design_resampler(cfg->input_rate, (uint32_t)kSymbolRate * kSps * cfg->oversample, rd, false)) return VDL2HIP_E_INVAL;
+		const uint64_t max_in = (cfg->max_block_bytes ? cfg->max_block_bytes : 320000u) / sample_bytes((int)cfg->sample_fmt);
+		rs_max_out = (max_in * rd.L + rd.M - 1) / rd.M + 1;
+		if(rs_max_out >= (1ull << 31)) return VDL2HIP_E_INVAL;
+	}
 	*out = nullptr;
 	int ndev = 0;
 	if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -778,6 +859,8 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 	if(!c) return VDL2HIP_E_NOMEM;
 	c->cfg = *cfg; c->cfg.freqs = nullptr;
 	c->C = (int)count; c->chan_first = (int)first; c->os = (int)cfg->oversample; c->fmt = (int)cfg->sample_fmt;
+	c->in_fmt = c->fmt;
+	if(resample) { c->rs.on = true; c->fmt = VDL2HIP_FMT_CF32; }    // what the channeliser and the referee read is r[]
 	c->freqs.assign(cfg->freqs + first, cfg->freqs + first + count);
 	const uint32_t fs = (uint32_t)kSymbolRate * kSps * cfg->oversample;
 	c->lpf = design_lpf(8000.f / (float)fs, 0.5f);                // input_lpf_init(), demod.c:45-46,367-370
@@ -790,7 +873,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 
 	const uint32_t max_bytes = cfg->max_block_bytes ? cfg->max_block_bytes : 320000u;
 	const size_t sb = sample_bytes(c->fmt);
-	const uint64_t max_samples = max_bytes / sb + c->os;
+	const uint64_t max_samples = (resample ? rs_max_out : max_bytes / sb) + c->os;
 	const uint64_t dmax = max_samples / c->os + 1;
 	uint32_t cap = 1; while(cap < kSlots * dmax + kHistory + 1024) cap <<= 1;   // kSlots feeds may be in flight (fronts of i+1, i+2 over back of i)
 	c->cap = cap;
@@ -836,6 +919,23 @@ int vdl2hip_create(const vdl2hip_cfg *cfg, vdl2hip_ctx **out) {
 		DEV_CHK(hipEventCreate(&sl.ev_front));
 	}
 	DEV_ALLOC(c->d_bf, sizeof(BlockForm)); DEV_ALLOC(c->d_lut, sizeof(Lut4) * 256); DEV_ALLOC(c->d_tab, sizeof(Tables));
+	if(resample) {
+		auto &rs = c->rs;
+		if(!design_resampler(cfg->input_rate, fs, rd)) { vdl2hip_destroy(c); return VDL2HIP_E_INVAL; }
+		rs.L = rd.L; rs.M = rd.M; rs.T = rd.T; rs.cap = rs_max_out;
+		rs.span_cap = (uint32_t)((255ull * rs.M + rs.L - 1) / rs.L) + rs.T;             // a tile's 256 outputs: the span of their b, and the T - 1 samples before
+		const size_t tap_bytes = (size_t)rs.L * rs.T * sizeof(float);
+		rs.taps_lds = tap_bytes <= kResTapsLds;
+		rs.lds = (size_t)rs.span_cap * sizeof(float2) + (rs.taps_lds ? tap_bytes : 0);
+		// walk order (resample.h): column q of the table is phase (q M) mod L, the phase of every output n with n mod L = q
+		std::vector<float> walk((size_t)rs.L * rs.T);
+		for(uint32_t j = 0; j < rs.T; j++) for(uint32_t q = 0; q < rs.L; q++) walk[(size_t)j * rs.L + q] = rd.taps[(size_t)j * rs.L + (size_t)((uint64_t)q * rs.M % rs.L)];
+		DEV_ALLOC(rs.d_taps, tap_bytes);
+		DEV_CHK(hipMemcpy(rs.d_taps, walk.data(), tap_bytes, hipMemcpyHostToDevice));
+		for(auto &t : rs.d_tail) { DEV_ALLOC(t, (size_t)rs.T * sizeof(float2)); DEV_CHK(hipMemset(t, 0, (size_t)rs.T * sizeof(float2))); }   // x[i < 0] = 0
+		for(auto &o : rs.d_out) DEV_ALLOC(o, (size_t)rs.cap * sizeof(float2) + 16);
+		for(auto &sl : c->slot) for(auto &e : sl.ev_rs) DEV_CHK(hipEventCreate(&e));
+	}
 	DEV_ALLOC(c->d_dphi, 4 * count); DEV_ALLOC(c->d_freq, 4 * count); DEV_ALLOC(c->d_ppmthr, 4 * count);
 	DEV_ALLOC(c->d_carry[0], sb * kMaxOversample); DEV_ALLOC(c->d_carry[1], sb * kMaxOversample);       // fewer than `oversample` samples left over
 	const size_t nring = (size_t)count * cap;
@@ -982,7 +1082,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	if(nbytes == 0) return VDL2HIP_OK;                             // process_buf_*: len == 0 is a no-op (demod.c:341,358)
 	if(nbytes > c->in_cap) return VDL2HIP_E_TOOBIG;
-	nbytes -= nbytes % sample_bytes(c->fmt);
+	nbytes -= nbytes % sample_bytes(c->in_fmt);
 	if(c->pinned_pending) { HIPCHK(hipEventSynchronize(c->pinned_pending)); c->pinned_pending = nullptr; }
 	const int k = (int)(c->feed_no % kSlots);
 	{ int r = collect_slot(c, c->slot[k]); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
@@ -996,7 +1096,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	// Nothing in flight and a large block from page-locked memory (the first block of a stream, or of a timed region): the copy is cut in
 	// kColdParts pieces and the channeliser follows them piece by piece (feed_common), instead of idling for the whole transfer -
 	// 2.6 ms for a 134 MB block.  In a running stream the copy of block i+1 is hidden behind the kernels of block i and goes in one piece.
-	bool parts = !wait_copy && nbytes >= kColdMinBytes;
+	bool parts = !wait_copy && nbytes >= kColdMinBytes && !c->rs.on;      // (a block that is resampled goes through k_resample whole)
 	for(auto &sl : c->slot) if(sl.pending) parts = false;
 	c->cold.n = 0;
 	if(parts) {
@@ -1030,7 +1130,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 		c->pinned_pending = c->ev_copied[k];
 		if(!parts) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_copied[k], 0));
 	}
-	int r = feed_common(c, c->d_in[k], nbytes, parts);
+	int r = feed_block(c, c->d_in[k], nbytes, parts);
 	if(r == VDL2HIP_E_DEVICE) c->failed = true;          // part of the block's work may be queued, part not: the context is out of step with itself
 	return r;
 }
@@ -1044,10 +1144,10 @@ int vdl2hip_feed_device(vdl2hip_ctx *c, const void *dev_buf, size_t nbytes) {
 	OnDevice dev_guard(c);
 	if(nbytes == 0) return VDL2HIP_OK;
 	if(nbytes > c->in_cap) return VDL2HIP_E_TOOBIG;
-	if(((uintptr_t)dev_buf) % sample_bytes(c->fmt)) return VDL2HIP_E_INVAL;
-	nbytes -= nbytes % sample_bytes(c->fmt);
+	if(((uintptr_t)dev_buf) % sample_bytes(c->in_fmt)) return VDL2HIP_E_INVAL;
+	nbytes -= nbytes % sample_bytes(c->in_fmt);
 	if(c->failed) return VDL2HIP_E_DEVICE;
-	int r = feed_common(c, dev_buf, nbytes);
+	int r = feed_block(c, dev_buf, nbytes);
 	if(r == VDL2HIP_E_DEVICE) c->failed = true;
 	return r;
 }
@@ -1429,6 +1529,39 @@ int vdl2hip_read_decimated(vdl2hip_ctx *c, uint32_t chan, int64_t first, float *
 		done += m;
 	}
 	return (int)n;
+}
+
+int vdl2hip_read_resampled(vdl2hip_ctx *c, int64_t first, float *dst, size_t cap) {
+	if(!c || !dst || !c->rs.on) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	if(first < 0 || (uint64_t)first > c->rs.n_out) return VDL2HIP_E_INVAL;
+	size_t done = 0;
+	const size_t n = (size_t)std::min<uint64_t>(cap, c->rs.n_out - (uint64_t)first);
+	while(done < n) {
+		// the slot whose block holds r[pos] (the blocks of the last kSlots feeds, one after the other)
+		const uint64_t pos = (uint64_t)first + done;
+		int k = -1;
+		for(int i = 0; i < kSlots; i++) if(c->rs.count[i] && pos >= c->rs.first[i] && pos < c->rs.first[i] + c->rs.count[i]) k = i;
+		if(k < 0) return done ? (int)done : VDL2HIP_E_INVAL;      // older than what the device keeps
+		const size_t m = (size_t)std::min<uint64_t>(n - done, c->rs.first[k] + c->rs.count[k] - pos);
+		HIPCHK(hipMemcpy(dst + 2 * done, c->rs.d_out[k] + (pos - c->rs.first[k]), m * sizeof(float2), hipMemcpyDeviceToHost));
+		done += m;
+	}
+	return (int)n;
+}
+
+int vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t *L, uint32_t *M, uint32_t *T, float *taps, size_t cap) {
+	ResamplerDesign d;
+	if(!design_resampler(input_rate, output_rate, d, false)) return VDL2HIP_E_INVAL;       // (a refused ratio)
+	if(L) *L = d.L;
+	if(M) *M = d.M;
+	if(T) *T = d.T;
+	if(!taps || (size_t)d.L * d.T > cap) return VDL2HIP_E_TOOBIG;
+	if(!design_resampler(input_rate, output_rate, d)) return VDL2HIP_E_INVAL;
+	memcpy(taps, d.taps.data(), d.taps.size() * sizeof(float));
+	return (int)d.taps.size();
 }
 
 // test hook (not declared in vdl2hip.h): what the sync kernels left for decimated samples first .. first+count-1 of one channel - the tabulated

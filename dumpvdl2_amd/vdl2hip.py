@@ -43,6 +43,7 @@ EXPORTS = [
     "vdl2hip_group_create", "vdl2hip_group_destroy", "vdl2hip_group_feed", "vdl2hip_group_feed_pinned", "vdl2hip_group_sync", "vdl2hip_group_drain",
     "vdl2hip_group_set_drain_lag", "vdl2hip_group_counters", "vdl2hip_group_avlc_counters", "vdl2hip_group_size", "vdl2hip_group_ctx",
     "vdl2hip_group_uses_rccl", "vdl2hip_group_set_exchange", "vdl2hip_group_exchange",
+    "vdl2hip_read_resampled", "vdl2hip_resampler_design",
 ]
 
 
@@ -50,7 +51,8 @@ class Cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("centerfreq", C.c_uint32), ("oversample", C.c_uint32),
                 ("sample_fmt", C.c_uint32), ("nchan", C.c_uint32), ("freqs", C.POINTER(C.c_uint32)),
                 ("max_ppm", C.c_float), ("device", C.c_int32), ("max_block_bytes", C.c_uint32),
-                ("chan_first", C.c_uint32), ("chan_count", C.c_uint32)]
+                ("chan_first", C.c_uint32), ("chan_count", C.c_uint32),
+                ("reserved0", C.c_uint32), ("input_rate", C.c_uint32), ("reserved1", C.c_uint32)]     # (56 -> 64 bytes: vdl2hip.h)
 
 
 class CFrame(C.Structure):
@@ -70,7 +72,8 @@ class Stats(C.Structure):
                 ("overflow_feeds", C.c_uint64), ("cold_start_feeds", C.c_uint64),
                 ("referee_scans", C.c_uint64), ("referee_cached", C.c_uint64), ("referee_refused", C.c_uint64), ("referee_short", C.c_uint64), ("referee_rewalks", C.c_uint64),
                 ("referee_candidate_scans", C.c_uint64), ("referee_header_scans", C.c_uint64), ("referee_symbol_scans", C.c_uint64),
-                ("referee_redone_next", C.c_uint64), ("referee_unmet", C.c_uint64), ("referee_retried", C.c_uint64)]
+                ("referee_redone_next", C.c_uint64), ("referee_unmet", C.c_uint64), ("referee_retried", C.c_uint64),
+                ("resampled_samples", C.c_uint64), ("resample_ms", C.c_double)]
 
 
 class PackedFrame(C.Structure):
@@ -124,6 +127,9 @@ def load_library(path: str = None):
     L.vdl2hip_get_lpf.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.vdl2hip_get_nco_step.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.vdl2hip_read_decimated.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_read_resampled"):                # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_read_resampled.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t]
+        L.vdl2hip_resampler_design.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -167,17 +173,35 @@ def pack_raw_frame(frame: dict, station_id: Optional[str] = None, tv_sec: int = 
     return bytes(out[:n])
 
 
+def resampler_design(input_rate: int, output_rate: int):
+    """The resampler a receiver created with input_rate uses in front of its channeliser (output_rate = 105000 * oversample):
+    (L, M, T, taps) with taps float32 [T, L] in prototype order, taps[j, p] = h[j L + p].  Needs no GPU.  Raises Vdl2HipError for a
+    ratio the library refuses (vdl2hip.h)."""
+    Lib = load_library()
+    L, M, T = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    r = Lib.vdl2hip_resampler_design(input_rate, output_rate, C.byref(L), C.byref(M), C.byref(T), None, 0)
+    if r != -4:                                               # VDL2HIP_E_TOOBIG: the sizes are known now
+        raise Vdl2HipError(f"vdl2hip_resampler_design: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    taps = np.zeros(L.value * T.value, dtype=np.float32)
+    r = Lib.vdl2hip_resampler_design(input_rate, output_rate, C.byref(L), C.byref(M), C.byref(T), taps.ctypes.data, taps.size)
+    if r != taps.size:
+        raise Vdl2HipError(f"vdl2hip_resampler_design: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return L.value, M.value, T.value, taps.reshape(T.value, L.value)
+
+
 class Receiver:
     """One multi-channel VDL2 receiver on one GPU (= the reference's set of demod threads)."""
 
     def __init__(self, centerfreq: int, freqs: Sequence[int], oversample: int = 20, sample_fmt: int = FMT_S16LE,
                  max_ppm: float = 0.0, device: int = 0, max_block_bytes: int = 320000,
-                 chan_first: int = 0, chan_count: int = 0):
+                 chan_first: int = 0, chan_count: int = 0, input_rate: int = 0):
+        """input_rate: the rate of the IQ that will be fed, Hz; 0 = 105000 * oversample.  Any other supported rate is resampled on
+        the device ahead of the channeliser (vdl2hip.h, "Resampling")."""
         self.L = load_library()
         self.freqs = list(freqs)
         self._freq_arr = (C.c_uint32 * len(self.freqs))(*self.freqs)
         cfg = Cfg(C.sizeof(Cfg), centerfreq, oversample, sample_fmt, len(self.freqs), self._freq_arr,
-                  max_ppm, device, max_block_bytes, chan_first, chan_count)
+                  max_ppm, device, max_block_bytes, chan_first, chan_count, 0, input_rate, 0)
         h = C.c_void_p()
         self._chk(self.L.vdl2hip_create(C.byref(cfg), C.byref(h)), "vdl2hip_create")
         self.h = h
@@ -349,6 +373,12 @@ class Receiver:
         n = self._chk(self.L.vdl2hip_read_decimated(self.h, chan, first, buf.ctypes.data, count), "vdl2hip_read_decimated")
         return buf[:n]
 
+    def read_resampled(self, first: int, count: int) -> np.ndarray:
+        """up to `count` (re, im) pairs of the resampled stream r[first ...] (receivers created with input_rate; the last six feeds' are kept)"""
+        buf = np.zeros((count, 2), dtype=np.float32)
+        n = self._chk(self.L.vdl2hip_read_resampled(self.h, first, buf.ctypes.data, count), "vdl2hip_read_resampled")
+        return buf[:n]
+
 
 def _frame_dict(f):
     return dict(chan=f.chan, freq=f.freq, idx=f.idx, octets=bytes(C.string_at(f.octets, f.len)) if f.len else b"",
@@ -362,11 +392,11 @@ class ReceiverGroup:
     used by bench.py is Receiver + dist.ShardedFeeder).  `devices` may name a device more than once (virtual shards)."""
 
     def __init__(self, centerfreq: int, freqs: Sequence[int], devices: Sequence[int], oversample: int = 20,
-                 sample_fmt: int = FMT_S16LE, max_ppm: float = 0.0, max_block_bytes: int = 320000):
+                 sample_fmt: int = FMT_S16LE, max_ppm: float = 0.0, max_block_bytes: int = 320000, input_rate: int = 0):
         self.L = load_library()
         self.freqs = list(freqs)
         self._freq_arr = (C.c_uint32 * len(self.freqs))(*self.freqs)
-        cfg = Cfg(C.sizeof(Cfg), centerfreq, oversample, sample_fmt, len(self.freqs), self._freq_arr, max_ppm, 0, max_block_bytes, 0, 0)
+        cfg = Cfg(C.sizeof(Cfg), centerfreq, oversample, sample_fmt, len(self.freqs), self._freq_arr, max_ppm, 0, max_block_bytes, 0, 0, 0, input_rate, 0)
         dev = (C.c_int32 * len(devices))(*devices)
         h = C.c_void_p()
         r = self.L.vdl2hip_group_create(C.byref(cfg), dev, len(devices), C.byref(h))

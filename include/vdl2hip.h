@@ -35,7 +35,10 @@ extern "C" {
                                  *    the TIMED channeliser launches - profiling on, cold-start feeds excluded - not every launch.)
                                  * 6: vdl2hip_stats.referee_redone_next (a feed's walk no longer waits for the check of the feed before)
                                  *    VDL2HIP_FMT_CF32: one more accepted value of vdl2hip_cfg.sample_fmt - no structure, no entry point and no
-                                 *    result for the other formats changed, so the version stayed */
+                                 *    result for the other formats changed, so the version stayed
+                                 *    vdl2hip_cfg.input_rate (the structure grew at its end, 56 -> 64 bytes; a struct_size of 56 is still taken and
+                                 *    means input_rate 0), vdl2hip_stats.resampled_samples / resample_ms (at its end), vdl2hip_read_resampled(),
+                                 *    vdl2hip_resampler_design(): nothing changed for a caller that does not set input_rate, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -101,7 +104,33 @@ typedef struct {
 	uint32_t max_block_bytes;   /* largest block a feed call may carry; 0 = 320000 (FILE_BUFSIZE) */
 	uint32_t chan_first;        /* multi-GPU sharding: this context decodes channels            */
 	uint32_t chan_count;        /*   [chan_first, chan_first+chan_count) of freqs[]; 0 = all     */
+	uint32_t reserved0;         /* ignored (the tail padding of the 56-byte structure, which callers never initialised) */
+	uint32_t input_rate;        /* Hz: the rate of the IQ the caller feeds.  0 or 105000 * oversample: nothing is resampled (the same
+	                             * kernels, the same results to the bit).  Anything else: see "Resampling" below */
+	uint32_t reserved1;         /* must be 0 */
 } vdl2hip_cfg;
+#define VDL2HIP_CFG_SIZE_V1 56u   /* sizeof(vdl2hip_cfg) before input_rate: still accepted as struct_size, by vdl2hip_create() and vdl2hip_group_create() */
+
+/* Resampling (not in the reference, which sets its radio to 105000 * oversample itself, src/dumpvdl2.c:1073).  With
+ * fout = 105000 * oversample, g = gcd(input_rate, fout), L = fout / g, M = input_rate / g the receiver converts the caller's stream
+ * x[] (converted to float exactly as the formats are converted otherwise; x[i < 0] = 0) to
+ *     r[n] = sum_{j=0}^{T-1} h[j L + p_n] x[b_n - j],   p_n = (n M) mod L,   b_n = floor(n M / L)
+ * on the device, ahead of the channeliser, and IS a VDL2HIP_FMT_CF32 receiver at 105000 * oversample fed r[] from there on - frames,
+ * counters and every channel's decimated stream are those of that receiver, to the bit (vdl2hip_read_resampled() returns r[]).
+ *  - h[] is what vdl2hip_resampler_design() returns: a Kaiser-windowed sinc, L T float32 taps; with fmin = min(input_rate, fout):
+ *    ripple <= 0.01 dB over |f| <= 0.40 fmin, >= 80 dB down for |f| >= 0.60 fmin (what folds back lands outside 0.40 fmin), every
+ *    phase's DC gain within 3e-4 of 1.  Channels should lie within +-0.40 fmin of the centre frequency.
+ *  - After N input samples exactly the outputs with b_n <= N - 1 exist: ceil(N L / M).  r[n] is computed in float32, real and imaginary
+ *    part separately, always in the same order of operations: the stream depends on the input stream alone, not on how it was cut
+ *    into feeds (a feed may be a single sample).  n M is kept in 64 bits: good for 2^50 samples.
+ *  - The filter is causal: everything arrives (L T - 1) / (2 L) INPUT samples late - one or two decimated samples (105 kS/s) - and so
+ *    do sync_sample and end_sample of every frame against the same capture at the native rate.
+ *  - VDL2HIP_E_INVAL, before a device is looked for: L > 1024 (keeps the tap table small: 1024 x 29 floats), input_rate > 8 fout or
+ *    4 input_rate < fout (these bound T, which grows with M / L: 29 .. 34 taps per phase near 1 : 1, 219 at 8 : 1).
+ *  - max_block_bytes, vdl2hip_feed*() sizes and the alignment vdl2hip_feed_device() wants stay those of the caller's format at the
+ *    caller's rate; vdl2hip_stats.input_samples counts the caller's samples, resampled_samples the samples of r[].
+ *  - A large page-locked block to an idle receiver is not copied in pieces (cold_start_feeds stays 0).
+ *  - In a group every member resamples the whole block itself (cheap; the exchange moves the caller's bytes). */
 
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
@@ -118,7 +147,8 @@ typedef struct {
 	float    nf_pwr_dbfs;
 	float    ppm_error;
 	int64_t  burst_ord;         /* ordinal of the burst on its channel (0,1,...) */
-	int64_t  sync_sample;       /* decimated-sample index (105 kS/s clock) at which the preamble locked */
+	int64_t  sync_sample;       /* decimated-sample index (105 kS/s clock) at which the preamble locked (a receiver that resamples -
+	                             * cfg.input_rate - sees everything (L T - 1) / (2 L) input samples late: one or two of these samples) */
 	int64_t  end_sample;        /* decimated-sample index at which the burst was complete */
 	/* avlc_parse()'s first checks (src/avlc.c:163-199), done on the device: */
 	uint32_t avlc_status;       /* VDL2HIP_AVLC_OK / _TOO_SHORT (len < 11) / _BAD_FCS (crc16_ccitt residue != 0xF0B8) */
@@ -185,6 +215,8 @@ typedef struct {
 	                             * NOT be run again (below).  A monitor, not a proof: a scan can meet its witness before it meets the reference's
 	                             * trajectory (measured share of stretches that are not the reference's bit for bit: DESIGN 5) */
 	uint64_t referee_retried;   /* ABI 6.  ... and those that were: listed and scanned again from twice as far back (VDL2HIP_REF_RETRY) */
+	uint64_t resampled_samples; /* receivers with cfg.input_rate: samples of the resampled stream r[] made so far (0 otherwise) */
+	double   resample_ms;       /* ... and the summed HIP-event time of the resampler's launches (profiling level 2, like the other stages) */
 } vdl2hip_stats;
 
 int  vdl2hip_abi_version(void);
@@ -300,6 +332,13 @@ int  vdl2hip_get_nco_step(vdl2hip_ctx *ctx, uint32_t chan, uint32_t *dphi); /* =
 /* Copy up to `cap` decimated (re,im) pairs of one channel starting at decimated index `first`
  * (must still be inside the device history window); returns the count copied. */
 int  vdl2hip_read_decimated(vdl2hip_ctx *ctx, uint32_t chan, int64_t first, float *dst, size_t cap);
+/* Copy up to `cap` (re,im) pairs of the resampled stream r[first ...] (receivers with cfg.input_rate; VDL2HIP_E_INVAL on any other).
+ * The device keeps the last six feeds' output: at least the whole most recent feed is readable.  Returns the count copied. */
+int  vdl2hip_read_resampled(vdl2hip_ctx *ctx, int64_t first, float *dst, size_t cap);
+/* The resampler's design for input_rate -> output_rate (= 105000 * oversample), on the host in double precision, no GPU needed: writes
+ * L, M, T (taps per phase) and, if they fit in `cap` floats, the L T taps in prototype order h[j L + p].  Returns L T, VDL2HIP_E_TOOBIG
+ * if `cap` is too small (L, M, T are written all the same; taps may be NULL then), VDL2HIP_E_INVAL for the ratios vdl2hip_create() refuses. */
+int  vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t *L, uint32_t *M, uint32_t *T, float *taps, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@
  *                                 scan of the referee's): collected blocks give the same frames at 5-7x the rate
  *   --sample-format U8|S16_LE|CF32  (the reference's token is S16_LE, src/dumpvdl2.c:849; CF32 - interleaved float32 I, Q, full scale 1.0,
  *                                 what GNU Radio file sinks and SoapySDR write - is this library's own, VDL2HIP_FMT_CF32)
+ *   --sample-rate <Hz>            the rate of the file, where it is not 105000 * oversample (this library's own: the reference sets its
+ *                                 radios to that rate and takes files at it).  The receiver resamples on the GPU, vdl2hip_cfg.input_rate;
+ *                                 rates it does not take (vdl2hip.h) are refused
  *   --oversample <n>  --centerfreq <Hz>  --max-ppm <x>  --station-id <s>
  *   --avlc-filter                 deliver only frames that pass avlc_parse()'s first checks (length, FCS) - src/avlc.c:168-187
  *   --statsd-out <path>           at exit, write the per-channel counters in the reference's statsd names
@@ -57,7 +60,7 @@ int main(int argc, char **argv) {
 	const char *infile = NULL, *rawpath = NULL, *statsd_path = NULL;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
-	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0;
+	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0, input_rate = 0;
 	float max_ppm = 0.f;
 	int fmt_set = 0;
 	for(int i = 1; i < argc; i++) {
@@ -71,6 +74,7 @@ int main(int argc, char **argv) {
 			else if(!strcmp(argv[i], "CF32")) fmt = VDL2HIP_FMT_CF32;
 			else { fprintf(stderr, "Unknown sample format\n"); return 1; }
 		}
+		else if(!strcmp(a, "--sample-rate")) { NEEDARG(); input_rate = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--oversample")) { NEEDARG(); oversample = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--centerfreq")) { NEEDARG(); centerfreq = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--max-ppm")) { NEEDARG(); max_ppm = strtof(argv[++i], NULL); }
@@ -83,7 +87,7 @@ int main(int argc, char **argv) {
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
 	}
 	(void)fmt_set;
-	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--oversample n] [--centerfreq Hz] "
+	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
@@ -91,6 +95,7 @@ int main(int argc, char **argv) {
 	}
 	const uint32_t sample_rate = SYMBOL_RATE * 10u * oversample;             /* src/dumpvdl2.c:1073 */
 	fprintf(stderr, "Sampling rate set to %u sps\n", sample_rate);
+	if(input_rate && input_rate != sample_rate) fprintf(stderr, "Input at %u sps is resampled to that rate\n", input_rate);
 	if(centerfreq == 0) {                                                      /* calc_centerfreq(), src/dumpvdl2.c:168-180 */
 		uint32_t lo = freqs[0], hi = freqs[0];
 		for(uint32_t i = 0; i < nfreq; i++) { if(freqs[i] < lo) lo = freqs[i]; if(freqs[i] > hi) hi = freqs[i]; }
@@ -105,11 +110,13 @@ int main(int argc, char **argv) {
 	memset(&cfg, 0, sizeof cfg);
 	cfg.struct_size = sizeof cfg; cfg.centerfreq = centerfreq; cfg.oversample = oversample; cfg.sample_fmt = fmt;
 	if(per_feed == 0) {
-		const uint32_t dec = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_CF32 ? 8u : fmt == VDL2HIP_FMT_S16LE ? 4u : 2u) / oversample;      /* decimated samples per block */
+		const uint32_t blk = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_CF32 ? 8u : fmt == VDL2HIP_FMT_S16LE ? 4u : 2u);                   /* samples per block */
+		const uint32_t dec = (uint32_t)((uint64_t)blk * (SYMBOL_RATE * 10u) / (input_rate ? input_rate : sample_rate));              /* decimated samples per block */
 		per_feed = dec ? (64000u + dec - 1) / dec : 1;
 	}
 	if(per_feed > 64) per_feed = 64;
 	cfg.nchan = nfreq; cfg.freqs = freqs; cfg.max_ppm = max_ppm; cfg.device = 0; cfg.max_block_bytes = (size_t)per_feed * FILE_BUFSIZE;
+	cfg.input_rate = input_rate;
 	vdl2hip_ctx *rx = NULL;
 	int r = vdl2hip_create(&cfg, &rx);
 	if(r != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_create: %s\n", vdl2hip_strerror(r)); return 3; }
