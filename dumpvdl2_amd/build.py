@@ -7,7 +7,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvdl2hip.so")
-SOURCES = ["vdl2hip.hip", "group.inc", "ubench.inc", "kernels.h", "resample.h", "resample_design.h", "vdl2_core.h", "design.h", "tables.h"]
+SOURCES = ["vdl2hip.hip", "group.inc", "ubench.inc", "kernels.h", "resample.h", "resample_design.h", "spectrum.h", "spectrum_design.h", "vdl2_core.h", "design.h", "tables.h"]
 # -ffp-contract=off: the walker/burst code must keep the reference's mul/add sequence;
 # the channeliser asks for FMAs explicitly where it wants them.
 # -fno-slp-vectorize: packed FP32 issues at half rate on CDNA4, so a v_pk_add the SLP vectoriser glues together from two scalar
@@ -84,7 +84,7 @@ def build_cli(out_path=None):
     src = os.path.join(root, "tools", "vdl2hip_iqfile.c")
     if not os.path.exists(out_path) or os.path.getmtime(out_path) < max(os.path.getmtime(src), os.path.getmtime(LIB) if os.path.exists(LIB) else 0):
         subprocess.check_call(["gcc", "-std=gnu11", "-O2", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src,
-                               "-L", HERE, "-lvdl2hip", "-Wl,-rpath," + HERE, "-o", out_path])
+                               "-L", HERE, "-lvdl2hip", "-Wl,-rpath," + HERE, "-lm", "-o", out_path])
     return out_path
 
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +18,8 @@
 #include "kernels.h"
 #include "resample.h"
 #include "resample_design.h"
+#include "spectrum.h"
+#include "spectrum_design.h"
 #include "tables.h"
 
 using namespace vdl2;
@@ -93,6 +96,7 @@ struct OutSlot {
 	bool rest_pending = false, has_chk = false; int nseg = 1; int64_t seglen = 0; K4Args k4{}; SpecOut *d_spec_of = nullptr;
 	hipEvent_t ev_stitch = nullptr, ev_chk = nullptr; uint32_t *d_rqflag2 = nullptr;
 	hipEvent_t ev_rs[2] = {}; bool rs_timed = false;   // resampling receivers: start / stop of this feed's k_resample (profiling level 2)
+	hipEvent_t ev_mon[4] = {}; int mon_timed = 0;      // input monitor: start / stop of this feed's k_spectrum and k_spectrum_reduce (profiling level 2); how many of the two were timed
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -110,8 +114,17 @@ struct vdl2hip_ctx {
 		uint64_t first[kSlots] = {}, count[kSlots] = {};              // ... and which part of r[] it holds
 		uint64_t n_in = 0, n_out = 0;                                 // samples taken / made so far
 	} rs;
+	// Input monitor (spectrum.h, vdl2hip_spectrum_*): off unless enabled.  pos: samples fed since it was enabled; carry: the
+	// samples of the incomplete segment the stream stands in, where that segment will be analysed (two buffers, alternating)
+	struct {
+		bool on = false; uint32_t nfft = 0, window = 0, stride = 1, log2n = 0, threads = 0; size_t lds = 0;
+		double sum_w = 0.0, enbw = 0.0; uint64_t pos = 0, segments = 0; uint32_t ncarry = 0; int carry_sel = 0;
+		float *d_w = nullptr; float2 *d_tw = nullptr, *d_carry[2] = {nullptr, nullptr}; double *d_rows = nullptr, *d_acc = nullptr;
+		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
+		hipStream_t rd = nullptr; double *h_acc = nullptr;      // the read's own stream and page-locked landing place (kept until the receiver goes)
+	} mon;
 	bool specialised = false;
-	std::vector<uint32_t> freqs, dphi;
+	std::vector<uint32_t> freqs, dphi, all_freqs;
 	LpfCoeffs lpf{};
 	BlockForm bf{};
 	hipStream_t stream = nullptr;
@@ -229,6 +242,8 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	HIPCHK(hipEventSynchronize(sl.done));
 	sl.pending = false;
 	if(sl.rs_timed) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->stats.resample_ms += ms; else (void)hipGetLastError(); sl.rs_timed = false; }
+	for(int i = 0; i < sl.mon_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_mon[2 * i], sl.ev_mon[2 * i + 1]) == hipSuccess) c->mon.kernel_ms += ms; else (void)hipGetLastError(); }
+	sl.mon_timed = 0;
 	if(c->profiling && sl.ev_valid) {
 		hipEvent_t *ev = sl.ev;
 		float ms = 0.f;
@@ -471,9 +486,14 @@ static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipE
 	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
 	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
 }
+static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes);
 static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
-	if(!c->rs.on) return feed_common(c, dev_in, nbytes, in_parts);
+	// (the monitor sees a block once nothing can refuse it any more, and ahead of everything else that reads it)
 	if(c->failed) return VDL2HIP_E_DEVICE;
+	if(!c->rs.on) {
+		if(c->mon.on) { int r = monitor_block(c, dev_in, nbytes); if(r != VDL2HIP_OK) return r; }
+		return feed_common(c, dev_in, nbytes, in_parts);
+	}
 	auto &rs = c->rs;
 	const int k = (int)(c->feed_no % kSlots);
 	OutSlot &sl = c->slot[k];
@@ -482,6 +502,7 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	// outputs n with b_n = floor(n M / L) <= N - 1 exist after N input samples: ceil(N L / M) of them (64 bits: 2^50 samples)
 	const uint64_t N0 = rs.n_in, N1 = N0 + nin, n0 = rs.n_out, n1 = (N1 * rs.L + rs.M - 1) / rs.M, nout = n1 - n0;
 	if(nout > rs.cap) return VDL2HIP_E_TOOBIG;
+	if(c->mon.on) { int r = monitor_block(c, dev_in, nbytes); if(r != VDL2HIP_OK) return r; }
 	K0Args a{};
 	a.in = dev_in; a.tail_in = rs.d_tail[rs.tail_sel]; a.tail_out = rs.d_tail[rs.tail_sel ^ 1]; a.taps = rs.d_taps; a.out = rs.d_out[k];
 	a.q0 = n0 % rs.L; a.t0 = n0 * rs.M - N0 * rs.L;                  // b_{n0} >= N0: output n0 is the first that needed a sample of this block
@@ -500,6 +521,70 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	c->stats.input_samples += nin - nout;                           // (feed_common counted the block it saw) the caller's samples
 	c->stats.resampled_samples += nout;
 	return r;
+}
+
+// The input monitor's share of a feed (spectrum.h): on the front stream ahead of everything else that reads the block, so it is
+// ordered with the copy into d_in[k], with that buffer's reuse and with a caller's device buffer exactly as the channeliser is.
+// Host bookkeeping: the stream position (64 bits), the segments this feed completes, which of them are analysed, what is carried.
+template<int FMT>
+static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->stream, e0, e1, 0, a)
+	switch(c->mon.nfft / c->mon.threads) {                           // samples per lane (spec_threads(): 1, 2, 4 up to N = 1024, 8, 16)
+		case 1: SPEC_LAUNCH(1); break;
+		case 2: SPEC_LAUNCH(2); break;
+		case 4: SPEC_LAUNCH(4); break;
+		case 8: SPEC_LAUNCH(8); break;
+		default: SPEC_LAUNCH(16); break;
+	}
+	#undef SPEC_LAUNCH
+}
+static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
+	auto &m = c->mon;
+	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
+	if(nin == 0) return VDL2HIP_OK;
+	if(nin >= (1ull << 32)) return VDL2HIP_E_TOOBIG;
+	const uint64_t N = m.nfft, pos0 = m.pos, pos1 = pos0 + nin;
+	const uint64_t j0 = pos0 / N, j1 = pos1 / N;                          // the segments the stream stands in before and after: [j0, j1) are completed
+	const uint64_t ja = (j0 + m.stride - 1) / m.stride * m.stride;        // the first of them that is analysed
+	const uint64_t nseg = ja < j1 ? (j1 - 1 - ja) / m.stride + 1 : 0;
+	const uint32_t o1 = (uint32_t)(pos1 % N);
+	const uint32_t ncarry_out = j1 % m.stride == 0 ? o1 : 0;               // (a segment that stride skips is not kept)
+	m.pos = pos1;
+	if(nseg == 0 && ncarry_out == 0) { m.ncarry = 0; return VDL2HIP_OK; }
+	SpecArgs a{};
+	a.in = dev_in; a.carry_in = m.d_carry[m.carry_sel]; a.carry_out = m.d_carry[m.carry_sel ^ 1]; a.w = m.d_w; a.tw = m.d_tw; a.rows = m.d_rows;
+	a.rel0 = (int64_t)(ja * N) - (int64_t)pos0; a.carry_rel = (int64_t)(j1 * N) - (int64_t)pos0; a.seg_step = (uint64_t)m.stride * N;
+	a.nin = (uint32_t)nin; a.ncarry = m.ncarry; a.ncarry_out = ncarry_out; a.nseg = (uint32_t)nseg;
+	a.run = (uint32_t)std::max<uint64_t>(1, (nseg + kSpecMaxRows - 1) / kSpecMaxRows); a.N = m.nfft; a.log2n = m.log2n;
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nseg + a.run - 1) / a.run);      // (no segment: workgroup 0 still moves the carry on)
+	if(grid > kSpecMaxRows || (int64_t)a.ncarry + a.rel0 < 0) return VDL2HIP_E_INVAL;       // (never)
+	OutSlot &sl = c->slot[c->feed_no % kSlots];
+	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
+	const bool timed = c->profiling >= 2;
+	if(timed) for(auto &e : sl.ev_mon) if(!e) HIPCHK(hipEventCreate(&e));
+	hipEvent_t *e = sl.ev_mon;
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
+	else launch_spectrum<0>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
+	if(nseg) {
+		const uint32_t W = m.nfft + kSpecLevels;
+		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->stream, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0,
+		                      (const double *)m.d_rows, m.d_acc, (uint32_t)grid, m.nfft);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(m.ev_last, c->stream));
+	if(timed) sl.mon_timed = nseg ? 2 : 1;
+	m.queued = true; m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
+	return VDL2HIP_OK;
+}
+// wait for what the monitor has queued and give its buffers back (the event stays with the context)
+static void monitor_free(vdl2hip_ctx *c) {
+	auto &m = c->mon;
+	if(m.queued && m.ev_last) (void)hipEventSynchronize(m.ev_last);
+	void *q[] = { m.d_w, m.d_tw, m.d_carry[0], m.d_carry[1], m.d_rows, m.d_acc };
+	for(void *p : q) if(p) (void)hipFree(p);
+	m.d_w = nullptr; m.d_tw = nullptr; m.d_carry[0] = m.d_carry[1] = nullptr; m.d_rows = nullptr; m.d_acc = nullptr;
+	m.on = false; m.queued = false; m.nfft = 0;
 }
 
 // The burst-rate back end of one feed (K4 walk, K4b noise floor, K5 burst decoder, frame finish), on three streams of its own so
@@ -783,6 +868,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 		if(sl.ev_stitch) (void)hipEventDestroy(sl.ev_stitch);
 		if(sl.ev_chk) (void)hipEventDestroy(sl.ev_chk);
 		for(auto &e : sl.ev_rs) if(e) (void)hipEventDestroy(e);
+		for(auto &e : sl.ev_mon) if(e) (void)hipEventDestroy(e);
 		if(sl.h_mail) (void)hipHostFree(sl.h_mail);
 		if(sl.done) (void)hipEventDestroy(sl.done);
 		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
@@ -796,6 +882,10 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	for(auto &p : c->d_ref) if(p) (void)hipFree(p);
 	for(auto &p : c->rs.d_out) if(p) (void)hipFree(p);
 	{ void *q[] = { c->rs.d_taps, c->rs.d_tail[0], c->rs.d_tail[1] }; for(void *p : q) if(p) (void)hipFree(p); }
+	monitor_free(c);
+	if(c->mon.ev_last) (void)hipEventDestroy(c->mon.ev_last);
+	if(c->mon.rd) (void)hipStreamDestroy(c->mon.rd);
+	if(c->mon.h_acc) (void)hipHostFree(c->mon.h_acc);
 	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
 	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
 	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
@@ -862,6 +952,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	c->in_fmt = c->fmt;
 	if(resample) { c->rs.on = true; c->fmt = VDL2HIP_FMT_CF32; }    // what the channeliser and the referee read is r[]
 	c->freqs.assign(cfg->freqs + first, cfg->freqs + first + count);
+	c->all_freqs.assign(cfg->freqs, cfg->freqs + cfg->nchan);
 	const uint32_t fs = (uint32_t)kSymbolRate * kSps * cfg->oversample;
 	c->lpf = design_lpf(8000.f / (float)fs, 0.5f);                // input_lpf_init(), demod.c:45-46,367-370
 	c->specialised = (c->os == 10 || c->os == 13 || c->os == 20);
@@ -1096,7 +1187,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	// Nothing in flight and a large block from page-locked memory (the first block of a stream, or of a timed region): the copy is cut in
 	// kColdParts pieces and the channeliser follows them piece by piece (feed_common), instead of idling for the whole transfer -
 	// 2.6 ms for a 134 MB block.  In a running stream the copy of block i+1 is hidden behind the kernels of block i and goes in one piece.
-	bool parts = !wait_copy && nbytes >= kColdMinBytes && !c->rs.on;      // (a block that is resampled goes through k_resample whole)
+	bool parts = !wait_copy && nbytes >= kColdMinBytes && !c->rs.on && !c->mon.on;      // (a block that is resampled goes through k_resample whole, one the monitor sees through k_spectrum)
 	for(auto &sl : c->slot) if(sl.pending) parts = false;
 	c->cold.n = 0;
 	if(parts) {
@@ -1566,6 +1657,120 @@ int vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t
 
 // test hook (not declared in vdl2hip.h): what the sync kernels left for decimated samples first .. first+count-1 of one channel - the tabulated
 // metric {pherr (its sign: the referee's mark), slope} and the candidate bit, one byte per sample
+// ---- the input monitor (vdl2hip.h, "Input monitor"; kernels: spectrum.h) ----
+int vdl2hip_spectrum_window(uint32_t nfft, uint32_t window, float *w, size_t cap) {
+	SpectrumDesign d;
+	if(!design_spectrum(nfft, window, d, false)) return VDL2HIP_E_INVAL;
+	if(!w || cap < nfft) return VDL2HIP_E_TOOBIG;
+	memcpy(w, d.w.data(), (size_t)nfft * sizeof(float));
+	return (int)nfft;
+}
+
+int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_spectrum_cfg)) return VDL2HIP_E_INVAL;
+	SpectrumDesign d;
+	if(cfg->nfft != 0 && !design_spectrum(cfg->nfft, cfg->window, d)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	auto &m = c->mon;
+	monitor_free(c);
+	for(auto &sl : c->slot) sl.mon_timed = 0;                        // (what an earlier monitor's launches took is not this one's)
+	if(cfg->nfft == 0) return VDL2HIP_OK;
+	if(!m.ev_last) HIPCHK(hipEventCreateWithFlags(&m.ev_last, hipEventDisableTiming));
+	if(!m.rd) HIPCHK(hipStreamCreateWithFlags(&m.rd, hipStreamNonBlocking));
+	if(!m.h_acc) HIPCHK(hipHostMalloc((void **)&m.h_acc, ((size_t)kSpecMaxN + kSpecLevels) * sizeof(double), hipHostMallocDefault));
+	const size_t N = cfg->nfft, W = N + kSpecLevels;
+	struct { void **p; size_t bytes; } al[] = { { (void **)&m.d_w, N * sizeof(float) }, { (void **)&m.d_tw, N * sizeof(float2) },
+		{ (void **)&m.d_carry[0], N * sizeof(float2) }, { (void **)&m.d_carry[1], N * sizeof(float2) },
+		{ (void **)&m.d_rows, (size_t)kSpecMaxRows * W * sizeof(double) }, { (void **)&m.d_acc, W * sizeof(double) } };
+	for(auto &x : al) if(hipMalloc(x.p, x.bytes) != hipSuccess) { (void)hipGetLastError(); monitor_free(c); return VDL2HIP_E_NOMEM; }
+	if(hipMemcpy(m.d_w, d.w.data(), N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemcpy(m.d_tw, d.tw.data(), N * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemset(m.d_acc, 0, W * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { monitor_free(c); return VDL2HIP_E_DEVICE; }
+	m.nfft = cfg->nfft; m.window = cfg->window; m.stride = cfg->stride ? cfg->stride : 1; m.log2n = d.log2n;
+	m.threads = spec_threads(m.nfft); m.lds = spec_lds_bytes(m.nfft);
+	m.sum_w = d.sum_w; m.enbw = d.enbw_bins;
+	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.queued = false;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+
+// the accumulators as they stand once everything the monitor has queued is done: [nfft] sums of |X|^2, then the level sums
+static int monitor_fetch(vdl2hip_ctx *c, std::vector<double> &acc) {
+	auto &m = c->mon;
+	acc.assign((size_t)m.nfft + kSpecLevels, 0.0);
+	if(!m.queued) return VDL2HIP_OK;                                 // nothing has touched them since they were zeroed
+	// on a stream of the monitor's own, behind the event of its last launch: the read waits for nothing else - not for the feeds in
+	// flight, not for what the process has on the default stream
+	HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
+	HIPCHK(hipMemcpyAsync(m.h_acc, m.d_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost, m.rd));
+	HIPCHK(hipStreamSynchronize(m.rd));
+	memcpy(acc.data(), m.h_acc, acc.size() * sizeof(double));
+	return VDL2HIP_OK;
+}
+static void monitor_power(const vdl2hip_ctx *c, const std::vector<double> &acc, double *power) {
+	const auto &m = c->mon;
+	const double scale = m.segments ? 1.0 / ((double)m.segments * m.sum_w * m.sum_w) : 0.0;
+	for(uint32_t i = 0; i < m.nfft; i++) power[i] = acc[i] * scale;
+}
+
+int vdl2hip_spectrum_read(vdl2hip_ctx *c, vdl2hip_spectrum_info *info, double *power, size_t cap, int reset) {
+	if(!c || !c->mon.on || (info && info->struct_size != sizeof(vdl2hip_spectrum_info))) return VDL2HIP_E_INVAL;
+	auto &m = c->mon;
+	if(power && cap < m.nfft) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	std::vector<double> acc;
+	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
+	const uint32_t N = m.nfft;
+	if(info) {
+		memset(info, 0, sizeof *info);
+		info->struct_size = sizeof *info; info->nfft = N; info->window = m.window; info->stride = m.stride;
+		info->sample_rate = c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample;
+		info->centerfreq = c->cfg.centerfreq;
+		info->segments = m.segments; info->samples = m.segments * N; info->clipped = (uint64_t)acc[N + 3];
+		info->enbw_bins = m.enbw;
+		if(info->samples) { const double n = (double)info->samples; info->mean_power = acc[N] / n; info->dc_i = acc[N + 1] / n; info->dc_q = acc[N + 2] / n; }
+		info->peak = (float)acc[N + 4];
+		info->kernel_ms = (float)m.kernel_ms;
+	}
+	if(power) monitor_power(c, acc, power);
+	if(reset) {
+		// (on the front stream: behind the launches that are queued, ahead of the next feed's)
+		HIPCHK(hipMemsetAsync(m.d_acc, 0, acc.size() * sizeof(double), c->stream));
+		HIPCHK(hipEventRecord(m.ev_last, c->stream));
+		m.queued = true; m.segments = 0;
+	}
+	return (int)N;
+}
+
+int vdl2hip_spectrum_channels(vdl2hip_ctx *c, float *dbfs, size_t cap) {
+	if(!c || !c->mon.on || !dbfs) return VDL2HIP_E_INVAL;
+	auto &m = c->mon;
+	const size_t nchan = c->all_freqs.size();
+	if(cap < nchan) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	std::vector<double> acc;
+	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
+	const uint32_t N = m.nfft;
+	std::vector<double> power(N);
+	monitor_power(c, acc, power.data());
+	const double fs = (double)(c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample), cf = (double)c->cfg.centerfreq;
+	for(size_t ch = 0; ch < nchan; ch++) {
+		const double f = (double)c->all_freqs[ch];
+		double sum = 0.0, best = 0.0; bool any = false; uint32_t nearest = 0;
+		for(uint32_t i = 0; i < N; i++) {
+			const double d = std::fabs(cf + ((double)i - (double)(N / 2)) * fs / (double)N - f);
+			if(d <= 12500.0) { sum += power[i]; any = true; }
+			if(i == 0 || d < best) { best = d; nearest = i; }
+		}
+		if(!any) sum = power[nearest];
+		dbfs[ch] = sum > 0.0 ? (float)(10.0 * std::log10(sum / m.enbw)) : -INFINITY;
+	}
+	return (int)nchan;
+}
+
 int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {
 	if(!c || !pf || !cand || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);

@@ -44,7 +44,9 @@ EXPORTS = [
     "vdl2hip_group_set_drain_lag", "vdl2hip_group_counters", "vdl2hip_group_avlc_counters", "vdl2hip_group_size", "vdl2hip_group_ctx",
     "vdl2hip_group_uses_rccl", "vdl2hip_group_set_exchange", "vdl2hip_group_exchange",
     "vdl2hip_read_resampled", "vdl2hip_resampler_design",
+    "vdl2hip_spectrum_window", "vdl2hip_spectrum_enable", "vdl2hip_spectrum_read", "vdl2hip_spectrum_channels",
 ]
+WIN_RECT, WIN_HANN, WIN_BH4 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_WIN_* (the input monitor's analysis windows)
 
 
 class Cfg(C.Structure):
@@ -74,6 +76,18 @@ class Stats(C.Structure):
                 ("referee_candidate_scans", C.c_uint64), ("referee_header_scans", C.c_uint64), ("referee_symbol_scans", C.c_uint64),
                 ("referee_redone_next", C.c_uint64), ("referee_unmet", C.c_uint64), ("referee_retried", C.c_uint64),
                 ("resampled_samples", C.c_uint64), ("resample_ms", C.c_double)]
+
+
+class SpectrumCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32), ("stride", C.c_uint32)]
+
+
+class SpectrumInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32), ("stride", C.c_uint32),
+                ("sample_rate", C.c_uint32), ("centerfreq", C.c_uint32),
+                ("segments", C.c_uint64), ("samples", C.c_uint64), ("clipped", C.c_uint64),
+                ("enbw_bins", C.c_double), ("mean_power", C.c_double), ("dc_i", C.c_double), ("dc_q", C.c_double),
+                ("peak", C.c_float), ("kernel_ms", C.c_float)]
 
 
 class PackedFrame(C.Structure):
@@ -130,6 +144,11 @@ def load_library(path: str = None):
     if hasattr(L, "vdl2hip_read_resampled"):                # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
         L.vdl2hip_read_resampled.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t]
         L.vdl2hip_resampler_design.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_spectrum_enable"):               # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_spectrum_window.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.vdl2hip_spectrum_enable.argtypes = [C.c_void_p, C.POINTER(SpectrumCfg)]
+        L.vdl2hip_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumInfo), C.c_void_p, C.c_size_t, C.c_int]
+        L.vdl2hip_spectrum_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -187,6 +206,33 @@ def resampler_design(input_rate: int, output_rate: int):
     if r != taps.size:
         raise Vdl2HipError(f"vdl2hip_resampler_design: {Lib.vdl2hip_strerror(r).decode()} ({r})")
     return L.value, M.value, T.value, taps.reshape(T.value, L.value)
+
+
+def spectrum_window(nfft: int, window: int = WIN_HANN) -> np.ndarray:
+    """The input monitor's analysis window w[0 .. nfft) as float32 (vdl2hip.h, "Input monitor").  Needs no GPU.  Raises Vdl2HipError
+    for an nfft (a power of two in 64 .. 4096) or a window the library refuses."""
+    Lib = load_library()
+    w = np.zeros(max(1, nfft), dtype=np.float32)
+    r = Lib.vdl2hip_spectrum_window(nfft, window, w.ctypes.data, w.size)
+    if r != nfft or r <= 0:
+        raise Vdl2HipError(f"vdl2hip_spectrum_window: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return w
+
+
+def _spectrum_read(Lib, ctx, reset: bool, power: bool) -> dict:
+    """vdl2hip_spectrum_read() on a context handle -> dict of every info field, plus freq_hz and power where asked for"""
+    info = SpectrumInfo(C.sizeof(SpectrumInfo))
+    p = np.zeros(4096 if power else 0, dtype=np.float64)      # (the largest nfft: one call, whatever the monitor was enabled with)
+    r = Lib.vdl2hip_spectrum_read(ctx, C.byref(info), p.ctypes.data if power else None, p.size, int(reset))
+    if r < 0:
+        raise Vdl2HipError(f"vdl2hip_spectrum_read: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    p = p[:r].copy()
+    out = {k: getattr(info, k) for k, _ in SpectrumInfo._fields_ if k != "struct_size"}
+    if power:
+        n = info.nfft
+        out["freq_hz"] = info.centerfreq + (np.arange(n, dtype=np.float64) - n // 2) * (info.sample_rate / n)
+        out["power"] = p
+    return out
 
 
 class Receiver:
@@ -372,6 +418,27 @@ class Receiver:
         buf = np.zeros((count, 2), dtype=np.float32)
         n = self._chk(self.L.vdl2hip_read_decimated(self.h, chan, first, buf.ctypes.data, count), "vdl2hip_read_decimated")
         return buf[:n]
+
+    def spectrum_enable(self, nfft: int = 1024, window: int = WIN_HANN, stride: int = 1) -> None:
+        """switch the input monitor on from the next feed (vdl2hip.h, "Input monitor"): a Welch-averaged power spectrum of nfft bins
+        and level statistics of the stream as fed; every stride-th segment of nfft samples is analysed.  Zeroes what was accumulated."""
+        cfg = SpectrumCfg(C.sizeof(SpectrumCfg), nfft, window, stride)
+        self._chk(self.L.vdl2hip_spectrum_enable(self.h, C.byref(cfg)), "vdl2hip_spectrum_enable")
+
+    def spectrum_disable(self) -> None:
+        cfg = SpectrumCfg(C.sizeof(SpectrumCfg), 0, 0, 0)
+        self._chk(self.L.vdl2hip_spectrum_enable(self.h, C.byref(cfg)), "vdl2hip_spectrum_enable")
+
+    def spectrum(self, reset: bool = False, power: bool = True) -> dict:
+        """what the monitor has accumulated: every field of vdl2hip_spectrum_info and, unless power=False, `power` (float64 [nfft],
+        ascending frequency, 1.0 = a full-scale tone on a bin) with `freq_hz`.  reset: zero the accumulators afterwards."""
+        return _spectrum_read(self.L, self.h, reset, power)
+
+    def channel_levels(self) -> np.ndarray:
+        """dBFS in +-12.5 kHz around every channel of the receiver's frequency list, from the monitor's spectrum (float32 [nchan])"""
+        out = np.zeros(len(self.freqs), dtype=np.float32)
+        self._chk(self.L.vdl2hip_spectrum_channels(self.h, out.ctypes.data, out.size), "vdl2hip_spectrum_channels")
+        return out
 
     def read_resampled(self, first: int, count: int) -> np.ndarray:
         """up to `count` (re, im) pairs of the resampled stream r[first ...] (receivers created with input_rate; the last six feeds' are kept)"""

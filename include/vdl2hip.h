@@ -38,7 +38,9 @@ extern "C" {
                                  *    result for the other formats changed, so the version stayed
                                  *    vdl2hip_cfg.input_rate (the structure grew at its end, 56 -> 64 bytes; a struct_size of 56 is still taken and
                                  *    means input_rate 0), vdl2hip_stats.resampled_samples / resample_ms (at its end), vdl2hip_read_resampled(),
-                                 *    vdl2hip_resampler_design(): nothing changed for a caller that does not set input_rate, so the version stayed */
+                                 *    vdl2hip_resampler_design(): nothing changed for a caller that does not set input_rate, so the version stayed
+                                 *    vdl2hip_spectrum_window() / _enable() / _read() / _channels() with vdl2hip_spectrum_cfg / _info: the input monitor, off
+                                 *    unless enabled - new entry points and structures only, nothing existing changed size or meaning, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -131,6 +133,45 @@ typedef struct {
  *    caller's rate; vdl2hip_stats.input_samples counts the caller's samples, resampled_samples the samples of r[].
  *  - A large page-locked block to an idle receiver is not copied in pieces (cold_start_feeds stays 0).
  *  - In a group every member resamples the whole block itself (cheap; the exchange moves the caller's bytes). */
+
+/* Input monitor (not in the reference, whose users look at their wideband input with a second program): an optional power spectrum
+ * and level statistics of the CALLER's stream - the samples as fed, ahead of the resampler, at cfg.input_rate if that is set and at
+ * 105000 * oversample otherwise - computed on the device from the block the channeliser is about to read.  Off unless enabled; with it
+ * off nothing is launched and every result is what it was, to the bit.
+ *  - Samples.  x[i] is the float value of input sample i as the formats are converted everywhere else (VDL2HIP_FMT_* above: u8 the
+ *    correctly rounded (b - 127.5f) / 127.5f, s16 k / 32768.0f, cf32 the value itself); i counts from the first sample fed after
+ *    vdl2hip_spectrum_enable().
+ *  - Segments.  Segment j is x[j N .. (j + 1) N), N = nfft.  It is ANALYSED iff it is complete and j % stride == 0: which segments
+ *    are analysed depends on the stream alone, not on how it was cut into feeds (a feed may be one sample, a segment may span many).
+ *  - Transform.  w[] is what vdl2hip_spectrum_window() returns (designed on the host in double, rounded once to float32).  For an
+ *    analysed segment s:  X_s[k] = sum_n w[n] x[j N + n] exp(-2 pi i k n / N).
+ *  - Accumulation.  power[i] = (1 / S) sum_s |X_s[k]|^2 / (sum_n w[n])^2,  k = (i + N / 2) mod N,  S = analysed segments so far (all
+ *    zero while S = 0).  power[] is in ascending frequency: bin i is at centerfreq + (i - N / 2) sample_rate / N.  A full-scale complex
+ *    tone on a bin centre reads 1.0 (0 dBFS); for a noise density divide by enbw_bins = N sum w^2 / (sum w)^2.  The transform and
+ *    |X|^2 are computed in float32, the sums over segments in float64.
+ *  - Windows, all periodic, t = 2 pi n / N:  VDL2HIP_WIN_RECT 1;  VDL2HIP_WIN_HANN 0.5 - 0.5 cos t;  VDL2HIP_WIN_BH4
+ *    0.35875 - 0.48829 cos t + 0.14128 cos 2t - 0.01168 cos 3t (its sidelobes, 92 dB down, sit below the float32 floor).
+ *  - nfft: a power of two in 64 .. 4096.  stride 0 means 1.
+ *  - Levels, over the samples of the analysed segments, unwindowed: samples = S N; mean_power = mean of re^2 + im^2; dc_i, dc_q = mean
+ *    I, mean Q; peak = max over samples of max(|re|, |im|); clipped = samples with a component at the rail, stated on the float value
+ *    v:  u8 |v| == 1.0f (bytes 0 and 255);  s16 v == -1.0f or v == 32767 / 32768.0f;  cf32 |v| >= 1.0f (a NaN does not count).
+ *  - Determinism.  The same sequence of calls gives the same bits (no floating-point atomics anywhere).  The same stream cut
+ *    differently gives segments, samples, clipped and peak exactly, and power[], mean_power, dc_* within 1e-12 relative (only the order
+ *    of float64 additions moves).
+ *  - With the monitor on, a large page-locked block to an idle receiver is not copied in pieces (cold_start_feeds stays 0).
+ *  - Groups: there is no group call.  Every member is fed the whole block, so vdl2hip_group_ctx(g, 0) is the handle. */
+#define VDL2HIP_WIN_RECT 0
+#define VDL2HIP_WIN_HANN 1
+#define VDL2HIP_WIN_BH4  2
+typedef struct { uint32_t struct_size, nfft, window, stride; } vdl2hip_spectrum_cfg;   /* nfft 0: off; stride 0 means 1 */
+typedef struct {
+	uint32_t struct_size, nfft, window, stride;
+	uint32_t sample_rate, centerfreq;          /* of the analysed stream */
+	uint64_t segments, samples, clipped;
+	double   enbw_bins, mean_power, dc_i, dc_q;
+	float    peak, kernel_ms;                  /* kernel_ms: summed HIP-event time of the monitor's launches at profiling level 2, else 0
+	                                            * (of the feeds collected so far: after vdl2hip_sync(), all of them) */
+} vdl2hip_spectrum_info;                       /* 88 bytes */
 
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
@@ -339,6 +380,24 @@ int  vdl2hip_read_resampled(vdl2hip_ctx *ctx, int64_t first, float *dst, size_t 
  * L, M, T (taps per phase) and, if they fit in `cap` floats, the L T taps in prototype order h[j L + p].  Returns L T, VDL2HIP_E_TOOBIG
  * if `cap` is too small (L, M, T are written all the same; taps may be NULL then), VDL2HIP_E_INVAL for the ratios vdl2hip_create() refuses. */
 int  vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t *L, uint32_t *M, uint32_t *T, float *taps, size_t cap);
+
+/* ---- Input monitor (see "Input monitor" above) ----
+ * The window: returns nfft and writes w[0 .. nfft) if cap >= nfft, else VDL2HIP_E_TOOBIG; VDL2HIP_E_INVAL for an nfft or a window
+ * that is not taken.  Host only, needs no GPU. */
+int  vdl2hip_spectrum_window(uint32_t nfft, uint32_t window, float *w, size_t cap);
+/* Switch the monitor on (or, with nfft 0, off: its buffers are freed).  Allowed at any time between feeds; takes effect with the next
+ * feed, zeroes the accumulators and restarts the sample count i at 0.  VDL2HIP_E_INVAL for a bad struct_size, nfft or window, before
+ * anything is allocated or changed. */
+int  vdl2hip_spectrum_enable(vdl2hip_ctx *ctx, const vdl2hip_spectrum_cfg *cfg);
+/* What the monitor has accumulated.  Waits only for the monitor's own work queued so far (an event behind its last launch), delivers
+ * no frames and changes nothing in what vdl2hip_drain() or vdl2hip_sync() later return.  info->struct_size must be set; `info` or
+ * `power` may be NULL; power[0 .. nfft) needs cap >= nfft, else VDL2HIP_E_TOOBIG.  `reset` zeroes the accumulators after the copy;
+ * the position i runs on, so later segments stay where they were.  Monitor off: VDL2HIP_E_INVAL.  Returns nfft. */
+int  vdl2hip_spectrum_read(vdl2hip_ctx *ctx, vdl2hip_spectrum_info *info, double *power, size_t cap, int reset);
+/* The level of every channel c of cfg.freqs (all nchan of them, not only this shard's), host arithmetic on the same accumulators:
+ * with B_c = { i : |f_i - freqs[c]| <= 12500 Hz }, or the single nearest bin if that set is empty,
+ * dbfs[c] = 10 log10(sum_{B_c} power[i] / enbw_bins), -INFINITY if the sum is 0.  Returns nchan; VDL2HIP_E_TOOBIG if cap < nchan. */
+int  vdl2hip_spectrum_channels(vdl2hip_ctx *ctx, float *dbfs, size_t cap);
 
 #ifdef __cplusplus
 }

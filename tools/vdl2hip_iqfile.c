@@ -19,11 +19,17 @@
  *                                 ("dumpvdl2[.<station-id>].<freq>.<counter>:<n>|c", src/statsd.c:34-65,153-160)
  *   --raw-frames-out <path>       write every frame in the reference's raw-frame archive format, so that a stock
  *                                 `dumpvdl2 --raw-frames-file <path>` decodes them through the full protocol stack
+ *   --spectrum-out <path>         (this library's own) switch the input monitor on and, at exit, write what it saw of the file as fed: a
+ *                                 "# key value" line per field of vdl2hip_spectrum_info, then "freq_hz dbfs" per bin, ascending; the
+ *                                 per-channel summary lines gain " level=<x> dBFS" (vdl2hip_spectrum_channels)
+ *   --spectrum-nfft <n>           bins: a power of two in 64 .. 4096 (default 1024)
+ *   --spectrum-window rect|hann|bh4   (default hann)
  *   freq [freq ...]               channel frequencies in Hz; default: the CSC, 136975000
  * and prints one line per AVLC frame (metadata in the reference's "[S:…] [L:…] [F:…] [#idx]" style + hex octets).
  * Everything after avlc_decoder_queue_push() (AVLC/ACARS/X.25/... decoding, formatters) is out of scope here.
  */
 #include <inttypes.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -57,7 +63,8 @@ static void on_frame(const vdl2hip_frame *f, void *user) {
 }
 
 int main(int argc, char **argv) {
-	const char *infile = NULL, *rawpath = NULL, *statsd_path = NULL;
+	const char *infile = NULL, *rawpath = NULL, *statsd_path = NULL, *spectrum_path = NULL;
+	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
 	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0, input_rate = 0;
@@ -82,13 +89,23 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--raw-frames-out")) { NEEDARG(); rawpath = argv[++i]; }
 		else if(!strcmp(a, "--statsd-out")) { NEEDARG(); statsd_path = argv[++i]; }
 		else if(!strcmp(a, "--avlc-filter")) avlc_filter = 1;
+		else if(!strcmp(a, "--spectrum-out")) { NEEDARG(); spectrum_path = argv[++i]; }
+		else if(!strcmp(a, "--spectrum-nfft")) { NEEDARG(); spectrum_nfft = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--spectrum-window")) {
+			NEEDARG(); i++;
+			if(!strcmp(argv[i], "rect")) spectrum_window = VDL2HIP_WIN_RECT;
+			else if(!strcmp(argv[i], "hann")) spectrum_window = VDL2HIP_WIN_HANN;
+			else if(!strcmp(argv[i], "bh4")) spectrum_window = VDL2HIP_WIN_BH4;
+			else { fprintf(stderr, "Unknown spectrum window\n"); return 1; }
+		}
 		else if(!strcmp(a, "--blocks-per-feed")) { NEEDARG(); per_feed = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return 1; }
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
 	}
 	(void)fmt_set;
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
-			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] [freq ...]\n", argv[0]); return 1; }
+			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
+			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
 		freqs[nfreq++] = CSC_FREQ;
@@ -122,6 +139,12 @@ int main(int argc, char **argv) {
 	if(r != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_create: %s\n", vdl2hip_strerror(r)); return 3; }
 
 	if(avlc_filter) vdl2hip_set_avlc_filter(rx, 1);
+	if(spectrum_path) {
+		vdl2hip_spectrum_cfg sc = { sizeof sc, spectrum_nfft, spectrum_window, 1 };
+		if(spectrum_nfft == 0 || (r = vdl2hip_spectrum_enable(rx, &sc)) != VDL2HIP_OK) {
+			fprintf(stderr, "vdl2hip_spectrum_enable: %s\n", vdl2hip_strerror(spectrum_nfft ? r : VDL2HIP_E_INVAL)); return 3;
+		}
+	}
 
 	unsigned char *buf = malloc((size_t)per_feed * FILE_BUFSIZE);
 	if(!buf) { perror("malloc"); return 3; }
@@ -138,16 +161,39 @@ int main(int argc, char **argv) {
 	} while(len == FILE_BUFSIZE);
 	free(buf);
 	uint64_t cnt[VDL2HIP_NUM_COUNTERS];
+	static float level[1024];
+	const int have_levels = spectrum_path && vdl2hip_spectrum_channels(rx, level, 1024) == (int)nfreq;
 	for(uint32_t c = 0; c < nfreq; c++)
-		if(vdl2hip_counters(rx, c, cnt) == VDL2HIP_OK)
-			fprintf(stderr, "%u Hz: sync.good=%" PRIu64 " crc.good=%" PRIu64 " blocks=%" PRIu64 "/%" PRIu64 " msg.good=%" PRIu64 " fec_bad=%" PRIu64 "\n",
+		if(vdl2hip_counters(rx, c, cnt) == VDL2HIP_OK) {
+			fprintf(stderr, "%u Hz: sync.good=%" PRIu64 " crc.good=%" PRIu64 " blocks=%" PRIu64 "/%" PRIu64 " msg.good=%" PRIu64 " fec_bad=%" PRIu64,
 					freqs[c], cnt[VDL2HIP_CNT_SYNC_GOOD], cnt[VDL2HIP_CNT_CRC_GOOD], cnt[VDL2HIP_CNT_BLOCKS_FEC_OK],
 					cnt[VDL2HIP_CNT_BLOCKS_PROCESSED], cnt[VDL2HIP_CNT_MSG_GOOD], cnt[VDL2HIP_CNT_ERR_FEC_BAD]);
+			if(have_levels) fprintf(stderr, " level=%.2f dBFS", (double)level[c]);
+			fprintf(stderr, "\n");
+		}
 	fprintf(stderr, "%lu frames\n", nframes);
 	{
 		vdl2hip_stats st;                                                       /* the drain calls only count buffer overflows: say so */
 		if(vdl2hip_get_stats(rx, &st) == VDL2HIP_OK && st.overflow_feeds)
 			fprintf(stderr, "warning: device output buffers overflowed in %llu block(s): frames were dropped\n", (unsigned long long)st.overflow_feeds);
+	}
+	if(spectrum_path) {
+		static double power[4096];
+		vdl2hip_spectrum_info si;
+		memset(&si, 0, sizeof si); si.struct_size = sizeof si;
+		int n = vdl2hip_spectrum_read(rx, &si, power, 4096, 0);
+		FILE *so = n > 0 ? fopen(spectrum_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# nfft %u\n# window %u\n# stride %u\n# sample_rate %u\n# centerfreq %u\n", si.nfft, si.window, si.stride, si.sample_rate, si.centerfreq);
+			fprintf(so, "# segments %" PRIu64 "\n# samples %" PRIu64 "\n# clipped %" PRIu64 "\n", si.segments, si.samples, si.clipped);
+			fprintf(so, "# enbw_bins %.9g\n# mean_power %.9g\n# dc_i %.9g\n# dc_q %.9g\n# peak %.9g\n# kernel_ms %.6g\n",
+					si.enbw_bins, si.mean_power, si.dc_i, si.dc_q, (double)si.peak, (double)si.kernel_ms);
+			for(int i = 0; i < n; i++)                                              /* bin i: centerfreq + (i - nfft / 2) sample_rate / nfft */
+				fprintf(so, "%.3f %.4f\n", (double)si.centerfreq + ((double)i - (double)(n / 2)) * (double)si.sample_rate / (double)n,
+						power[i] > 0.0 ? 10.0 * log10(power[i]) : -INFINITY);
+			fclose(so);
+		}
+		else fprintf(stderr, "spectrum not written: %s\n", n < 0 ? vdl2hip_strerror(n) : "cannot open file");
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
