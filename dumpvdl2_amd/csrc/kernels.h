@@ -520,6 +520,44 @@ __device__ __forceinline__ float u8_level(uint32_t i) {
 }
 __global__ void k_u8_level_probe(float *out) { const uint32_t i = threadIdx.x; out[i] = u8_level(i); out[256 + i] = ((float)i - 127.5f) / 127.5f; }
 
+// debug kernel (tests/test_gpu_core_probe.py): the DEVICE builds of vdl2_core.h's element-wise pieces, each called as the product calls
+// it, one lane per element, plain loads and stores.  in: core_probe_in_words(kind) 32-bit words per element, out: core_probe_out_words(kind)
+enum { PROBE_PHASE = 0, PROBE_PHASE_FAST, PROBE_MAG, PROBE_METRIC, PROBE_SCREEN, PROBE_SLICE, PROBE_VERTEX, PROBE_PPM, PROBE_KINDS };
+VDL2_HD int core_probe_in_words(int kind) { return kind <= PROBE_MAG ? 2 : (kind <= PROBE_SCREEN ? kPreamble : 3); }
+VDL2_HD int core_probe_out_words(int kind) { return (kind <= PROBE_MAG || kind == PROBE_VERTEX) ? 1 : 2; }
+__global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, uint32_t n, float *out, const Tables *tab) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if(i >= n) return;
+	const float *x = in + (size_t)i * core_probe_in_words(kind);
+	float *o = out + (size_t)i * core_probe_out_words(kind);
+	switch(kind) {
+	case PROBE_PHASE: o[0] = phase_of(cf32{x[0], x[1]}); break;
+	case PROBE_PHASE_FAST: o[0] = phase_fast(cf32{x[0], x[1]}); break;
+	case PROBE_MAG: o[0] = mag_of(cf32{x[0], x[1]}); break;
+	case PROBE_METRIC: {
+		float ph[kPreamble];
+		for(int j = 0; j < kPreamble; j++) ph[j] = x[j];
+		sync_metric(ph, *tab, o[0], o[1]);
+	} break;
+	case PROBE_SCREEN: {
+		float ph[kPreamble];
+		for(int j = 0; j < kPreamble; j++) ph[j] = x[j];
+		o[0] = sync_metric_screen(ph, kPreamble); o[1] = sync_metric_screen(ph, kScreenEarly);
+	} break;
+	case PROBE_SLICE: {
+		int neg = 0;
+		const int idx = slice_symbol(x[0], x[1], x[2], neg);
+		o[0] = __int_as_float(idx); o[1] = __int_as_float(neg);
+	} break;
+	case PROBE_VERTEX: o[0] = parabola_vertex(x[0], x[1], x[2]); break;
+	case PROBE_PPM: {
+		const uint32_t freq = __float_as_uint(x[1]);
+		o[0] = ppm_of(x[0], freq); o[1] = ppm_gate_threshold(freq, x[2]);
+	} break;
+	default: break;
+	}
+}
+
 // U8: the build for unsigned-byte input (the reference's default for --iq-file and what an RTL-SDR delivers): its tiles are fetched a tile
 // ahead and converted without per-sample range checks or divisions, as the s16 tiles of the other build are (round 6c: the generic
 // staging path cost a 256-channel receiver 18 % of its channeliser: 4.46 against 3.77 ms per 16 s).  Only instantiated where the tile

@@ -335,7 +335,8 @@ VDL2_HD float phase_fast(cf32 y) {
 	const bool steep = ay > ax;
 #if VDL2_DEVICE_PASS
 	// branch-free, 19 instructions.  A zero sample gives 0 (v_mul_legacy: 0 * inf = 0); a sample so small that v_rcp overflows
-	// gives a NaN, which the screening kernel reads as "flag it"
+	// gives an infinity (measured: never a NaN, tests/test_gpu_core_probe.py), which makes a NaN of every screening value it
+	// enters, and that the screening kernel reads as "flag it"
 	const float mx = steep ? ay : ax, mn = __builtin_amdgcn_fmed3f(ax, ay, 0.f);
 	float t;
 	// (the s_nop is the wait state a VALU read of a transcendental result needs on gfx940+; the compiler does not look inside)

@@ -1548,6 +1548,32 @@ int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
 	return rc;
 }
 
+// test hook (not declared in vdl2hip.h; tests/test_gpu_core_probe.py): the device builds of vdl2_core.h's element-wise pieces on n elements.
+// kind 0 phase_of, 1 phase_fast, 2 mag_of: in (re, im), out 1 float; 3 sync_metric: in 16 phases, out (pherr, slope); 4 sync_metric_screen:
+// in 16 phases in turns, out (16 taps, kScreenEarly taps); 5 slice_symbol: in (phi, prev_phi, vdphi), out int32 (index, neg);
+// 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold).  Needs no receiver
+int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
+	if(kind < 0 || kind >= PROBE_KINDS || !in || !out || n == 0 || n > (size_t)1 << 26) return VDL2HIP_E_INVAL;
+	const size_t nin = n * (size_t)core_probe_in_words(kind) * 4, nout = n * (size_t)core_probe_out_words(kind) * 4;
+	float *d_in = nullptr, *d_out = nullptr; Tables *d_tab = nullptr;
+	int rc = VDL2HIP_OK;
+	if(hipMalloc((void **)&d_in, nin) != hipSuccess || hipMalloc((void **)&d_out, nout) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess) rc = VDL2HIP_E_NOMEM;
+	if(rc == VDL2HIP_OK) {
+		Tables *tab = new Tables; build_tables(*tab);
+		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice) != hipSuccess
+		   || hipMemset(d_out, 0, nout) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+		delete tab;
+	}
+	if(rc == VDL2HIP_OK) {
+		hipLaunchKernelGGL(k_core_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, (const float *)d_in, (uint32_t)n, d_out, (const Tables *)d_tab);
+		if(hipGetLastError() != hipSuccess || hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(d_in) (void)hipFree(d_in);
+	if(d_out) (void)hipFree(d_out);
+	if(d_tab) (void)hipFree(d_tab);
+	return rc;
+}
+
 #ifdef VDL2_K1_PROF
 int vdl2hip_debug_k1_prof(unsigned long long out[16], int reset) {
 	static unsigned long long h[64][16];
@@ -1790,6 +1816,24 @@ int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t
 		const size_t m = std::min<size_t>(n - done, c->cap - slot);
 		HIPCHK(hipMemcpy(pf + 2 * done, c->d_pf + ch * c->cap + slot, m * sizeof(cf32), hipMemcpyDeviceToHost));
 		done += m;
+	}
+	return (int)n;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_sync_screen.py): the screening tier's verdicts, flag[i] = bit first + i of the d_flag ring
+int vdl2hip_debug_read_flags(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, uint8_t *flag) {
+	if(!c || !flag || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
+	// (up to the end of the last word: the bits past the last valid sample are the kernel's too, and must be zero)
+	const size_t n = std::min<size_t>(count, (size_t)(((c->k_total + 63) & ~(int64_t)63) - first)), ch = chan - c->chan_first;
+	std::vector<uint64_t> words(c->cap >> 6);
+	HIPCHK(hipMemcpy(words.data(), c->d_flag + ch * (c->cap >> 6), words.size() * 8, hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < n; i++) {
+		const uint32_t slot = (uint32_t)(first + (int64_t)i) & (c->cap - 1);
+		flag[i] = (uint8_t)((words[slot >> 6] >> (slot & 63)) & 1u);
 	}
 	return (int)n;
 }

@@ -392,6 +392,15 @@ class Receiver:
         n = self._chk(f(self.h, chan, first, count, pf.ctypes.data, cand.ctypes.data), "vdl2hip_debug_read_sync")
         return pf[:n], cand[:n]
 
+    def read_flags(self, chan: int, first: int, count: int) -> np.ndarray:
+        """test hook: the screening tier's verdicts of one channel, one byte per sample ("the exact metric may be under the threshold");
+        may reach past the last sample fed, to the end of its 64-sample word"""
+        f = self.L.vdl2hip_debug_read_flags
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_size_t, C.c_void_p]
+        flag = np.zeros(count, dtype=np.uint8)
+        n = self._chk(f(self.h, chan, first, count, flag.ctypes.data), "vdl2hip_debug_read_flags")
+        return flag[:n]
+
     def set_profiling(self, level) -> None:
         """0/False off, 1/True: time the channeliser kernel only, 2: every stage (a few percent slower)"""
         self._chk(self.L.vdl2hip_set_profiling(self.h, int(level)), "vdl2hip_set_profiling")

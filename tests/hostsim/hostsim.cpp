@@ -399,6 +399,23 @@ void hostsim_metric_early(const float *ph, int64_t n, float *early) {
 	}
 }
 int hostsim_screen_early_taps() { return kScreenEarly; }
+// the same two values of n windows of phases that are in turns already (what phase_fast() delivers)
+void hostsim_screen_turns(const float *pt, int64_t n, float *screen, float *early) {
+	for(int64_t i = 0; i < n; i++) { screen[i] = sync_metric_screen(pt + 16 * i); early[i] = sync_metric_screen(pt + 16 * i, kScreenEarly); }
+}
+// the host builds of the other element-wise pieces, for tests/core_reference.py (the numpy restatements are held to these bit for bit)
+void hostsim_slice(const float *in3, int64_t n, int32_t *idx, int32_t *neg) {
+	for(int64_t i = 0; i < n; i++) { int ng = 0; idx[i] = slice_symbol(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2], ng); neg[i] = ng; }
+}
+void hostsim_vertex(const float *in3, int64_t n, float *out) { for(int64_t i = 0; i < n; i++) out[i] = parabola_vertex(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2]); }
+void hostsim_ppm(const float *vdphi, const uint32_t *freq, const float *max_ppm, int64_t n, float *ppm, float *thr) {
+	for(int64_t i = 0; i < n; i++) { ppm[i] = ppm_of(vdphi[i], freq[i]); thr[i] = ppm_gate_threshold(freq[i], max_ppm[i]); }
+}
+void hostsim_metric_tables(float *pr_phase16, float *lrx16, float *lr_den) {
+	static Tables T; build_tables(T);
+	memcpy(pr_phase16, T.pr_phase, sizeof T.pr_phase); memcpy(lrx16, T.lrx, sizeof T.lrx); *lr_den = T.lr_den;
+}
+float hostsim_pi_below() { return kPiBelow; }
 
 // more of tables.h: preamble phases (units of pi/4 are checked by the caller), Gray map, FCS table, first PRBS bits, RS field
 void hostsim_misc_tables(float *pr_phase16, uint8_t *gray8, uint16_t *crc256, uint8_t *prbs64, uint8_t *gf_exp8) {
