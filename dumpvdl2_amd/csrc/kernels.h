@@ -522,9 +522,10 @@ __global__ void k_u8_level_probe(float *out) { const uint32_t i = threadIdx.x; o
 
 // debug kernel (tests/test_gpu_core_probe.py): the DEVICE builds of vdl2_core.h's element-wise pieces, each called as the product calls
 // it, one lane per element, plain loads and stores.  in: core_probe_in_words(kind) 32-bit words per element, out: core_probe_out_words(kind)
-enum { PROBE_PHASE = 0, PROBE_PHASE_FAST, PROBE_MAG, PROBE_METRIC, PROBE_SCREEN, PROBE_SLICE, PROBE_VERTEX, PROBE_PPM, PROBE_KINDS };
-VDL2_HD int core_probe_in_words(int kind) { return kind <= PROBE_MAG ? 2 : (kind <= PROBE_SCREEN ? kPreamble : 3); }
-VDL2_HD int core_probe_out_words(int kind) { return (kind <= PROBE_MAG || kind == PROBE_VERTEX) ? 1 : 2; }
+// (PROBE_HEADER, tests/test_gpu_burst_probe.py: the walker's header_to_geometry() on a 25-bit word)
+enum { PROBE_PHASE = 0, PROBE_PHASE_FAST, PROBE_MAG, PROBE_METRIC, PROBE_SCREEN, PROBE_SLICE, PROBE_VERTEX, PROBE_PPM, PROBE_HEADER, PROBE_KINDS };
+VDL2_HD int core_probe_in_words(int kind) { return kind == PROBE_HEADER ? 1 : kind <= PROBE_MAG ? 2 : (kind <= PROBE_SCREEN ? kPreamble : 3); }
+VDL2_HD int core_probe_out_words(int kind) { return kind == PROBE_HEADER ? 4 : (kind <= PROBE_MAG || kind == PROBE_VERTEX) ? 1 : 2; }
 __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, uint32_t n, float *out, const Tables *tab) {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if(i >= n) return;
@@ -553,6 +554,10 @@ __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, u
 	case PROBE_PPM: {
 		const uint32_t freq = __float_as_uint(x[1]);
 		o[0] = ppm_of(x[0], freq); o[1] = ppm_gate_threshold(freq, x[2]);
+	} break;
+	case PROBE_HEADER: {
+		const Geometry g = header_to_geometry(__float_as_uint(x[0]), tab->hdr_H, tab->hdr_fix);
+		o[0] = __int_as_float(g.status); o[1] = __uint_as_float(g.syndrome); o[2] = __uint_as_float(g.tl_bits); o[3] = __uint_as_float(g.want_bits);
 	} break;
 	default: break;
 	}
@@ -2197,6 +2202,67 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 #endif
 constexpr int kBurstWaves = VDL2_K5_WAVES;
 constexpr int kK5MaxChan = 1024;          // most channels a receiver may have (vdl2hip_create): a wavefront of the burst decoder keeps all their burst-list offsets in LDS
+// debug kernels (tests/test_gpu_burst_probe.py): the DEVICE build of the burst decoder's pieces, each called as burst_body calls it.
+// Workgroups of kBurstWaves wavefronts on BurstShared[kBurstWaves] of dynamic LDS; a wavefront sets its BurstShared up once and takes
+// elements wave_id, wave_id + (wavefronts of the launch), ... in that order, each on the LDS state the one before has left.
+//   k_burst_probe_wave  in 64 words -> sh.flag_err / sh.lanek; out kBProbeWaveOut words: wave_first_flag, wave_count_flags, the 64 values
+//                       wave_excl_scan64 leaves, its total, wave_min64 (of the values before the scan)
+//   k_burst_probe_rs    in 255 octets + npar (stride 256) -> sh.tab; out the row after rs_decode_row (stride 256) and sh.u_ret
+//   k_burst_probe       (behind k_burst) element i is bursts[i] on ring y + i * cap of its own, referee off; counters of channel
+//                       bursts[i].chan; frames, pool and ctl as k_burst fills them (ctl set up by the hook as reset_out_ctl does)
+// (The first two stand BEFORE burst_body on purpose, and the RS one has its call inlined on the spot: the inliner then meets
+// decode_burst's call of rs_decode_row as that function's only one, as it does without these kernels, and the product kernels keep
+// their registers, spills and LDS to the figure - a second caller at that moment left rs_decode_row out of line in k_burst.)
+enum { BPROBE_WAVE = 0, BPROBE_RS, BPROBE_BURST, BPROBE_KINDS };
+constexpr int kBProbeWaveOut = 68, kBProbeRsStride = 256;
+struct BurstProbeArgs {
+	uint32_t n; const Tables *tab; OutCtl *ctl;
+	const uint32_t *win; uint32_t *wout;
+	const uint8_t *rin; uint8_t *rout; int32_t *rret;
+	const Burst *bursts; const uint32_t *freq; const cf32 *y; uint32_t cap, mask; unsigned long long *cnt; OutFrame *frames; uint8_t *pool;
+};
+__global__ __launch_bounds__(64 * kBurstWaves) void k_burst_probe_wave(BurstProbeArgs a) {
+	extern __shared__ __align__(16) unsigned char k5_lds[];       // BurstShared[kBurstWaves]
+	BurstShared &sh = reinterpret_cast<BurstShared *>(k5_lds)[threadIdx.x >> 6];
+	const uint32_t wave_id = blockIdx.x * kBurstWaves + (threadIdx.x >> 6), nwaves = gridDim.x * kBurstWaves;
+	burst_shared_init(*a.tab, wave_id, a.ctl, sh);
+	for(uint32_t i = wave_id; i < a.n; i += nwaves) {
+		const uint32_t *x = a.win + (size_t)i * 64;
+		uint32_t *o = a.wout + (size_t)i * kBProbeWaveOut;
+		WAVE_FOR(l)
+			sh.lanek[l] = x[l]; sh.flag_err[l] = (int32_t)x[l];
+		WAVE_END
+		const int first = wave_first_flag(sh.flag_err), count = wave_count_flags(sh.flag_err);
+		const uint32_t mn = wave_min64(sh.lanek);
+		WAVE_SYNC();
+		const uint32_t total = wave_excl_scan64(sh.lanek);
+		WAVE_FOR(l)
+			o[2 + l] = sh.lanek[l];
+			if(l == 0) { o[0] = (uint32_t)first; o[1] = (uint32_t)count; o[66] = total; o[67] = mn; }
+		WAVE_END
+		WAVE_SYNC();
+	}
+}
+__global__ __launch_bounds__(64 * kBurstWaves) void k_burst_probe_rs(BurstProbeArgs a) {
+	extern __shared__ __align__(16) unsigned char k5_lds[];       // BurstShared[kBurstWaves]
+	BurstShared &sh = reinterpret_cast<BurstShared *>(k5_lds)[threadIdx.x >> 6];
+	const uint32_t wave_id = blockIdx.x * kBurstWaves + (threadIdx.x >> 6), nwaves = gridDim.x * kBurstWaves;
+	burst_shared_init(*a.tab, wave_id, a.ctl, sh);
+	for(uint32_t i = wave_id; i < a.n; i += nwaves) {
+		const uint8_t *x = a.rin + (size_t)i * kBProbeRsStride;
+		uint8_t *o = a.rout + (size_t)i * kBProbeRsStride;
+		WAVE_FOR(l)
+			for(int j = l; j < kRsN; j += 64) sh.tab[j] = x[j];
+		WAVE_END
+		[[clang::always_inline]] rs_decode_row(sh.tab, (int)x[kRsN], sh);
+		WAVE_FOR(l)
+			for(int j = l; j < kRsN; j += 64) o[j] = sh.tab[j];
+			if(l == 0) a.rret[i] = sh.u_ret;
+		WAVE_END
+		WAVE_SYNC();
+	}
+}
+
 // (the LDS is dynamic so that the compiler does not see its size: it would size the register budget by the LDS-limited occupancy
 // and take 169, more than a channeliser wave leaves)
 // (the body of k_burst: `block` of `nblocks` workgroups of kBurstWaves wavefronts)
@@ -2327,6 +2393,21 @@ __global__ __launch_bounds__(64 * kFrameWaves) void k_frame_finish(OutFrame *fra
 			WAVE_SYNC();
 		}
 	}
+}
+
+// debug kernel (tests/test_gpu_burst_probe.py; see k_burst_probe_wave above): decode_burst() on the device, one burst per element
+__global__ __launch_bounds__(64 * kBurstWaves) void k_burst_probe(BurstProbeArgs a) {
+	extern __shared__ __align__(16) unsigned char k5_lds[];       // BurstShared[kBurstWaves]
+	BurstShared &sh = reinterpret_cast<BurstShared *>(k5_lds)[threadIdx.x >> 6];
+	const uint32_t wave_id = blockIdx.x * kBurstWaves + (threadIdx.x >> 6), nwaves = gridDim.x * kBurstWaves;
+	burst_shared_init(*a.tab, wave_id, a.ctl, sh);
+	for(uint32_t i = wave_id; i < a.n; i += nwaves) {
+		const Burst b = a.bursts[i];
+		ChanView v{ a.y + (size_t)i * a.cap, nullptr, nullptr, a.mask };
+		decode_burst(b, a.freq[b.chan], *a.tab, v, a.cnt + (size_t)b.chan * kNumCounters, a.frames, a.pool, a.ctl, sh);
+		WAVE_SYNC();
+	}
+	burst_reserve_done(a.frames, sh);
 }
 
 }  // namespace vdl2

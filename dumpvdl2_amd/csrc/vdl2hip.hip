@@ -1551,7 +1551,8 @@ int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
 // test hook (not declared in vdl2hip.h; tests/test_gpu_core_probe.py): the device builds of vdl2_core.h's element-wise pieces on n elements.
 // kind 0 phase_of, 1 phase_fast, 2 mag_of: in (re, im), out 1 float; 3 sync_metric: in 16 phases, out (pherr, slope); 4 sync_metric_screen:
 // in 16 phases in turns, out (16 taps, kScreenEarly taps); 5 slice_symbol: in (phi, prev_phi, vdphi), out int32 (index, neg);
-// 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold).  Needs no receiver
+// 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold); 8 header_to_geometry:
+// in a 25-bit header word (uint32), out uint32 (status, syndrome, tl_bits, want_bits).  Needs no receiver
 int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
 	if(kind < 0 || kind >= PROBE_KINDS || !in || !out || n == 0 || n > (size_t)1 << 26) return VDL2HIP_E_INVAL;
 	const size_t nin = n * (size_t)core_probe_in_words(kind) * 4, nout = n * (size_t)core_probe_out_words(kind) * 4;
@@ -1571,6 +1572,140 @@ int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
 	if(d_in) (void)hipFree(d_in);
 	if(d_out) (void)hipFree(d_out);
 	if(d_tab) (void)hipFree(d_tab);
+	return rc;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): the device build of the burst decoder's pieces on n elements, `grid`
+// workgroups of kBurstWaves wavefronts (kernels.h: k_burst_probe_wave, k_burst_probe_rs, k_burst_probe).  Needs no receiver.
+//   kind 0 (wave primitives)  in uint32 [n][64], out uint32 [n][68]: first flag, flag count, 64 scanned values, their total, the minimum
+//   kind 1 (rs_decode_row)    in uint8 [n][256]: 255 octets and npar (0, 2, 4 or 6); out uint8 [n][256]: the row, then int32 [n]: the return value
+//   kind 2 (decode_burst)     in Burst [n], element i on ring y[i][ring_len] (cf32, ring_len a power of two), freq [nchan], referee off.  The output
+//                             control block starts as a feed's does (the counters behind the wavefronts' own shares) with capacities cap_frames and
+//                             cap_pool; behind the records and behind the pool lie guard_frames records and guard_pool octets, everything filled with
+//                             0xA5 beforehand.  Returned: frames [cap_frames + guard_frames], pool [cap_pool + guard_pool], ctl (an OutCtl), cnt
+//                             [nchan][20]; `out` is not used
+int vdl2hip_debug_burst_probe(int kind, const void *in, size_t n, unsigned grid, void *out, const uint32_t *freq, uint32_t nchan, const float *y, uint32_t ring_len,
+		uint32_t cap_frames, uint32_t cap_pool, uint32_t guard_frames, uint32_t guard_pool, void *frames, uint8_t *pool, void *ctl, unsigned long long *cnt) {
+	if(kind < 0 || kind >= BPROBE_KINDS || !in || n == 0 || n > (size_t)1 << 20 || grid == 0 || grid > 1024) return VDL2HIP_E_INVAL;
+	const uint32_t nwaves = grid * (uint32_t)kBurstWaves;
+	size_t nin = 0, nout = 0;
+	if(kind == BPROBE_WAVE) { nin = n * 64 * 4; nout = n * (size_t)kBProbeWaveOut * 4; }
+	else if(kind == BPROBE_RS) {
+		nin = n * (size_t)kBProbeRsStride; nout = n * (size_t)kBProbeRsStride + n * 4;
+		for(size_t i = 0; i < n; i++) { const uint8_t np = ((const uint8_t *)in)[i * kBProbeRsStride + kRsN]; if(np > kRsPar || (np & 1)) return VDL2HIP_E_INVAL; }
+	} else {
+		nin = n * sizeof(Burst);
+		if(!freq || nchan == 0 || !y || ring_len < 64 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || !frames || !pool || !ctl || !cnt) return VDL2HIP_E_INVAL;
+		if(cap_frames > 1u << 20 || cap_pool > 1u << 26 || guard_frames > 1u << 16 || guard_pool > 1u << 20 || n * (size_t)ring_len > (size_t)1 << 26) return VDL2HIP_E_INVAL;
+		for(size_t i = 0; i < n; i++) {
+			const Burst &b = ((const Burst *)in)[i];
+			if(b.chan < 0 || (uint32_t)b.chan >= nchan || b.nsym < 1 || b.nsym > kMaxSyms || b.tl_bits == 0 || b.tl_bits > kMaxTl || b.t_first < 0 || b.prev_n < -2) return VDL2HIP_E_INVAL;
+		}
+	}
+	if(kind != BPROBE_BURST && !out) return VDL2HIP_E_INVAL;
+	const size_t nfr = (size_t)cap_frames + guard_frames, npool = (size_t)cap_pool + guard_pool;
+	void *d_in = nullptr, *d_out = nullptr; Tables *d_tab = nullptr; OutCtl *d_ctl = nullptr;
+	uint32_t *d_freq = nullptr; cf32 *d_y = nullptr; unsigned long long *d_cnt = nullptr; OutFrame *d_frames = nullptr; uint8_t *d_pool = nullptr;
+	int rc = VDL2HIP_OK;
+	if(hipMalloc(&d_in, nin) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess || hipMalloc((void **)&d_ctl, sizeof(OutCtl)) != hipSuccess) rc = VDL2HIP_E_NOMEM;
+	if(rc == VDL2HIP_OK && nout && hipMalloc(&d_out, nout) != hipSuccess) rc = VDL2HIP_E_NOMEM;
+	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
+		if(hipMalloc((void **)&d_freq, (size_t)nchan * 4) != hipSuccess || hipMalloc((void **)&d_y, n * (size_t)ring_len * sizeof(cf32)) != hipSuccess
+		   || hipMalloc((void **)&d_cnt, (size_t)nchan * kNumCounters * 8) != hipSuccess || hipMalloc((void **)&d_frames, (nfr + 1) * sizeof(OutFrame)) != hipSuccess
+		   || hipMalloc((void **)&d_pool, npool + 4) != hipSuccess) rc = VDL2HIP_E_NOMEM;
+	}
+	OutCtl h_ctl; memset(&h_ctl, 0, sizeof h_ctl);
+	h_ctl.cap_frames = cap_frames; h_ctl.cap_pool = cap_pool;
+	h_ctl.nframes = burst_reserve_initial_frames(nwaves); h_ctl.pool_used = burst_reserve_initial_pool(nwaves);     // (kernels.h: reset_out_ctl)
+	if(rc == VDL2HIP_OK) {
+		Tables *tab = new Tables; build_tables(*tab);
+		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice) != hipSuccess
+		   || hipMemcpy(d_ctl, &h_ctl, sizeof h_ctl, hipMemcpyHostToDevice) != hipSuccess || (nout && hipMemset(d_out, 0, nout) != hipSuccess)) rc = VDL2HIP_E_DEVICE;
+		delete tab;
+	}
+	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
+		if(hipMemcpy(d_freq, freq, (size_t)nchan * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_y, y, n * (size_t)ring_len * sizeof(cf32), hipMemcpyHostToDevice) != hipSuccess
+		   || hipMemset(d_cnt, 0, (size_t)nchan * kNumCounters * 8) != hipSuccess || hipMemset(d_frames, 0xA5, (nfr + 1) * sizeof(OutFrame)) != hipSuccess
+		   || hipMemset(d_pool, 0xA5, npool + 4) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(rc == VDL2HIP_OK) {
+		BurstProbeArgs a{ (uint32_t)n, d_tab, d_ctl, (const uint32_t *)d_in, (uint32_t *)d_out, (const uint8_t *)d_in, (uint8_t *)d_out,
+		                  (int32_t *)((uint8_t *)d_out + n * (size_t)kBProbeRsStride), (const Burst *)d_in, d_freq, d_y, ring_len, ring_len - 1, d_cnt, d_frames, d_pool };
+		const unsigned lds = (unsigned)(sizeof(BurstShared) * kBurstWaves);
+		if(kind == BPROBE_WAVE) hipLaunchKernelGGL(k_burst_probe_wave, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+		else if(kind == BPROBE_RS) hipLaunchKernelGGL(k_burst_probe_rs, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+		else hipLaunchKernelGGL(k_burst_probe, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+		if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(rc == VDL2HIP_OK && nout && hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
+		if(hipMemcpy(frames, d_frames, nfr * sizeof(OutFrame), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(pool, d_pool, npool, hipMemcpyDeviceToHost) != hipSuccess
+		   || hipMemcpy(ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cnt, d_cnt, (size_t)nchan * kNumCounters * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(d_in) (void)hipFree(d_in);
+	if(d_out) (void)hipFree(d_out);
+	if(d_tab) (void)hipFree(d_tab);
+	if(d_ctl) (void)hipFree(d_ctl);
+	if(d_freq) (void)hipFree(d_freq);
+	if(d_y) (void)hipFree(d_y);
+	if(d_cnt) (void)hipFree(d_cnt);
+	if(d_frames) (void)hipFree(d_frames);
+	if(d_pool) (void)hipFree(d_pool);
+	return rc;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): k_frame_finish itself, `grid` workgroups, on the caller's record list
+// (nrec records, tombstones - chan < 0 - among them), octet pool, control block (an OutCtl: nframes, cap_frames; nvalid and pool_out_used zero)
+// and noise-floor rings ring[nchan][ring_len] (ring_len a power of two).  Returned: frames_out [nrec], pool_out [pool_out_cap] (both 0xA5 where
+// nothing was delivered), the whole OutMail (mail_out: sizeof(OutMail) octets, see vdl2hip_debug_sizeof_outmail) and the AVLC counters acnt [nchan][10].
+// Needs no receiver
+int vdl2hip_debug_sizeof_outmail(void) { return (int)sizeof(OutMail); }
+int vdl2hip_debug_frame_finish(unsigned grid, const void *frames_in, uint32_t nrec, const uint8_t *pool, uint32_t pool_len, const void *ctl_in, const float *ring, uint32_t ring_len,
+		uint32_t nchan, void *frames_out, uint8_t *pool_out, uint32_t pool_out_cap, void *mail_out, unsigned long long *acnt) {
+	if(grid == 0 || grid > 1024 || !ctl_in || !ring || ring_len == 0 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || nchan == 0 || nchan > 1024 || !frames_out || !pool_out || !mail_out || !acnt
+	   || nrec > 1u << 20 || pool_len > 1u << 28 || (nrec && !frames_in) || (pool_len && !pool)) return VDL2HIP_E_INVAL;
+	OutCtl h_ctl; memcpy(&h_ctl, ctl_in, sizeof h_ctl);
+	const uint32_t nf = h_ctl.nframes < h_ctl.cap_frames ? h_ctl.nframes : h_ctl.cap_frames;
+	if(nf > nrec || h_ctl.nvalid != 0 || h_ctl.pool_out_used != 0) return VDL2HIP_E_INVAL;
+	size_t need = 0;
+	for(uint32_t i = 0; i < nf; i++) {
+		const OutFrame &f = ((const OutFrame *)frames_in)[i];
+		if(f.chan < 0) continue;
+		if((uint32_t)f.chan >= nchan || f.len > 1u << 20 || (size_t)f.pool_off + f.len > pool_len) return VDL2HIP_E_INVAL;
+		need += ((size_t)f.len + 3) & ~(size_t)3;
+	}
+	if(need > pool_out_cap) return VDL2HIP_E_INVAL;
+	OutFrame *d_frames = nullptr, *d_fout = nullptr; uint8_t *d_pool = nullptr, *d_pout = nullptr; OutMail *d_mail = nullptr; Tables *d_tab = nullptr; float *d_ring = nullptr; unsigned long long *d_acnt = nullptr;
+	int rc = VDL2HIP_OK;
+	const size_t rec_bytes = ((size_t)nrec + 1) * sizeof(OutFrame), ring_bytes = (size_t)nchan * ring_len * 4;
+	if(hipMalloc((void **)&d_frames, rec_bytes) != hipSuccess || hipMalloc((void **)&d_fout, rec_bytes) != hipSuccess || hipMalloc((void **)&d_pool, (size_t)pool_len + 4) != hipSuccess
+	   || hipMalloc((void **)&d_pout, (size_t)pool_out_cap + 4) != hipSuccess || hipMalloc((void **)&d_mail, sizeof(OutMail)) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess
+	   || hipMalloc((void **)&d_ring, ring_bytes) != hipSuccess || hipMalloc((void **)&d_acnt, (size_t)nchan * kNumAvlcCounters * 8) != hipSuccess) rc = VDL2HIP_E_NOMEM;
+	if(rc == VDL2HIP_OK) {
+		Tables *tab = new Tables; build_tables(*tab);
+		OutMail *mail = new OutMail; memset(mail, 0xA5, sizeof *mail); mail->ctl = h_ctl;
+		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_mail, mail, sizeof(OutMail), hipMemcpyHostToDevice) != hipSuccess
+		   || (nrec && hipMemcpy(d_frames, frames_in, (size_t)nrec * sizeof(OutFrame), hipMemcpyHostToDevice) != hipSuccess) || (pool_len && hipMemcpy(d_pool, pool, pool_len, hipMemcpyHostToDevice) != hipSuccess)
+		   || hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_acnt, 0, (size_t)nchan * kNumAvlcCounters * 8) != hipSuccess
+		   || hipMemset(d_fout, 0xA5, rec_bytes) != hipSuccess || hipMemset(d_pout, 0xA5, (size_t)pool_out_cap + 4) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+		delete tab; delete mail;
+	}
+	if(rc == VDL2HIP_OK) {
+		hipLaunchKernelGGL(k_frame_finish, dim3(grid), dim3(64 * kFrameWaves), 0, 0, d_frames, (const uint8_t *)d_pool, d_mail, (const Tables *)d_tab, d_acnt, (const float *)d_ring, ring_len - 1, d_fout, d_pout);
+		if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(rc == VDL2HIP_OK) {
+		if((nrec && hipMemcpy(frames_out, d_fout, (size_t)nrec * sizeof(OutFrame), hipMemcpyDeviceToHost) != hipSuccess) || (pool_out_cap && hipMemcpy(pool_out, d_pout, pool_out_cap, hipMemcpyDeviceToHost) != hipSuccess)
+		   || hipMemcpy(mail_out, d_mail, sizeof(OutMail), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(acnt, d_acnt, (size_t)nchan * kNumAvlcCounters * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
+	}
+	if(d_frames) (void)hipFree(d_frames);
+	if(d_fout) (void)hipFree(d_fout);
+	if(d_pool) (void)hipFree(d_pool);
+	if(d_pout) (void)hipFree(d_pout);
+	if(d_mail) (void)hipFree(d_mail);
+	if(d_tab) (void)hipFree(d_tab);
+	if(d_ring) (void)hipFree(d_ring);
+	if(d_acnt) (void)hipFree(d_acnt);
 	return rc;
 }
 

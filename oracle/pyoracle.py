@@ -99,6 +99,9 @@ def _bind(L):
     L.vdl2o_crc16.restype = C.c_uint16
     L.vdl2o_crc16.argtypes = [C.c_void_p, C.c_uint32, C.c_uint16]
     L.vdl2o_chebyshev.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.vdl2o_decode_bits.restype = C.c_int
+    L.vdl2o_decode_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(Frame), C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     return L
 
 
@@ -239,3 +242,21 @@ def rs_decode(block255, fec_octets):
     d = (C.c_uint8 * 255)(*block255)
     r = lib().vdl2o_rs_decode(d, fec_octets)
     return r, bytes(d)
+
+
+def decode_bits(bits, frame_pwr=0.0625):
+    """decode_vdl2_burst() on a FIFO of channel bits as the slicer appends them (header included, still scrambled; one bit per
+    element): (frames, counters) - frames as dicts with idx, octets, synd_weight, datalen_octets, num_fec_corrections and
+    frame_pwr_dbfs (10 log10 of frame_pwr, the burst's mean |y|^2), counters as a list of NUM_COUNTERS"""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    cap_f, cap_o = 4096, 1 << 15
+    fr = (Frame * cap_f)()
+    oc = (C.c_uint8 * cap_o)()
+    no = C.c_uint32()
+    cnt = (C.c_uint64 * NUM_COUNTERS)()
+    n = lib().vdl2o_decode_bits(b.ctypes.data, b.size, frame_pwr, fr, cap_f, oc, cap_o, C.byref(no), cnt)
+    assert n >= 0, "vdl2o_decode_bits: more frames than the binding has room for"
+    pool = bytes(oc[:no.value])
+    out = [dict(idx=f.idx, octets=pool[f.octets_off:f.octets_off + f.len], synd_weight=f.synd_weight, datalen_octets=f.datalen_octets,
+                num_fec_corrections=f.num_fec_corrections, frame_pwr_dbfs=f.frame_pwr_dbfs) for f in fr[:n]]
+    return out, list(cnt)

@@ -657,6 +657,40 @@ out:
 	v->decstate = DS_IDLE;
 }
 
+/* A burst given as the channel bits the slicer would have appended to the FIFO - header included, still scrambled, three per
+ * symbol (demod.c:270-274) - through the decoder above, header state and data state, exactly as demod() drives it: the FIFO is
+ * looked at after every symbol, and decoded when it holds want_bits (demod.c:275-281).  frame_pwr: v->frame_pwr at that point
+ * (it decides decoder.msg.good_loud and is what the frames report); the channel is otherwise a fresh one.  Frames go to
+ * frames[cap_frames] (octets_off into octets[cap_octets]; *noctets: octets used), counters[] receives the channel's counters.
+ * Returns the number of frames, or -1 if they or their octets do not fit. */
+int vdl2o_decode_bits(const uint8_t *bits, uint32_t nbits, float frame_pwr, vdl2o_frame *frames, uint32_t cap_frames,
+		uint8_t *octets, uint32_t cap_octets, uint32_t *noctets, uint64_t counters[VDL2O_NUM_COUNTERS]) {
+	pthread_once(&gf_once, gf_setup);
+	pthread_once(&hdr_once, hdr_setup);
+	chan_t ch, *v = &ch;
+	memset(v, 0, sizeof *v);
+	v->bits = calloc(K_FIFO_BITS, 1);
+	v->mag_nf = 2.0f;
+	v->bursts = 1;
+	chan_demod_reset(v);
+	v->frame_pwr = frame_pwr;
+	for(uint32_t i = 0; i < nbits && v->decstate != DS_IDLE; ) {
+		if(v->b_end + 3 > K_FIFO_BITS) break;                               /* bitstream_append_msbfirst, bitstream.c:45-56 */
+		for(int j = 0; j < 3 && i < nbits; j++) v->bits[v->b_end++] = bits[i++] & 1;
+		if(v->b_end - v->b_start >= v->want_bits) chan_decode_burst(NULL, v);
+	}
+	int ret = (int)v->nfr;
+	if(v->nfr > cap_frames || v->noct > cap_octets) ret = -1;
+	else {
+		if(v->nfr) memcpy(frames, v->fr, v->nfr * sizeof *frames);
+		if(v->noct) memcpy(octets, v->oct, v->noct);
+	}
+	if(noctets) *noctets = (uint32_t)v->noct;
+	if(counters) memcpy(counters, v->cnt, sizeof v->cnt);
+	free(v->bits); free(v->fr); free(v->oct);
+	return ret;
+}
+
 /* ======================================================================
  * preamble search + D8PSK slicer: demod.c:98-286
  * ==================================================================== */

@@ -112,6 +112,10 @@ uint16_t vdl2o_crc16(const uint8_t *data, uint32_t len, uint16_t init); /* crc.c
 void vdl2o_chebyshev(float fc, float ripple_pct, float A[3], float B[3]); /* chebyshev.c:67-119, 2 poles */
 int  vdl2o_avlc_screen(const uint8_t *buf, uint32_t len, uint32_t *dst, uint32_t *src, int *dir);  /* avlc.c:163-236 up to the addresses */
 
+/* decode_vdl2_burst() (header state, then data state) on a FIFO of channel bits as the slicer appends them: see vdl2_oracle.c */
+int  vdl2o_decode_bits(const uint8_t *bits, uint32_t nbits, float frame_pwr, vdl2o_frame *frames, uint32_t cap_frames,
+		uint8_t *octets, uint32_t cap_octets, uint32_t *noctets, uint64_t counters[VDL2O_NUM_COUNTERS]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -459,4 +459,55 @@ int hostsim_rs_decode(uint8_t *row, int npar) {
 	return sh.u_ret;
 }
 
+// ---- the burst decoder's pieces on the inputs of tests/burst_reference.py (the GPU build takes the same ones: vdl2hip_debug_burst_probe) ----
+// the wave primitives as the product calls them: 64 words per element -> first flag, flag count, the 64 scanned values, their total, the minimum
+void hostsim_wave_prims(const uint32_t *in, int64_t n, uint32_t *out) {
+	static BurstShared sh;
+	for(int64_t i = 0; i < n; i++) {
+		const uint32_t *x = in + 64 * i; uint32_t *o = out + 68 * i;
+		WAVE_FOR(l)
+			sh.lanek[l] = x[l]; sh.flag_err[l] = (int32_t)x[l];
+		WAVE_END
+		o[0] = (uint32_t)wave_first_flag(sh.flag_err); o[1] = (uint32_t)wave_count_flags(sh.flag_err);
+		o[67] = wave_min64(sh.lanek);
+		o[66] = wave_excl_scan64(sh.lanek);
+		WAVE_FOR(l)
+			o[2 + l] = sh.lanek[l];
+		WAVE_END
+	}
+}
+// header_to_geometry() on n 25-bit words: (status, syndrome, tl_bits, want_bits) each
+void hostsim_header_geometry(const uint32_t *hdr, int64_t n, uint32_t *out) {
+	static Tables T; static bool init = false;
+	if(!init) { build_tables(T); init = true; }
+	for(int64_t i = 0; i < n; i++) { const Geometry g = header_to_geometry(hdr[i], T.hdr_H, T.hdr_fix); out[4 * i] = (uint32_t)g.status; out[4 * i + 1] = g.syndrome; out[4 * i + 2] = g.tl_bits; out[4 * i + 3] = g.want_bits; }
+}
+// decode_burst() on n bursts, burst i on ring y + i * ring_len of its own, referee off, as `nwaves` wavefronts would take them (wavefront w:
+// bursts w, w + nwaves, ... on one BurstShared, with the wavefront's own share of the output); outputs as vdl2hip_debug_burst_probe's:
+// frames [cap_frames + guard_frames], pool [cap_pool + guard_pool] (0xA5 where nothing was written), the control block, cnt [nchan][20]
+int hostsim_decode_burst(const Burst *bursts, int64_t n, uint32_t nwaves, const uint32_t *freq, uint32_t nchan, const float *y, uint32_t ring_len,
+		uint32_t cap_frames, uint32_t cap_pool, uint32_t guard_frames, uint32_t guard_pool, OutFrame *frames, uint8_t *pool, OutCtl *ctl, unsigned long long *cnt) {
+	static Tables T; static bool init = false;
+	if(!init) { build_tables(T); init = true; }
+	if(nwaves == 0 || ring_len < 64 || (ring_len & (ring_len - 1))) return -1;
+	for(int64_t i = 0; i < n; i++) if(bursts[i].chan < 0 || (uint32_t)bursts[i].chan >= nchan || bursts[i].nsym < 1 || bursts[i].nsym > kMaxSyms || bursts[i].tl_bits == 0 || bursts[i].tl_bits > kMaxTl) return -1;
+	memset(frames, 0xA5, ((size_t)cap_frames + guard_frames) * sizeof(OutFrame)); memset(pool, 0xA5, (size_t)cap_pool + guard_pool);
+	memset(cnt, 0, (size_t)nchan * kNumCounters * sizeof *cnt); memset(ctl, 0, sizeof *ctl);
+	ctl->cap_frames = cap_frames; ctl->cap_pool = cap_pool;
+	ctl->nframes = burst_reserve_initial_frames(nwaves); ctl->pool_used = burst_reserve_initial_pool(nwaves);
+	static BurstShared sh;
+	for(uint32_t w = 0; w < nwaves; w++) {
+		burst_shared_init(T, w, ctl, sh);
+		for(int64_t i = w; i < n; i += nwaves) {
+			const Burst &b = bursts[i];
+			ChanView v{ reinterpret_cast<const cf32 *>(y) + (size_t)i * ring_len, nullptr, nullptr, ring_len - 1 };
+			decode_burst(b, freq[b.chan], T, v, cnt + (size_t)b.chan * kNumCounters, frames, pool, ctl, sh);
+		}
+		burst_reserve_done(frames, sh);
+	}
+	return 0;
+}
+int hostsim_sizeof_burst() { return (int)sizeof(Burst); }
+int hostsim_sizeof_outctl() { return (int)sizeof(OutCtl); }
+
 }

@@ -61,7 +61,7 @@ class HostSim:
         n = self.L.hostsim_num_frames(self.h)
         fr = self.L.hostsim_frames(self.h)
         pool = self.L.hostsim_pool(self.h)
-        base = C.addressof(pool.contents) if n else 0
+        base = C.addressof(pool.contents) if pool else 0      # (no octets at all - only zero-length frames - is a NULL pool)
         out = []
         for i in range(n):
             f = fr[i]
