@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include "resample_design.h"
 #include "spectrum.h"
 #include "spectrum_design.h"
+#include "activity.h"
 #include "tables.h"
 
 using namespace vdl2;
@@ -97,6 +99,7 @@ struct OutSlot {
 	hipEvent_t ev_stitch = nullptr, ev_chk = nullptr; uint32_t *d_rqflag2 = nullptr;
 	hipEvent_t ev_rs[2] = {}; bool rs_timed = false;   // resampling receivers: start / stop of this feed's k_resample (profiling level 2)
 	hipEvent_t ev_mon[4] = {}; int mon_timed = 0;      // input monitor: start / stop of this feed's k_spectrum and k_spectrum_reduce (profiling level 2); how many of the two were timed
+	hipEvent_t ev_act[4] = {}; int act_timed = 0;      // activity monitor: the same for this feed's k_activity_power and k_activity_scan
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -123,6 +126,17 @@ struct vdl2hip_ctx {
 		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
 		hipStream_t rd = nullptr; double *h_acc = nullptr;      // the read's own stream and page-locked landing place (kept until the receiver goes)
 	} mon;
+	// Activity monitor (activity.h, vdl2hip_activity_*): off unless enabled.  k_on: the decimated samples made before it was enabled;
+	// bins: complete so far; carry: per channel the float32 sum of what the stream holds of the incomplete bin it stands in (two
+	// buffers, alternating); acc / st: the scan's accumulators and the transmission under way, per channel
+	struct {
+		bool on = false; uint32_t B = 0, H = 0, S = 0; float thr_dbfs = 0.f, thr = 0.f; int64_t k_on = 0; uint64_t bins = 0;
+		float *d_series = nullptr, *d_carry[2] = {nullptr, nullptr}, *d_edges = nullptr; int carry_sel = 0;
+		ActChan *d_acc = nullptr; ActState *d_st = nullptr;
+		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
+		hipStream_t rd = nullptr; uint8_t *h_buf = nullptr;       // the read's own stream and page-locked landing place (kept until the receiver goes)
+	} act;
+	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
 	LpfCoeffs lpf{};
@@ -244,6 +258,8 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(sl.rs_timed) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->stats.resample_ms += ms; else (void)hipGetLastError(); sl.rs_timed = false; }
 	for(int i = 0; i < sl.mon_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_mon[2 * i], sl.ev_mon[2 * i + 1]) == hipSuccess) c->mon.kernel_ms += ms; else (void)hipGetLastError(); }
 	sl.mon_timed = 0;
+	for(int i = 0; i < sl.act_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_act[2 * i], sl.ev_act[2 * i + 1]) == hipSuccess) c->act.kernel_ms += ms; else (void)hipGetLastError(); }
+	sl.act_timed = 0;
 	if(c->profiling && sl.ev_valid) {
 		hipEvent_t *ev = sl.ev;
 		float ms = 0.f;
@@ -313,6 +329,47 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0) {
 		if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
 	}
 	return rc;
+}
+
+// The activity monitor's share of a feed (activity.h): on the front stream directly behind the channeliser - k_chanfir, every piece
+// of a cold-start feed, k_fixup where it is not fused - and ahead of the sync kernels.  Everything that rewrites y (the referee's
+// scans, on the back streams) waits for an ev_front, which is recorded behind the sync kernels of its feed, and writes nothing at
+// or beyond that feed's last sample (k_ref_scan_multi: n_hi <= in_end / os - 1): what the monitor reads of this feed, [k0, k0 + D),
+// is the channeliser's.  Host bookkeeping: the bin the stream stands in, the bins this feed completes, which carry is current.
+static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
+	auto &m = c->act;
+	const uint64_t B = m.B, t0 = (uint64_t)(k0 - m.k_on), t1 = t0 + (uint64_t)D;
+	const uint64_t m0 = t0 / B, m1 = t1 / B, nb = m1 - m0;
+	ActArgs a{};
+	a.y = (const float2 *)c->d_y; a.series = m.d_series; a.carry_in = m.d_carry[m.carry_sel]; a.carry_out = m.d_carry[m.carry_sel ^ 1];
+	a.k0 = k0; a.m0 = m0; a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = (uint32_t)D; a.B = m.B; a.nbt = (uint32_t)nb + 1;
+	a.cap = c->cap; a.mask = c->cap - 1; a.S = m.S; a.smask = m.S - 1;
+	// bins per workgroup: some 4096 workgroups over the channels, each with one to eight chunks' worth of samples
+	const uint64_t per = std::min<uint64_t>(8 * kActChunk, std::max<uint64_t>(kActChunk, (uint64_t)D * (uint64_t)c->C / 4096));
+	a.run = (uint32_t)std::max<uint64_t>(1, per / B);
+	const unsigned gx = (a.nbt + a.run - 1) / a.run;
+	const bool timed = c->profiling >= 2;
+	if(timed) for(auto &e : sl.ev_act) if(!e) HIPCHK(hipEventCreate(&e));
+	hipEvent_t *e = sl.ev_act;
+	hipExtLaunchKernelGGL(k_activity_power, dim3(gx, (unsigned)c->C), dim3(kActThreads), 0u, c->stream, timed ? e[0] : nullptr, timed ? e[1] : nullptr, 0, a);
+	if(nb) {
+		ActScanArgs sa{ m.d_series, m.d_acc, m.d_st, m.d_edges, m.thr, m0, (uint32_t)nb, m.H, m.S, m.S - 1 };
+		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->stream, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0, sa);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(m.ev_last, c->stream));
+	if(timed) sl.act_timed = nb ? 2 : 1;
+	m.queued = true; m.bins = m1; m.carry_sel ^= 1;
+	return VDL2HIP_OK;
+}
+// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context)
+static void activity_free(vdl2hip_ctx *c) {
+	auto &m = c->act;
+	if(m.queued && m.ev_last) (void)hipEventSynchronize(m.ev_last);
+	void *q[] = { m.d_series, m.d_carry[0], m.d_carry[1], m.d_edges, m.d_acc, m.d_st };
+	for(void *p : q) if(p) (void)hipFree(p);
+	m.d_series = nullptr; m.d_carry[0] = m.d_carry[1] = nullptr; m.d_edges = nullptr; m.d_acc = nullptr; m.d_st = nullptr;
+	m.on = false; m.queued = false;
 }
 
 static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
@@ -390,6 +447,8 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 			LAUNCH_EV(k_fixup, dim3((unsigned)((D + 255) / 256), (unsigned)c->C), dim3(256), st, EV(2), EV(3), k2);
 		}
 		c->tcarry_sel ^= 1;
+		// this feed's y is complete on the front stream: the activity monitor reads it here, ahead of the sync kernels (activity_feed)
+		if(c->act.on) { int r = activity_feed(c, sl, c->k_total, D); if(r != VDL2HIP_OK) return r; }
 	}
 	if(nrem) hipLaunchKernelGGL(k_carry, dim3(1), dim3(64), 0, st, a, (void *)c->d_carry[c->carry_sel ^ 1], nrem);
 	c->carry_sel ^= 1; c->ncarry = nrem;
@@ -869,6 +928,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 		if(sl.ev_chk) (void)hipEventDestroy(sl.ev_chk);
 		for(auto &e : sl.ev_rs) if(e) (void)hipEventDestroy(e);
 		for(auto &e : sl.ev_mon) if(e) (void)hipEventDestroy(e);
+		for(auto &e : sl.ev_act) if(e) (void)hipEventDestroy(e);
 		if(sl.h_mail) (void)hipHostFree(sl.h_mail);
 		if(sl.done) (void)hipEventDestroy(sl.done);
 		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
@@ -886,6 +946,10 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	if(c->mon.ev_last) (void)hipEventDestroy(c->mon.ev_last);
 	if(c->mon.rd) (void)hipStreamDestroy(c->mon.rd);
 	if(c->mon.h_acc) (void)hipHostFree(c->mon.h_acc);
+	activity_free(c);
+	if(c->act.ev_last) (void)hipEventDestroy(c->act.ev_last);
+	if(c->act.rd) (void)hipStreamDestroy(c->act.rd);
+	if(c->act.h_buf) (void)hipHostFree(c->act.h_buf);
 	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
 	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
 	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
@@ -966,6 +1030,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	const size_t sb = sample_bytes(c->fmt);
 	const uint64_t max_samples = (resample ? rs_max_out : max_bytes / sb) + c->os;
 	const uint64_t dmax = max_samples / c->os + 1;
+	c->dmax = dmax;
 	uint32_t cap = 1; while(cap < kSlots * dmax + kHistory + 1024) cap <<= 1;   // kSlots feeds may be in flight (fronts of i+1, i+2 over back of i)
 	c->cap = cap;
 	c->in_cap = max_bytes;
@@ -1930,6 +1995,157 @@ int vdl2hip_spectrum_channels(vdl2hip_ctx *c, float *dbfs, size_t cap) {
 		dbfs[ch] = sum > 0.0 ? (float)(10.0 * std::log10(sum / m.enbw)) : -INFINITY;
 	}
 	return (int)nchan;
+}
+
+// ---- the activity monitor (vdl2hip.h, "Activity monitor"; kernels: activity.h) ----
+static_assert(sizeof(ActChan) == sizeof(vdl2hip_activity_chan) && offsetof(ActChan, hist) == offsetof(vdl2hip_activity_chan, hist), "the host copies the device's accumulators as they are");
+static float activity_edge(int i) { return (float)std::pow(10.0, (double)(-120 + 2 * i) / 10.0); }
+int vdl2hip_activity_edges(float *edges, size_t cap) {
+	if(!edges || cap < (size_t)kActBuckets - 1) return VDL2HIP_E_TOOBIG;
+	for(int i = 0; i < kActBuckets - 1; i++) edges[i] = activity_edge(i);
+	return kActBuckets - 1;
+}
+
+// test hook (not declared in vdl2hip.h; host only): the scan's word step (act_scan_word) over `count` words of nbits[i] <= 64 busy flags
+// each, from an idle start -> out = { transmissions, longest_bins, open, first bin of the open transmission }
+int vdl2hip_debug_activity_words(const uint64_t *busy, const uint32_t *nbits, uint32_t count, uint32_t hang_bins, uint64_t out[4]) {
+	if(!busy || !nbits || !out || hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
+	ActState st{}; uint64_t tx = 0, longest = 0, base = 0;
+	for(uint32_t i = 0; i < count; i++) {
+		if(nbits[i] == 0 || nbits[i] > 64 || (nbits[i] < 64 && (busy[i] >> nbits[i]) != 0)) return VDL2HIP_E_INVAL;
+		act_scan_word(busy[i], nbits[i], hang_bins, base, st, tx, longest);
+		base += nbits[i];
+	}
+	out[0] = tx; out[1] = longest; out[2] = st.open; out[3] = st.open ? st.first : 0;
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
+// one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
+// series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.
+int vdl2hip_debug_activity_power(const float *y, uint32_t cap, int64_t k0, uint32_t D, uint32_t B, uint64_t t0, uint32_t run, float carry_in, float *series, uint32_t S, float *carry_out) {
+	if(!y || !series || !carry_out || !cap || (cap & (cap - 1)) || !S || (S & (S - 1)) || B < kActMinBin || B > kActMaxBin || !D || D > cap || !run || k0 < 0 || ((uintptr_t)y & 15)) return VDL2HIP_E_INVAL;
+	const uint64_t m0 = t0 / B, nb = (t0 + D) / B - m0;
+	if(nb > S) return VDL2HIP_E_TOOBIG;
+	ActArgs a{};
+	a.y = (const float2 *)y; a.series = series; a.carry_in = &carry_in; a.carry_out = carry_out; a.k0 = k0; a.m0 = m0;
+	a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = D; a.B = B; a.nbt = (uint32_t)nb + 1; a.run = run; a.cap = cap; a.mask = cap - 1; a.S = S; a.smask = S - 1;
+	// staging arrays with a guard zone of NaNs behind each: a store or a load beyond the kernel's sizes shows
+	constexpr int G = 64;
+	std::vector<float> p(kActLdsP + G), sb(kActMaxSubs + G), gr(kActLdsG + G);
+	bool bad = false;
+	for(uint32_t bx = 0; bx * run < a.nbt; bx++) {
+		uint32_t j = bx * run;
+		const uint32_t jend = j + run < a.nbt ? j + run : a.nbt;
+		int64_t pos = act_run_start(a, j);
+		bool fresh = true;
+		float acc[kActThreads] = {};
+		while(j < jend) {
+			const ActPlan k = act_plan(a, j, jend, pos, fresh);
+			if(k.pos < 0 || k.pos + k.len > D || k.nseg > (uint32_t)kActMaxSegs || k.nsb > (uint32_t)kActMaxSubs || k.ngr > (uint32_t)kActLdsG || act_pad(k.o + k.len) >= (uint32_t)kActLdsP) return VDL2HIP_E_DEVICE;
+			for(auto *v : { &p, &sb, &gr }) std::fill(v->begin(), v->end(), NAN);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<0>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<1>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<2>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<3>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(int i = 0; i < G; i++) bad = bad || !std::isnan(p[kActLdsP + i]) || !std::isnan(sb[kActMaxSubs + i]) || !std::isnan(gr[kActLdsG + i]);
+			if(!k.fin0) { pos += kActChunk; fresh = false; }
+			else { j += k.nseg; pos += k.len; fresh = true; }
+		}
+	}
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+
+int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_activity_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	const uint32_t B = cfg->bin_samples ? cfg->bin_samples : 105u;
+	if(B < kActMinBin || B > kActMaxBin || cfg->hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
+	if(cfg->series_bins > kActMaxSeries || (cfg->series_bins & (cfg->series_bins - 1)) != 0) return VDL2HIP_E_INVAL;
+	if(std::isnan(cfg->threshold_dbfs)) return VDL2HIP_E_INVAL;
+	uint32_t S = 1; while(S < cfg->series_bins || S < c->dmax / B + 2) S <<= 1;           // a feed's bins never overwrite one another in the ring
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	auto &m = c->act;
+	activity_free(c);
+	for(auto &sl : c->slot) sl.act_timed = 0;                        // (what an earlier monitor's launches took is not this one's)
+	const size_t C = (size_t)c->C, host_bytes = C * (sizeof(ActChan) + sizeof(ActState));
+	if(!m.ev_last) HIPCHK(hipEventCreateWithFlags(&m.ev_last, hipEventDisableTiming));
+	if(!m.rd) HIPCHK(hipStreamCreateWithFlags(&m.rd, hipStreamNonBlocking));
+	if(!m.h_buf) HIPCHK(hipHostMalloc((void **)&m.h_buf, host_bytes, hipHostMallocDefault));
+	struct { void **p; size_t bytes; } al[] = { { (void **)&m.d_series, C * S * sizeof(float) }, { (void **)&m.d_carry[0], C * sizeof(float) },
+		{ (void **)&m.d_carry[1], C * sizeof(float) }, { (void **)&m.d_edges, kActBuckets * sizeof(float) },
+		{ (void **)&m.d_acc, C * sizeof(ActChan) }, { (void **)&m.d_st, C * sizeof(ActState) } };
+	for(auto &x : al) if(hipMalloc(x.p, x.bytes) != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_NOMEM; }
+	float edges[kActBuckets] = {};
+	(void)vdl2hip_activity_edges(edges, kActBuckets);
+	bool ok = hipMemcpy(m.d_edges, edges, sizeof edges, hipMemcpyHostToDevice) == hipSuccess;
+	for(auto &x : al) if(x.p != (void **)&m.d_edges) ok = ok && hipMemset(*x.p, 0, x.bytes) == hipSuccess;
+	if(!ok || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_DEVICE; }
+	m.B = B; m.H = cfg->hang_bins; m.S = S; m.thr_dbfs = cfg->threshold_dbfs; m.thr = (float)std::pow(10.0, (double)cfg->threshold_dbfs / 10.0);
+	m.k_on = c->k_total; m.bins = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.queued = false;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_activity_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	activity_free(c);
+	for(auto &sl : c->slot) sl.act_timed = 0;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_activity_read(vdl2hip_ctx *c, vdl2hip_activity_info *info, vdl2hip_activity_chan *chans, size_t cap_chans, int reset) {
+	if(!c || !c->act.on || (info && info->struct_size != sizeof(vdl2hip_activity_info))) return VDL2HIP_E_INVAL;
+	auto &m = c->act;
+	const size_t C = (size_t)c->C;
+	if(chans && cap_chans < C) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	if(chans) {
+		ActState *st = (ActState *)(m.h_buf + C * sizeof(ActChan));
+		if(m.queued) {
+			// on a stream of the monitor's own, behind the event of its last launch: the read waits for nothing else - not for the feeds
+			// in flight, not for what the process has on the default stream
+			HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
+			HIPCHK(hipMemcpyAsync(m.h_buf, m.d_acc, C * sizeof(ActChan), hipMemcpyDeviceToHost, m.rd));
+			HIPCHK(hipMemcpyAsync(st, m.d_st, C * sizeof(ActState), hipMemcpyDeviceToHost, m.rd));
+			HIPCHK(hipStreamSynchronize(m.rd));
+		} else memset(m.h_buf, 0, C * (sizeof(ActChan) + sizeof(ActState)));      // nothing has touched them since they were zeroed
+		memcpy(chans, m.h_buf, C * sizeof(ActChan));
+		for(size_t i = 0; i < C; i++) { chans[i].open = st[i].open; chans[i].reserved = 0; if(!chans[i].bins) chans[i].max_power = chans[i].min_power = 0.f; }
+	}
+	if(info) {
+		memset(info, 0, sizeof *info);
+		info->struct_size = sizeof *info; info->bin_samples = m.B; info->hang_bins = m.H; info->series_bins = m.S;
+		info->threshold_dbfs = m.thr_dbfs; info->threshold_power = m.thr; info->first_sample = m.k_on; info->bins = m.bins;
+		info->kernel_ms = (float)m.kernel_ms;
+	}
+	if(reset) {
+		// (on the front stream: behind the launches that are queued, ahead of the next feed's; the transmission under way is kept)
+		HIPCHK(hipMemsetAsync(m.d_acc, 0, C * sizeof(ActChan), c->stream));
+		HIPCHK(hipEventRecord(m.ev_last, c->stream));
+		m.queued = true;
+	}
+	return chans ? (int)C : 0;
+}
+
+int vdl2hip_activity_series(vdl2hip_ctx *c, uint32_t chan, int64_t first_bin, float *dst, size_t cap) {
+	if(!c || !c->act.on || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
+	auto &m = c->act;
+	if(first_bin < 0 || (uint64_t)first_bin > m.bins || m.bins - (uint64_t)first_bin > m.S) return VDL2HIP_E_INVAL;
+	const size_t n = std::min<size_t>(cap, (size_t)(m.bins - (uint64_t)first_bin));
+	if(n == 0) return 0;
+	if(!dst) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	const float *base = m.d_series + (size_t)(chan - (uint32_t)c->chan_first) * m.S;
+	const size_t p0 = (size_t)((uint64_t)first_bin & (m.S - 1)), n0 = std::min<size_t>(n, m.S - p0);
+	HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
+	HIPCHK(hipMemcpyAsync(dst, base + p0, n0 * sizeof(float), hipMemcpyDeviceToHost, m.rd));
+	if(n0 < n) HIPCHK(hipMemcpyAsync(dst + n0, base, (n - n0) * sizeof(float), hipMemcpyDeviceToHost, m.rd));
+	HIPCHK(hipStreamSynchronize(m.rd));
+	return (int)n;
 }
 
 int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {

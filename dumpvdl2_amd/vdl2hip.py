@@ -45,6 +45,7 @@ EXPORTS = [
     "vdl2hip_group_uses_rccl", "vdl2hip_group_set_exchange", "vdl2hip_group_exchange",
     "vdl2hip_read_resampled", "vdl2hip_resampler_design",
     "vdl2hip_spectrum_window", "vdl2hip_spectrum_enable", "vdl2hip_spectrum_read", "vdl2hip_spectrum_channels",
+    "vdl2hip_activity_edges", "vdl2hip_activity_enable", "vdl2hip_activity_disable", "vdl2hip_activity_read", "vdl2hip_activity_series",
 ]
 WIN_RECT, WIN_HANN, WIN_BH4 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_WIN_* (the input monitor's analysis windows)
 
@@ -88,6 +89,28 @@ class SpectrumInfo(C.Structure):
                 ("segments", C.c_uint64), ("samples", C.c_uint64), ("clipped", C.c_uint64),
                 ("enbw_bins", C.c_double), ("mean_power", C.c_double), ("dc_i", C.c_double), ("dc_q", C.c_double),
                 ("peak", C.c_float), ("kernel_ms", C.c_float)]
+
+
+class ActivityCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bin_samples", C.c_uint32), ("hang_bins", C.c_uint32), ("series_bins", C.c_uint32),
+                ("threshold_dbfs", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ActivityInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bin_samples", C.c_uint32), ("hang_bins", C.c_uint32), ("series_bins", C.c_uint32),
+                ("threshold_dbfs", C.c_float), ("threshold_power", C.c_float), ("first_sample", C.c_int64), ("bins", C.c_uint64),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ActivityChan(C.Structure):
+    _fields_ = [("bins", C.c_uint64), ("busy_bins", C.c_uint64), ("transmissions", C.c_uint64), ("longest_bins", C.c_uint64),
+                ("sum_power", C.c_double), ("max_power", C.c_float), ("min_power", C.c_float), ("open", C.c_uint32), ("reserved", C.c_uint32),
+                ("hist", C.c_uint64 * 64)]
+
+
+ACTIVITY_CHAN_DTYPE = np.dtype([("bins", "<u8"), ("busy_bins", "<u8"), ("transmissions", "<u8"), ("longest_bins", "<u8"),
+                                ("sum_power", "<f8"), ("max_power", "<f4"), ("min_power", "<f4"), ("open", "<u4"), ("reserved", "<u4"),
+                                ("hist", "<u8", (64,))])     # vdl2hip_activity_chan, 568 bytes
 
 
 class PackedFrame(C.Structure):
@@ -149,6 +172,12 @@ def load_library(path: str = None):
         L.vdl2hip_spectrum_enable.argtypes = [C.c_void_p, C.POINTER(SpectrumCfg)]
         L.vdl2hip_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumInfo), C.c_void_p, C.c_size_t, C.c_int]
         L.vdl2hip_spectrum_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_activity_enable"):               # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_activity_edges.argtypes = [C.c_void_p, C.c_size_t]
+        L.vdl2hip_activity_enable.argtypes = [C.c_void_p, C.POINTER(ActivityCfg)]
+        L.vdl2hip_activity_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_activity_read.argtypes = [C.c_void_p, C.POINTER(ActivityInfo), C.c_void_p, C.c_size_t, C.c_int]
+        L.vdl2hip_activity_series.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_size_t]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -233,6 +262,47 @@ def _spectrum_read(Lib, ctx, reset: bool, power: bool) -> dict:
         out["freq_hz"] = info.centerfreq + (np.arange(n, dtype=np.float64) - n // 2) * (info.sample_rate / n)
         out["power"] = p
     return out
+
+
+def activity_edges() -> np.ndarray:
+    """The 63 edges E[i] = float32(10^((-120 + 2 i) / 10)) of the activity monitor's 64 level buckets (vdl2hip.h, "Activity monitor").
+    Needs no GPU."""
+    Lib = load_library()
+    e = np.zeros(63, dtype=np.float32)
+    r = Lib.vdl2hip_activity_edges(e.ctypes.data, e.size)
+    if r != 63:
+        raise Vdl2HipError(f"vdl2hip_activity_edges: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return e
+
+
+def _err(Lib, r, what):
+    if r < 0:
+        raise Vdl2HipError(f"{what}: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return r
+
+
+def _activity_enable(Lib, ctx, bin_samples, threshold_dbfs, hang_bins, series_bins) -> None:
+    cfg = ActivityCfg(C.sizeof(ActivityCfg), bin_samples, hang_bins, series_bins, threshold_dbfs, 0)
+    _err(Lib, Lib.vdl2hip_activity_enable(ctx, C.byref(cfg)), "vdl2hip_activity_enable")
+
+
+def _activity_read(Lib, ctx, nchan: int, reset: bool) -> dict:
+    """vdl2hip_activity_read() on a context handle -> dict of every info field plus one numpy array per field of vdl2hip_activity_chan
+    ([C], hist [C, 64]; its `bins` under the name chan_bins) for the context's own channels, first to last"""
+    info = ActivityInfo(C.sizeof(ActivityInfo))
+    ch = np.zeros(nchan, dtype=ACTIVITY_CHAN_DTYPE)
+    n = _err(Lib, Lib.vdl2hip_activity_read(ctx, C.byref(info), ch.ctypes.data, ch.size, int(reset)), "vdl2hip_activity_read")
+    out = {k: getattr(info, k) for k, _ in ActivityInfo._fields_ if k not in ("struct_size", "reserved")}
+    for k in ACTIVITY_CHAN_DTYPE.names:
+        if k != "reserved":
+            out["chan_bins" if k == "bins" else k] = ch[k][:n].copy()     # (info.bins: complete so far; chan_bins: since the last reset)
+    return out
+
+
+def _activity_series(Lib, ctx, chan: int, first_bin: int, count: int) -> np.ndarray:
+    buf = np.zeros(max(1, count), dtype=np.float32)
+    n = _err(Lib, Lib.vdl2hip_activity_series(ctx, chan, first_bin, buf.ctypes.data, count), "vdl2hip_activity_series")
+    return buf[:n]
 
 
 class Receiver:
@@ -449,6 +519,24 @@ class Receiver:
         self._chk(self.L.vdl2hip_spectrum_channels(self.h, out.ctypes.data, out.size), "vdl2hip_spectrum_channels")
         return out
 
+    def activity_enable(self, bin_samples: int = 105, threshold_dbfs: float = -40.0, hang_bins: int = 0, series_bins: int = 0) -> None:
+        """switch the activity monitor on from the next feed (vdl2hip.h, "Activity monitor"): the power of every channel's decimated
+        stream in bins of bin_samples (105 = 1 ms); a bin is busy above threshold_dbfs, a transmission bridges up to hang_bins idle bins;
+        the device keeps the last series_bins values per channel (a power of two; 0: what one feed can complete)."""
+        _activity_enable(self.L, self.h, bin_samples, threshold_dbfs, hang_bins, series_bins)
+
+    def activity_disable(self) -> None:
+        self._chk(self.L.vdl2hip_activity_disable(self.h), "vdl2hip_activity_disable")
+
+    def activity(self, reset: bool = False) -> dict:
+        """what the monitor has accumulated: the fields of vdl2hip_activity_info, and per field of vdl2hip_activity_chan a numpy array
+        over this receiver's channels (hist: [C, 64]; bins since the last reset: chan_bins).  reset: zero the accumulators afterwards (the bin position runs on)."""
+        return _activity_read(self.L, self.h, self.chan_count, reset)
+
+    def activity_series(self, chan: int, first_bin: int, count: int) -> np.ndarray:
+        """up to `count` bin powers p[first_bin ...] of channel `chan` (its index in the frequency list), float32"""
+        return _activity_series(self.L, self.h, chan, first_bin, count)
+
     def read_resampled(self, first: int, count: int) -> np.ndarray:
         """up to `count` (re, im) pairs of the resampled stream r[first ...] (receivers created with input_rate; the last six feeds' are kept)"""
         buf = np.zeros((count, 2), dtype=np.float32)
@@ -549,6 +637,32 @@ class ReceiverGroup:
             if n >= 0:
                 return buf[:2 * n].reshape(-1, 2)
         raise Vdl2HipError("no member owns that channel")
+
+    def member(self, i: int):
+        """the context handle of member i (vdl2hip_group_ctx): what the per-context calls take - vdl2hip_spectrum_*, vdl2hip_activity_*"""
+        return C.c_void_p(self.L.vdl2hip_group_ctx(self.h, i))
+
+    def activity_enable(self, bin_samples: int = 105, threshold_dbfs: float = -40.0, hang_bins: int = 0, series_bins: int = 0) -> None:
+        """the activity monitor of every member (there is no group call: each member monitors its own channels)"""
+        for i in range(self.size()):
+            _activity_enable(self.L, self.member(i), bin_samples, threshold_dbfs, hang_bins, series_bins)
+
+    def activity_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_activity_disable(self.member(i)), "vdl2hip_activity_disable")
+
+    def activity(self, member: int, reset: bool = False) -> dict:
+        """Receiver.activity() of one member: its own channels, first to last"""
+        return _activity_read(self.L, self.member(member), len(self.freqs), reset)
+
+    def activity_series(self, chan: int, first_bin: int, count: int) -> np.ndarray:
+        """Receiver.activity_series() from the member that owns channel `chan`"""
+        buf = np.zeros(max(1, count), dtype=np.float32)
+        for i in range(self.size()):
+            n = self.L.vdl2hip_activity_series(self.member(i), chan, first_bin, buf.ctypes.data, count)
+            if n >= 0:
+                return buf[:n]
+        raise Vdl2HipError("no member holds that channel and bin")
 
     def close(self):
         if getattr(self, "h", None):

@@ -40,7 +40,9 @@ extern "C" {
                                  *    means input_rate 0), vdl2hip_stats.resampled_samples / resample_ms (at its end), vdl2hip_read_resampled(),
                                  *    vdl2hip_resampler_design(): nothing changed for a caller that does not set input_rate, so the version stayed
                                  *    vdl2hip_spectrum_window() / _enable() / _read() / _channels() with vdl2hip_spectrum_cfg / _info: the input monitor, off
-                                 *    unless enabled - new entry points and structures only, nothing existing changed size or meaning, so the version stayed */
+                                 *    unless enabled - new entry points and structures only, nothing existing changed size or meaning, so the version stayed
+                                 *    vdl2hip_activity_edges() / _enable() / _disable() / _read() / _series() with vdl2hip_activity_cfg / _info / _chan: the
+                                 *    activity monitor, off unless enabled - again new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -172,6 +174,58 @@ typedef struct {
 	float    peak, kernel_ms;                  /* kernel_ms: summed HIP-event time of the monitor's launches at profiling level 2, else 0
 	                                            * (of the feeds collected so far: after vdl2hip_sync(), all of them) */
 } vdl2hip_spectrum_info;                       /* 88 bytes */
+
+/* Activity monitor (not in the reference, which reports what it decoded and nothing about what else was on a channel): an optional
+ * power envelope of every channel's DECIMATED stream in fixed time bins, and from it the share of time a channel is occupied, the
+ * transmissions it carried, a level histogram and a short series per channel - collisions, bursts too weak to synchronise and other
+ * users of the channel included.  Off unless enabled; with it off nothing is launched or allocated and every result is what it was,
+ * to the bit.  On, frames, counters and the decimated stream are still exactly what they were: the monitor only reads.
+ *  - Samples.  y_c[k] is decimated sample k (the 105 kS/s clock of sync_sample) of channel c as the channeliser wrote it, BEFORE any
+ *    stretch of it is replaced by the referee: the monitor runs on the front stream directly behind the channeliser, ahead of the sync
+ *    kernels, and everything that rewrites y waits for the end of those.
+ *  - Bins.  B = bin_samples, 10 <= B <= 10500; 0 means 105 (1 ms, 10.5 symbols).  k_on = the decimated samples produced before
+ *    vdl2hip_activity_enable().  Bin m covers k_on + m B .. k_on + (m + 1) B - 1 and  p_c[m] = (1 / B) sum (re^2 + im^2)  over it, in
+ *    float32.  A bin exists once it is complete; which bins exist depends on the stream alone, not on how it was cut into feeds (a feed
+ *    may add no decimated sample, a bin may span many feeds).  A bin that straddles feeds is finished from a carried float32 partial
+ *    sum per channel; the monitor never reads y behind the current feed's first sample.
+ *  - Accuracy.  Against the same y summed in float64,  |p - p_ref| <= (B + 4) 2^-24 p_ref:  every term is non-negative, so any order
+ *    of float32 additions stays inside (B - 1) 2^-24; the square, the add and the division take the rest.  The same sequence of calls
+ *    gives the same bits (no floating-point atomics; the order of additions is fixed by the bin and by where the feeds were cut, not
+ *    by the launch); the same stream cut differently gives values within twice that bound of each other.
+ *  - Busy.  thr = (float)10^(threshold_dbfs / 10), computed in double and rounded once (threshold_power).  Bin m is busy iff
+ *    p_c[m] > thr, a float32 comparison.  A NaN threshold is refused.
+ *  - Transmissions.  H = hang_bins, 0 <= H <= 255.  A transmission is a maximal set of busy bins in which consecutive busy bins are
+ *    separated by at most H idle bins; its length is last busy - first busy + 1 bins; it is counted at its first busy bin.  It is
+ *    `open` after a bin iff at most H idle bins have followed its last busy bin.  The state is carried per channel across feeds.
+ *  - Histogram.  64 buckets; edges E[i] = (float)10^((-120 + 2 i) / 10), i = 0 .. 62, computed in double and rounded once
+ *    (vdl2hip_activity_edges());  bucket(p) = #{ i : E[i] <= p }  in 0 .. 63.
+ *  - Accumulators per channel, since enable or the last reset: bins, busy_bins, transmissions, longest_bins (a transmission still
+ *    open counts with what it has so far), sum_power (float64: the bins of a feed in words of 64, each word summed by a fixed tree, the
+ *    words in order), max_power and min_power (float32, 0 while bins is 0), hist[64], and open.
+ *  - Series.  The device keeps the last series_bins values of p_c[m] per channel: a power of two, raised to at least the bins one
+ *    feed of max_block_bytes can complete; 0 means that minimum; above 2^20 is refused.
+ *  - Reset zeroes the accumulators after the copy.  The bin position runs on; an open transmission stays open and is not counted a
+ *    second time.
+ *  - Channels are addressed by their index in cfg.freqs, like vdl2hip_counters(); one outside this context's shard: VDL2HIP_E_INVAL.
+ *    Groups get no group call: vdl2hip_group_ctx(g, k) is the handle for member k's channels.
+ *  - A receiver that resamples monitors the stream it decodes: nothing is special there. */
+typedef struct { uint32_t struct_size, bin_samples, hang_bins, series_bins; float threshold_dbfs; uint32_t reserved; } vdl2hip_activity_cfg;   /* bin_samples 0 = 105; reserved must be 0 */
+typedef struct {
+	uint32_t struct_size, bin_samples, hang_bins, series_bins;    /* as in force (series_bins: what the ring holds) */
+	float    threshold_dbfs, threshold_power;
+	int64_t  first_sample;                     /* k_on */
+	uint64_t bins;                             /* complete so far, the same for every channel */
+	float    kernel_ms;                        /* summed HIP-event time of the monitor's launches at profiling level 2, else 0 (of the feeds
+	                                            * collected so far: after vdl2hip_sync(), all of them) */
+	uint32_t reserved;
+} vdl2hip_activity_info;                       /* 48 bytes */
+typedef struct {
+	uint64_t bins, busy_bins, transmissions, longest_bins;
+	double   sum_power;
+	float    max_power, min_power;
+	uint32_t open, reserved;
+	uint64_t hist[64];
+} vdl2hip_activity_chan;                       /* 568 bytes */
 
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
@@ -398,6 +452,24 @@ int  vdl2hip_spectrum_read(vdl2hip_ctx *ctx, vdl2hip_spectrum_info *info, double
  * with B_c = { i : |f_i - freqs[c]| <= 12500 Hz }, or the single nearest bin if that set is empty,
  * dbfs[c] = 10 log10(sum_{B_c} power[i] / enbw_bins), -INFINITY if the sum is 0.  Returns nchan; VDL2HIP_E_TOOBIG if cap < nchan. */
 int  vdl2hip_spectrum_channels(vdl2hip_ctx *ctx, float *dbfs, size_t cap);
+
+/* ---- Activity monitor (see "Activity monitor" above) ----
+ * The histogram's 63 edges: returns 63 and writes edges[0 .. 63) if cap >= 63, else VDL2HIP_E_TOOBIG.  Host only, needs no GPU. */
+int  vdl2hip_activity_edges(float *edges, size_t cap);
+/* Switch the monitor on.  Allowed between feeds; takes effect with the next feed.  Enabling again restarts at the then-current
+ * decimated sample with zeroed state.  VDL2HIP_E_INVAL for a bad struct_size, bin_samples, hang_bins, series_bins, threshold or
+ * reserved, before anything is allocated or changed: a monitor that was on stays as it was. */
+int  vdl2hip_activity_enable(vdl2hip_ctx *ctx, const vdl2hip_activity_cfg *cfg);
+/* Switch it off: its buffers are freed, later feeds launch nothing. */
+int  vdl2hip_activity_disable(vdl2hip_ctx *ctx);
+/* What the monitor has accumulated.  Waits only for the monitor's own work queued so far (an event behind its last launch), delivers
+ * no frames and changes nothing in what vdl2hip_drain() or vdl2hip_sync() later return.  info->struct_size must be set.  chans[i] is
+ * channel chan_first + i; returns the number of channels written (0 if chans is NULL), VDL2HIP_E_TOOBIG if cap_chans is smaller than
+ * the shard's channel count.  `info` or `chans` may be NULL.  Monitor off: VDL2HIP_E_INVAL. */
+int  vdl2hip_activity_read(vdl2hip_ctx *ctx, vdl2hip_activity_info *info, vdl2hip_activity_chan *chans, size_t cap_chans, int reset);
+/* Copy up to `cap` values p[first_bin ...] of one channel (index in cfg.freqs); returns the count (0 is legal for first_bin ==
+ * info.bins).  VDL2HIP_E_INVAL for a bin older than what the ring holds or beyond bins, a channel outside the shard, the monitor off. */
+int  vdl2hip_activity_series(vdl2hip_ctx *ctx, uint32_t chan, int64_t first_bin, float *dst, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,14 @@
  *                                 per-channel summary lines gain " level=<x> dBFS" (vdl2hip_spectrum_channels)
  *   --spectrum-nfft <n>           bins: a power of two in 64 .. 4096 (default 1024)
  *   --spectrum-window rect|hann|bh4   (default hann)
+ *   --activity-out <path>         (this library's own) switch the activity monitor on and, at exit, write what every channel carried: a
+ *                                 "# key value" line per field of vdl2hip_activity_info, then per channel
+ *                                 "freq_hz bins busy_bins occupancy transmissions longest_ms mean_dbfs max_dbfs p10_dbfs p50_dbfs"
+ *                                 (the percentiles from the level histogram, as the centre of the 2 dB bucket); the per-channel
+ *                                 summary lines gain " busy=<x>% tx=<n>"
+ *   --activity-bin <samples>      bin length in decimated samples, 10 .. 10500 (default 105 = 1 ms)
+ *   --activity-threshold <dBFS>   a bin above it is busy (default -40)
+ *   --activity-hang <bins>        idle bins a transmission bridges, 0 .. 255 (default 0)
  *   freq [freq ...]               channel frequencies in Hz; default: the CSC, 136975000
  * and prints one line per AVLC frame (metadata in the reference's "[S:…] [L:…] [F:…] [#idx]" style + hex octets).
  * Everything after avlc_decoder_queue_push() (AVLC/ACARS/X.25/... decoding, formatters) is out of scope here.
@@ -45,6 +53,15 @@ static FILE *raw_out;
 static const char *station_id;
 static unsigned long nframes;
 
+/* the centre, in dBFS, of the level bucket that holds the bin of rank ceil(q bins) - bucket i spans -122 + 2 i .. -120 + 2 i dBFS */
+static double hist_percentile(const vdl2hip_activity_chan *ch, double q) {
+	uint64_t want = (uint64_t)ceil(q * (double)ch->bins), seen = 0;
+	if(want < 1) want = 1;
+	for(int i = 0; i < 64; i++) { seen += ch->hist[i]; if(seen >= want) return -121.0 + 2.0 * i; }
+	return NAN;
+}
+static double dbfs_of(double p) { return p > 0.0 ? 10.0 * log10(p) : -INFINITY; }
+
 static void on_frame(const vdl2hip_frame *f, void *user) {
 	(void)user;
 	nframes++;
@@ -65,6 +82,8 @@ static void on_frame(const vdl2hip_frame *f, void *user) {
 int main(int argc, char **argv) {
 	const char *infile = NULL, *rawpath = NULL, *statsd_path = NULL, *spectrum_path = NULL;
 	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
+	const char *activity_path = NULL;
+	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
 	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0, input_rate = 0;
@@ -98,6 +117,10 @@ int main(int argc, char **argv) {
 			else if(!strcmp(argv[i], "bh4")) spectrum_window = VDL2HIP_WIN_BH4;
 			else { fprintf(stderr, "Unknown spectrum window\n"); return 1; }
 		}
+		else if(!strcmp(a, "--activity-out")) { NEEDARG(); activity_path = argv[++i]; }
+		else if(!strcmp(a, "--activity-bin")) { NEEDARG(); activity_bin = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--activity-threshold")) { NEEDARG(); activity_thr = strtof(argv[++i], NULL); }
+		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--blocks-per-feed")) { NEEDARG(); per_feed = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return 1; }
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
@@ -105,7 +128,8 @@ int main(int argc, char **argv) {
 	(void)fmt_set;
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
-			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] [freq ...]\n", argv[0]); return 1; }
+			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
+			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
 		freqs[nfreq++] = CSC_FREQ;
@@ -145,6 +169,12 @@ int main(int argc, char **argv) {
 			fprintf(stderr, "vdl2hip_spectrum_enable: %s\n", vdl2hip_strerror(spectrum_nfft ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
+	if(activity_path) {
+		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
+		if(activity_bin == 0 || (r = vdl2hip_activity_enable(rx, &ac)) != VDL2HIP_OK) {
+			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
+		}
+	}
 
 	unsigned char *buf = malloc((size_t)per_feed * FILE_BUFSIZE);
 	if(!buf) { perror("malloc"); return 3; }
@@ -163,12 +193,17 @@ int main(int argc, char **argv) {
 	uint64_t cnt[VDL2HIP_NUM_COUNTERS];
 	static float level[1024];
 	const int have_levels = spectrum_path && vdl2hip_spectrum_channels(rx, level, 1024) == (int)nfreq;
+	static vdl2hip_activity_chan act[1024];
+	vdl2hip_activity_info ai;
+	memset(&ai, 0, sizeof ai); ai.struct_size = sizeof ai;
+	const int nact = activity_path ? vdl2hip_activity_read(rx, &ai, act, 1024, 0) : 0;
 	for(uint32_t c = 0; c < nfreq; c++)
 		if(vdl2hip_counters(rx, c, cnt) == VDL2HIP_OK) {
 			fprintf(stderr, "%u Hz: sync.good=%" PRIu64 " crc.good=%" PRIu64 " blocks=%" PRIu64 "/%" PRIu64 " msg.good=%" PRIu64 " fec_bad=%" PRIu64,
 					freqs[c], cnt[VDL2HIP_CNT_SYNC_GOOD], cnt[VDL2HIP_CNT_CRC_GOOD], cnt[VDL2HIP_CNT_BLOCKS_FEC_OK],
 					cnt[VDL2HIP_CNT_BLOCKS_PROCESSED], cnt[VDL2HIP_CNT_MSG_GOOD], cnt[VDL2HIP_CNT_ERR_FEC_BAD]);
 			if(have_levels) fprintf(stderr, " level=%.2f dBFS", (double)level[c]);
+			if(nact == (int)nfreq) fprintf(stderr, " busy=%.2f%% tx=%" PRIu64, act[c].bins ? 100.0 * (double)act[c].busy_bins / (double)act[c].bins : 0.0, act[c].transmissions);
 			fprintf(stderr, "\n");
 		}
 	fprintf(stderr, "%lu frames\n", nframes);
@@ -194,6 +229,23 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "spectrum not written: %s\n", n < 0 ? vdl2hip_strerror(n) : "cannot open file");
+	}
+	if(activity_path) {
+		FILE *so = nact == (int)nfreq ? fopen(activity_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# bin_samples %u\n# hang_bins %u\n# series_bins %u\n# threshold_dbfs %.9g\n# threshold_power %.9g\n", ai.bin_samples, ai.hang_bins,
+					ai.series_bins, (double)ai.threshold_dbfs, (double)ai.threshold_power);
+			fprintf(so, "# first_sample %" PRId64 "\n# bins %" PRIu64 "\n# kernel_ms %.6g\n", ai.first_sample, ai.bins, (double)ai.kernel_ms);
+			const double bin_ms = 1000.0 * (double)ai.bin_samples / (SYMBOL_RATE * 10.0);
+			for(uint32_t c = 0; c < nfreq; c++) {
+				const vdl2hip_activity_chan *ch = &act[c];
+				fprintf(so, "%u %" PRIu64 " %" PRIu64 " %.6f %" PRIu64 " %.3f %.2f %.2f %.1f %.1f\n", freqs[c], ch->bins, ch->busy_bins,
+						ch->bins ? (double)ch->busy_bins / (double)ch->bins : 0.0, ch->transmissions, (double)ch->longest_bins * bin_ms,
+						dbfs_of(ch->bins ? ch->sum_power / (double)ch->bins : 0.0), dbfs_of((double)ch->max_power), hist_percentile(ch, 0.10), hist_percentile(ch, 0.50));
+			}
+			fclose(so);
+		}
+		else fprintf(stderr, "activity not written: %s\n", nact < 0 ? vdl2hip_strerror(nact) : "cannot open file");
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
