@@ -464,6 +464,11 @@ template<int CTRL, int ROWS>
 __device__ __forceinline__ float dpp_bcast(float v) {               // row_bcast:15 (0x142) / row_bcast:31 (0x143) into the rows of ROWS, 0 elsewhere
 	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xf, false));
 }
+template<int CTRL, int ROWS>
+__device__ __forceinline__ float dpp_bcast_keep(float old, float v) {   // the same, the other rows keep `old`: handed a value that is 0 there (an earlier result
+	// of the same broadcast), it gives what dpp_bcast gives without a register being cleared for it first
+	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROWS, 0xf, false));
+}
 __device__ __forceinline__ float dpp_wave_shr1_keep(float lane0, float v) {   // value of lane - 1 across the whole wavefront, lane 0: `lane0`
 	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
 }
@@ -586,6 +591,11 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 	__shared__ __align__(16) float4 qpow[64];     // Q^(l+1), l = 0..63: what a carry contributes to lane l's end state
 	__shared__ __align__(16) float park[4 * 4 * 4 * 4];   // per wave: carried state and the end-of-feed state, [wave][4][CR][4]
 	__shared__ int fallback;                      // fused fix-up: some wave of this workgroup gave up waiting for the previous segment's state
+	// four channels per wave, two blocks per lane: the zero-start outputs of a lane's first block wait in LDS for the scan, [c][tid] -
+	// the rolled block loop then selects nothing (it chose between two register sets with a v_cndmask per value and block), and the
+	// second block's sample loop has eight registers more
+	constexpr bool kParkY = OS != 0 && CR >= 4 && R == 2;
+	__shared__ __align__(8) float2 ypark[kParkY ? CR * 256 : 1];
 	extern __shared__ __align__(16) unsigned char smem[];
 	if(VDL2_K1_PRIO) __builtin_amdgcn_s_setprio(VDL2_K1_PRIO);
 	const int os = OS ? OS : a.os;
@@ -717,11 +727,18 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 			}
 		} else if(!CF32 && kPrefetch && fast_now) {
 			// the usual case - a cs16 tile that lies entirely inside this feed's block: no per-sample range or carry checks
-			const uint32_t *src = (const uint32_t *)a.in + (sbase - a.ncarry);
+			// The tile is staged from pre[] and from nowhere else: a tile that was not fetched ahead (the first one after a tile of
+			// another kind) is fetched into pre[] here.  With a choice per word between pre[k] and a load, the look-ahead lived in two
+			// sets of registers and was copied from one to the other and back in every tile.
+			if(!have_pre) {
+				const uint32_t *src = (const uint32_t *)a.in + (sbase - a.ncarry);
+				#pragma unroll
+				for(int k = 0; k < kPre; k++) pre[k] = src[tid + 256 * k];
+			}
 			#pragma unroll
 			for(int k = 0; k < kPre; k++) {
 				const int t = tid + 256 * k;
-				const uint32_t w = have_pre ? pre[k] : src[t];
+				const uint32_t w = pre[k];
 				const int l = t / run, m = t - l * run;
 				tile[m * 65 + l] = make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f);
 			}
@@ -741,8 +758,12 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				tile[m * 65 + l] = make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f);
 			}
 		} else {
+			// (the tile's first sample is made opaque: the compiler otherwise carries this path's four load addresses from tile to tile,
+			// eight vector registers that the tiles of the fast paths pay for)
+			int64_t sb = sbase;
+			asm volatile("" : "+s"(sb));
 			for(int t = tid; t < tile_n; t += 256) {
-				const int64_t sidx = sbase + t;
+				const int64_t sidx = sb + t;
 				float re = 0.f, im = 0.f;
 				if(sidx < (int64_t)a.nlogical) load_sample<CF32>(a, sidx, re, im);
 				const int l = t / run, m = t - l * run;
@@ -822,8 +843,14 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				t0r[c] = n0r; t0i[c] = n0i; t1r[c] = n1r; t1i[c] = n1i;
 				const float yr = __builtin_fmaf(c0, n0r, __builtin_fmaf(c1, n1r, c2 * lr[c]));
 				const float yi = __builtin_fmaf(c0, n0i, __builtin_fmaf(c1, n1i, c2 * li[c]));
-				if(i == ib && lane == lb) svp[c] = make_float4(n0r, n0i, n1r, n1i);
-				if(i == 0) { ya[c][0] = yr; ya[c][1] = yi; } else { yb[c][0] = yr; yb[c][1] = yi; }
+				if(kParkY) {
+					if(i == 0) ypark[c * 256 + tid] = make_float2(yr, yi);
+					yb[c][0] = yr; yb[c][1] = yi;                       // (what the last block leaves)
+				} else if(i == 0) { ya[c][0] = yr; ya[c][1] = yi; } else { yb[c][0] = yr; yb[c][1] = yi; }
+			}
+			if(i == ib && lane == lb) {
+				#pragma unroll
+				for(int c = 0; c < CR; c++) svp[c] = make_float4(t0r[c], t0i[c], t1r[c], t1i[c]);
 			}
 		}
 
@@ -847,34 +874,43 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		}
 		{
 			const float4 qa = qpow[lane & 15];                  // Q^(p+1): only rows 1 and 3 receive a non-zero operand
+			// (the four operands are cleared once per broadcast, not once per channel: the rows a broadcast leaves alone stay 0)
+			float o0r = 0.f, o0i = 0.f, o1r = 0.f, o1i = 0.f;
 			#pragma unroll
 			for(int c = 0; c < CR; c++) {
-				const float o0r = dpp_bcast<0x142, 0xa>(t0r[c]), o0i = dpp_bcast<0x142, 0xa>(t0i[c]);
-				const float o1r = dpp_bcast<0x142, 0xa>(t1r[c]), o1i = dpp_bcast<0x142, 0xa>(t1i[c]);
+				o0r = dpp_bcast_keep<0x142, 0xa>(o0r, t0r[c]); o0i = dpp_bcast_keep<0x142, 0xa>(o0i, t0i[c]);
+				o1r = dpp_bcast_keep<0x142, 0xa>(o1r, t1r[c]); o1i = dpp_bcast_keep<0x142, 0xa>(o1i, t1i[c]);
 				t0r[c] = __builtin_fmaf(qa.x, o0r, __builtin_fmaf(qa.y, o1r, t0r[c])); t0i[c] = __builtin_fmaf(qa.x, o0i, __builtin_fmaf(qa.y, o1i, t0i[c]));
 				t1r[c] = __builtin_fmaf(qa.z, o0r, __builtin_fmaf(qa.w, o1r, t1r[c])); t1i[c] = __builtin_fmaf(qa.z, o0i, __builtin_fmaf(qa.w, o1i, t1i[c]));
 			}
 			const float4 qb = qpow[(lane - 32) & 63];           // Q^(lane-31) for lanes 32..63 (rows 2 and 3)
+			o0r = o0i = o1r = o1i = 0.f;
 			#pragma unroll
 			for(int c = 0; c < CR; c++) {
-				const float o0r = dpp_bcast<0x143, 0xc>(t0r[c]), o0i = dpp_bcast<0x143, 0xc>(t0i[c]);
-				const float o1r = dpp_bcast<0x143, 0xc>(t1r[c]), o1i = dpp_bcast<0x143, 0xc>(t1i[c]);
+				o0r = dpp_bcast_keep<0x143, 0xc>(o0r, t0r[c]); o0i = dpp_bcast_keep<0x143, 0xc>(o0i, t0i[c]);
+				o1r = dpp_bcast_keep<0x143, 0xc>(o1r, t1r[c]); o1i = dpp_bcast_keep<0x143, 0xc>(o1i, t1i[c]);
 				t0r[c] = __builtin_fmaf(qb.x, o0r, __builtin_fmaf(qb.y, o1r, t0r[c])); t0i[c] = __builtin_fmaf(qb.x, o0i, __builtin_fmaf(qb.y, o1i, t0i[c]));
 				t1r[c] = __builtin_fmaf(qb.z, o0r, __builtin_fmaf(qb.w, o1r, t1r[c])); t1i[c] = __builtin_fmaf(qb.z, o0i, __builtin_fmaf(qb.w, o1i, t1i[c]));
 			}
 		}
 		const float4 qp = qpow[lane];
+		// (the channel index is made opaque here: what depends on it - row addresses, cvalid - is then scalar arithmetic of this tile;
+		// hoisted out of the tile loop it was a dozen SGPR pairs too many, spilled to VGPR lanes and fetched back with v_readlane)
+		int cb = cbase;
+		asm volatile("" : "+s"(cb));
+		const bool seg_last = rem <= L || ts == a.tiles - 1;      // (uniform) the tile that ends the segment's valid part
 		#pragma unroll
 		for(int c = 0; c < CR; c++) {
 			// add what the carried state contributes, then each lane needs the state at the START of its run
 			const float4 cy = carry[c];
 			t0r[c] = __builtin_fmaf(qp.x, cy.x, __builtin_fmaf(qp.y, cy.z, t0r[c])); t0i[c] = __builtin_fmaf(qp.x, cy.y, __builtin_fmaf(qp.y, cy.w, t0i[c]));
 			t1r[c] = __builtin_fmaf(qp.z, cy.x, __builtin_fmaf(qp.w, cy.z, t1r[c])); t1i[c] = __builtin_fmaf(qp.z, cy.y, __builtin_fmaf(qp.w, cy.w, t1i[c]));
-			float T0r = dpp_wave_shr1(t0r[c]), T0i = dpp_wave_shr1(t0i[c]), T1r = dpp_wave_shr1(t1r[c]), T1i = dpp_wave_shr1(t1i[c]);
-			if(lane == 0) { T0r = cy.x; T0i = cy.y; T1r = cy.z; T1i = cy.w; }
-			const bool cvalid = cbase + c < a.nchan;
+			// (lane 0 keeps the carried state: the move writes over it in every other lane)
+			const float T0r = dpp_wave_shr1_keep(cy.x, t0r[c]), T0i = dpp_wave_shr1_keep(cy.y, t0i[c]), T1r = dpp_wave_shr1_keep(cy.z, t1r[c]), T1i = dpp_wave_shr1_keep(cy.w, t1i[c]);
+			const bool cvalid = cb + c < a.nchan;
 			const int64_t kloc = kbase + (int64_t)lane * R;
-			cf32 *yout = a.y + (size_t)(cbase + c) * a.cap;
+			cf32 *yout = a.y + (size_t)(cb + c) * a.cap;
+			if(kParkY) { const float2 y0 = ypark[c * 256 + tid]; ya[c][0] = y0.x; ya[c][1] = y0.y; }
 			// outputs of the run, completed with the decayed run-start state (cP[i] = (c0,c1) P^(i+1))
 			const float f0r = __builtin_fmaf(bf.cP[0][0], T0r, __builtin_fmaf(bf.cP[0][1], T1r, ya[c][0])), f0i = __builtin_fmaf(bf.cP[0][0], T0i, __builtin_fmaf(bf.cP[0][1], T1i, ya[c][1]));
 			if(R > 1) {
@@ -897,28 +933,40 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 					if(cvalid && kloc < a.D) yout[(uint32_t)(a.k0 + kloc) & a.mask] = cf32{f0r, f0i};
 				}
 			}
-			if(cvalid && lane == lb && (rem <= L || ts == a.tiles - 1)) {
-				// state at the end of the segment's valid part, with zero state at the segment start
-				const float *Pp = bf.Pp[ib + 1];
-				float4 e;
-				const float4 sv = svp[c];
-				e.x = sv.x + (Pp[0] * T0r + Pp[1] * T1r); e.y = sv.y + (Pp[0] * T0i + Pp[1] * T1i);
-				e.z = sv.z + (Pp[2] * T0r + Pp[3] * T1r); e.w = sv.w + (Pp[2] * T0i + Pp[3] * T1i);
-				a.seg_end[(size_t)(cbase + c) * a.nseg_cap + seg] = e;
-				sendp[c] = e;
-				if(a.fuse) {
-					// publish for the next segment's workgroup: each word carries the feed's epoch, so no flag and no fence
-					// (an agent-scope release would write back the whole L2 of this XCD)
-					unsigned long long *pub = a.seg_pub + ((size_t)(cbase + c) * a.nseg_cap + seg) * 4;
-					const unsigned long long ep = (unsigned long long)a.pub_epoch << 32;
-					__hip_atomic_store(pub + 0, ep | __float_as_uint(e.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					__hip_atomic_store(pub + 1, ep | __float_as_uint(e.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					__hip_atomic_store(pub + 2, ep | __float_as_uint(e.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					__hip_atomic_store(pub + 3, ep | __float_as_uint(e.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		if(seg_last) {
+			// the tile that ends the segment's valid part (one in a.tiles): a branch of its own, taken by the whole wavefront or not at
+			// all.  The run-start state is formed again, from the same operands - the carried state is still where it was.
+			#pragma unroll
+			for(int c = 0; c < CR; c++) {
+				const float4 cy = carry[c];
+				const float T0r = dpp_wave_shr1_keep(cy.x, t0r[c]), T0i = dpp_wave_shr1_keep(cy.y, t0i[c]), T1r = dpp_wave_shr1_keep(cy.z, t1r[c]), T1i = dpp_wave_shr1_keep(cy.w, t1i[c]);
+				if(cb + c < a.nchan && lane == lb) {
+					// state at the end of the segment's valid part, with zero state at the segment start
+					const float *Pp = bf.Pp[ib + 1];
+					float4 e;
+					const float4 sv = svp[c];
+					e.x = sv.x + (Pp[0] * T0r + Pp[1] * T1r); e.y = sv.y + (Pp[0] * T0i + Pp[1] * T1i);
+					e.z = sv.z + (Pp[2] * T0r + Pp[3] * T1r); e.w = sv.w + (Pp[2] * T0i + Pp[3] * T1i);
+					a.seg_end[(size_t)(cb + c) * a.nseg_cap + seg] = e;
+					sendp[c] = e;
+					if(a.fuse) {
+						// publish for the next segment's workgroup: each word carries the feed's epoch, so no flag and no fence
+						// (an agent-scope release would write back the whole L2 of this XCD)
+						unsigned long long *pub = a.seg_pub + ((size_t)(cb + c) * a.nseg_cap + seg) * 4;
+						const unsigned long long ep = (unsigned long long)a.pub_epoch << 32;
+						__hip_atomic_store(pub + 0, ep | __float_as_uint(e.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+						__hip_atomic_store(pub + 1, ep | __float_as_uint(e.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+						__hip_atomic_store(pub + 2, ep | __float_as_uint(e.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+						__hip_atomic_store(pub + 3, ep | __float_as_uint(e.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					}
 				}
 			}
-			// carry into the next tile = state at the end of lane 63's run
-			if(lane == 63) carry[c] = make_float4(t0r[c], t0i[c], t1r[c], t1i[c]);
+		}
+		// carry into the next tile = state at the end of lane 63's run
+		if(lane == 63) {
+			#pragma unroll
+			for(int c = 0; c < CR; c++) carry[c] = make_float4(t0r[c], t0i[c], t1r[c], t1i[c]);
 		}
 	}
 	K1_MARK(4);
@@ -1147,7 +1195,8 @@ __global__ __launch_bounds__(kK3Threads) void k_sync_screen(K3Args a) {
 	const int64_t nblk = a.nbase + (int64_t)blockIdx.x * kK3Tile;
 	const cf32 *y = a.y + (size_t)c * a.cap;
 	constexpr int kFull = (kK3Tile + 150) / kK3Threads, kRest = (kK3Tile + 150) % kK3Threads;
-	if(nblk >= 150 && nblk + kK3Tile <= a.k1) {
+	const bool full_tile = nblk >= 150 && nblk + kK3Tile <= a.k1;      // (uniform)
+	if(full_tile) {
 		// the whole tile and its history exist (all but the first and last block of a channel): no per-sample range tests, ring
 		// offsets in 32 bits, all loads in flight before the first phase is worked out
 		const uint32_t r0 = (uint32_t)(nblk - 150) + tid;
@@ -1190,9 +1239,30 @@ __global__ __launch_bounds__(kK3Threads) void k_sync_screen(K3Args a) {
 		verdict[s0 + 10 * q] = !(ps >= kScreenThr);      // a NaN (sample too small for phase_fast) goes to the exact tier
 	}
 	__syncthreads();
+	constexpr int kWordsPerWave = (kK3Tile / 64) / (kK3Threads / 64);
+	if(full_tile) {
+		// every sample of the tile exists and nblk is a multiple of 64: a word's verdict bytes go straight into the ballot, no
+		// per-sample range test, the ring slot of the word in 32 bits (uniform: the wavefront's first word + j)
+		const int lane = tid & 63;
+		const uint32_t w0 = (uint32_t)(nblk >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6) * kWordsPerWave;
+		uint64_t *frow = a.flag + (size_t)c * (a.cap >> 6);
+		const uint8_t *vrow = verdict + 64 * kWordsPerWave * (tid >> 6) + lane;
+		const unsigned long long all = a.screen_all != 0 ? ~0ull : 0ull;
+		uint8_t vb[kWordsPerWave];
+		unsigned long long bits[kWordsPerWave];
+		#pragma unroll
+		for(int j = 0; j < kWordsPerWave; j++) vb[j] = vrow[64 * j];
+		#pragma unroll
+		for(int j = 0; j < kWordsPerWave; j++) bits[j] = __builtin_amdgcn_ballot_w64(vb[j] != 0) | all;
+		if(lane == 0) {
+			#pragma unroll
+			for(int j = 0; j < kWordsPerWave; j++) frow[(w0 + j) & (a.mask >> 6)] = bits[j];
+		}
+		return;
+	}
 	#pragma unroll
-	for(int j = 0; j < (kK3Tile / 64) / (kK3Threads / 64); j++) {
-		const int word = (tid >> 6) * ((kK3Tile / 64) / (kK3Threads / 64)) + j;
+	for(int j = 0; j < kWordsPerWave; j++) {
+		const int word = (tid >> 6) * kWordsPerWave + j;
 		const int64_t n = nblk + 64 * word + (tid & 63);
 		const unsigned long long bits = __ballot(n < a.k1 && (verdict[64 * word + (tid & 63)] != 0 || a.screen_all != 0));
 		if((tid & 63) == 0 && n < a.k1) a.flag[(size_t)c * (a.cap >> 6) + ((uint32_t)(n >> 6) & (a.mask >> 6))] = bits;
@@ -1754,7 +1824,7 @@ __global__ __launch_bounds__(64 * kNfWaves, 4) void k_nf_prepare(K4bArgs a) {
 }
 
 // Four wavefronts per workgroup, each with a group of updates of its own: a workgroup then takes exactly the room one
-// channeliser workgroup leaves on a CU (a wave per SIMD inside its 120 registers, 37 KB of LDS), where single-wave workgroups
+// channeliser workgroup leaves on a CU (a wave per SIMD inside its 120 registers; of LDS a <20,2,4> channeliser workgroup frees 35 KB - its tile, tables and parked outputs - beside the 23 KB four of them leave), where single-wave workgroups
 // each kept a whole channeliser workgroup out for as long as they lived (measured: the replay beside the channeliser cost the
 // front 0.29 ms per 256-channel step).
 __global__ __launch_bounds__(64 * kNfWaves, 4) void k_nf_replay(K4bArgs a) {
