@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -22,6 +24,7 @@
 #include "spectrum.h"
 #include "spectrum_design.h"
 #include "activity.h"
+#include "capture.h"
 #include "tables.h"
 
 using namespace vdl2;
@@ -100,6 +103,10 @@ struct OutSlot {
 	hipEvent_t ev_rs[2] = {}; bool rs_timed = false;   // resampling receivers: start / stop of this feed's k_resample (profiling level 2)
 	hipEvent_t ev_mon[4] = {}; int mon_timed = 0;      // input monitor: start / stop of this feed's k_spectrum and k_spectrum_reduce (profiling level 2); how many of the two were timed
 	hipEvent_t ev_act[4] = {}; int act_timed = 0;      // activity monitor: the same for this feed's k_activity_power and k_activity_scan
+	// burst capture (capture.h): the feed's header and records (one allocation: the header and the first records come to the host in one
+	// small copy), windows and totals, the IQ pool; cap_on: this feed's back end is followed by the capture's launches
+	CapHdr *d_cap_hdr = nullptr; CapRec *d_cap_rec = nullptr; CapPlan *d_cap_plan = nullptr; uint64_t *d_cap_tot = nullptr; cf32 *d_cap_pool = nullptr;
+	uint8_t *h_cap = nullptr; bool cap_on = false; hipEvent_t ev_cap[4] = {}; int cap_timed = 0;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -136,6 +143,15 @@ struct vdl2hip_ctx {
 		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
 		hipStream_t rd = nullptr; uint8_t *h_buf = nullptr;       // the read's own stream and page-locked landing place (kept until the receiver goes)
 	} act;
+	// Burst capture (capture.h, vdl2hip_capture_*): off unless enabled.  queue: the records of the collected feeds, oldest first, each
+	// with the IQ of its feed (one allocation per feed, shared by its records; iq_off: where the record's window begins in it)
+	struct CapItem { vdl2hip_burst r; std::shared_ptr<std::vector<float>> iq; };
+	struct {
+		bool on = false; uint32_t pre = 0, post = 0, flags = 0, pool = 0;
+		uint64_t bursts = 0, iq_samples = 0, iq_dropped = 0; double kernel_ms = 0.0;
+		uint8_t *h_stage = nullptr; size_t stage_cap = 0;      // page-locked landing place of a feed's records and IQ (kept until the receiver goes)
+		std::deque<CapItem> queue;
+	} capt;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
@@ -245,11 +261,14 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 }
 
 static int launch_back(vdl2hip_ctx *c, OutSlot &sl);
+static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st);
+static void capture_free(vdl2hip_ctx *c);
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, struct OutSlot *succ);
 static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto);
 // A short feed (fewer than two walk segments' worth of samples; the reference's own 320 000-byte blocks are 4 000): launch_back()
 static bool feed_is_small(const vdl2hip_ctx *c, int64_t D);
 
+static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
@@ -260,6 +279,8 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.mon_timed = 0;
 	for(int i = 0; i < sl.act_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_act[2 * i], sl.ev_act[2 * i + 1]) == hipSuccess) c->act.kernel_ms += ms; else (void)hipGetLastError(); }
 	sl.act_timed = 0;
+	for(int i = 0; i < sl.cap_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_cap[2 * i], sl.ev_cap[2 * i + 1]) == hipSuccess) c->capt.kernel_ms += ms; else (void)hipGetLastError(); }
+	sl.cap_timed = 0;
 	if(c->profiling && sl.ev_valid) {
 		hipEvent_t *ev = sl.ev;
 		float ms = 0.f;
@@ -282,9 +303,10 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(ctl.overflow) c->stats.overflow_feeds++;
 	c->stats.bursts += std::min(ctl.nbursts, ctl.cap_bursts);
 	const uint32_t nf = std::min(ctl.nvalid, ctl.cap_frames);
+	const OutFrame *fr = nullptr;
 	if(nf) {
 		const uint32_t pool_n = std::min(ctl.pool_out_used, ctl.cap_pool);
-		const OutFrame *fr; const uint8_t *po;
+		const uint8_t *po;
 		if(nf <= (uint32_t)kMailFrames && pool_n <= (uint32_t)kMailPool) {
 			// a handful of frames (the usual case for a block of a live receiver): they have come with the control block
 			fr = sl.h_mail->frames; po = sl.h_mail->pool;
@@ -313,6 +335,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 			if(!c->avlc_filter || fr[i].avlc_status == AVLC_OK) c->queue.push_back(HostFrame{ fr[i], pool });
 		}
 	}
+	if(sl.cap_on) { sl.cap_on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	return ctl.overflow ? VDL2HIP_E_OVERFLOW : VDL2HIP_OK;
 }
 
@@ -407,6 +430,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	}
 
 	sl.ev_valid = false;
+	sl.cap_on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
 		// (a cold-start feed launches the channeliser in pieces that wait for the pieces of the copy: not a kernel duration, not timed)
@@ -809,6 +833,98 @@ static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto) {
 	}
 }
 
+// ---- the burst capture's share of a feed (vdl2hip.h, "Burst capture"; kernels: capture.h) ----
+// The ring behind the window.  The capture of feed i reads y from iq_first >= sync_sample - kCapMaxPre on, while the channelisers
+// of up to kSlots - 1 later feeds may be writing (feed i + kSlots takes feed i's slot, and collect_slot() has waited for feed i
+// before that).  They write [k_end, k_end + (kSlots - 1) dmax), which in a ring of `cap` >= kSlots dmax + kHistory + 1024 samples
+// (vdl2hip_create) lands on samples older than k_end - dmax - kHistory - 1024 <= k0 - kHistory - 1024, k0 being feed i's first
+// sample.  A burst is handed over in the feed that brings its last symbol, so end_sample >= k0; the longest burst is 56 320 samples
+// from its first symbol to its last and its sync lies a unique word before that: iq_first > k0 - 56 320 - 200 - 4 096 = k0 - 60 616
+// > k0 - kHistory - 1024 = k0 - 66 560.  The 5 944 samples between the two are why pre stops at 4 096.  A window is at most
+// 4 096 + 56 520 + 1 024 < 2^16 pairs long.
+static_assert(kCapMaxPre + 56320 + 200 < kHistory + 1024, "a window begins inside what the ring keeps behind a feed");
+static_assert(sizeof(CapRec) == sizeof(vdl2hip_burst) && sizeof(vdl2hip_burst) == 128 && offsetof(CapRec, iq_first) == offsetof(vdl2hip_burst, iq_first)
+              && offsetof(CapRec, frames) == offsetof(vdl2hip_burst, frames) && offsetof(CapRec, mean_power) == offsetof(vdl2hip_burst, mean_power)
+              && offsetof(CapRec, phase_err_max) == offsetof(vdl2hip_burst, phase_err_max), "the host copies the device's records as they are");
+static_assert(sizeof(vdl2hip_capture_cfg) == 24 && sizeof(vdl2hip_capture_info) == 56 && sizeof(CapHdr) == 16, "vdl2hip.h states these sizes");
+static_assert(kCapMaxChan == kK5MaxChan, "k_capture_copy keeps every channel's offsets in LDS");
+constexpr uint32_t kCapMailRecs = 32;      // records that come to the host with the header, in one small copy (most feeds of a live receiver hold a handful of bursts)
+constexpr size_t kCapMailBytes = sizeof(CapHdr) + kCapMailRecs * sizeof(CapRec);
+
+static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->capt;
+	CapArgs a{};
+	a.y = c->d_y; a.bursts = sl.d_bursts; a.nb_chan = sl.d_nbchan; a.freq = c->d_freq;
+	a.plan = sl.d_cap_plan; a.tot = sl.d_cap_tot; a.rec = sl.d_cap_rec; a.pool = sl.d_cap_pool; a.hdr = sl.d_cap_hdr;
+	a.k_end = sl.back_k0 + sl.back_D; a.pool_samples = m.pool; a.cap_bursts_chan = c->cap_bursts_chan; a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first;
+	a.cap = c->cap; a.mask = c->cap - 1; a.pre = m.pre; a.post = m.post;
+	const bool timed = c->profiling >= 2;
+	if(timed) for(auto &e : sl.ev_cap) if(!e) HIPCHK(hipEventCreate(&e));
+	hipEvent_t *e = sl.ev_cap;
+	hipExtLaunchKernelGGL(k_capture_plan, dim3((unsigned)c->C), dim3(64), 0u, st, timed ? e[0] : nullptr, timed ? e[1] : nullptr, 0, a);
+	// a workgroup per burst, bounded like the burst decoder's wavefronts (16 .. 2048 of them, by the feed's size): 8 .. 512
+	const unsigned grid = std::min(512u, std::max(8u, sl.k5_waves / 4));
+	hipExtLaunchKernelGGL(k_capture_copy, dim3(grid), dim3(kCapThreads), 0u, st, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(sl.h_cap, sl.d_cap_hdr, kCapMailBytes, hipMemcpyDeviceToHost, st));
+	if(timed) sl.cap_timed = 2;
+	return VDL2HIP_OK;
+}
+// A collected feed's records (the first have come with the header) and the used part of its IQ pool, joined with the feed's frames -
+// all of them, whatever the AVLC filter lets through - and appended to the queue.
+static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+	auto &m = c->capt;
+	if(!m.on || !sl.h_cap) return VDL2HIP_OK;
+	const CapHdr h = *reinterpret_cast<const CapHdr *>(sl.h_cap);
+	const uint32_t nrec = (uint32_t)std::min<uint64_t>(h.nrec, (uint64_t)c->C * c->cap_bursts_chan);
+	const uint64_t pairs = std::min<uint64_t>(h.pairs, m.pool);
+	if(nrec == 0) return VDL2HIP_OK;
+	const CapRec *rec = reinterpret_cast<const CapRec *>(sl.h_cap + sizeof(CapHdr));
+	const size_t rec_bytes = nrec > kCapMailRecs ? sizeof(CapRec) * (size_t)nrec : 0, need = rec_bytes + (size_t)pairs * sizeof(cf32);
+	if(need > m.stage_cap) {
+		if(m.h_stage) (void)hipHostFree(m.h_stage);
+		m.h_stage = nullptr; m.stage_cap = 0;
+		const size_t cap = std::max<size_t>(need + need / 2, 1u << 20);
+		HIPCHK(hipHostMalloc((void **)&m.h_stage, cap, hipHostMallocDefault));
+		m.stage_cap = cap;
+	}
+	if(rec_bytes) { HIPCHK(hipMemcpyAsync(m.h_stage, sl.d_cap_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream_out)); rec = reinterpret_cast<const CapRec *>(m.h_stage); }
+	if(pairs) HIPCHK(hipMemcpyAsync(m.h_stage + rec_bytes, sl.d_cap_pool, (size_t)pairs * sizeof(cf32), hipMemcpyDeviceToHost, c->stream_out));
+	if(need) HIPCHK(hipStreamSynchronize(c->stream_out));
+	const float *iqp = reinterpret_cast<const float *>(m.h_stage + rec_bytes);
+	auto iq = pairs ? std::make_shared<std::vector<float>>(iqp, iqp + 2 * (size_t)pairs) : std::make_shared<std::vector<float>>();
+	struct Join { uint32_t frames = 0, ok = 0; int32_t fec = -1, last_idx = -1; };
+	std::map<std::pair<int32_t, int64_t>, Join> join;
+	for(uint32_t i = 0; i < nf; i++) {
+		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
+		Join &j = join[{ fr[i].chan + c->chan_first, fr[i].burst_ord }];
+		j.frames++; if(fr[i].avlc_status == AVLC_OK) j.ok++;
+		if(fr[i].idx >= j.last_idx) { j.last_idx = fr[i].idx; j.fec = fr[i].num_fec_corrections; }
+	}
+	for(uint32_t i = 0; i < nrec; i++) {
+		vdl2hip_burst r;
+		memcpy(&r, rec + i, sizeof r);
+		if(r.iq_off + r.iq_count > pairs) { r.iq_count = 0; r.iq_off = 0; r.flags |= VDL2HIP_BURST_NO_ROOM; }      // (never)
+		m.bursts++; m.iq_samples += r.iq_count; if(r.flags & VDL2HIP_BURST_NO_ROOM) m.iq_dropped++;
+		auto it = join.find({ (int32_t)r.chan, r.burst_ord });
+		if(it != join.end()) { r.frames = it->second.frames; r.frames_ok = it->second.ok; r.fec_corrections = it->second.fec; }
+		if((m.flags & VDL2HIP_CAPTURE_FAILED_ONLY) && r.frames_ok != 0) continue;
+		m.queue.push_back(vdl2hip_ctx::CapItem{ r, iq });
+	}
+	return VDL2HIP_OK;
+}
+// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed; the events stay with the slots)
+static void capture_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) {
+		void *q[] = { sl.d_cap_hdr, sl.d_cap_plan, sl.d_cap_tot, sl.d_cap_pool };
+		for(void *p : q) if(p) (void)hipFree(p);
+		sl.d_cap_hdr = nullptr; sl.d_cap_rec = nullptr; sl.d_cap_plan = nullptr; sl.d_cap_tot = nullptr; sl.d_cap_pool = nullptr;
+		if(sl.h_cap) (void)hipHostFree(sl.h_cap);
+		sl.h_cap = nullptr; sl.cap_on = false; sl.cap_timed = 0;
+	}
+	c->capt.queue.clear();
+	c->capt.on = false;
+}
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const bool small = sl.small;
@@ -867,6 +983,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		const unsigned ff_grid = std::min(256u, (sl.k5_waves * (unsigned)kResSlots * 2 / kFrameChunk + kFrameWaves - 1) / kFrameWaves);
 		hipLaunchKernelGGL(k_frame_finish, dim3(ff_grid), dim3(64 * kFrameWaves), 0, s5_, sl.d_frames, (const uint8_t *)sl.d_pool, sl.d_mail, (const Tables *)c->d_tab,
 		                   c->d_acnt, (const float *)c->d_nfring, c->nf_ring - 1, sl.d_frames_out, sl.d_pool_out);
+		// the burst capture reads this feed's burst lists and y here: both passes of the burst decoder and its scans are done
+		if(sl.cap_on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 	}
 	// the control block and the first few delivered frames in one copy (collect_slot)
 	HIPCHK(hipMemcpyAsync(sl.h_mail, sl.d_mail, sizeof(OutMail), hipMemcpyDeviceToHost, s5_));
@@ -929,6 +1047,7 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 		for(auto &e : sl.ev_rs) if(e) (void)hipEventDestroy(e);
 		for(auto &e : sl.ev_mon) if(e) (void)hipEventDestroy(e);
 		for(auto &e : sl.ev_act) if(e) (void)hipEventDestroy(e);
+		for(auto &e : sl.ev_cap) if(e) (void)hipEventDestroy(e);
 		if(sl.h_mail) (void)hipHostFree(sl.h_mail);
 		if(sl.done) (void)hipEventDestroy(sl.done);
 		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
@@ -950,6 +1069,8 @@ void vdl2hip_destroy(vdl2hip_ctx *c) {
 	if(c->act.ev_last) (void)hipEventDestroy(c->act.ev_last);
 	if(c->act.rd) (void)hipStreamDestroy(c->act.rd);
 	if(c->act.h_buf) (void)hipHostFree(c->act.h_buf);
+	capture_free(c);
+	if(c->capt.h_stage) (void)hipHostFree(c->capt.h_stage);
 	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
 	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
 	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
@@ -2146,6 +2267,149 @@ int vdl2hip_activity_series(vdl2hip_ctx *c, uint32_t chan, int64_t first_bin, fl
 	if(n0 < n) HIPCHK(hipMemcpyAsync(dst + n0, base, (n - n0) * sizeof(float), hipMemcpyDeviceToHost, m.rd));
 	HIPCHK(hipStreamSynchronize(m.rd));
 	return (int)n;
+}
+
+// ---- the burst capture (vdl2hip.h, "Burst capture"; kernels: capture.h) ----
+int vdl2hip_capture_enable(vdl2hip_ctx *c, const vdl2hip_capture_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_capture_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(cfg->pre_samples > kCapMaxPre || cfg->post_samples > kCapMaxPost || (cfg->flags & ~VDL2HIP_CAPTURE_FAILED_ONLY) || cfg->pool_samples > kCapMaxPool) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier capture is in flight any more
+	auto &m = c->capt;
+	capture_free(c);
+	const uint32_t pool = cfg->pool_samples ? cfg->pool_samples : kCapDefPool;
+	const size_t nb = (size_t)c->C * c->cap_bursts_chan;
+	for(auto &sl : c->slot) {
+		bool ok = hipMalloc((void **)&sl.d_cap_hdr, sizeof(CapHdr) + std::max<size_t>(nb, kCapMailRecs) * sizeof(CapRec)) == hipSuccess
+			&& hipMalloc((void **)&sl.d_cap_plan, nb * sizeof(CapPlan)) == hipSuccess && hipMalloc((void **)&sl.d_cap_tot, (size_t)c->C * 8) == hipSuccess
+			&& hipMalloc((void **)&sl.d_cap_pool, (size_t)pool * sizeof(cf32)) == hipSuccess
+			&& hipHostMalloc((void **)&sl.h_cap, kCapMailBytes, hipHostMallocDefault) == hipSuccess;
+		if(!ok) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_NOMEM; }
+		sl.d_cap_rec = reinterpret_cast<CapRec *>(sl.d_cap_hdr + 1);
+		memset(sl.h_cap, 0, kCapMailBytes);
+		if(hipMemset(sl.d_cap_hdr, 0, kCapMailBytes) != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
+	}
+	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
+	m.pre = cfg->pre_samples; m.post = cfg->post_samples; m.flags = cfg->flags; m.pool = pool;
+	m.bursts = m.iq_samples = m.iq_dropped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_capture_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->capt.on && !c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
+	capture_free(c);
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_capture_info_get(vdl2hip_ctx *c, vdl2hip_capture_info *info) {
+	if(!c || !c->capt.on || !info || info->struct_size != sizeof(vdl2hip_capture_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->capt;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->pre_samples = m.pre; info->post_samples = m.post; info->flags = m.flags; info->pool_samples = m.pool;
+	info->bursts = m.bursts; info->iq_samples = m.iq_samples; info->iq_dropped = m.iq_dropped; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used) {
+	if(!c || !c->capt.on || (!recs && cap_recs) || (!iq && cap_pairs)) return VDL2HIP_E_INVAL;
+	auto &q = c->capt.queue;
+	size_t n = 0, used = 0;
+	while(!q.empty() && n < cap_recs) {
+		const vdl2hip_ctx::CapItem &it = q.front();
+		if(used + it.r.iq_count > cap_pairs) break;
+		recs[n] = it.r;
+		recs[n].iq_off = used;
+		if(it.r.iq_count) memcpy(iq + 2 * used, it.iq->data() + 2 * it.r.iq_off, (size_t)it.r.iq_count * 2 * sizeof(float));
+		used += it.r.iq_count;
+		n++;
+		q.pop_front();
+	}
+	if(pairs_used) *pairs_used = used;
+	return (int)n;
+}
+
+// test hooks (not declared in vdl2hip.h; host only, need no GPU): the capture's per-burst steps on the CPU, lane by lane and level by level.
+// A burst as the hooks take it (64 bytes):
+struct CapDebugBurst { int32_t nsym; uint32_t tl_bits; int64_t t_first, sync_sample, end_sample, ord, prev_n; float prev_phi0, vdphi, ppm; uint32_t pad_; };
+static Burst cap_debug_burst(const CapDebugBurst &d) {
+	Burst b{};
+	b.nsym = d.nsym; b.tl_bits = d.tl_bits; b.t_first = d.t_first; b.sync_sample = d.sync_sample; b.end_sample = d.end_sample; b.ord = d.ord; b.prev_n = d.prev_n;
+	b.prev_phi0 = d.prev_phi0; b.vdphi = d.vdphi; b.ppm = d.ppm;
+	return b;
+}
+// One burst over y, a channel's ring of ring_len (re, im) pairs (a power of two, 16-byte aligned), its window placed at pair `off`
+// of a pool: -> the record (iq_off = off) and iq[0 .. iq_count).  VDL2HIP_E_DEVICE if a store went outside the window's place.
+int vdl2hip_debug_capture_burst(const float *y, uint32_t ring_len, const void *burst, uint32_t pre, uint32_t post, int64_t k_end, uint64_t off, uint32_t chan, uint32_t freq,
+		vdl2hip_burst *rec, float *iq, size_t cap_pairs) {
+	if(!y || !burst || !rec || (ring_len & (ring_len - 1)) || ring_len < 2 || ((uintptr_t)y & 15) || pre > kCapMaxPre || post > kCapMaxPost || off > (1u << 24)) return VDL2HIP_E_INVAL;
+	const Burst b = cap_debug_burst(*static_cast<const CapDebugBurst *>(burst));
+	if(b.nsym < 0 || b.sync_sample < 0 || b.end_sample < b.sync_sample || b.end_sample >= k_end || b.t_first < 0 || b.t_first + (int64_t)(b.nsym > 0 ? b.nsym - 1 : 0) * kSpsDec >= k_end) return VDL2HIP_E_INVAL;
+	CapPlan p{};
+	cap_window(b, pre, post, k_end, p.first, p.count);
+	if(iq && p.count > cap_pairs) return VDL2HIP_E_TOOBIG;               // (a window longer than the ring goes round it: the steps mask every index)
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	constexpr size_t G = 4;                                           // guard pairs of NaN on either side of the window's place
+	const size_t base = (size_t)(off & 1u) + 2 * G;                  // (the pool begins on a 16-byte boundary; the window at a pair of off's parity)
+	std::vector<float4> store((base + p.count + 2 * G + 3) / 2 + 1);
+	cf32 *pool = reinterpret_cast<cf32 *>(store.data());
+	for(size_t i = 0; i < 2 * store.size(); i++) pool[i] = cf32{ NAN, NAN };
+	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_copy(yc, ring_len - 1, p.first, p.count, pool + base, off, l, kCapThreads);
+	bool bad = false;
+	for(size_t i = 0; i < 2 * store.size(); i++) if(i < base || i >= base + p.count) bad = bad || !std::isnan(pool[i].re) || !std::isnan(pool[i].im);
+	std::vector<CapPart> part(kCapThreads);
+	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) part[l] = cap_quality_run(yc, ring_len - 1, b, l, kCapThreads);
+	for(uint32_t s = kCapThreads / 2; s >= 1; s >>= 1) for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_tree_step(part.data(), l, s);
+	CapRec r{};
+	cap_record(b, chan, freq, p, off, true, part[0], r);
+	memcpy(rec, &r, sizeof r);
+	if(iq && p.count) memcpy(iq, pool + base, (size_t)p.count * sizeof(cf32));
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+// The offsets of a feed's bursts as the two kernels work them out - bursts[c * cap_bursts_chan + i], i < nb_chan[c]; the scans go in
+// rounds of 64 with a carry as the wavefronts' do (integer sums: their order changes nothing) - and the room decision:
+// -> iq_off, iq_count, flags per burst in record order, hdr = { records, pairs of the pool in use }.  Returns the number of records.
+int vdl2hip_debug_capture_plan(const void *bursts, const uint32_t *nb_chan, uint32_t nchan, uint32_t cap_bursts_chan, uint32_t pre, uint32_t post, int64_t k_end,
+		uint64_t pool_samples, uint64_t *iq_off, uint32_t *iq_count, uint32_t *flags, size_t cap_recs, uint64_t hdr[2]) {
+	if(!bursts || !nb_chan || !hdr || !nchan || nchan > (uint32_t)kCapMaxChan || !cap_bursts_chan || pre > kCapMaxPre || post > kCapMaxPost) return VDL2HIP_E_INVAL;
+	const CapDebugBurst *db = static_cast<const CapDebugBurst *>(bursts);
+	std::vector<CapPlan> plan((size_t)nchan * cap_bursts_chan);
+	std::vector<uint64_t> tot(nchan), bbo(nchan + 1);
+	std::vector<uint32_t> bbn(nchan + 1);
+	for(uint32_t c = 0; c < nchan; c++) {                                // k_capture_plan
+		const uint32_t nb = std::min(nb_chan[c], cap_bursts_chan);
+		uint64_t carry = 0;
+		for(uint32_t w = 0; w < nb; w += 64) {
+			uint32_t inc = 0;
+			for(uint32_t l = 0; l < 64 && w + l < nb; l++) {
+				CapPlan &p = plan[(size_t)c * cap_bursts_chan + w + l];
+				cap_window(cap_debug_burst(db[(size_t)c * cap_bursts_chan + w + l]), pre, post, k_end, p.first, p.count);
+				p.off = carry + inc; inc += p.count;
+			}
+			carry += inc;
+		}
+		tot[c] = carry;
+	}
+	uint32_t total = 0; uint64_t ototal = 0;                             // k_capture_copy: the channels' offsets
+	for(uint32_t c = 0; c < nchan; c++) { bbn[c] = total; bbo[c] = ototal; total += std::min(nb_chan[c], cap_bursts_chan); ototal += tot[c]; }
+	bbn[nchan] = total; bbo[nchan] = ototal;
+	hdr[0] = total; hdr[1] = 0;
+	if((iq_off || iq_count || flags) && cap_recs < total) return VDL2HIP_E_TOOBIG;
+	for(uint32_t g = 0; g < total; g++) {
+		const int c = cap_find_chan(bbn.data(), (int)nchan, g);
+		const uint32_t i = g - bbn[c];
+		const CapPlan &p = plan[(size_t)c * cap_bursts_chan + i];
+		const uint64_t off = bbo[c] + p.off;
+		const bool fits = off + p.count <= pool_samples;
+		if(iq_off) iq_off[g] = fits ? off : 0;
+		if(iq_count) iq_count[g] = fits ? p.count : 0;
+		if(flags) flags[g] = fits ? 0u : kCapNoRoom;
+		if(fits && cap_is_last_fit(bbn.data(), (int)nchan, plan.data(), cap_bursts_chan, g, c, i, off + p.count, pool_samples, total)) hdr[1] = off + p.count;
+	}
+	return (int)total;
 }
 
 int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {

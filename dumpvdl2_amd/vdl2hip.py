@@ -46,7 +46,9 @@ EXPORTS = [
     "vdl2hip_read_resampled", "vdl2hip_resampler_design",
     "vdl2hip_spectrum_window", "vdl2hip_spectrum_enable", "vdl2hip_spectrum_read", "vdl2hip_spectrum_channels",
     "vdl2hip_activity_edges", "vdl2hip_activity_enable", "vdl2hip_activity_disable", "vdl2hip_activity_read", "vdl2hip_activity_series",
+    "vdl2hip_capture_enable", "vdl2hip_capture_disable", "vdl2hip_capture_info_get", "vdl2hip_capture_read",
 ]
+CAPTURE_FAILED_ONLY, BURST_NO_ROOM = 1, 1   # include/vdl2hip.h: VDL2HIP_CAPTURE_FAILED_ONLY (cfg.flags), VDL2HIP_BURST_NO_ROOM (vdl2hip_burst.flags)
 WIN_RECT, WIN_HANN, WIN_BH4 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_WIN_* (the input monitor's analysis windows)
 
 
@@ -111,6 +113,25 @@ class ActivityChan(C.Structure):
 ACTIVITY_CHAN_DTYPE = np.dtype([("bins", "<u8"), ("busy_bins", "<u8"), ("transmissions", "<u8"), ("longest_bins", "<u8"),
                                 ("sum_power", "<f8"), ("max_power", "<f4"), ("min_power", "<f4"), ("open", "<u4"), ("reserved", "<u4"),
                                 ("hist", "<u8", (64,))])     # vdl2hip_activity_chan, 568 bytes
+
+
+class CaptureCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pre_samples", C.c_uint32), ("post_samples", C.c_uint32), ("flags", C.c_uint32),
+                ("pool_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CaptureInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pre_samples", C.c_uint32), ("post_samples", C.c_uint32), ("flags", C.c_uint32),
+                ("pool_samples", C.c_uint32), ("reserved", C.c_uint32), ("bursts", C.c_uint64), ("iq_samples", C.c_uint64),
+                ("iq_dropped", C.c_uint64), ("kernel_ms", C.c_float), ("reserved2", C.c_uint32)]
+
+
+BURST_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("burst_ord", "<i8"), ("sync_sample", "<i8"), ("end_sample", "<i8"), ("first_symbol", "<i8"),
+                        ("nsym", "<u4"), ("tl_bits", "<u4"), ("ppm_error", "<f4"), ("dphi", "<f4"), ("prev_phase", "<f4"), ("flags", "<u4"),
+                        ("iq_first", "<i8"), ("iq_count", "<u4"), ("reserved", "<u4"), ("iq_off", "<u8"),
+                        ("frames", "<u4"), ("frames_ok", "<u4"), ("fec_corrections", "<i4"), ("weak_symbols", "<u4"),
+                        ("mean_power", "<f4"), ("min_power", "<f4"), ("max_power", "<f4"),
+                        ("phase_err_rms", "<f4"), ("phase_err_mean", "<f4"), ("phase_err_max", "<f4")])     # vdl2hip_burst, 128 bytes
 
 
 class PackedFrame(C.Structure):
@@ -178,6 +199,11 @@ def load_library(path: str = None):
         L.vdl2hip_activity_disable.argtypes = [C.c_void_p]
         L.vdl2hip_activity_read.argtypes = [C.c_void_p, C.POINTER(ActivityInfo), C.c_void_p, C.c_size_t, C.c_int]
         L.vdl2hip_activity_series.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_capture_enable"):                # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_capture_enable.argtypes = [C.c_void_p, C.POINTER(CaptureCfg)]
+        L.vdl2hip_capture_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_capture_info_get.argtypes = [C.c_void_p, C.POINTER(CaptureInfo)]
+        L.vdl2hip_capture_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -303,6 +329,37 @@ def _activity_series(Lib, ctx, chan: int, first_bin: int, count: int) -> np.ndar
     buf = np.zeros(max(1, count), dtype=np.float32)
     n = _err(Lib, Lib.vdl2hip_activity_series(ctx, chan, first_bin, buf.ctypes.data, count), "vdl2hip_activity_series")
     return buf[:n]
+
+
+def _capture_enable(Lib, ctx, pre, post, failed_only, pool_samples) -> None:
+    cfg = CaptureCfg(C.sizeof(CaptureCfg), pre, post, CAPTURE_FAILED_ONLY if failed_only else 0, pool_samples, 0)
+    _err(Lib, Lib.vdl2hip_capture_enable(ctx, C.byref(cfg)), "vdl2hip_capture_enable")
+
+
+def _capture_info(Lib, ctx) -> dict:
+    info = CaptureInfo(C.sizeof(CaptureInfo))
+    _err(Lib, Lib.vdl2hip_capture_info_get(ctx, C.byref(info)), "vdl2hip_capture_info_get")
+    return {k: getattr(info, k) for k, _ in CaptureInfo._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+
+
+def _capture_read(Lib, ctx, cap_recs: int = 4096, cap_pairs: int = 1 << 20):
+    """vdl2hip_capture_read() until nothing more comes -> (records as dicts with every field of vdl2hip_burst but `reserved`,
+    their windows as complex64 arrays).  cap_recs / cap_pairs: the buffers of one call (a window longer than cap_pairs would
+    never be delivered: 2^16 pairs hold any)."""
+    recs = np.zeros(max(1, cap_recs), dtype=BURST_DTYPE)
+    iq = np.zeros((max(1, cap_pairs), 2), dtype=np.float32)
+    out, wins = [], []
+    while True:
+        used = C.c_size_t(0)
+        n = _err(Lib, Lib.vdl2hip_capture_read(ctx, recs.ctypes.data, cap_recs, iq.ctypes.data, cap_pairs, C.byref(used)), "vdl2hip_capture_read")
+        if n == 0:
+            break
+        for r in recs[:n]:
+            d = {k: r[k].item() for k in BURST_DTYPE.names if k != "reserved"}
+            off, cnt = d["iq_off"], d["iq_count"]
+            wins.append(iq[off:off + cnt].copy().view(np.complex64).reshape(-1))
+            out.append(d)
+    return out, wins
 
 
 class Receiver:
@@ -537,6 +594,24 @@ class Receiver:
         """up to `count` bin powers p[first_bin ...] of channel `chan` (its index in the frequency list), float32"""
         return _activity_series(self.L, self.h, chan, first_bin, count)
 
+    def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
+        """switch the burst capture on from the next feed (vdl2hip.h, "Burst capture"): of every burst handed to the burst decoder the
+        decimated IQ from `pre` samples before its sync to `post` after its last symbol, its timing and a phase-error quality figure.
+        failed_only: deliver only bursts without a good frame; pool_samples: IQ pairs a feed may capture (0: 2^20)."""
+        _capture_enable(self.L, self.h, pre, post, failed_only, pool_samples)
+
+    def capture_disable(self) -> None:
+        self._chk(self.L.vdl2hip_capture_disable(self.h), "vdl2hip_capture_disable")
+
+    def capture_info(self) -> dict:
+        """the configuration in force and bursts / iq_samples / iq_dropped / kernel_ms of the feeds collected so far"""
+        return _capture_info(self.L, self.h)
+
+    def capture_read(self, cap_recs: int = 4096, cap_pairs: int = 1 << 20):
+        """the bursts of the feeds collected so far (sync() or drain()), oldest first: (list of dicts - the fields of vdl2hip_burst -,
+        list of complex64 arrays - their IQ windows, empty where iq_count is 0)"""
+        return _capture_read(self.L, self.h, cap_recs, cap_pairs)
+
     def read_resampled(self, first: int, count: int) -> np.ndarray:
         """up to `count` (re, im) pairs of the resampled stream r[first ...] (receivers created with input_rate; the last six feeds' are kept)"""
         buf = np.zeros((count, 2), dtype=np.float32)
@@ -663,6 +738,22 @@ class ReceiverGroup:
             if n >= 0:
                 return buf[:n]
         raise Vdl2HipError("no member holds that channel and bin")
+
+    def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
+        """the burst capture of every member (there is no group call: each member captures its own channels' bursts)"""
+        for i in range(self.size()):
+            _capture_enable(self.L, self.member(i), pre, post, failed_only, pool_samples)
+
+    def capture_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_capture_disable(self.member(i)), "vdl2hip_capture_disable")
+
+    def capture_info(self, member: int) -> dict:
+        return _capture_info(self.L, self.member(member))
+
+    def capture_read(self, member: int, cap_recs: int = 4096, cap_pairs: int = 1 << 20):
+        """Receiver.capture_read() of one member: its own channels' bursts (chan: the index in the group's frequency list)"""
+        return _capture_read(self.L, self.member(member), cap_recs, cap_pairs)
 
     def close(self):
         if getattr(self, "h", None):

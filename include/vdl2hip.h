@@ -42,7 +42,9 @@ extern "C" {
                                  *    vdl2hip_spectrum_window() / _enable() / _read() / _channels() with vdl2hip_spectrum_cfg / _info: the input monitor, off
                                  *    unless enabled - new entry points and structures only, nothing existing changed size or meaning, so the version stayed
                                  *    vdl2hip_activity_edges() / _enable() / _disable() / _read() / _series() with vdl2hip_activity_cfg / _info / _chan: the
-                                 *    activity monitor, off unless enabled - again new entry points and structures only, so the version stayed */
+                                 *    activity monitor, off unless enabled - again new entry points and structures only, so the version stayed
+                                 *    vdl2hip_capture_enable() / _disable() / _info_get() / _read() with vdl2hip_capture_cfg / _info and vdl2hip_burst: the
+                                 *    burst capture, off unless enabled - new entry points and structures only once more, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -226,6 +228,59 @@ typedef struct {
 	uint32_t open, reserved;
 	uint64_t hist[64];
 } vdl2hip_activity_chan;                       /* 568 bytes */
+
+/* Burst capture (not in the reference, which reports a burst only through the frames it yields): for every burst handed to the burst
+ * decoder, a window of the channel's DECIMATED stream around it, its timing, and a phase-error quality figure computed on the device
+ * from the same samples - what a burst looked like on air and how good it was, whether it decoded or not.  Off unless enabled; with
+ * it off nothing is launched or allocated and every result is what it was, to the bit.  On, frames, counters and the decimated stream
+ * are still exactly what they were: the capture is a read-only pass behind the frame finisher of each feed.
+ *  - Which bursts.  Every burst whose header decoded - the ones vdl2hip_stats.bursts counts - in the feed whose burst decoder decodes
+ *    it (the feed that brings its last symbol), decoded successfully or not.  A preamble lock whose header fails (crc.bad, too_long,
+ *    no_fec) never becomes a burst and is not captured.
+ *  - IQ window.  pre = pre_samples <= 4096, post = post_samples <= 1024; k_end = the decimated samples that exist at the end of that
+ *    feed.  iq_first = max(0, sync_sample - pre), iq_last = min(end_sample + post, k_end - 1), iq_count = iq_last - iq_first + 1.  The
+ *    values are y_c[iq_first .. iq_last] as they stand when that feed's burst decoder has finished: after both of its passes and every
+ *    referee scan of the feed, so stretches the referee rewrote for this feed are included.  (With the referee on, a LATER feed already
+ *    under way may rewrite a stretch just ahead of its own first sample while the window is copied; a single feed, or the referee off,
+ *    gives exactly what vdl2hip_read_decimated() returns after vdl2hip_sync().)  pre = 256 covers ramp-up and the 16-symbol unique
+ *    word.  Only post makes the window depend on how the stream was cut into feeds; with post = 0 it does not.
+ *  - Quality, over the burst's nsym symbols: t_m = first_symbol + 10 m; phi_m = the phase of y[t_m], the decoder's own double-precision
+ *    atan2 narrowed to float; phi_-1 = prev_phase; u_m = exactly the number the decoder's slicer rounds - float32 (phi_m - phi_m-1)
+ *    - dphi, wrapped by 2 pi in double, divided by pi / 4 in double, narrowed to float; e_m = u_m - roundf(u_m), in units of pi / 4.
+ *    Sums are float64 in a fixed order (contiguous runs of symbols per lane, a fixed tree over the lanes, no atomics):
+ *      phase_err_rms = (float)(sqrt(sum e^2 / nsym) pi / 4), phase_err_mean = (float)((sum e / nsym) pi / 4) - the residual carrier
+ *      slope -, phase_err_max = (float)(max |e| pi / 4), weak_symbols = #{ m : |e_m| > 0.25f } - symbols nearer to a decision boundary
+ *      than to a constellation point -, mean_power = (float)(sum p_m / nsym) with p_m = re^2 + im^2 of y[t_m] in float32 (two
+ *      products, one addition), min_power and max_power the smallest and largest p_m.
+ *  - Order.  The records of one feed are ordered by (channel, position in the channel's burst list), feeds follow one another in
+ *    feed order: the same sequence of calls gives the same bytes.
+ *  - Room.  Each feed in flight has an IQ pool of pool_samples pairs (0 means 2^20; above 2^24 is refused).  Offsets are the exclusive
+ *    prefix sum of iq_count in record order; a burst whose window ends beyond the pool gets iq_count = 0 and VDL2HIP_BURST_NO_ROOM in
+ *    flags - its quality fields are still valid - and vdl2hip_capture_info.iq_dropped counts these.  Records never run out.
+ *  - Outcome, joined on the host when the feed is collected, independent of vdl2hip_set_avlc_filter(): frames = the frames the burst
+ *    produced, frames_ok = those with avlc_status == VDL2HIP_AVLC_OK, fec_corrections = num_fec_corrections of its last frame, -1
+ *    without one.  VDL2HIP_CAPTURE_FAILED_ONLY delivers only the records with frames_ok == 0 (filtered on the host: the device
+ *    captures everything, and vdl2hip_capture_info counts everything).
+ *  - chan is the index in cfg.freqs.  Groups get no group call: vdl2hip_group_ctx(g, k) is the handle for member k's channels. */
+#define VDL2HIP_CAPTURE_FAILED_ONLY 1u
+#define VDL2HIP_BURST_NO_ROOM       1u
+typedef struct { uint32_t struct_size, pre_samples, post_samples, flags, pool_samples, reserved; } vdl2hip_capture_cfg;  /* 24 bytes; reserved must be 0 */
+typedef struct {
+	uint32_t chan, freq;                  /* index in cfg.freqs, Hz */
+	int64_t  burst_ord, sync_sample, end_sample, first_symbol;   /* first_symbol: the sample of the first symbol after the unique word */
+	uint32_t nsym, tl_bits;
+	float    ppm_error, dphi, prev_phase; /* what the decoder used: the burst's ppm figure, its phase slope per symbol, the phase before symbol 0 */
+	uint32_t flags;                       /* VDL2HIP_BURST_* */
+	int64_t  iq_first; uint32_t iq_count, reserved; uint64_t iq_off;   /* pairs; iq_off into the caller's buffer of that vdl2hip_capture_read() */
+	uint32_t frames, frames_ok; int32_t fec_corrections; uint32_t weak_symbols;
+	float    mean_power, min_power, max_power, phase_err_rms, phase_err_mean, phase_err_max;
+} vdl2hip_burst;                               /* 128 bytes */
+typedef struct {
+	uint32_t struct_size, pre_samples, post_samples, flags, pool_samples, reserved;   /* as in force */
+	uint64_t bursts, iq_samples, iq_dropped;   /* captured by the device in the feeds collected so far: records, pairs, windows without room */
+	float    kernel_ms;                        /* summed HIP-event time of the capture's launches at profiling level 2, else 0 */
+	uint32_t reserved2;
+} vdl2hip_capture_info;                        /* 56 bytes */
 
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
@@ -470,6 +525,21 @@ int  vdl2hip_activity_read(vdl2hip_ctx *ctx, vdl2hip_activity_info *info, vdl2hi
 /* Copy up to `cap` values p[first_bin ...] of one channel (index in cfg.freqs); returns the count (0 is legal for first_bin ==
  * info.bins).  VDL2HIP_E_INVAL for a bin older than what the ring holds or beyond bins, a channel outside the shard, the monitor off. */
 int  vdl2hip_activity_series(vdl2hip_ctx *ctx, uint32_t chan, int64_t first_bin, float *dst, size_t cap);
+
+/* ---- Burst capture (see "Burst capture" above) ----
+ * Switch the capture on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way, drops
+ * what is queued unread and starts afresh.  VDL2HIP_E_INVAL for a bad struct_size, pre_samples, post_samples, flags, pool_samples or
+ * reserved, before anything is allocated or changed: a capture that was on stays as it was. */
+int  vdl2hip_capture_enable(vdl2hip_ctx *ctx, const vdl2hip_capture_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_capture_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Capture off: VDL2HIP_E_INVAL. */
+int  vdl2hip_capture_info_get(vdl2hip_ctx *ctx, vdl2hip_capture_info *info);
+/* Like vdl2hip_drain_packed(): the records of the feeds collected so far (by vdl2hip_sync() or a drain, which respects the drain lag),
+ * oldest first, with their windows in iq[] as (re, im) float pairs - record i's at pair recs[i].iq_off.  What does not fit - records
+ * or their IQ - stays queued for the next call; the call never waits for the device itself.  Returns the number of records written,
+ * *pairs_used the pairs (pairs_used may be NULL).  Capture off: VDL2HIP_E_INVAL. */
+int  vdl2hip_capture_read(vdl2hip_ctx *ctx, vdl2hip_burst *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,16 @@
  *   --activity-bin <samples>      bin length in decimated samples, 10 .. 10500 (default 105 = 1 ms)
  *   --activity-threshold <dBFS>   a bin above it is busy (default -40)
  *   --activity-hang <bins>        idle bins a transmission bridges, 0 .. 255 (default 0)
+ *   --bursts-out <path>           (this library's own) switch the burst capture on and, at exit, write every burst handed to the burst decoder,
+ *                                 decoded or not: a "# key value" line per field of vdl2hip_capture_info, then per burst every field of
+ *                                 vdl2hip_burst in the structure's order - "chan freq burst_ord sync_sample end_sample first_symbol nsym
+ *                                 tl_bits ppm_error dphi prev_phase flags iq_first iq_count iq_off frames frames_ok fec_corrections
+ *                                 weak_symbols mean_power min_power max_power phase_err_rms phase_err_mean phase_err_max"
+ *   --bursts-iq <path>            the bursts' IQ windows one after the other as cf32 (interleaved float32 I, Q at 105 kS/s); iq_off of a
+ *                                 burst's line is then the pair in this file its window begins at (without the option: 0)
+ *   --bursts-failed-only          only the bursts that produced no frame that passes the AVLC checks
+ *   --bursts-pre <samples>        decimated samples kept ahead of the sync, 0 .. 4096 (default 256)
+ *   --bursts-post <samples>       ... and behind the last symbol, 0 .. 1024 (default 32)
  *   freq [freq ...]               channel frequencies in Hz; default: the CSC, 136975000
  * and prints one line per AVLC frame (metadata in the reference's "[S:…] [L:…] [F:…] [#idx]" style + hex octets).
  * Everything after avlc_decoder_queue_push() (AVLC/ACARS/X.25/... decoding, formatters) is out of scope here.
@@ -62,6 +72,32 @@ static double hist_percentile(const vdl2hip_activity_chan *ch, double q) {
 }
 static double dbfs_of(double p) { return p > 0.0 ? 10.0 * log10(p) : -INFINITY; }
 
+/* burst capture: the records so far (written at exit, behind the totals), the IQ file as it grows */
+static vdl2hip_burst *bursts;
+static size_t nbursts, cap_bursts;
+static FILE *bursts_iq;
+static uint64_t bursts_iq_pairs;
+static int take_bursts(vdl2hip_ctx *rx) {
+	enum { RECS = 256, PAIRS = 1 << 18 };                                       /* (a window is shorter than 2^16 pairs) */
+	static vdl2hip_burst rec[RECS];
+	static float iq[2 * PAIRS];
+	for(;;) {
+		size_t used = 0;
+		const int n = vdl2hip_capture_read(rx, rec, RECS, iq, PAIRS, &used);
+		if(n <= 0) return n;
+		if(nbursts + (size_t)n > cap_bursts) {
+			cap_bursts = 2 * (nbursts + (size_t)n);
+			bursts = realloc(bursts, cap_bursts * sizeof *bursts);
+			if(!bursts) { perror("realloc"); exit(3); }
+		}
+		for(int i = 0; i < n; i++) {
+			rec[i].iq_off = bursts_iq ? bursts_iq_pairs + rec[i].iq_off : 0;
+			bursts[nbursts++] = rec[i];
+		}
+		if(bursts_iq) { fwrite(iq, 2 * sizeof(float), used, bursts_iq); bursts_iq_pairs += used; }
+	}
+}
+
 static void on_frame(const vdl2hip_frame *f, void *user) {
 	(void)user;
 	nframes++;
@@ -84,6 +120,8 @@ int main(int argc, char **argv) {
 	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
+	const char *bursts_path = NULL, *bursts_iq_path = NULL;
+	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
 	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0, input_rate = 0;
@@ -121,6 +159,11 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--activity-bin")) { NEEDARG(); activity_bin = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--activity-threshold")) { NEEDARG(); activity_thr = strtof(argv[++i], NULL); }
 		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--bursts-out")) { NEEDARG(); bursts_path = argv[++i]; }
+		else if(!strcmp(a, "--bursts-iq")) { NEEDARG(); bursts_iq_path = argv[++i]; }
+		else if(!strcmp(a, "--bursts-failed-only")) bursts_flags |= VDL2HIP_CAPTURE_FAILED_ONLY;
+		else if(!strcmp(a, "--bursts-pre")) { NEEDARG(); bursts_pre = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--bursts-post")) { NEEDARG(); bursts_post = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--blocks-per-feed")) { NEEDARG(); per_feed = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(a[0] == '-' && a[1]) { fprintf(stderr, "unknown option %s\n", a); return 1; }
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
@@ -129,7 +172,8 @@ int main(int argc, char **argv) {
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
-			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [freq ...]\n", argv[0]); return 1; }
+			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] "
+			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
 		freqs[nfreq++] = CSC_FREQ;
@@ -146,6 +190,8 @@ int main(int argc, char **argv) {
 	FILE *f = !strcmp(infile, "-") ? stdin : fopen(infile, "r");
 	if(!f) { perror("Could not open input file"); return 2; }
 	if(rawpath && !(raw_out = fopen(rawpath, "w"))) { perror("Could not open raw frames output"); return 2; }
+	if(bursts_iq_path && !bursts_path) { fprintf(stderr, "--bursts-iq needs --bursts-out\n"); return 1; }
+	if(bursts_iq_path && !(bursts_iq = fopen(bursts_iq_path, "w"))) { perror("Could not open bursts IQ output"); return 2; }
 
 	vdl2hip_cfg cfg;
 	memset(&cfg, 0, sizeof cfg);
@@ -175,6 +221,10 @@ int main(int argc, char **argv) {
 			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
+	if(bursts_path) {
+		vdl2hip_capture_cfg cc = { sizeof cc, bursts_pre, bursts_post, bursts_flags, 0, 0 };
+		if((r = vdl2hip_capture_enable(rx, &cc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_capture_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+	}
 
 	unsigned char *buf = malloc((size_t)per_feed * FILE_BUFSIZE);
 	if(!buf) { perror("malloc"); return 3; }
@@ -187,6 +237,7 @@ int main(int argc, char **argv) {
 		if(len != FILE_BUFSIZE) vdl2hip_set_drain_lag(rx, 0);                   /* the last feed: every frame out */
 		if((r = vdl2hip_feed(rx, buf, held)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_feed: %s\n", vdl2hip_strerror(r)); return 3; }
 		if((r = vdl2hip_drain(rx, on_frame, NULL)) < 0) { fprintf(stderr, "vdl2hip_drain: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		held = 0;
 	} while(len == FILE_BUFSIZE);
 	free(buf);
@@ -246,6 +297,26 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "activity not written: %s\n", nact < 0 ? vdl2hip_strerror(nact) : "cannot open file");
+	}
+	if(bursts_path) {
+		vdl2hip_capture_info ci;
+		memset(&ci, 0, sizeof ci); ci.struct_size = sizeof ci;
+		r = vdl2hip_capture_info_get(rx, &ci);
+		FILE *so = r == VDL2HIP_OK ? fopen(bursts_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# pre_samples %u\n# post_samples %u\n# flags %u\n# pool_samples %u\n", ci.pre_samples, ci.post_samples, ci.flags, ci.pool_samples);
+			fprintf(so, "# bursts %" PRIu64 "\n# iq_samples %" PRIu64 "\n# iq_dropped %" PRIu64 "\n# kernel_ms %.6g\n", ci.bursts, ci.iq_samples, ci.iq_dropped, (double)ci.kernel_ms);
+			for(size_t i = 0; i < nbursts; i++) {
+				const vdl2hip_burst *b = &bursts[i];
+				fprintf(so, "%u %u %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %u %u %.9g %.9g %.9g %u %" PRId64 " %u %" PRIu64 " %u %u %d %u %.9g %.9g %.9g %.9g %.9g %.9g\n",
+						b->chan, b->freq, b->burst_ord, b->sync_sample, b->end_sample, b->first_symbol, b->nsym, b->tl_bits, (double)b->ppm_error, (double)b->dphi,
+						(double)b->prev_phase, b->flags, b->iq_first, b->iq_count, b->iq_off, b->frames, b->frames_ok, b->fec_corrections, b->weak_symbols,
+						(double)b->mean_power, (double)b->min_power, (double)b->max_power, (double)b->phase_err_rms, (double)b->phase_err_mean, (double)b->phase_err_max);
+			}
+			fclose(so);
+		}
+		else fprintf(stderr, "bursts not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+		if(bursts_iq) fclose(bursts_iq);
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
