@@ -1,0 +1,399 @@
+// debug_hooks.inc - included at the end of vdl2hip.hip (uses its file-local helpers: collect_pending, launch_scans, HIPCHK ...).
+// Every vdl2hip_debug_* entry point: the hooks the tests and the measurement scripts reach the library's pieces through.  None is
+// declared in vdl2hip.h.  What a hook allocates it holds in DevBuf / Event locals (hostmem.h): every way out releases everything.
+
+// What the hooks below say three times over each: was the call good, a host block to a buffer (all of it, or its first `bytes`), a
+// buffer filled with a byte, a buffer back to the host, the decoder's tables built and sent
+static bool hip_ok(hipError_t e) { return e == hipSuccess; }
+template<typename T> static bool dbg_up(const DevBuf<T> &d, const void *src, size_t bytes) { return hip_ok(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); }
+template<typename T> static bool dbg_up(const DevBuf<T> &d, const void *src) { return dbg_up(d, src, d.bytes()); }
+template<typename T> static bool dbg_fill(const DevBuf<T> &d, int v) { return hip_ok(hipMemset(d, v, d.bytes())); }
+template<typename T> static bool dbg_down(void *dst, const DevBuf<T> &d, size_t bytes) { return hip_ok(hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost)); }
+template<typename T> static bool dbg_down(void *dst, const DevBuf<T> &d) { return dbg_down(dst, d, d.bytes()); }
+static bool dbg_tables(const DevBuf<Tables> &d) { auto tab = std::make_unique<Tables>(); build_tables(*tab); return dbg_up(d, tab.get()); }
+
+// Builds with a VDL2_*_PROF switch (kernels.h): the kernel's per-slot counters, [64][K] in a device symbol, summed over the slots
+// into out[K], and set back to zero if asked
+template<int K> static int prof_read(const void *symbol, unsigned long long *out, int reset) {
+	unsigned long long h[64][K];
+	if(hipMemcpyFromSymbol(h, symbol, sizeof h) != hipSuccess) return -3;
+	for(int k = 0; k < K; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
+	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(symbol, h, sizeof h) != hipSuccess) return -3; }
+	return 0;
+}
+
+extern "C" {
+
+// test hook (not declared in vdl2hip.h; host only, needs no receiver and no GPU): what the process holds through the owners of
+// hostmem.h right now -> out = { device buffers, page-locked buffers, events }
+int vdl2hip_debug_live_resources(long long out[3]) {
+	if(!out) return VDL2HIP_E_INVAL;
+	for(int i = 0; i < 3; i++) out[i] = hostmem::g_live[i].load();
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_parity.py): "no_fuse" = run the segment-start fix-up as the separate kernel
+// k_fixup instead of inside K1 (bit-identical results); "force_timeout" = make every look-back hand-off fail (producers publish
+// under a wrong epoch), so that the fall-back path is taken by every workgroup and can be tested
+int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
+	if(!c || !name) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	if(strcmp(name, "no_fuse") == 0) { c->fuse_k2 = value == 0; return VDL2HIP_OK; }
+	if(strcmp(name, "force_timeout") == 0) { c->debug_force_timeout = value != 0; return VDL2HIP_OK; }
+	if(strcmp(name, "force_mismatch") == 0) { c->debug_force_mismatch = value != 0; return VDL2HIP_OK; }   // every channel walked again with the next feed's walk already done is taken to have ended differently: the next feed is redone for it
+	if(strcmp(name, "walk_ahead_below") == 0) { c->walk_ahead_below = (double)value; c->walk_ahead_auto = true; return VDL2HIP_OK; }   // (tests: feeds of fewer channel-samples than this let the next walk go ahead)
+	if(strcmp(name, "walk_ahead") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->walk_ahead = (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // 1: the next feed's walk goes ahead of a feed's check, for every feed; 0: a feed's walk waits for the check of the feed before (round 5's schedule)
+	if(strcmp(name, "exact_tier") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->debug_exact_tier = (int)value; return VDL2HIP_OK; }   // 1 (default): the exact sync tier's dense form, k_sync_dense; 0: the word-at-a-time form it replaced, k_sync_exact4 (bit-identical results)
+	if(strcmp(name, "screen_all") == 0) { c->debug_screen_all = value != 0; return VDL2HIP_OK; }   // the screening tier flags every sample (flags are only ever conservative: same frames), so that the exact tier runs at its worst-case density
+	if(strcmp(name, "force_again") == 0) { c->debug_force_again = value != 0; return VDL2HIP_OK; }   // every channel of every long feed is stitched a second time (the referee's walk-again path)
+	if(strcmp(name, "referee") == 0) { if(value && !c->d_refhist) return VDL2HIP_E_INVAL; c->referee = value != 0; return VDL2HIP_OK; }   // (on only where it was on at create: the history ring)
+	if(strcmp(name, "ref_warm") == 0) { if(value < 0 || value > c->ref_T - 4096) return VDL2HIP_E_INVAL; c->ref_warm = value; return VDL2HIP_OK; }
+	return VDL2HIP_E_INVAL;
+}
+
+// test hook (not declared in vdl2hip.h): the referee's scan on [n_lo, n_hi] of one channel, with the raw input the most recent feed could
+// reach - the decimated stream there is then the reference's own, to be read back with vdl2hip_read_decimated().  1: done, 0: refused
+int vdl2hip_debug_exact_window_many(vdl2hip_ctx *c, uint32_t chan, int64_t n_lo, int64_t n_hi, uint32_t count, int64_t stride, float *ms) {
+	if(!c || !c->d_refhist || chan >= (uint32_t)c->C || c->feed_no == 0 || count == 0 || count > 65536) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	DevBuf<int> d_out; std::vector<int> h(count, 0);
+	if(!hip_ok(d_out.alloc(count))) return VDL2HIP_E_NOMEM;
+	Event e0, e1;
+	if(!hip_ok(e0.ensure()) || !hip_ok(e1.ensure())) return VDL2HIP_E_DEVICE;
+	hipExtLaunchKernelGGL(k_ref_probe, dim3(count), dim3(64), 0, c->streams.front, e0, e1, 0, c->d_ref[(c->feed_no - 1) % kSlots].get(), (int)chan, c->C, n_lo, n_hi, stride, d_out.get());
+	if(!hip_ok(hipStreamSynchronize(c->streams.front)) || !dbg_down(h.data(), d_out)) return VDL2HIP_E_DEVICE;
+	if(ms) { float t = 0.f; (void)hipEventElapsedTime(&t, e0, e1); *ms = t; }
+	int n = 0; for(int v : h) n += v;
+	return n;            // stretches done (of `count`)
+}
+// test hook (not declared in vdl2hip.h): the same through k_ref_scan_multi - `count` stretches (chan[i], lo[i], hi[i]) side by side;
+// returns the number of scans run, *ms = the kernels' time.  with_retry: as the product's launches do it - the scans that have not met
+// their witness are listed and run again from ref_retry_mul times further back (without: they are counted as unmet and published)
+int vdl2hip_debug_scan_multi2(vdl2hip_ctx *c, const int32_t *chan, const int64_t *lo, const int64_t *hi, uint32_t count, int with_retry, float *ms) {
+	if(!c || !c->d_refhist || c->feed_no == 0 || count == 0 || count > 65536 || !chan || !lo || !hi) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	std::vector<ScanReq> h(count);
+	for(uint32_t i = 0; i < count; i++) { if(chan[i] < 0 || chan[i] >= c->C) return VDL2HIP_E_INVAL; h[i] = ScanReq{ chan[i], REF_CANDIDATE, lo[i], hi[i] }; }
+	DevBuf<ScanReq> d_sq, d_rt; DevBuf<uint32_t> d_n;
+	if(!hip_ok(d_sq.alloc(count)) || !hip_ok(d_n.alloc(2)) || !hip_ok(d_rt.alloc(kRetryScans))) return VDL2HIP_E_NOMEM;
+	uint32_t before[8] = {0}, after[8] = {0};
+	const uint32_t nn[2] = { count, 0u };
+	Event e0, e1;
+	if(!hip_ok(e0.ensure()) || !hip_ok(e1.ensure()) || !dbg_up(d_sq, h.data()) || !dbg_up(d_n, nn) || !dbg_down(before, c->d_refstats, sizeof before)) return VDL2HIP_E_DEVICE;
+	RefChan *ref = c->d_ref[(c->feed_no - 1) % kSlots];
+	launch_scans(c, c->streams.front, ref, 0xfffeu, d_sq, nullptr, d_n, count, c->k_total, with_retry ? d_rt.get() : nullptr, d_n + 1, e0, e1);
+	if(!hip_ok(hipStreamSynchronize(c->streams.front)) || !dbg_down(after, c->d_refstats, sizeof after)) return VDL2HIP_E_DEVICE;
+	if(ms) { float t = 0.f; (void)hipEventElapsedTime(&t, e0, e1); *ms = t; }
+	return (int)(after[0] - before[0]);
+}
+int vdl2hip_debug_exact_window(vdl2hip_ctx *c, uint32_t chan, int64_t n_lo, int64_t n_hi) { return vdl2hip_debug_exact_window_many(c, chan, n_lo, n_hi, 1, 0, nullptr); }
+
+// test hook (not declared in vdl2hip.h): what the DPP controls the channeliser's scan relies on do on this device
+int vdl2hip_debug_u8_levels(float out[512]) {        // out[0..255]: the channeliser's division-free (i - 127.5) / 127.5, out[256..511]: the division (tests)
+	DevBuf<float> d;
+	if(!hip_ok(d.alloc(512))) return VDL2HIP_E_NOMEM;
+	hipLaunchKernelGGL(k_u8_level_probe, dim3(1), dim3(256), 0, 0, d);
+	return dbg_down(out, d) ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
+}
+
+int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
+	DevBuf<float> d_in, d_out;
+	if(!hip_ok(d_in.alloc(64)) || !hip_ok(d_out.alloc(256))) return VDL2HIP_E_NOMEM;
+	if(!dbg_up(d_in, in)) return VDL2HIP_E_DEVICE;
+	hipLaunchKernelGGL(k_dpp_probe, dim3(1), dim3(64), 0, 0, (const float *)d_in, d_out);
+	return dbg_down(out, d_out) ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_core_probe.py): the device builds of vdl2_core.h's element-wise pieces on n elements.
+// kind 0 phase_of, 1 phase_fast, 2 mag_of: in (re, im), out 1 float; 3 sync_metric: in 16 phases, out (pherr, slope); 4 sync_metric_screen:
+// in 16 phases in turns, out (16 taps, kScreenEarly taps); 5 slice_symbol: in (phi, prev_phi, vdphi), out int32 (index, neg);
+// 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold); 8 header_to_geometry:
+// in a 25-bit header word (uint32), out uint32 (status, syndrome, tl_bits, want_bits).  Needs no receiver
+int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
+	if(kind < 0 || kind >= PROBE_KINDS || !in || !out || n == 0 || n > (size_t)1 << 26) return VDL2HIP_E_INVAL;
+	DevBuf<float> d_in, d_out; DevBuf<Tables> d_tab;
+	if(!hip_ok(d_in.alloc(n * (size_t)core_probe_in_words(kind))) || !hip_ok(d_out.alloc(n * (size_t)core_probe_out_words(kind))) || !hip_ok(d_tab.alloc(1))) return VDL2HIP_E_NOMEM;
+	if(!dbg_tables(d_tab) || !dbg_up(d_in, in) || !dbg_fill(d_out, 0)) return VDL2HIP_E_DEVICE;
+	hipLaunchKernelGGL(k_core_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, (const float *)d_in, (uint32_t)n, d_out, (const Tables *)d_tab);
+	return hip_ok(hipGetLastError()) && dbg_down(out, d_out) ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): the device build of the burst decoder's pieces on n elements, `grid`
+// workgroups of kBurstWaves wavefronts (kernels.h: k_burst_probe_wave, k_burst_probe_rs, k_burst_probe).  Needs no receiver.
+//   kind 0 (wave primitives)  in uint32 [n][64], out uint32 [n][68]: first flag, flag count, 64 scanned values, their total, the minimum
+//   kind 1 (rs_decode_row)    in uint8 [n][256]: 255 octets and npar (0, 2, 4 or 6); out uint8 [n][256]: the row, then int32 [n]: the return value
+//   kind 2 (decode_burst)     in Burst [n], element i on ring y[i][ring_len] (cf32, ring_len a power of two), freq [nchan], referee off.  The output
+//                             control block starts as a feed's does (the counters behind the wavefronts' own shares) with capacities cap_frames and
+//                             cap_pool; behind the records and behind the pool lie guard_frames records and guard_pool octets, everything filled with
+//                             0xA5 beforehand.  Returned: frames [cap_frames + guard_frames], pool [cap_pool + guard_pool], ctl (an OutCtl), cnt
+//                             [nchan][20]; `out` is not used
+int vdl2hip_debug_burst_probe(int kind, const void *in, size_t n, unsigned grid, void *out, const uint32_t *freq, uint32_t nchan, const float *y, uint32_t ring_len,
+		uint32_t cap_frames, uint32_t cap_pool, uint32_t guard_frames, uint32_t guard_pool, void *frames, uint8_t *pool, void *ctl, unsigned long long *cnt) {
+	if(kind < 0 || kind >= BPROBE_KINDS || !in || n == 0 || n > (size_t)1 << 20 || grid == 0 || grid > 1024) return VDL2HIP_E_INVAL;
+	const uint32_t nwaves = grid * (uint32_t)kBurstWaves;
+	const bool burst = kind == BPROBE_BURST;
+	size_t nin = 0, nout = 0;
+	if(kind == BPROBE_WAVE) { nin = n * 64 * 4; nout = n * (size_t)kBProbeWaveOut * 4; }
+	else if(kind == BPROBE_RS) {
+		nin = n * (size_t)kBProbeRsStride; nout = n * (size_t)kBProbeRsStride + n * 4;
+		for(size_t i = 0; i < n; i++) { const uint8_t np = ((const uint8_t *)in)[i * kBProbeRsStride + kRsN]; if(np > kRsPar || (np & 1)) return VDL2HIP_E_INVAL; }
+	} else {
+		nin = n * sizeof(Burst);
+		if(!freq || nchan == 0 || !y || ring_len < 64 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || !frames || !pool || !ctl || !cnt) return VDL2HIP_E_INVAL;
+		if(cap_frames > 1u << 20 || cap_pool > 1u << 26 || guard_frames > 1u << 16 || guard_pool > 1u << 20 || n * (size_t)ring_len > (size_t)1 << 26) return VDL2HIP_E_INVAL;
+		for(size_t i = 0; i < n; i++) {
+			const Burst &b = ((const Burst *)in)[i];
+			if(b.chan < 0 || (uint32_t)b.chan >= nchan || b.nsym < 1 || b.nsym > kMaxSyms || b.tl_bits == 0 || b.tl_bits > kMaxTl || b.t_first < 0 || b.prev_n < -2) return VDL2HIP_E_INVAL;
+		}
+	}
+	if(!burst && !out) return VDL2HIP_E_INVAL;
+	const size_t nfr = (size_t)cap_frames + guard_frames, npool = (size_t)cap_pool + guard_pool;
+	DevBuf<uint8_t> d_in, d_out, d_pool; DevBuf<Tables> d_tab; DevBuf<OutCtl> d_ctl;
+	DevBuf<uint32_t> d_freq; DevBuf<cf32> d_y; DevBuf<unsigned long long> d_cnt; DevBuf<OutFrame> d_frames;
+	if(!hip_ok(d_in.alloc(nin)) || !hip_ok(d_tab.alloc(1)) || !hip_ok(d_ctl.alloc(1)) || (nout && !hip_ok(d_out.alloc(nout)))) return VDL2HIP_E_NOMEM;
+	if(burst && (!hip_ok(d_freq.alloc(nchan)) || !hip_ok(d_y.alloc(n * (size_t)ring_len)) || !hip_ok(d_cnt.alloc((size_t)nchan * kNumCounters))
+	             || !hip_ok(d_frames.alloc(nfr + 1)) || !hip_ok(d_pool.alloc(npool + 4)))) return VDL2HIP_E_NOMEM;
+	OutCtl h_ctl; memset(&h_ctl, 0, sizeof h_ctl);
+	h_ctl.cap_frames = cap_frames; h_ctl.cap_pool = cap_pool;
+	h_ctl.nframes = burst_reserve_initial_frames(nwaves); h_ctl.pool_used = burst_reserve_initial_pool(nwaves);     // (kernels.h: reset_out_ctl)
+	if(!dbg_tables(d_tab) || !dbg_up(d_in, in) || !dbg_up(d_ctl, &h_ctl) || (nout && !dbg_fill(d_out, 0))) return VDL2HIP_E_DEVICE;
+	if(burst && (!dbg_up(d_freq, freq) || !dbg_up(d_y, y) || !dbg_fill(d_cnt, 0) || !dbg_fill(d_frames, 0xA5) || !dbg_fill(d_pool, 0xA5))) return VDL2HIP_E_DEVICE;
+	BurstProbeArgs a{ (uint32_t)n, d_tab, d_ctl, (const uint32_t *)d_in.get(), (uint32_t *)d_out.get(), d_in, d_out,
+	                  (int32_t *)(d_out.get() + n * (size_t)kBProbeRsStride), (const Burst *)d_in.get(), d_freq, d_y, ring_len, ring_len - 1, d_cnt, d_frames, d_pool };
+	const unsigned lds = (unsigned)(sizeof(BurstShared) * kBurstWaves);
+	if(kind == BPROBE_WAVE) hipLaunchKernelGGL(k_burst_probe_wave, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+	else if(kind == BPROBE_RS) hipLaunchKernelGGL(k_burst_probe_rs, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+	else hipLaunchKernelGGL(k_burst_probe, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
+	if(!hip_ok(hipGetLastError()) || !hip_ok(hipDeviceSynchronize())) return VDL2HIP_E_DEVICE;
+	if(nout && !dbg_down(out, d_out)) return VDL2HIP_E_DEVICE;
+	if(burst && (!dbg_down(frames, d_frames, nfr * sizeof(OutFrame)) || !dbg_down(pool, d_pool, npool) || !dbg_down(ctl, d_ctl) || !dbg_down(cnt, d_cnt))) return VDL2HIP_E_DEVICE;
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): k_frame_finish itself, `grid` workgroups, on the caller's record list
+// (nrec records, tombstones - chan < 0 - among them), octet pool, control block (an OutCtl: nframes, cap_frames; nvalid and pool_out_used zero)
+// and noise-floor rings ring[nchan][ring_len] (ring_len a power of two).  Returned: frames_out [nrec], pool_out [pool_out_cap] (both 0xA5 where
+// nothing was delivered), the whole OutMail (mail_out: sizeof(OutMail) octets, see vdl2hip_debug_sizeof_outmail) and the AVLC counters acnt [nchan][10].
+// Needs no receiver
+int vdl2hip_debug_sizeof_outmail(void) { return (int)sizeof(OutMail); }
+int vdl2hip_debug_frame_finish(unsigned grid, const void *frames_in, uint32_t nrec, const uint8_t *pool, uint32_t pool_len, const void *ctl_in, const float *ring, uint32_t ring_len,
+		uint32_t nchan, void *frames_out, uint8_t *pool_out, uint32_t pool_out_cap, void *mail_out, unsigned long long *acnt) {
+	if(grid == 0 || grid > 1024 || !ctl_in || !ring || ring_len == 0 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || nchan == 0 || nchan > 1024 || !frames_out || !pool_out || !mail_out || !acnt
+	   || nrec > 1u << 20 || pool_len > 1u << 28 || (nrec && !frames_in) || (pool_len && !pool)) return VDL2HIP_E_INVAL;
+	OutCtl h_ctl; memcpy(&h_ctl, ctl_in, sizeof h_ctl);
+	const uint32_t nf = h_ctl.nframes < h_ctl.cap_frames ? h_ctl.nframes : h_ctl.cap_frames;
+	if(nf > nrec || h_ctl.nvalid != 0 || h_ctl.pool_out_used != 0) return VDL2HIP_E_INVAL;
+	size_t need = 0;
+	for(uint32_t i = 0; i < nf; i++) {
+		const OutFrame &f = ((const OutFrame *)frames_in)[i];
+		if(f.chan < 0) continue;
+		if((uint32_t)f.chan >= nchan || f.len > 1u << 20 || (size_t)f.pool_off + f.len > pool_len) return VDL2HIP_E_INVAL;
+		need += ((size_t)f.len + 3) & ~(size_t)3;
+	}
+	if(need > pool_out_cap) return VDL2HIP_E_INVAL;
+	DevBuf<OutFrame> d_frames, d_fout; DevBuf<uint8_t> d_pool, d_pout; DevBuf<OutMail> d_mail; DevBuf<Tables> d_tab; DevBuf<float> d_ring; DevBuf<unsigned long long> d_acnt;
+	if(!hip_ok(d_frames.alloc((size_t)nrec + 1)) || !hip_ok(d_fout.alloc((size_t)nrec + 1)) || !hip_ok(d_pool.alloc((size_t)pool_len + 4)) || !hip_ok(d_pout.alloc((size_t)pool_out_cap + 4))
+	   || !hip_ok(d_mail.alloc(1)) || !hip_ok(d_tab.alloc(1)) || !hip_ok(d_ring.alloc((size_t)nchan * ring_len)) || !hip_ok(d_acnt.alloc((size_t)nchan * kNumAvlcCounters))) return VDL2HIP_E_NOMEM;
+	auto mail = std::make_unique<OutMail>(); memset(mail.get(), 0xA5, sizeof(OutMail)); mail->ctl = h_ctl;
+	if(!dbg_tables(d_tab) || !dbg_up(d_mail, mail.get()) || (nrec && !dbg_up(d_frames, frames_in, (size_t)nrec * sizeof(OutFrame))) || (pool_len && !dbg_up(d_pool, pool, pool_len))
+	   || !dbg_up(d_ring, ring) || !dbg_fill(d_acnt, 0) || !dbg_fill(d_fout, 0xA5) || !dbg_fill(d_pout, 0xA5)) return VDL2HIP_E_DEVICE;
+	hipLaunchKernelGGL(k_frame_finish, dim3(grid), dim3(64 * kFrameWaves), 0, 0, d_frames, (const uint8_t *)d_pool, d_mail, (const Tables *)d_tab, d_acnt, (const float *)d_ring, ring_len - 1, d_fout, d_pout);
+	if(!hip_ok(hipGetLastError()) || !hip_ok(hipDeviceSynchronize())) return VDL2HIP_E_DEVICE;
+	if((nrec && !dbg_down(frames_out, d_fout, (size_t)nrec * sizeof(OutFrame))) || (pool_out_cap && !dbg_down(pool_out, d_pout, pool_out_cap))
+	   || !dbg_down(mail_out, d_mail) || !dbg_down(acnt, d_acnt)) return VDL2HIP_E_DEVICE;
+	return VDL2HIP_OK;
+}
+
+// Builds with a VDL2_*_PROF switch (kernels.h): the kernels' own counters (prof_read)
+#ifdef VDL2_K1_PROF
+int vdl2hip_debug_k1_prof(unsigned long long out[16], int reset) { return prof_read<16>(HIP_SYMBOL(vdl2_k1_prof), out, reset); }
+#endif
+#ifdef VDL2_K3B_PROF
+int vdl2hip_debug_k3b_prof(unsigned long long out[16], int reset) { return prof_read<16>(HIP_SYMBOL(vdl2_k3b_prof), out, reset); }
+#endif
+#ifdef VDL2_K5_PROF
+int vdl2hip_debug_k5_prof(unsigned long long out[16], int reset) { return prof_read<16>(HIP_SYMBOL(vdl2_k5_prof), out, reset); }
+int vdl2hip_debug_nf_prof(unsigned long long out[16], int reset) { return prof_read<16>(HIP_SYMBOL(vdl2_nf_prof), out, reset); }
+int vdl2hip_debug_k4_prof(unsigned long long out[24], int reset) { return prof_read<24>(HIP_SYMBOL(vdl2_k4_prof), out, reset); }
+#endif
+
+// test hook (not declared in vdl2hip.h; host only): the scan's word step (act_scan_word) over `count` words of nbits[i] <= 64 busy flags
+// each, from an idle start -> out = { transmissions, longest_bins, open, first bin of the open transmission }
+int vdl2hip_debug_activity_words(const uint64_t *busy, const uint32_t *nbits, uint32_t count, uint32_t hang_bins, uint64_t out[4]) {
+	if(!busy || !nbits || !out || hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
+	ActState st{}; uint64_t tx = 0, longest = 0, base = 0;
+	for(uint32_t i = 0; i < count; i++) {
+		if(nbits[i] == 0 || nbits[i] > 64 || (nbits[i] < 64 && (busy[i] >> nbits[i]) != 0)) return VDL2HIP_E_INVAL;
+		act_scan_word(busy[i], nbits[i], hang_bins, base, st, tx, longest);
+		base += nbits[i];
+	}
+	out[0] = tx; out[1] = longest; out[2] = st.open; out[3] = st.open ? st.first : 0;
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
+// one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
+// series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.
+int vdl2hip_debug_activity_power(const float *y, uint32_t cap, int64_t k0, uint32_t D, uint32_t B, uint64_t t0, uint32_t run, float carry_in, float *series, uint32_t S, float *carry_out) {
+	if(!y || !series || !carry_out || !cap || (cap & (cap - 1)) || !S || (S & (S - 1)) || B < kActMinBin || B > kActMaxBin || !D || D > cap || !run || k0 < 0 || ((uintptr_t)y & 15)) return VDL2HIP_E_INVAL;
+	const uint64_t m0 = t0 / B, nb = (t0 + D) / B - m0;
+	if(nb > S) return VDL2HIP_E_TOOBIG;
+	ActArgs a{};
+	a.y = (const float2 *)y; a.series = series; a.carry_in = &carry_in; a.carry_out = carry_out; a.k0 = k0; a.m0 = m0;
+	a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = D; a.B = B; a.nbt = (uint32_t)nb + 1; a.run = run; a.cap = cap; a.mask = cap - 1; a.S = S; a.smask = S - 1;
+	// staging arrays with a guard zone of NaNs behind each: a store or a load beyond the kernel's sizes shows
+	constexpr int G = 64;
+	std::vector<float> p(kActLdsP + G), sb(kActMaxSubs + G), gr(kActLdsG + G);
+	bool bad = false;
+	for(uint32_t bx = 0; bx * run < a.nbt; bx++) {
+		uint32_t j = bx * run;
+		const uint32_t jend = j + run < a.nbt ? j + run : a.nbt;
+		int64_t pos = act_run_start(a, j);
+		bool fresh = true;
+		float acc[kActThreads] = {};
+		while(j < jend) {
+			const ActPlan k = act_plan(a, j, jend, pos, fresh);
+			if(k.pos < 0 || k.pos + k.len > D || k.nseg > (uint32_t)kActMaxSegs || k.nsb > (uint32_t)kActMaxSubs || k.ngr > (uint32_t)kActLdsG || act_pad(k.o + k.len) >= (uint32_t)kActLdsP) return VDL2HIP_E_DEVICE;
+			for(auto *v : { &p, &sb, &gr }) std::fill(v->begin(), v->end(), NAN);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<0>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<1>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<2>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<3>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
+			for(int i = 0; i < G; i++) bad = bad || !std::isnan(p[kActLdsP + i]) || !std::isnan(sb[kActMaxSubs + i]) || !std::isnan(gr[kActLdsG + i]);
+			if(!k.fin0) { pos += kActChunk; fresh = false; }
+			else { j += k.nseg; pos += k.len; fresh = true; }
+		}
+	}
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+
+// test hooks (not declared in vdl2hip.h; host only, need no GPU): the capture's per-burst steps on the CPU, lane by lane and level by level.
+// A burst as the hooks take it (64 bytes):
+struct CapDebugBurst { int32_t nsym; uint32_t tl_bits; int64_t t_first, sync_sample, end_sample, ord, prev_n; float prev_phi0, vdphi, ppm; uint32_t pad_; };
+static Burst cap_debug_burst(const CapDebugBurst &d) {
+	Burst b{};
+	b.nsym = d.nsym; b.tl_bits = d.tl_bits; b.t_first = d.t_first; b.sync_sample = d.sync_sample; b.end_sample = d.end_sample; b.ord = d.ord; b.prev_n = d.prev_n;
+	b.prev_phi0 = d.prev_phi0; b.vdphi = d.vdphi; b.ppm = d.ppm;
+	return b;
+}
+// One burst over y, a channel's ring of ring_len (re, im) pairs (a power of two, 16-byte aligned), its window placed at pair `off`
+// of a pool: -> the record (iq_off = off) and iq[0 .. iq_count).  VDL2HIP_E_DEVICE if a store went outside the window's place.
+int vdl2hip_debug_capture_burst(const float *y, uint32_t ring_len, const void *burst, uint32_t pre, uint32_t post, int64_t k_end, uint64_t off, uint32_t chan, uint32_t freq,
+		vdl2hip_burst *rec, float *iq, size_t cap_pairs) {
+	if(!y || !burst || !rec || (ring_len & (ring_len - 1)) || ring_len < 2 || ((uintptr_t)y & 15) || pre > kCapMaxPre || post > kCapMaxPost || off > (1u << 24)) return VDL2HIP_E_INVAL;
+	const Burst b = cap_debug_burst(*static_cast<const CapDebugBurst *>(burst));
+	if(b.nsym < 0 || b.sync_sample < 0 || b.end_sample < b.sync_sample || b.end_sample >= k_end || b.t_first < 0 || b.t_first + (int64_t)(b.nsym > 0 ? b.nsym - 1 : 0) * kSpsDec >= k_end) return VDL2HIP_E_INVAL;
+	CapPlan p{};
+	cap_window(b, pre, post, k_end, p.first, p.count);
+	if(iq && p.count > cap_pairs) return VDL2HIP_E_TOOBIG;               // (a window longer than the ring goes round it: the steps mask every index)
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	constexpr size_t G = 4;                                           // guard pairs of NaN on either side of the window's place
+	const size_t base = (size_t)(off & 1u) + 2 * G;                  // (the pool begins on a 16-byte boundary; the window at a pair of off's parity)
+	std::vector<float4> store((base + p.count + 2 * G + 3) / 2 + 1);
+	cf32 *pool = reinterpret_cast<cf32 *>(store.data());
+	for(size_t i = 0; i < 2 * store.size(); i++) pool[i] = cf32{ NAN, NAN };
+	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_copy(yc, ring_len - 1, p.first, p.count, pool + base, off, l, kCapThreads);
+	bool bad = false;
+	for(size_t i = 0; i < 2 * store.size(); i++) if(i < base || i >= base + p.count) bad = bad || !std::isnan(pool[i].re) || !std::isnan(pool[i].im);
+	std::vector<CapPart> part(kCapThreads);
+	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) part[l] = cap_quality_run(yc, ring_len - 1, b, l, kCapThreads);
+	for(uint32_t s = kCapThreads / 2; s >= 1; s >>= 1) for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_tree_step(part.data(), l, s);
+	CapRec r{};
+	cap_record(b, chan, freq, p, off, true, part[0], r);
+	memcpy(rec, &r, sizeof r);
+	if(iq && p.count) memcpy(iq, pool + base, (size_t)p.count * sizeof(cf32));
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+// The offsets of a feed's bursts as the two kernels work them out - bursts[c * cap_bursts_chan + i], i < nb_chan[c]; the scans go in
+// rounds of 64 with a carry as the wavefronts' do (integer sums: their order changes nothing) - and the room decision:
+// -> iq_off, iq_count, flags per burst in record order, hdr = { records, pairs of the pool in use }.  Returns the number of records.
+int vdl2hip_debug_capture_plan(const void *bursts, const uint32_t *nb_chan, uint32_t nchan, uint32_t cap_bursts_chan, uint32_t pre, uint32_t post, int64_t k_end,
+		uint64_t pool_samples, uint64_t *iq_off, uint32_t *iq_count, uint32_t *flags, size_t cap_recs, uint64_t hdr[2]) {
+	if(!bursts || !nb_chan || !hdr || !nchan || nchan > (uint32_t)kCapMaxChan || !cap_bursts_chan || pre > kCapMaxPre || post > kCapMaxPost) return VDL2HIP_E_INVAL;
+	const CapDebugBurst *db = static_cast<const CapDebugBurst *>(bursts);
+	std::vector<CapPlan> plan((size_t)nchan * cap_bursts_chan);
+	std::vector<uint64_t> tot(nchan), bbo(nchan + 1);
+	std::vector<uint32_t> bbn(nchan + 1);
+	for(uint32_t c = 0; c < nchan; c++) {                                // k_capture_plan
+		const uint32_t nb = std::min(nb_chan[c], cap_bursts_chan);
+		uint64_t carry = 0;
+		for(uint32_t w = 0; w < nb; w += 64) {
+			uint32_t inc = 0;
+			for(uint32_t l = 0; l < 64 && w + l < nb; l++) {
+				CapPlan &p = plan[(size_t)c * cap_bursts_chan + w + l];
+				cap_window(cap_debug_burst(db[(size_t)c * cap_bursts_chan + w + l]), pre, post, k_end, p.first, p.count);
+				p.off = carry + inc; inc += p.count;
+			}
+			carry += inc;
+		}
+		tot[c] = carry;
+	}
+	uint32_t total = 0; uint64_t ototal = 0;                             // k_capture_copy: the channels' offsets
+	for(uint32_t c = 0; c < nchan; c++) { bbn[c] = total; bbo[c] = ototal; total += std::min(nb_chan[c], cap_bursts_chan); ototal += tot[c]; }
+	bbn[nchan] = total; bbo[nchan] = ototal;
+	hdr[0] = total; hdr[1] = 0;
+	if((iq_off || iq_count || flags) && cap_recs < total) return VDL2HIP_E_TOOBIG;
+	for(uint32_t g = 0; g < total; g++) {
+		const int c = cap_find_chan(bbn.data(), (int)nchan, g);
+		const uint32_t i = g - bbn[c];
+		const CapPlan &p = plan[(size_t)c * cap_bursts_chan + i];
+		const uint64_t off = bbo[c] + p.off;
+		const bool fits = off + p.count <= pool_samples;
+		if(iq_off) iq_off[g] = fits ? off : 0;
+		if(iq_count) iq_count[g] = fits ? p.count : 0;
+		if(flags) flags[g] = fits ? 0u : kCapNoRoom;
+		if(fits && cap_is_last_fit(bbn.data(), (int)nchan, plan.data(), cap_bursts_chan, g, c, i, off + p.count, pool_samples, total)) hdr[1] = off + p.count;
+	}
+	return (int)total;
+}
+
+// test hook (not declared in vdl2hip.h): what the sync kernels left for decimated samples first .. first+count-1 of one channel - the tabulated
+// metric {pherr (its sign: the referee's mark), slope} and the candidate bit, one byte per sample
+int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {
+	if(!c || !pf || !cand || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
+	const size_t n = std::min<size_t>(count, (size_t)(c->k_total - first)), ch = chan - c->chan_first;
+	std::vector<uint64_t> words(c->cap >> 6);
+	HIPCHK(hipMemcpy(words.data(), c->d_cand + ch * (c->cap >> 6), words.size() * 8, hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < n; i++) {
+		const uint32_t slot = (uint32_t)(first + (int64_t)i) & (c->cap - 1);
+		cand[i] = (uint8_t)((words[slot >> 6] >> (slot & 63)) & 1u);
+	}
+	size_t done = 0;
+	while(done < n) {
+		const uint32_t slot = (uint32_t)(first + (int64_t)done) & (c->cap - 1);
+		const size_t m = std::min<size_t>(n - done, c->cap - slot);
+		HIPCHK(hipMemcpy(pf + 2 * done, c->d_pf + ch * c->cap + slot, m * sizeof(cf32), hipMemcpyDeviceToHost));
+		done += m;
+	}
+	return (int)n;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_sync_screen.py): the screening tier's verdicts, flag[i] = bit first + i of the d_flag ring
+int vdl2hip_debug_read_flags(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, uint8_t *flag) {
+	if(!c || !flag || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
+	// (up to the end of the last word: the bits past the last valid sample are the kernel's too, and must be zero)
+	const size_t n = std::min<size_t>(count, (size_t)(((c->k_total + 63) & ~(int64_t)63) - first)), ch = chan - c->chan_first;
+	std::vector<uint64_t> words(c->cap >> 6);
+	HIPCHK(hipMemcpy(words.data(), c->d_flag + ch * (c->cap >> 6), words.size() * 8, hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < n; i++) {
+		const uint32_t slot = (uint32_t)(first + (int64_t)i) & (c->cap - 1);
+		flag[i] = (uint8_t)((words[slot >> 6] >> (slot & 63)) & 1u);
+	}
+	return (int)n;
+}
+
+}  // extern "C"

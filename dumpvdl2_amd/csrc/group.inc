@@ -209,7 +209,7 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 			ok = g->p_gend() == ncclSuccess && ok;
 			if(ok) {
 				sent = true; g->last_form = 3;
-				for(int i = 0; i < n; i++) { GRPCHK(hipSetDevice(g->dev[i])); GRPCHK(hipEventRecord(g->ready[k][i], g->xs[i])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->stream, g->ready[k][i], 0)); }
+				for(int i = 0; i < n; i++) { GRPCHK(hipSetDevice(g->dev[i])); GRPCHK(hipEventRecord(g->ready[k][i], g->xs[i])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->streams.front, g->ready[k][i], 0)); }
 			} else {
 				fprintf(stderr, "vdl2hip: RCCL all-gather failed - falling back to peer copies\n");
 				g->use_rccl = false;
@@ -230,8 +230,8 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 					GRPCHK(hipMemcpyPeerAsync(g->blk[k][i] + off[j], g->dev[i], g->blk[k][j] + off[j], g->dev[j], off[j + 1] - off[j], st));
 					used[(d - 1) % npx] = 1;
 				}
-				GRPCHK(hipStreamWaitEvent(g->ctx[i]->stream, g->own[k][i], 0));
-				for(int x = 0; x < npx; x++) if(used[x]) { GRPCHK(hipEventRecord(g->got[k][i][x], g->px[i][x])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->stream, g->got[k][i][x], 0)); }
+				GRPCHK(hipStreamWaitEvent(g->ctx[i]->streams.front, g->own[k][i], 0));
+				for(int x = 0; x < npx; x++) if(used[x]) { GRPCHK(hipEventRecord(g->got[k][i][x], g->px[i][x])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->streams.front, g->got[k][i][x], 0)); }
 			}
 		}
 	} else if(n == 1 && wait_copy) {
@@ -257,7 +257,7 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 			ok = g->p_gend() == ncclSuccess && ok;
 			if(ok) {
 				sent = true; g->last_form = 1;
-				for(int i = 0; i < n; i++) { GRPCHK(hipSetDevice(g->dev[i])); GRPCHK(hipEventRecord(g->ready[k][i], g->xs[i])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->stream, g->ready[k][i], 0)); }
+				for(int i = 0; i < n; i++) { GRPCHK(hipSetDevice(g->dev[i])); GRPCHK(hipEventRecord(g->ready[k][i], g->xs[i])); GRPCHK(hipStreamWaitEvent(g->ctx[i]->streams.front, g->ready[k][i], 0)); }
 			} else {
 				// nothing of this block has reached a member's receiver yet: the peer-copy fan-out below redoes the whole exchange
 				fprintf(stderr, "vdl2hip: RCCL broadcast failed - falling back to peer copies\n");
@@ -268,13 +268,13 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 		if(!sent) {
 			g->last_form = 0;
 			GRPCHK(hipSetDevice(g->dev[0]));
-			GRPCHK(hipStreamWaitEvent(g->ctx[0]->stream, g->own[k][0], 0));
+			GRPCHK(hipStreamWaitEvent(g->ctx[0]->streams.front, g->own[k][0], 0));
 			for(int i = 1; i < n; i++) {
 				GRPCHK(hipSetDevice(g->dev[i]));
 				GRPCHK(hipStreamWaitEvent(g->xs[i], g->own[k][0], 0));
 				GRPCHK(hipMemcpyPeerAsync(g->blk[k][i], g->dev[i], g->blk[k][0], g->dev[0], nbytes, g->xs[i]));
 				GRPCHK(hipEventRecord(g->ready[k][i], g->xs[i]));
-				GRPCHK(hipStreamWaitEvent(g->ctx[i]->stream, g->ready[k][i], 0));
+				GRPCHK(hipStreamWaitEvent(g->ctx[i]->streams.front, g->ready[k][i], 0));
 			}
 		}
 	}

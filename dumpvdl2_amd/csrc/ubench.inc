@@ -126,22 +126,15 @@ extern "C" {
 // out[6] compute units used for the conversions   out[7] milliseconds the measurement took
 int vdl2hip_debug_ubench(int device, double out[8]) {
 	if(!out) return VDL2HIP_E_INVAL;
-	// the caller's current device is put back, and whatever was allocated is released, on every way out
-	struct Scope {
-		int prev = -1; float *o = nullptr, *taps = nullptr; ub::Clk *dclk = nullptr; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-		~Scope() {
-			if(o) (void)hipFree(o); if(taps) (void)hipFree(taps); if(dclk) (void)hipFree(dclk);
-			for(auto &e : ev) if(e) (void)hipEventDestroy(e);
-			if(prev >= 0) (void)hipSetDevice(prev);
-		}
-	} sc;
+	// the caller's current device is put back on every way out (and the buffers and events below release themselves)
+	struct Scope { int prev = -1; ~Scope() { if(prev >= 0) (void)hipSetDevice(prev); } } sc;
 	if(hipGetDevice(&sc.prev) != hipSuccess) sc.prev = -1;
 	HIPCHK(hipSetDevice(device));
 	hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, device));
 	const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-	HIPCHK(hipMalloc((void **)&sc.o, (size_t)cus * 8 * 256 * sizeof(float))); HIPCHK(hipMalloc((void **)&sc.taps, 40 * sizeof(float))); HIPCHK(hipMalloc((void **)&sc.dclk, sizeof(ub::Clk)));
-	for(auto &e : sc.ev) HIPCHK(hipEventCreate(&e));
-	float *o = sc.o, *taps = sc.taps; ub::Clk *dclk = sc.dclk; hipEvent_t e0 = sc.ev[0], e1 = sc.ev[1], ea = sc.ev[2], eb = sc.ev[3];
+	DevBuf<float> o, taps; DevBuf<ub::Clk> dclk; Event e0, e1, ea, eb;
+	HIPCHK(o.alloc((size_t)cus * 8 * 256)); HIPCHK(taps.alloc(40)); HIPCHK(dclk.alloc(1));
+	for(Event *e : { &e0, &e1, &ea, &eb }) HIPCHK(e->ensure());
 	float h_taps[40]; for(int i = 0; i < 40; i++) h_taps[i] = 0.01f * (float)(i + 1);
 	HIPCHK(hipMemcpy(taps, h_taps, sizeof h_taps, hipMemcpyHostToDevice));
 	HIPCHK(hipEventRecord(ea, nullptr));

@@ -26,8 +26,10 @@
 #include "activity.h"
 #include "capture.h"
 #include "tables.h"
+#include "hostmem.h"
 
 using namespace vdl2;
+using hostmem::DevBuf; using hostmem::PinnedBuf; using hostmem::Event;
 
 static_assert(VDL2HIP_NUM_COUNTERS == kNumCounters, "counter enum out of sync");
 
@@ -75,38 +77,74 @@ static uint32_t defer_scans_for(int64_t D, int C) {
 // of streams to queues depends on every stream the process has created so far, and a receiver made after a hundred others had come
 // and gone ran 30-60 % slower than the same receiver in a fresh process (bench.py's secondary workloads, round 6).
 constexpr int kSidePre = 3, kSideBurst = 2;
+// the streams of one receiver: not owned by it - kept when the receiver goes, taken over by the next one on the same device
+struct StreamSet {
+	int device = -1; hipStream_t front = nullptr, copy = nullptr, out = nullptr, back = nullptr, nf = nullptr, pre[kSidePre] = {}, burst[kSideBurst] = {};
+	template<typename F> void each(F f) { for(hipStream_t *p : { &front, &copy, &out, &back, &nf }) f(*p); for(auto &x : pre) f(x); for(auto &x : burst) f(x); }
+};
 constexpr int kSlots = VDL2HIP_MAX_DRAIN_LAG + 1;   // feeds in flight (vdl2hip_set_drain_lag: at most kSlots - 1 undelivered).  Six: a feed's way through the device of a receiver of few channels - front 1 ms, the scans ahead of the walk 1.5, walk, the next feed's walk (the second walks are queued behind it), burst decoder and its scans 1.5-2.5 - is four to six fronts long (rank-sized receivers, walk ahead: 2.22 / 1.46 / 1.56 ms per step with four slots, 1.76 / 1.29 / 1.45 with six; with 256 channels it is three fronts and four slots were enough)
 
 }  // namespace
 
+// Start / stop events of the (at most two) kernels one tap launches per feed, created when profiling level 2 first asks for them;
+// n: how many of the pairs the slot's last feed used.  The runtime stamps the events with the kernels' own start and stop (LAUNCH_EV).
+struct KernelTimes {
+	Event ev[4]; int n = 0; bool armed = false;
+	// (an event that cannot be created leaves the feed untimed, not failed)
+	bool arm(bool timed) { armed = timed; if(timed) for(auto &x : ev) if(x.ensure() != hipSuccess) armed = false; return armed; }
+	hipEvent_t e(int i) const { return armed ? (hipEvent_t)ev[i] : (hipEvent_t) nullptr; }
+	void launched(int pairs) { n = armed ? pairs : 0; }
+	// the feed is done (collect_slot): its kernels' durations are added to `ms`
+	void collect(double &ms) {
+		for(int i = 0; i < n; i++) { float t = 0.f; if(hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) == hipSuccess) ms += t; else (void)hipGetLastError(); }
+		n = 0;
+	}
+};
+
+// Reading a tap's device state behind its last launch: on a stream of the tap's own, behind the event of that launch, so that the
+// read waits for nothing else - not for the feeds in flight, not for what the process has on the default stream.  The event, the
+// stream and the page-locked landing place stay with the context when the tap is disabled, and go with it.
+struct TapRead {
+	Event last; bool queued = false; hipStream_t rd = nullptr; PinnedBuf land;
+	~TapRead() { if(rd) (void)hipStreamDestroy(rd); }
+	hipError_t mark(hipStream_t front) { const hipError_t e = hipEventRecord(last, front); if(e == hipSuccess) queued = true; return e; }
+	hipError_t fetch(void *dst_host, const void *src_dev, size_t bytes) {
+		hipError_t e = hipStreamWaitEvent(rd, last, 0);
+		if(e == hipSuccess) e = hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, rd);
+		return e == hipSuccess ? hipStreamSynchronize(rd) : e;
+	}
+};
+
 struct OutSlot {
-	Burst *d_bursts = nullptr; uint32_t *d_nbchan = nullptr;
-	OutFrame *d_frames = nullptr; uint8_t *d_pool = nullptr;
-	OutMail *d_mail = nullptr; OutCtl *d_ctl = nullptr;   // control block + the first few delivered frames, contiguous (d_ctl = &d_mail->ctl): one small copy brings both
-	OutFrame *d_frames_out = nullptr; uint8_t *d_pool_out = nullptr;    // what k_frame_finish delivers (no tombstones, no holes): what the host copies
-	EvalChunk *d_log = nullptr; uint32_t *d_nlog = nullptr;   // the walker's evaluation log of this feed (read by K4b)
-	uint32_t *d_dq = nullptr; ScanReq *d_sq = nullptr;      // referee, long feeds: the bursts that wait for a scan, the stretches they wait for (counts: d_rqn[1], d_rqn[2])
-	RefReq *d_rq = nullptr; uint32_t *d_rqn = nullptr, *d_rqflag = nullptr; RefBad *d_rqbad = nullptr;
-	ScanReq *d_retry = nullptr;            // [3][kRetryScans]: the unmet scans of the scans ahead of the walk / of the check / of the burst decoder (counts: d_rqn[4..6])
-	ScanReq *d_pq = nullptr; hipEvent_t ev_pre = nullptr;      // referee: the stretches around marked candidates, made exact between the front and the walk (count: d_rqn[3])
-	OutMail *h_mail = nullptr;             // pinned
-	hipEvent_t done = nullptr, ev_front = nullptr, ev_walk = nullptr, ev_nf = nullptr, ev[kNumEv] = {};
+	DevBuf<Burst> d_bursts; DevBuf<uint32_t> d_nbchan;
+	DevBuf<OutFrame> d_frames; DevBuf<uint8_t> d_pool;
+	DevBuf<OutMail> d_mail; OutCtl *d_ctl = nullptr;   // control block + the first few delivered frames, contiguous (d_ctl = &d_mail->ctl, not owned): one small copy brings both
+	DevBuf<OutFrame> d_frames_out; DevBuf<uint8_t> d_pool_out;    // what k_frame_finish delivers (no tombstones, no holes): what the host copies
+	DevBuf<EvalChunk> d_log; DevBuf<uint32_t> d_nlog;   // the walker's evaluation log of this feed (read by K4b)
+	DevBuf<uint32_t> d_dq; DevBuf<ScanReq> d_sq;      // referee, long feeds: the bursts that wait for a scan, the stretches they wait for (counts: d_rqn[1], d_rqn[2])
+	DevBuf<RefReq> d_rq; DevBuf<uint32_t> d_rqn, d_rqflag; DevBuf<RefBad> d_rqbad;
+	DevBuf<ScanReq> d_retry;            // [3][kRetryScans]: the unmet scans of the scans ahead of the walk / of the check / of the burst decoder (counts: d_rqn[4..6])
+	DevBuf<ScanReq> d_pq; Event ev_pre;      // referee: the stretches around marked candidates, made exact between the front and the walk (count: d_rqn[3])
+	PinnedBuf h_mail;                      // an OutMail
+	Event done, ev_front, ev_walk, ev_nf, ev[kNumEv];
 	bool pending = false, ev_valid = false, fused = false; int ev_level = 0;
 	uint64_t seq = 0;
 	int64_t back_D = 0, back_k0 = 0;        // the burst-rate back end of this feed (launch_back, launch_rest): its decimated samples, the first one's number
 	bool k1_timed = false;                 // the channeliser launch of this feed carries start/stop events (not on a cold-start feed: its pieces wait for copies in between)
 	bool prescan = false;                  // referee: the stretches around this feed's marked candidates are scanned ahead of its walk
 	// launch_back() / launch_rest(): the walk and check of this feed are queued, what follows them is not yet (rest_pending); what the
-	// second walks need of the first: its arguments, segmentation and speculative walks; has_chk: the walk noted decisions to a list that is checked
+	// second walks need of the first: its arguments, segmentation and speculative walks (d_spec_of: one of the context's two sets, not owned);
+	// has_chk: the walk noted decisions to a list that is checked
 	bool rest_pending = false, has_chk = false; int nseg = 1; int64_t seglen = 0; K4Args k4{}; SpecOut *d_spec_of = nullptr;
-	hipEvent_t ev_stitch = nullptr, ev_chk = nullptr; uint32_t *d_rqflag2 = nullptr;
-	hipEvent_t ev_rs[2] = {}; bool rs_timed = false;   // resampling receivers: start / stop of this feed's k_resample (profiling level 2)
-	hipEvent_t ev_mon[4] = {}; int mon_timed = 0;      // input monitor: start / stop of this feed's k_spectrum and k_spectrum_reduce (profiling level 2); how many of the two were timed
-	hipEvent_t ev_act[4] = {}; int act_timed = 0;      // activity monitor: the same for this feed's k_activity_power and k_activity_scan
+	Event ev_stitch, ev_chk; DevBuf<uint32_t> d_rqflag2;
+	// profiling level 2, per tap: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
+	// k_activity_power and k_activity_scan (activity monitor) / k_capture_plan and k_capture_copy (burst capture)
+	KernelTimes rs_t, mon_t, act_t, cap_t;
 	// burst capture (capture.h): the feed's header and records (one allocation: the header and the first records come to the host in one
-	// small copy), windows and totals, the IQ pool; cap_on: this feed's back end is followed by the capture's launches
-	CapHdr *d_cap_hdr = nullptr; CapRec *d_cap_rec = nullptr; CapPlan *d_cap_plan = nullptr; uint64_t *d_cap_tot = nullptr; cf32 *d_cap_pool = nullptr;
-	uint8_t *h_cap = nullptr; bool cap_on = false; hipEvent_t ev_cap[4] = {}; int cap_timed = 0;
+	// small copy; d_rec = the records behind the header, not owned), windows and totals, the IQ pool, the small copy's page-locked landing
+	// place.  Given back as one when the capture is disabled (capture_free); cap_on: this feed's back end is followed by the capture's launches
+	struct { DevBuf<CapHdr> d_hdr; CapRec *d_rec = nullptr; DevBuf<CapPlan> d_plan; DevBuf<uint64_t> d_tot; DevBuf<cf32> d_pool; PinnedBuf h_mail; } cap;
+	bool cap_on = false;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -119,29 +157,28 @@ struct vdl2hip_ctx {
 	int in_fmt = 0;
 	struct {
 		bool on = false; uint32_t L = 0, M = 0, T = 0, span_cap = 0; size_t lds = 0; bool taps_lds = false;
-		float *d_taps = nullptr; float2 *d_tail[2] = {nullptr, nullptr}; int tail_sel = 0;
-		float2 *d_out[kSlots] = {}; uint64_t cap = 0;                 // per slot: a feed's resampled block (samples)
+		DevBuf<float> d_taps; DevBuf<float2> d_tail[2]; int tail_sel = 0;
+		DevBuf<float2> d_out[kSlots]; uint64_t cap = 0;                 // per slot: a feed's resampled block (samples)
 		uint64_t first[kSlots] = {}, count[kSlots] = {};              // ... and which part of r[] it holds
 		uint64_t n_in = 0, n_out = 0;                                 // samples taken / made so far
 	} rs;
 	// Input monitor (spectrum.h, vdl2hip_spectrum_*): off unless enabled.  pos: samples fed since it was enabled; carry: the
-	// samples of the incomplete segment the stream stands in, where that segment will be analysed (two buffers, alternating)
+	// samples of the incomplete segment the stream stands in, where that segment will be analysed (two buffers, alternating).
+	// buf: what an enabled monitor holds on the device, given back as one (monitor_free); tap: the read behind the last launch (kept)
 	struct {
 		bool on = false; uint32_t nfft = 0, window = 0, stride = 1, log2n = 0, threads = 0; size_t lds = 0;
 		double sum_w = 0.0, enbw = 0.0; uint64_t pos = 0, segments = 0; uint32_t ncarry = 0; int carry_sel = 0;
-		float *d_w = nullptr; float2 *d_tw = nullptr, *d_carry[2] = {nullptr, nullptr}; double *d_rows = nullptr, *d_acc = nullptr;
-		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
-		hipStream_t rd = nullptr; double *h_acc = nullptr;      // the read's own stream and page-locked landing place (kept until the receiver goes)
+		struct { DevBuf<float> d_w; DevBuf<float2> d_tw, d_carry[2]; DevBuf<double> d_rows, d_acc; } buf;
+		TapRead tap; double kernel_ms = 0.0;
 	} mon;
 	// Activity monitor (activity.h, vdl2hip_activity_*): off unless enabled.  k_on: the decimated samples made before it was enabled;
 	// bins: complete so far; carry: per channel the float32 sum of what the stream holds of the incomplete bin it stands in (two
-	// buffers, alternating); acc / st: the scan's accumulators and the transmission under way, per channel
+	// buffers, alternating); acc / st: the scan's accumulators and the transmission under way, per channel.
+	// buf: what an enabled monitor holds on the device, given back as one (activity_free); tap: the read behind the last launch (kept)
 	struct {
 		bool on = false; uint32_t B = 0, H = 0, S = 0; float thr_dbfs = 0.f, thr = 0.f; int64_t k_on = 0; uint64_t bins = 0;
-		float *d_series = nullptr, *d_carry[2] = {nullptr, nullptr}, *d_edges = nullptr; int carry_sel = 0;
-		ActChan *d_acc = nullptr; ActState *d_st = nullptr;
-		hipEvent_t ev_last = nullptr; bool queued = false; double kernel_ms = 0.0;
-		hipStream_t rd = nullptr; uint8_t *h_buf = nullptr;       // the read's own stream and page-locked landing place (kept until the receiver goes)
+		struct { DevBuf<float> d_series, d_carry[2], d_edges; DevBuf<ActChan> d_acc; DevBuf<ActState> d_st; } buf;
+		int carry_sel = 0; TapRead tap; double kernel_ms = 0.0;
 	} act;
 	// Burst capture (capture.h, vdl2hip_capture_*): off unless enabled.  queue: the records of the collected feeds, oldest first, each
 	// with the IQ of its feed (one allocation per feed, shared by its records; iq_off: where the record's window begins in it)
@@ -149,7 +186,7 @@ struct vdl2hip_ctx {
 	struct {
 		bool on = false; uint32_t pre = 0, post = 0, flags = 0, pool = 0;
 		uint64_t bursts = 0, iq_samples = 0, iq_dropped = 0; double kernel_ms = 0.0;
-		uint8_t *h_stage = nullptr; size_t stage_cap = 0;      // page-locked landing place of a feed's records and IQ (kept until the receiver goes)
+		PinnedBuf stage;                                       // page-locked landing place of a feed's records and IQ, grown on demand (kept until the receiver goes)
 		std::deque<CapItem> queue;
 	} capt;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
@@ -157,40 +194,42 @@ struct vdl2hip_ctx {
 	std::vector<uint32_t> freqs, dphi, all_freqs;
 	LpfCoeffs lpf{};
 	BlockForm bf{};
-	hipStream_t stream = nullptr;
+	// Streams (kSidePre: which, of what priority, and why they come from a pool and go back to it: the one thing here the context
+	// does not own).  front: channeliser and sync kernels; copy / out: H2D of host-fed blocks, D2H of results; back: the walk; nf: the
+	// noise floor; pre: referee, VDL2HIP_REF_PRESCAN=1: the scans ahead of the walk, a stream per feed in flight (one stream would put
+	// them in a row: 4.4 ms each); burst: a burst stream per feed in flight (a burst decoder that waits for the referee - a scan over a
+	// whole burst takes milliseconds - does not hold up the next feed's)
+	StreamSet streams;
 	// device memory
-	BlockForm *d_bf = nullptr; Lut4 *d_lut = nullptr; Tables *d_tab = nullptr;
-	uint32_t *d_dphi = nullptr, *d_freq = nullptr; float *d_ppmthr = nullptr;
+	DevBuf<BlockForm> d_bf; DevBuf<Lut4> d_lut; DevBuf<Tables> d_tab;
+	DevBuf<uint32_t> d_dphi, d_freq; DevBuf<float> d_ppmthr;
 	// host-fed input: one device buffer + "copy done" event per slot, filled on a copy stream of its own so that the H2D of
 	// block i+1 runs beside the channeliser of block i (process_buf_*() hands over host memory: src/demod.c:356-365)
-	uint8_t *d_in[kSlots] = {}; hipEvent_t ev_copied[kSlots] = {}; size_t in_cap = 0;
-	hipStream_t stream_copy = nullptr, stream_out = nullptr;
-	hipEvent_t pinned_pending = nullptr;   // copy event of the last vdl2hip_feed_pinned() whose source buffer the caller may not touch yet
+	DevBuf<uint8_t> d_in[kSlots]; Event ev_copied[kSlots]; size_t in_cap = 0;
+	hipEvent_t pinned_pending = nullptr;   // (one of ev_copied[], not owned) copy event of the last vdl2hip_feed_pinned() whose source buffer the caller may not touch yet
 	// cold start (nothing in flight) of a large page-locked block: the copy goes in kColdParts pieces and the channeliser is launched
 	// piece by piece behind them, so that the first block of a stream does not wait for its whole H2D (feed_host)
-	struct { int n = 0; uint64_t samples[kColdParts] = {}; hipEvent_t ev[kColdParts] = {}; } cold;
-	uint8_t *h_stage = nullptr; size_t stage_cap = 0;   // pinned D2H staging for frame records + octets
-	uint8_t *d_carry[2] = {nullptr, nullptr}; int carry_sel = 0; uint32_t ncarry = 0;
-	cf32 *d_y = nullptr, *d_pf = nullptr; uint64_t *d_cand = nullptr, *d_flag = nullptr;
+	struct { int n = 0; uint64_t samples[kColdParts] = {}; Event ev[kColdParts]; } cold;
+	PinnedBuf stage;                       // page-locked D2H staging for frame records + octets, grown on demand
+	DevBuf<uint8_t> d_carry[2]; int carry_sel = 0; uint32_t ncarry = 0;
+	DevBuf<cf32> d_y, d_pf; DevBuf<uint64_t> d_cand, d_flag;
 	uint32_t cap = 0;
-	float4 *d_segend = nullptr; uint32_t nseg_cap = 0;
-	float4 *d_qpow = nullptr;
-	float4 *d_tcarry[2] = {nullptr, nullptr}; int tcarry_sel = 0;
-	unsigned long long *d_segpub = nullptr; uint32_t *d_synctmo = nullptr; bool fuse_k2 = true;   // K2 fused into K1 (one-step look-back between segments)
-	WalkState *d_ws = nullptr; unsigned long long *d_cnt = nullptr, *d_acnt = nullptr;
+	DevBuf<float4> d_segend; uint32_t nseg_cap = 0;
+	DevBuf<float4> d_qpow;
+	DevBuf<float4> d_tcarry[2]; int tcarry_sel = 0;
+	DevBuf<unsigned long long> d_segpub; DevBuf<uint32_t> d_synctmo; bool fuse_k2 = true;   // K2 fused into K1 (one-step look-back between segments)
+	DevBuf<WalkState> d_ws; DevBuf<unsigned long long> d_cnt, d_acnt;
 	// The reference's per-channel counters live in TWO rows per channel, one per writer: d_cnt is the burst decoder's (atomic adds from
 	// k_burst on the burst streams), d_wcnt = d_cnt + C * kNumCounters the walker's (sync.good, the header outcomes, ppm_reject: plain
 	// read-modify-writes on the walk stream, and the only row the walk-again snapshot saves and restores).  A reader adds the two.  With one
 	// row, a channel walked again wiped whatever the previous feed's burst decoder had added since the snapshot (round 5's red test).
-	unsigned long long *d_wcnt = nullptr;
-	NfState *d_nf = nullptr; int64_t *d_scfirst = nullptr, *d_sccum = nullptr;
-	float *d_nfring = nullptr, *d_lpbuf = nullptr; NfFeed *d_nffeed = nullptr; uint32_t cap_log = 0, cap_comb = 0, cap_hist = 0, nf_ring = 0;
+	unsigned long long *d_wcnt = nullptr;   // (the second half of d_cnt, not owned)
+	DevBuf<NfState> d_nf; DevBuf<int64_t> d_scfirst, d_sccum;
+	DevBuf<float> d_nfring, d_lpbuf; DevBuf<NfFeed> d_nffeed; uint32_t cap_log = 0, cap_comb = 0, cap_hist = 0, nf_ring = 0;
 	uint32_t cap_bursts_chan = 0;
-	SpecOut *d_spec[2] = {}; uint32_t *d_segstats = nullptr; int seg_max = 1; int64_t seg_min = 16384;   // segmented walk
+	DevBuf<SpecOut> d_spec[2]; DevBuf<uint32_t> d_segstats; int seg_max = 1; int64_t seg_min = 16384;   // segmented walk
 	OutSlot slot[kSlots];                  // per-feed output buffers: the fronts of feeds i+1, i+2 run while feed i's back still fills slot i%kSlots
 	uint64_t feed_no = 0; int drain_lag = 0;
-	hipStream_t stream_pre[kSidePre] = {};        // referee, VDL2HIP_REF_PRESCAN=1: the scans ahead of the walk, a stream per feed in flight (one stream would put them in a row: 4.4 ms each)
-	hipStream_t stream_back = nullptr, stream_nf = nullptr, stream_burst[kSideBurst] = {};   // (a burst stream per feed in flight: a burst decoder that waits for the referee - a scan over a whole burst takes milliseconds - does not hold up the next feed's)
 	OutCtl ctl_template{};                 // the capacities of a feed's output buffers (the counters are reset on the device: reset_out_ctl)
 	bool pooled = false;                   // its streams are complete and of the product's priorities: they go to the pool when the receiver is destroyed
 	bool avlc_filter = false, failed = false; int debug_force_timeout = 0, debug_force_again = 0, debug_exact_tier = 1, debug_screen_all = 0;
@@ -199,12 +238,12 @@ struct vdl2hip_ctx {
 	// buffer) while its back end runs; what lies before it - up to ref_T samples: the run-up of the scan + the longest burst - is kept
 	// in a ring (ref_hist), appended to by every feed (its last min(n, ref_T) samples).  ref_pieces: what of the stream the ring holds,
 	// contiguously, newest last: {first absolute sample, count, ring position of the first}.
-	bool referee = true; bool ref_prescan = false;   /* VDL2HIP_REF_PRESCAN=1: the stretches around marked candidates are made exact ahead of the walk - a rank-sized shard 4.05 -> 2.88 ms per step, 256 channels 7.2 -> 7.85: for receivers of few channels */ int64_t ref_warm = 3 << 16 /* 196 608: kernels.h */, ref_T = 0; uint8_t *d_refhist = nullptr; uint64_t ref_cap = 0, ref_wp = 0;
+	bool referee = true; bool ref_prescan = false;   /* VDL2HIP_REF_PRESCAN=1: the stretches around marked candidates are made exact ahead of the walk - a rank-sized shard 4.05 -> 2.88 ms per step, 256 channels 7.2 -> 7.85: for receivers of few channels */ int64_t ref_warm = 3 << 16 /* 196 608: kernels.h */, ref_T = 0; DevBuf<uint8_t> d_refhist; uint64_t ref_cap = 0, ref_wp = 0;
 	struct HistPiece { int64_t s0, n; uint64_t pos; }; std::vector<HistPiece> ref_pieces;
-	WalkState *d_ws_snap[2] = {}, *d_ws_tmp = nullptr; unsigned long long *d_cnt_snap[2] = {}, *d_cnt_tmp = nullptr; uint32_t rq_cap = 8192; uint32_t sq_alloc = 8192;
+	DevBuf<WalkState> d_ws_snap[2], d_ws_tmp; DevBuf<unsigned long long> d_cnt_snap[2], d_cnt_tmp; uint32_t rq_cap = 8192; uint32_t sq_alloc = 8192;
 	int walk_ahead = 1; bool walk_ahead_auto = true; double walk_ahead_below = 1.1e8; int debug_force_mismatch = 0;   // launch_back(): the walk of the next feed does not (1) / does (0) wait for this feed's check
 	int ref_retry_mul = 2;                 // a scan that has not met its witness is run again from this many times further back (0: not at all; VDL2HIP_REF_RETRY)
-	RefChan *d_ref[kSlots] = {}; unsigned long long *d_refdone = nullptr; uint32_t *d_refdonen = nullptr, *d_refstats = nullptr; uint8_t *d_mix = nullptr;
+	DevBuf<RefChan> d_ref[kSlots]; DevBuf<unsigned long long> d_refdone; DevBuf<uint32_t> d_refdonen, d_refstats; DevBuf<uint8_t> d_mix;
 	std::vector<uint64_t> statsd_prev;
 	std::vector<HostFrame> queue;
 	int64_t k_total = 0; uint64_t n_total = 0;
@@ -229,7 +268,7 @@ struct OnDevice {
 // Launch with the kernel's own start/stop stamped into two events (null: plain launch).  Used instead of hipEventRecord
 // pairs, which are separate queue entries and cost a few microseconds of stream time each.
 #define LAUNCH_EV(kernel, grid, block, stream, e0, e1, ...) hipExtLaunchKernelGGL(kernel, grid, block, 0u, stream, e0, e1, 0, __VA_ARGS__)
-#define EV(i) (prof_all ? ev[i] : (hipEvent_t) nullptr)
+#define EV(i) (prof_all ? (hipEvent_t)ev[i] : (hipEvent_t) nullptr)
 
 template<int OS, int R>
 static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, hipEvent_t e0, hipEvent_t e1) {
@@ -244,19 +283,19 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 	// oversample 20 and 10 the one that fetches its tiles ahead and stages them as they are)
 	if(c->fmt == VDL2HIP_FMT_CF32) {
 		switch(cr) {
-			case 4: hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
-			case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
-			default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1, false, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
+			case 4: hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
+			case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
+			default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
 		}
 		return;
 	}
 	switch(cr) {
 		case 4:
 			// (unsigned-byte input where the tile prefetch exists: the build that fetches and converts its tiles the way the s16 build does)
-			if constexpr(OS == 20 || OS == 10) { if(c->fmt == VDL2HIP_FMT_U8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, true>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break; } }
-			hipExtLaunchKernelGGL((k_chanfir<OS, R, 4>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
-		case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
-		default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1>), grid, block, (uint32_t)lds, c->stream, e0, e1, 0, b); break;
+			if constexpr(OS == 20 || OS == 10) { if(c->fmt == VDL2HIP_FMT_U8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break; } }
+			hipExtLaunchKernelGGL((k_chanfir<OS, R, 4>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
+		case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
+		default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
 	}
 }
 
@@ -274,15 +313,12 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
 	HIPCHK(hipEventSynchronize(sl.done));
 	sl.pending = false;
-	if(sl.rs_timed) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->stats.resample_ms += ms; else (void)hipGetLastError(); sl.rs_timed = false; }
-	for(int i = 0; i < sl.mon_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_mon[2 * i], sl.ev_mon[2 * i + 1]) == hipSuccess) c->mon.kernel_ms += ms; else (void)hipGetLastError(); }
-	sl.mon_timed = 0;
-	for(int i = 0; i < sl.act_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_act[2 * i], sl.ev_act[2 * i + 1]) == hipSuccess) c->act.kernel_ms += ms; else (void)hipGetLastError(); }
-	sl.act_timed = 0;
-	for(int i = 0; i < sl.cap_timed; i++) { float ms = 0.f; if(hipEventElapsedTime(&ms, sl.ev_cap[2 * i], sl.ev_cap[2 * i + 1]) == hipSuccess) c->capt.kernel_ms += ms; else (void)hipGetLastError(); }
-	sl.cap_timed = 0;
+	sl.rs_t.collect(c->stats.resample_ms);
+	sl.mon_t.collect(c->mon.kernel_ms);
+	sl.act_t.collect(c->act.kernel_ms);
+	sl.cap_t.collect(c->capt.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
-		hipEvent_t *ev = sl.ev;
+		const Event *ev = sl.ev;
 		float ms = 0.f;
 		if(sl.k1_timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { c->stats.chanfir_ms += ms; c->stats.chanfir_launches++; }
 		if(sl.ev_level >= 2) {
@@ -299,7 +335,8 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	}
 	if(sl.ev_valid) (void)hipGetLastError();   // (an event query that failed above is not a device error of the next feed)
 	sl.ev_valid = false;
-	const OutCtl ctl = sl.h_mail->ctl;
+	const OutMail *mail = sl.h_mail.as<OutMail>();
+	const OutCtl ctl = mail->ctl;
 	if(ctl.overflow) c->stats.overflow_feeds++;
 	c->stats.bursts += std::min(ctl.nbursts, ctl.cap_bursts);
 	const uint32_t nf = std::min(ctl.nvalid, ctl.cap_frames);
@@ -309,22 +346,16 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 		const uint8_t *po;
 		if(nf <= (uint32_t)kMailFrames && pool_n <= (uint32_t)kMailPool) {
 			// a handful of frames (the usual case for a block of a live receiver): they have come with the control block
-			fr = sl.h_mail->frames; po = sl.h_mail->pool;
+			fr = mail->frames; po = mail->pool;
 		} else {
 			// one pinned staging buffer, two asynchronous copies on a stream of their own (the burst stream may already hold the
 			// next feeds' kernels), one wait
 			const size_t fr_bytes = sizeof(OutFrame) * (size_t)nf, need = fr_bytes + pool_n;
-			if(need > c->stage_cap) {
-				if(c->h_stage) (void)hipHostFree(c->h_stage);
-				c->h_stage = nullptr; c->stage_cap = 0;
-				size_t cap = std::max<size_t>(need + need / 2, 1u << 20);
-				HIPCHK(hipHostMalloc((void **)&c->h_stage, cap, hipHostMallocDefault));
-				c->stage_cap = cap;
-			}
-			HIPCHK(hipMemcpyAsync(c->h_stage, sl.d_frames_out, fr_bytes, hipMemcpyDeviceToHost, c->stream_out));
-			if(pool_n) HIPCHK(hipMemcpyAsync(c->h_stage + fr_bytes, sl.d_pool_out, pool_n, hipMemcpyDeviceToHost, c->stream_out));
-			HIPCHK(hipStreamSynchronize(c->stream_out));
-			fr = reinterpret_cast<const OutFrame *>(c->h_stage); po = c->h_stage + fr_bytes;
+			HIPCHK(c->stage.reserve(need));
+			HIPCHK(hipMemcpyAsync(c->stage, sl.d_frames_out, fr_bytes, hipMemcpyDeviceToHost, c->streams.out));
+			if(pool_n) HIPCHK(hipMemcpyAsync(c->stage + fr_bytes, sl.d_pool_out, pool_n, hipMemcpyDeviceToHost, c->streams.out));
+			HIPCHK(hipStreamSynchronize(c->streams.out));
+			fr = c->stage.as<OutFrame>(); po = c->stage + fr_bytes;
 		}
 		auto pool = std::make_shared<std::vector<uint8_t>>(po, po + pool_n);
 		// frames of one feed are sorted when they are drained, so that feeds can be appended to the queue in order
@@ -364,35 +395,32 @@ static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
 	const uint64_t B = m.B, t0 = (uint64_t)(k0 - m.k_on), t1 = t0 + (uint64_t)D;
 	const uint64_t m0 = t0 / B, m1 = t1 / B, nb = m1 - m0;
 	ActArgs a{};
-	a.y = (const float2 *)c->d_y; a.series = m.d_series; a.carry_in = m.d_carry[m.carry_sel]; a.carry_out = m.d_carry[m.carry_sel ^ 1];
+	a.y = (const float2 *)c->d_y.get(); a.series = m.buf.d_series; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1];
 	a.k0 = k0; a.m0 = m0; a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = (uint32_t)D; a.B = m.B; a.nbt = (uint32_t)nb + 1;
 	a.cap = c->cap; a.mask = c->cap - 1; a.S = m.S; a.smask = m.S - 1;
 	// bins per workgroup: some 4096 workgroups over the channels, each with one to eight chunks' worth of samples
 	const uint64_t per = std::min<uint64_t>(8 * kActChunk, std::max<uint64_t>(kActChunk, (uint64_t)D * (uint64_t)c->C / 4096));
 	a.run = (uint32_t)std::max<uint64_t>(1, per / B);
 	const unsigned gx = (a.nbt + a.run - 1) / a.run;
-	const bool timed = c->profiling >= 2;
-	if(timed) for(auto &e : sl.ev_act) if(!e) HIPCHK(hipEventCreate(&e));
-	hipEvent_t *e = sl.ev_act;
-	hipExtLaunchKernelGGL(k_activity_power, dim3(gx, (unsigned)c->C), dim3(kActThreads), 0u, c->stream, timed ? e[0] : nullptr, timed ? e[1] : nullptr, 0, a);
+	KernelTimes &t = sl.act_t;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_activity_power, dim3(gx, (unsigned)c->C), dim3(kActThreads), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
 	if(nb) {
-		ActScanArgs sa{ m.d_series, m.d_acc, m.d_st, m.d_edges, m.thr, m0, (uint32_t)nb, m.H, m.S, m.S - 1 };
-		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->stream, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0, sa);
+		ActScanArgs sa{ m.buf.d_series, m.buf.d_acc, m.buf.d_st, m.buf.d_edges, m.thr, m0, (uint32_t)nb, m.H, m.S, m.S - 1 };
+		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, sa);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(m.ev_last, c->stream));
-	if(timed) sl.act_timed = nb ? 2 : 1;
-	m.queued = true; m.bins = m1; m.carry_sel ^= 1;
+	HIPCHK(m.tap.mark(c->streams.front));
+	t.launched(nb ? 2 : 1);
+	m.bins = m1; m.carry_sel ^= 1;
 	return VDL2HIP_OK;
 }
-// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context)
+// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap)
 static void activity_free(vdl2hip_ctx *c) {
 	auto &m = c->act;
-	if(m.queued && m.ev_last) (void)hipEventSynchronize(m.ev_last);
-	void *q[] = { m.d_series, m.d_carry[0], m.d_carry[1], m.d_edges, m.d_acc, m.d_st };
-	for(void *p : q) if(p) (void)hipFree(p);
-	m.d_series = nullptr; m.d_carry[0] = m.d_carry[1] = nullptr; m.d_edges = nullptr; m.d_acc = nullptr; m.d_st = nullptr;
-	m.on = false; m.queued = false;
+	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
+	m.buf = {};
+	m.on = false; m.tap.queued = false;
 }
 
 static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
@@ -405,8 +433,8 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	OutSlot &sl = c->slot[c->feed_no % kSlots];
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // its buffers are about to be reused
-	hipStream_t st = c->stream;
-	hipEvent_t *ev = sl.ev;
+	hipStream_t st = c->streams.front;
+	const Event *ev = sl.ev;
 	const bool prof = c->profiling != 0, prof_all = c->profiling >= 2;
 
 	K1Args a{};
@@ -437,7 +465,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		const bool cold = in_parts && c->cold.n > 1;
 		if(cold) c->stats.cold_start_feeds++;
 		sl.k1_timed = prof && !cold;
-		hipEvent_t e0 = sl.k1_timed ? ev[0] : nullptr, e1 = sl.k1_timed ? ev[1] : nullptr;
+		hipEvent_t e0 = sl.k1_timed ? (hipEvent_t)ev[0] : nullptr, e1 = sl.k1_timed ? (hipEvent_t)ev[1] : nullptr;
 		auto launch = [&](int seg0, int seg1, hipEvent_t s_ev, hipEvent_t p_ev) {
 			a.seg0 = seg0; a.seg1 = seg1;
 			if(c->specialised) {
@@ -566,8 +594,8 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 // fed that block from there on.
 template<int FMT>
 static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
-	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
-	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->stream, e0, e1, 0, a);
+	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
+	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
 }
 static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes);
 static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
@@ -592,13 +620,13 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	a.nin = (uint32_t)nin; a.nout = (uint32_t)nout; a.L = rs.L; a.M = rs.M; a.T = rs.T; a.span_cap = rs.span_cap;
 	const uint64_t per = (uint64_t)kResTile * kResTiles;
 	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nout + per - 1) / per);       // (no output: workgroup 0 still moves the tail on)
-	const bool timed = c->profiling >= 2;
-	hipEvent_t e0 = timed ? sl.ev_rs[0] : nullptr, e1 = timed ? sl.ev_rs[1] : nullptr;
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, e0, e1);
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, e0, e1);
-	else launch_resample<0>(c, a, grid, e0, e1);
+	KernelTimes &t = sl.rs_t;
+	t.arm(c->profiling >= 2);
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, t.e(0), t.e(1));
+	else launch_resample<0>(c, a, grid, t.e(0), t.e(1));
 	HIPCHK(hipGetLastError());
-	sl.rs_timed = timed;
+	t.launched(1);
 	rs.tail_sel ^= 1; rs.first[k] = n0; rs.count[k] = nout; rs.n_in = N1; rs.n_out = n1;
 	int r = feed_common(c, rs.d_out[k], (size_t)nout * sizeof(float2));
 	c->stats.input_samples += nin - nout;                           // (feed_common counted the block it saw) the caller's samples
@@ -611,7 +639,7 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 // Host bookkeeping: the stream position (64 bits), the segments this feed completes, which of them are analysed, what is carried.
 template<int FMT>
 static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
-	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->stream, e0, e1, 0, a)
+	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->streams.front, e0, e1, 0, a)
 	switch(c->mon.nfft / c->mon.threads) {                           // samples per lane (spec_threads(): 1, 2, 4 up to N = 1024, 8, 16)
 		case 1: SPEC_LAUNCH(1); break;
 		case 2: SPEC_LAUNCH(2); break;
@@ -635,7 +663,7 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	m.pos = pos1;
 	if(nseg == 0 && ncarry_out == 0) { m.ncarry = 0; return VDL2HIP_OK; }
 	SpecArgs a{};
-	a.in = dev_in; a.carry_in = m.d_carry[m.carry_sel]; a.carry_out = m.d_carry[m.carry_sel ^ 1]; a.w = m.d_w; a.tw = m.d_tw; a.rows = m.d_rows;
+	a.in = dev_in; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1]; a.w = m.buf.d_w; a.tw = m.buf.d_tw; a.rows = m.buf.d_rows;
 	a.rel0 = (int64_t)(ja * N) - (int64_t)pos0; a.carry_rel = (int64_t)(j1 * N) - (int64_t)pos0; a.seg_step = (uint64_t)m.stride * N;
 	a.nin = (uint32_t)nin; a.ncarry = m.ncarry; a.ncarry_out = ncarry_out; a.nseg = (uint32_t)nseg;
 	a.run = (uint32_t)std::max<uint64_t>(1, (nseg + kSpecMaxRows - 1) / kSpecMaxRows); a.N = m.nfft; a.log2n = m.log2n;
@@ -643,31 +671,28 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	if(grid > kSpecMaxRows || (int64_t)a.ncarry + a.rel0 < 0) return VDL2HIP_E_INVAL;       // (never)
 	OutSlot &sl = c->slot[c->feed_no % kSlots];
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
-	const bool timed = c->profiling >= 2;
-	if(timed) for(auto &e : sl.ev_mon) if(!e) HIPCHK(hipEventCreate(&e));
-	hipEvent_t *e = sl.ev_mon;
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
-	else launch_spectrum<0>(c, a, grid, timed ? e[0] : nullptr, timed ? e[1] : nullptr);
+	KernelTimes &t = sl.mon_t;
+	t.arm(c->profiling >= 2);
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, t.e(0), t.e(1));
+	else launch_spectrum<0>(c, a, grid, t.e(0), t.e(1));
 	if(nseg) {
 		const uint32_t W = m.nfft + kSpecLevels;
-		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->stream, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0,
-		                      (const double *)m.d_rows, m.d_acc, (uint32_t)grid, m.nfft);
+		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), t.e(3), 0,
+		                      (const double *)m.buf.d_rows, m.buf.d_acc.get(), (uint32_t)grid, m.nfft);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(m.ev_last, c->stream));
-	if(timed) sl.mon_timed = nseg ? 2 : 1;
-	m.queued = true; m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
+	HIPCHK(m.tap.mark(c->streams.front));
+	t.launched(nseg ? 2 : 1);
+	m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
 	return VDL2HIP_OK;
 }
-// wait for what the monitor has queued and give its buffers back (the event stays with the context)
+// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap)
 static void monitor_free(vdl2hip_ctx *c) {
 	auto &m = c->mon;
-	if(m.queued && m.ev_last) (void)hipEventSynchronize(m.ev_last);
-	void *q[] = { m.d_w, m.d_tw, m.d_carry[0], m.d_carry[1], m.d_rows, m.d_acc };
-	for(void *p : q) if(p) (void)hipFree(p);
-	m.d_w = nullptr; m.d_tw = nullptr; m.d_carry[0] = m.d_carry[1] = nullptr; m.d_rows = nullptr; m.d_acc = nullptr;
-	m.on = false; m.queued = false; m.nfft = 0;
+	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
+	m.buf = {};
+	m.on = false; m.tap.queued = false; m.nfft = 0;
 }
 
 // The burst-rate back end of one feed (K4 walk, K4b noise floor, K5 burst decoder, frame finish), on three streams of its own so
@@ -737,8 +762,8 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl) {
 	// microseconds: its whole back end goes onto the FRONT stream, behind its own sync kernels - no event hand-offs between streams -
 	// with the three noise-floor passes as one kernel.  Whoever follows on the front stream is then behind it anyway.
 	const bool small = feed_is_small(c, D);
-	hipStream_t sb_ = small ? c->stream : c->stream_back;
-	hipEvent_t *ev = sl.ev;
+	hipStream_t sb_ = small ? c->streams.front : c->streams.back;
+	const Event *ev = sl.ev;
 	const bool prof_all = sl.ev_valid && sl.ev_level >= 2;
 	sl.small = small; sl.has_chk = false; sl.nseg = 1; sl.seglen = D;
 	OutSlot &pv = c->slot[(sl.seq + kSlots - 1) % kSlots];
@@ -758,7 +783,7 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl) {
 		HIPCHK(hipStreamWaitEvent(sb_, sl.ev_front, 0));
 	}
 	if(D <= 0) hipLaunchKernelGGL(k_reset_ctl, dim3(1), dim3(1), 0, sb_, sl.d_ctl, 0u);     // (a feed with a front has had it reset by its last sync kernel)
-	hipStream_t sp_ = small ? c->stream : c->stream_pre[sl.seq % kSidePre];
+	hipStream_t sp_ = small ? c->streams.front : c->streams.pre[sl.seq % kSidePre];
 	if(D > 0 && sl.prescan) {
 		// Referee: the stretches the exact sync tier has listed (around its marked candidates) are made the reference's own NOW, beside
 		// the next feed's front and off the walk stream - the walk of this feed waits for them, the walk of the next one does not
@@ -855,43 +880,36 @@ static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
 	auto &m = c->capt;
 	CapArgs a{};
 	a.y = c->d_y; a.bursts = sl.d_bursts; a.nb_chan = sl.d_nbchan; a.freq = c->d_freq;
-	a.plan = sl.d_cap_plan; a.tot = sl.d_cap_tot; a.rec = sl.d_cap_rec; a.pool = sl.d_cap_pool; a.hdr = sl.d_cap_hdr;
+	a.plan = sl.cap.d_plan; a.tot = sl.cap.d_tot; a.rec = sl.cap.d_rec; a.pool = sl.cap.d_pool; a.hdr = sl.cap.d_hdr;
 	a.k_end = sl.back_k0 + sl.back_D; a.pool_samples = m.pool; a.cap_bursts_chan = c->cap_bursts_chan; a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first;
 	a.cap = c->cap; a.mask = c->cap - 1; a.pre = m.pre; a.post = m.post;
-	const bool timed = c->profiling >= 2;
-	if(timed) for(auto &e : sl.ev_cap) if(!e) HIPCHK(hipEventCreate(&e));
-	hipEvent_t *e = sl.ev_cap;
-	hipExtLaunchKernelGGL(k_capture_plan, dim3((unsigned)c->C), dim3(64), 0u, st, timed ? e[0] : nullptr, timed ? e[1] : nullptr, 0, a);
+	KernelTimes &t = sl.cap_t;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_capture_plan, dim3((unsigned)c->C), dim3(64), 0u, st, t.e(0), t.e(1), 0, a);
 	// a workgroup per burst, bounded like the burst decoder's wavefronts (16 .. 2048 of them, by the feed's size): 8 .. 512
 	const unsigned grid = std::min(512u, std::max(8u, sl.k5_waves / 4));
-	hipExtLaunchKernelGGL(k_capture_copy, dim3(grid), dim3(kCapThreads), 0u, st, timed ? e[2] : nullptr, timed ? e[3] : nullptr, 0, a);
+	hipExtLaunchKernelGGL(k_capture_copy, dim3(grid), dim3(kCapThreads), 0u, st, t.e(2), t.e(3), 0, a);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(sl.h_cap, sl.d_cap_hdr, kCapMailBytes, hipMemcpyDeviceToHost, st));
-	if(timed) sl.cap_timed = 2;
+	HIPCHK(hipMemcpyAsync(sl.cap.h_mail, sl.cap.d_hdr, kCapMailBytes, hipMemcpyDeviceToHost, st));
+	t.launched(2);
 	return VDL2HIP_OK;
 }
 // A collected feed's records (the first have come with the header) and the used part of its IQ pool, joined with the feed's frames -
 // all of them, whatever the AVLC filter lets through - and appended to the queue.
 static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
 	auto &m = c->capt;
-	if(!m.on || !sl.h_cap) return VDL2HIP_OK;
-	const CapHdr h = *reinterpret_cast<const CapHdr *>(sl.h_cap);
+	if(!m.on || !sl.cap.h_mail) return VDL2HIP_OK;
+	const CapHdr h = *sl.cap.h_mail.as<CapHdr>();
 	const uint32_t nrec = (uint32_t)std::min<uint64_t>(h.nrec, (uint64_t)c->C * c->cap_bursts_chan);
 	const uint64_t pairs = std::min<uint64_t>(h.pairs, m.pool);
 	if(nrec == 0) return VDL2HIP_OK;
-	const CapRec *rec = reinterpret_cast<const CapRec *>(sl.h_cap + sizeof(CapHdr));
+	const CapRec *rec = reinterpret_cast<const CapRec *>(sl.cap.h_mail + sizeof(CapHdr));
 	const size_t rec_bytes = nrec > kCapMailRecs ? sizeof(CapRec) * (size_t)nrec : 0, need = rec_bytes + (size_t)pairs * sizeof(cf32);
-	if(need > m.stage_cap) {
-		if(m.h_stage) (void)hipHostFree(m.h_stage);
-		m.h_stage = nullptr; m.stage_cap = 0;
-		const size_t cap = std::max<size_t>(need + need / 2, 1u << 20);
-		HIPCHK(hipHostMalloc((void **)&m.h_stage, cap, hipHostMallocDefault));
-		m.stage_cap = cap;
-	}
-	if(rec_bytes) { HIPCHK(hipMemcpyAsync(m.h_stage, sl.d_cap_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream_out)); rec = reinterpret_cast<const CapRec *>(m.h_stage); }
-	if(pairs) HIPCHK(hipMemcpyAsync(m.h_stage + rec_bytes, sl.d_cap_pool, (size_t)pairs * sizeof(cf32), hipMemcpyDeviceToHost, c->stream_out));
-	if(need) HIPCHK(hipStreamSynchronize(c->stream_out));
-	const float *iqp = reinterpret_cast<const float *>(m.h_stage + rec_bytes);
+	HIPCHK(m.stage.reserve(need));
+	if(rec_bytes) { HIPCHK(hipMemcpyAsync(m.stage, sl.cap.d_rec, rec_bytes, hipMemcpyDeviceToHost, c->streams.out)); rec = m.stage.as<CapRec>(); }
+	if(pairs) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.cap.d_pool, (size_t)pairs * sizeof(cf32), hipMemcpyDeviceToHost, c->streams.out));
+	if(need) HIPCHK(hipStreamSynchronize(c->streams.out));
+	const float *iqp = reinterpret_cast<const float *>(m.stage + rec_bytes);
 	auto iq = pairs ? std::make_shared<std::vector<float>>(iqp, iqp + 2 * (size_t)pairs) : std::make_shared<std::vector<float>>();
 	struct Join { uint32_t frames = 0, ok = 0; int32_t fec = -1, last_idx = -1; };
 	std::map<std::pair<int32_t, int64_t>, Join> join;
@@ -913,24 +931,19 @@ static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint
 	}
 	return VDL2HIP_OK;
 }
-// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed; the events stay with the slots)
+// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed; the slots' events and the
+// context's staging buffer stay)
 static void capture_free(vdl2hip_ctx *c) {
-	for(auto &sl : c->slot) {
-		void *q[] = { sl.d_cap_hdr, sl.d_cap_plan, sl.d_cap_tot, sl.d_cap_pool };
-		for(void *p : q) if(p) (void)hipFree(p);
-		sl.d_cap_hdr = nullptr; sl.d_cap_rec = nullptr; sl.d_cap_plan = nullptr; sl.d_cap_tot = nullptr; sl.d_cap_pool = nullptr;
-		if(sl.h_cap) (void)hipHostFree(sl.h_cap);
-		sl.h_cap = nullptr; sl.cap_on = false; sl.cap_timed = 0;
-	}
+	for(auto &sl : c->slot) { sl.cap = {}; sl.cap_on = false; sl.cap_t.n = 0; }
 	c->capt.queue.clear();
 	c->capt.on = false;
 }
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const bool small = sl.small;
-	hipStream_t sb_ = small ? c->stream : c->stream_back, sn_ = small ? c->stream : c->stream_nf, s5_ = small ? c->stream : c->stream_burst[sl.seq % kSideBurst];
+	hipStream_t sb_ = small ? c->streams.front : c->streams.back, sn_ = small ? c->streams.front : c->streams.nf, s5_ = small ? c->streams.front : c->streams.burst[sl.seq % kSideBurst];
 
-	hipEvent_t *ev = sl.ev;
+	const Event *ev = sl.ev;
 	const bool prof_all = sl.ev_valid && sl.ev_level >= 2;
 	sl.rest_pending = false;
 	if(D > 0 && sl.has_chk) {
@@ -1011,8 +1024,6 @@ static void fill_frame(const vdl2hip_ctx *c, const HostFrame &h, vdl2hip_frame &
 }
 
 namespace {
-// the streams of one receiver (see kSidePre): kept when the receiver goes, taken over by the next one on the same device
-struct StreamSet { int device = -1; hipStream_t front = nullptr, copy = nullptr, out = nullptr, back = nullptr, nf = nullptr, pre[kSidePre] = {}, burst[kSideBurst] = {}; };
 std::mutex g_pool_mutex;
 std::vector<StreamSet> g_pool;
 }  // namespace
@@ -1033,62 +1044,16 @@ const char *vdl2hip_strerror(int err) {
 	}
 }
 
+// Everything a receiver holds is a member that frees itself (hostmem.h) - except its streams, which go to the pool.  Nothing is
+// freed while a stream of the receiver may still be running something that reads it: all of them are waited for first.
 void vdl2hip_destroy(vdl2hip_ctx *c) {
 	if(!c) return;
 	OnDevice dev_guard(c);
-	if(c->stream) (void)hipStreamSynchronize(c->stream);
-	void *ptrs[] = { c->d_bf, c->d_lut, c->d_tab, c->d_dphi, c->d_freq, c->d_ppmthr, c->d_carry[0], c->d_carry[1], c->d_y, c->d_pf,
-	                 c->d_cand, c->d_flag, c->d_segend, c->d_qpow, c->d_tcarry[0], c->d_tcarry[1], c->d_ws, c->d_cnt, c->d_nf, c->d_scfirst, c->d_sccum, c->d_nfring, c->d_lpbuf, c->d_nffeed, c->d_spec[0], c->d_spec[1], c->d_segstats, c->d_acnt, c->d_segpub, c->d_synctmo };
-	for(auto &sl : c->slot) {
-		void *q[] = { sl.d_bursts, sl.d_nbchan, sl.d_frames, sl.d_pool, sl.d_frames_out, sl.d_pool_out, sl.d_mail, sl.d_log, sl.d_nlog, sl.d_rq, sl.d_rqn, sl.d_rqflag, sl.d_dq, sl.d_sq, sl.d_rqbad, sl.d_pq, sl.d_rqflag2, sl.d_retry };
-		for(void *p : q) if(p) (void)hipFree(p);
-		if(sl.ev_stitch) (void)hipEventDestroy(sl.ev_stitch);
-		if(sl.ev_chk) (void)hipEventDestroy(sl.ev_chk);
-		for(auto &e : sl.ev_rs) if(e) (void)hipEventDestroy(e);
-		for(auto &e : sl.ev_mon) if(e) (void)hipEventDestroy(e);
-		for(auto &e : sl.ev_act) if(e) (void)hipEventDestroy(e);
-		for(auto &e : sl.ev_cap) if(e) (void)hipEventDestroy(e);
-		if(sl.h_mail) (void)hipHostFree(sl.h_mail);
-		if(sl.done) (void)hipEventDestroy(sl.done);
-		if(sl.ev_walk) (void)hipEventDestroy(sl.ev_walk);
-		if(sl.ev_front) (void)hipEventDestroy(sl.ev_front);
-		if(sl.ev_pre) (void)hipEventDestroy(sl.ev_pre);
-		if(sl.ev_nf) (void)hipEventDestroy(sl.ev_nf);
-		for(int i = 0; i < kNumEv; i++) if(sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
-	}
-	if(c->h_stage) (void)hipHostFree(c->h_stage);
-	for(auto &p : c->d_in) if(p) (void)hipFree(p);
-	for(auto &p : c->d_ref) if(p) (void)hipFree(p);
-	for(auto &p : c->rs.d_out) if(p) (void)hipFree(p);
-	{ void *q[] = { c->rs.d_taps, c->rs.d_tail[0], c->rs.d_tail[1] }; for(void *p : q) if(p) (void)hipFree(p); }
-	monitor_free(c);
-	if(c->mon.ev_last) (void)hipEventDestroy(c->mon.ev_last);
-	if(c->mon.rd) (void)hipStreamDestroy(c->mon.rd);
-	if(c->mon.h_acc) (void)hipHostFree(c->mon.h_acc);
-	activity_free(c);
-	if(c->act.ev_last) (void)hipEventDestroy(c->act.ev_last);
-	if(c->act.rd) (void)hipStreamDestroy(c->act.rd);
-	if(c->act.h_buf) (void)hipHostFree(c->act.h_buf);
-	capture_free(c);
-	if(c->capt.h_stage) (void)hipHostFree(c->capt.h_stage);
-	{ void *q[] = { c->d_refhist, c->d_refdone, c->d_refdonen, c->d_refstats, c->d_mix, c->d_ws_snap[0], c->d_ws_snap[1], c->d_cnt_snap[0], c->d_cnt_snap[1], c->d_ws_tmp, c->d_cnt_tmp }; for(void *p : q) if(p) (void)hipFree(p); }
-	for(auto &e : c->ev_copied) if(e) (void)hipEventDestroy(e);
-	for(auto &e : c->cold.ev) if(e) (void)hipEventDestroy(e);
-	for(hipStream_t st_ : { c->stream_copy, c->stream_out, c->stream_back, c->stream_nf }) if(st_) (void)hipStreamSynchronize(st_);
-	for(auto &sp : c->stream_pre) if(sp) (void)hipStreamSynchronize(sp);
-	for(auto &sb5 : c->stream_burst) if(sb5) (void)hipStreamSynchronize(sb5);
-	for(void *p : ptrs) if(p) (void)hipFree(p);
-	if(c->stream && c->pooled) {
-		StreamSet ss; ss.device = c->cfg.device; ss.front = c->stream; ss.copy = c->stream_copy; ss.out = c->stream_out; ss.back = c->stream_back; ss.nf = c->stream_nf;
-		for(int i = 0; i < kSidePre; i++) ss.pre[i] = c->stream_pre[i];
-		for(int i = 0; i < kSideBurst; i++) ss.burst[i] = c->stream_burst[i];
+	c->streams.each([](hipStream_t st) { if(st) (void)hipStreamSynchronize(st); });
+	if(c->streams.front && c->pooled) {
 		std::lock_guard<std::mutex> lk(g_pool_mutex);
-		g_pool.push_back(ss);
-	} else {
-		for(hipStream_t st_ : { c->stream_copy, c->stream_out, c->stream_back, c->stream_nf, c->stream }) if(st_) (void)hipStreamDestroy(st_);
-		for(auto &sp : c->stream_pre) if(sp) (void)hipStreamDestroy(sp);
-		for(auto &sb5 : c->stream_burst) if(sb5) (void)hipStreamDestroy(sb5);
-	}
+		g_pool.push_back(c->streams);
+	} else c->streams.each([](hipStream_t st) { if(st) (void)hipStreamDestroy(st); });
 	delete c;
 }
 
@@ -1157,7 +1122,9 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	c->in_cap = max_bytes;
 	c->nseg_cap = (uint32_t)(dmax / (64 * c->run) + 2);
 
-	#define DEV_ALLOC(ptr, bytes) do { if(hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { vdl2hip_destroy(c); return VDL2HIP_E_NOMEM; } } while(0)
+	// (every way out of here that is a failure ends in vdl2hip_destroy(c): what the receiver holds by then goes with it)
+	// DEV_ALLOC(buffer, elements[, true: zeroed])
+	#define DEV_ALLOC(buf, ...) do { const hipError_t e_ = (buf).alloc(__VA_ARGS__); if(e_ != hipSuccess) { vdl2hip_destroy(c); return e_ == hipErrorOutOfMemory ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; } } while(0)
 	#define DEV_CHK(expr) do { if((expr) != hipSuccess) { vdl2hip_destroy(c); return VDL2HIP_E_DEVICE; } } while(0)
 	{
 		int prio_low = 0, prio_high = 0;
@@ -1166,63 +1133,60 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 		{
 			std::lock_guard<std::mutex> lk(g_pool_mutex);
 			for(size_t i = 0; i < g_pool.size(); i++) if(g_pool[i].device == cfg->device) {
-				const StreamSet ss = g_pool[i]; g_pool.erase(g_pool.begin() + (long)i);
-				c->stream = ss.front; c->stream_copy = ss.copy; c->stream_out = ss.out; c->stream_back = ss.back; c->stream_nf = ss.nf;
-				for(int k = 0; k < kSidePre; k++) c->stream_pre[k] = ss.pre[k];
-				for(int k = 0; k < kSideBurst; k++) c->stream_burst[k] = ss.burst[k];
+				c->streams = g_pool[i]; g_pool.erase(g_pool.begin() + (long)i);
 				from_pool = true;
 				break;
 			}
 		}
 		if(!from_pool) {
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_low));
+		c->streams.device = cfg->device;
+		DEV_CHK(hipStreamCreateWithPriority(&c->streams.front, hipStreamNonBlocking, prio_low));
 		// The walk goes first whenever it competes with the channeliser of a later feed (every later stage waits for it).  The
 		// noise-floor and burst streams do not: their many single-wave workgroups, dispatched with priority, each take the
 		// register slot of one of the four waves a channeliser workgroup needs on a CU and so keep whole workgroups out; at
 		// the front's priority they fill in while the sync kernels (few registers) run.  Measured at 256 channels
 		// (profiles/r02_stream_priorities.txt): all three high 7.10 ms/step, walk only 6.91, none 6.93; no difference at 8.
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream_back, hipStreamNonBlocking, prio_high));
-		DEV_CHK(hipStreamCreateWithPriority(&c->stream_nf, hipStreamNonBlocking, prio_low));
-		for(auto &sp : c->stream_pre) DEV_CHK(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, prio_high));
-		for(auto &sb5 : c->stream_burst) DEV_CHK(hipStreamCreateWithPriority(&sb5, hipStreamNonBlocking, prio_low));
-		DEV_CHK(hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
-		DEV_CHK(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
+		DEV_CHK(hipStreamCreateWithPriority(&c->streams.back, hipStreamNonBlocking, prio_high));
+		DEV_CHK(hipStreamCreateWithPriority(&c->streams.nf, hipStreamNonBlocking, prio_low));
+		for(auto &sp : c->streams.pre) DEV_CHK(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, prio_high));
+		for(auto &sb5 : c->streams.burst) DEV_CHK(hipStreamCreateWithPriority(&sb5, hipStreamNonBlocking, prio_low));
+		DEV_CHK(hipStreamCreateWithFlags(&c->streams.copy, hipStreamNonBlocking));
+		DEV_CHK(hipStreamCreateWithFlags(&c->streams.out, hipStreamNonBlocking));
 		}
 		c->pooled = true;
 	}
 	for(auto &sl : c->slot) {
-		DEV_CHK(hipEventCreate(&sl.done)); for(int i = 0; i < kNumEv; i++) DEV_CHK(hipEventCreate(&sl.ev[i]));
-		DEV_CHK(hipEventCreateWithFlags(&sl.ev_walk, hipEventDisableTiming)); DEV_CHK(hipEventCreateWithFlags(&sl.ev_nf, hipEventDisableTiming));
-		DEV_CHK(hipEventCreate(&sl.ev_front));
+		DEV_CHK(sl.done.ensure()); for(auto &e : sl.ev) DEV_CHK(e.ensure());
+		DEV_CHK(sl.ev_walk.ensure(hipEventDisableTiming)); DEV_CHK(sl.ev_nf.ensure(hipEventDisableTiming));
+		DEV_CHK(sl.ev_front.ensure());
 	}
-	DEV_ALLOC(c->d_bf, sizeof(BlockForm)); DEV_ALLOC(c->d_lut, sizeof(Lut4) * 256); DEV_ALLOC(c->d_tab, sizeof(Tables));
+	DEV_ALLOC(c->d_bf, 1); DEV_ALLOC(c->d_lut, 256); DEV_ALLOC(c->d_tab, 1);
 	if(resample) {
 		auto &rs = c->rs;
 		if(!design_resampler(cfg->input_rate, fs, rd)) { vdl2hip_destroy(c); return VDL2HIP_E_INVAL; }
 		rs.L = rd.L; rs.M = rd.M; rs.T = rd.T; rs.cap = rs_max_out;
 		rs.span_cap = (uint32_t)((255ull * rs.M + rs.L - 1) / rs.L) + rs.T;             // a tile's 256 outputs: the span of their b, and the T - 1 samples before
-		const size_t tap_bytes = (size_t)rs.L * rs.T * sizeof(float);
+		const size_t ntaps = (size_t)rs.L * rs.T, tap_bytes = ntaps * sizeof(float);
 		rs.taps_lds = tap_bytes <= kResTapsLds;
 		rs.lds = (size_t)rs.span_cap * sizeof(float2) + (rs.taps_lds ? tap_bytes : 0);
 		// walk order (resample.h): column q of the table is phase (q M) mod L, the phase of every output n with n mod L = q
-		std::vector<float> walk((size_t)rs.L * rs.T);
+		std::vector<float> walk(ntaps);
 		for(uint32_t j = 0; j < rs.T; j++) for(uint32_t q = 0; q < rs.L; q++) walk[(size_t)j * rs.L + q] = rd.taps[(size_t)j * rs.L + (size_t)((uint64_t)q * rs.M % rs.L)];
-		DEV_ALLOC(rs.d_taps, tap_bytes);
+		DEV_ALLOC(rs.d_taps, ntaps);
 		DEV_CHK(hipMemcpy(rs.d_taps, walk.data(), tap_bytes, hipMemcpyHostToDevice));
-		for(auto &t : rs.d_tail) { DEV_ALLOC(t, (size_t)rs.T * sizeof(float2)); DEV_CHK(hipMemset(t, 0, (size_t)rs.T * sizeof(float2))); }   // x[i < 0] = 0
-		for(auto &o : rs.d_out) DEV_ALLOC(o, (size_t)rs.cap * sizeof(float2) + 16);
-		for(auto &sl : c->slot) for(auto &e : sl.ev_rs) DEV_CHK(hipEventCreate(&e));
+		for(auto &t : rs.d_tail) DEV_ALLOC(t, rs.T, true);   // x[i < 0] = 0
+		for(auto &o : rs.d_out) DEV_ALLOC(o, (size_t)rs.cap + 2);      // (two samples of slack behind a block)
 	}
-	DEV_ALLOC(c->d_dphi, 4 * count); DEV_ALLOC(c->d_freq, 4 * count); DEV_ALLOC(c->d_ppmthr, 4 * count);
-	DEV_ALLOC(c->d_carry[0], sb * kMaxOversample); DEV_ALLOC(c->d_carry[1], sb * kMaxOversample);       // fewer than `oversample` samples left over
+	DEV_ALLOC(c->d_dphi, count); DEV_ALLOC(c->d_freq, count); DEV_ALLOC(c->d_ppmthr, count);
+	DEV_ALLOC(c->d_carry[0], sb * kMaxOversample); DEV_ALLOC(c->d_carry[1], sb * kMaxOversample);       // (bytes) fewer than `oversample` samples left over
 	const size_t nring = (size_t)count * cap;
-	DEV_ALLOC(c->d_y, nring * sizeof(cf32)); DEV_ALLOC(c->d_pf, nring * sizeof(cf32));
-	DEV_ALLOC(c->d_cand, nring / 8); DEV_ALLOC(c->d_flag, nring / 8);
-	DEV_ALLOC(c->d_segend, (size_t)count * c->nseg_cap * sizeof(float4));
-	DEV_ALLOC(c->d_qpow, 64 * sizeof(float4));
-	DEV_ALLOC(c->d_tcarry[0], count * sizeof(float4)); DEV_ALLOC(c->d_tcarry[1], count * sizeof(float4));
-	DEV_ALLOC(c->d_segpub, (size_t)count * c->nseg_cap * 4 * 8); DEV_ALLOC(c->d_synctmo, 4);
-	DEV_CHK(hipMemset(c->d_segpub, 0, (size_t)count * c->nseg_cap * 4 * 8)); DEV_CHK(hipMemset(c->d_synctmo, 0, 4));
+	static_assert(sizeof(cf32) == 8 && sizeof(float4) == 16 && sizeof(unsigned long long) == 8, "the sizes the counts below stand for");
+	DEV_ALLOC(c->d_y, nring, true); DEV_ALLOC(c->d_pf, nring, true);
+	DEV_ALLOC(c->d_cand, nring / 64, true); DEV_ALLOC(c->d_flag, nring / 64, true);      // a bit per sample (cap is a power of two >= 65536)
+	DEV_ALLOC(c->d_segend, (size_t)count * c->nseg_cap, true);
+	DEV_ALLOC(c->d_qpow, 64);
+	DEV_ALLOC(c->d_tcarry[0], count, true); DEV_ALLOC(c->d_tcarry[1], count, true);
+	DEV_ALLOC(c->d_segpub, (size_t)count * c->nseg_cap * 4, true); DEV_ALLOC(c->d_synctmo, 1, true);
 	// The fused fix-up makes a workgroup wait for the workgroup of the previous segment (one-step look-back, kernels.h).  The wait is
 	// short while the workgroups of a launch are dispatched in order and stay resident - one process per GPU, the deployment this
 	// library is built for.  On a GPU time-sliced between PROCESSES the driver saves and restores waves in no particular order and
@@ -1231,8 +1195,8 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	// VDL2HIP_NO_FUSE=1 selects the separate fix-up kernel k_fixup instead (no inter-workgroup wait at all, bit-identical results,
 	// ~3 % slower): worth setting where the GPU is permanently shared, so that no time is spent waiting.
 	c->fuse_k2 = getenv("VDL2HIP_NO_FUSE") == nullptr;
-	DEV_ALLOC(c->d_ws, count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt, 2 * (size_t)count * kNumCounters * 8); c->d_wcnt = c->d_cnt + (size_t)count * kNumCounters;
-	DEV_ALLOC(c->d_acnt, (size_t)count * kNumAvlcCounters * 8);
+	DEV_ALLOC(c->d_ws, count); DEV_ALLOC(c->d_cnt, 2 * (size_t)count * kNumCounters, true); c->d_wcnt = c->d_cnt + (size_t)count * kNumCounters;
+	DEV_ALLOC(c->d_acnt, (size_t)count * kNumAvlcCounters, true);
 	// a decodable burst occupies >= 22 symbols = 220 decimated samples (header + 3 data + 2 FEC octets)
 	c->cap_bursts_chan = (uint32_t)(dmax / 220 + 4);
 	uint64_t cap_b = (uint64_t)count * c->cap_bursts_chan;
@@ -1242,12 +1206,12 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	c->cap_log = 8192; c->cap_comb = c->cap_log + kNfTail; c->cap_hist = (uint32_t)(dmax / 3000 + 8);
 	cap_p += 2048 * kResPool;
 	c->ctl_template = OutCtl{ 0, 0, 0, 0, (uint32_t)cap_b, (uint32_t)cap_f, (uint32_t)cap_p, c->cap_log, 0, 0, {0, 0} };
-	DEV_ALLOC(c->d_nf, count * sizeof(NfState));
-	DEV_ALLOC(c->d_scfirst, (size_t)count * (c->cap_comb + 1) * 8); DEV_ALLOC(c->d_sccum, (size_t)count * (c->cap_comb + 1) * 8);
+	DEV_ALLOC(c->d_nf, count);
+	DEV_ALLOC(c->d_scfirst, (size_t)count * (c->cap_comb + 1)); DEV_ALLOC(c->d_sccum, (size_t)count * (c->cap_comb + 1));
 	// noise-floor history: a frame looks up the value at its burst's sync, at most kSlots feeds + one burst ago
 	c->nf_ring = 64; while(c->nf_ring < (kSlots + 2) * c->cap_hist) c->nf_ring <<= 1;
-	DEV_ALLOC(c->d_nfring, (size_t)count * c->nf_ring * 4);
-	DEV_ALLOC(c->d_lpbuf, (size_t)count * c->cap_hist * 4); DEV_ALLOC(c->d_nffeed, count * sizeof(NfFeed));
+	DEV_ALLOC(c->d_nfring, (size_t)count * c->nf_ring, true);
+	DEV_ALLOC(c->d_lpbuf, (size_t)count * c->cap_hist, true); DEV_ALLOC(c->d_nffeed, count, true);
 	{
 		// segments per feed: enough wavefronts to cover the walk's latency, not more than the chip holds at once
 		const char *e = getenv("VDL2HIP_SEG_MIN");
@@ -1257,22 +1221,17 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 		e = getenv("VDL2HIP_SEG_MAX");
 		if(e) smax = std::min<int64_t>(smax, atoll(e));
 		c->seg_max = (int)std::max<int64_t>(1, smax);
-		if(c->seg_max >= 2) for(auto &sp_ : c->d_spec) DEV_ALLOC(sp_, (size_t)count * 3 * (c->seg_max - 1) * sizeof(SpecOut));
-		DEV_ALLOC(c->d_segstats, (size_t)count * 2 * 4);
-		DEV_CHK(hipMemset(c->d_segstats, 0, (size_t)count * 2 * 4));
+		if(c->seg_max >= 2) for(auto &sp_ : c->d_spec) DEV_ALLOC(sp_, (size_t)count * 3 * (c->seg_max - 1));
+		DEV_ALLOC(c->d_segstats, (size_t)count * 2, true);
 	}
 	for(auto &sl : c->slot) {
-		DEV_ALLOC(sl.d_bursts, cap_b * sizeof(Burst)); DEV_ALLOC(sl.d_nbchan, count * 4);
-		DEV_ALLOC(sl.d_frames, cap_f * sizeof(OutFrame)); DEV_ALLOC(sl.d_pool, cap_p); DEV_ALLOC(sl.d_mail, sizeof(OutMail));
-		sl.d_ctl = &sl.d_mail->ctl;
-		DEV_CHK(hipMemset(sl.d_mail, 0, sizeof(OutMail)));
+		DEV_ALLOC(sl.d_bursts, cap_b); DEV_ALLOC(sl.d_nbchan, count, true);
+		DEV_ALLOC(sl.d_frames, cap_f); DEV_ALLOC(sl.d_pool, cap_p); DEV_ALLOC(sl.d_mail, 1, true);
+		sl.d_ctl = &sl.d_mail.get()->ctl;
 		DEV_CHK(hipMemcpy(sl.d_ctl, &c->ctl_template, sizeof(OutCtl), hipMemcpyHostToDevice));
-		DEV_ALLOC(sl.d_frames_out, cap_f * sizeof(OutFrame)); DEV_ALLOC(sl.d_pool_out, cap_p);
-		DEV_ALLOC(sl.d_log, (size_t)count * c->cap_log * sizeof(EvalChunk)); DEV_ALLOC(sl.d_nlog, count * 4);
-		DEV_CHK(hipMemset(sl.d_nlog, 0, count * 4));
-		DEV_CHK(hipHostMalloc((void **)&sl.h_mail, sizeof(OutMail), hipHostMallocDefault));
-		memset(sl.h_mail, 0, sizeof(OutMail));
-		DEV_CHK(hipMemset(sl.d_nbchan, 0, count * 4));
+		DEV_ALLOC(sl.d_frames_out, cap_f); DEV_ALLOC(sl.d_pool_out, cap_p);
+		DEV_ALLOC(sl.d_log, (size_t)count * c->cap_log); DEV_ALLOC(sl.d_nlog, count, true);
+		DEV_CHK(sl.h_mail.alloc(sizeof(OutMail), true));
 	}
 
 	if(const char *e = getenv("VDL2HIP_REFEREE")) c->referee = atoi(e) != 0;
@@ -1287,39 +1246,36 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	if(c->referee) {
 		c->ref_T = std::max(1, c->ref_retry_mul) * c->ref_warm + (int64_t)(kHistory + 256) * c->os + 4096;      // run-up (of a retry: ref_retry_mul times the configured one) + the longest burst (its symbols are sliced when its last one has arrived)
 		c->ref_cap = 1; while(c->ref_cap < (uint64_t)(kSlots + 2) * (uint64_t)c->ref_T) c->ref_cap <<= 1;
-		DEV_ALLOC(c->d_refhist, c->ref_cap * sb);
-		for(int k = 0; k < kSlots; k++) { DEV_ALLOC(c->d_ref[k], sizeof(RefChan)); DEV_CHK(hipMemset(c->d_ref[k], 0, sizeof(RefChan))); }
-		DEV_ALLOC(c->d_refdone, (size_t)count * kRefCache * 8); DEV_ALLOC(c->d_refdonen, (size_t)count * 4); DEV_ALLOC(c->d_refstats, 64); DEV_ALLOC(c->d_mix, count);
-		DEV_CHK(hipMemset(c->d_refdone, 0, (size_t)count * kRefCache * 8)); DEV_CHK(hipMemset(c->d_refdonen, 0, (size_t)count * 4)); DEV_CHK(hipMemset(c->d_refstats, 0, 64));
+		DEV_ALLOC(c->d_refhist, c->ref_cap * sb);      // (bytes)
+		for(auto &r : c->d_ref) DEV_ALLOC(r, 1, true);
+		DEV_ALLOC(c->d_refdone, (size_t)count * kRefCache, true); DEV_ALLOC(c->d_refdonen, count, true); DEV_ALLOC(c->d_refstats, 16, true); DEV_ALLOC(c->d_mix, count);
 		std::vector<uint8_t> mix(count);
 		for(uint32_t i = 0; i < count; i++) mix[i] = cfg->centerfreq != c->freqs[i];       // v->offset_tuning, demod.c:386
 		DEV_CHK(hipMemcpy(c->d_mix, mix.data(), count, hipMemcpyHostToDevice));
-		for(int k = 0; k < 2; k++) { DEV_ALLOC(c->d_ws_snap[k], count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt_snap[k], (size_t)count * kNumCounters * 8); }
-		DEV_ALLOC(c->d_ws_tmp, count * sizeof(WalkState)); DEV_ALLOC(c->d_cnt_tmp, (size_t)count * kNumCounters * 8);
+		for(int k = 0; k < 2; k++) { DEV_ALLOC(c->d_ws_snap[k], count); DEV_ALLOC(c->d_cnt_snap[k], (size_t)count * kNumCounters); }
+		DEV_ALLOC(c->d_ws_tmp, count); DEV_ALLOC(c->d_cnt_tmp, (size_t)count * kNumCounters);
 		// Walk ahead (launch_back): for receivers whose front does not hide the chain walk - scans - check (a feed's results then come a
 		// feed later: with 256 channels, where the front hides the chain anyway, that extra depth cost 10 % and more)
 		c->walk_ahead = (count >= 16 && count <= 64) ? 1 : 0;   // (8 channels: the walk itself is longer than the front, the second walks' extra launches cost more than they save: 1.22 against 1.11 ms)
 		c->sq_alloc = defer_scans_for((int64_t)dmax, (int)count);
 		for(auto &sl : c->slot) {
-			DEV_ALLOC(sl.d_rq, (size_t)c->rq_cap * sizeof(RefReq)); DEV_ALLOC(sl.d_rqn, 32); DEV_ALLOC(sl.d_retry, 3 * (size_t)kRetryScans * sizeof(ScanReq)); DEV_ALLOC(sl.d_rqflag, (size_t)count * 4);
-			DEV_ALLOC(sl.d_dq, (size_t)(c->sq_alloc / 2) * 4); DEV_ALLOC(sl.d_sq, (size_t)c->sq_alloc * sizeof(ScanReq));
-			DEV_ALLOC(sl.d_pq, (size_t)kPreScans * sizeof(ScanReq)); DEV_CHK(hipEventCreateWithFlags(&sl.ev_pre, hipEventDisableTiming));
-			DEV_ALLOC(sl.d_rqbad, (size_t)count * sizeof(RefBad)); DEV_CHK(hipMemset(sl.d_rqbad, 0, (size_t)count * sizeof(RefBad)));
-			DEV_ALLOC(sl.d_rqflag2, (size_t)count * 4); DEV_CHK(hipMemset(sl.d_rqflag2, 0, (size_t)count * 4));
-			DEV_CHK(hipEventCreateWithFlags(&sl.ev_stitch, hipEventDisableTiming)); DEV_CHK(hipEventCreateWithFlags(&sl.ev_chk, hipEventDisableTiming));
-			DEV_CHK(hipMemset(sl.d_rqn, 0, 32)); DEV_CHK(hipMemset(sl.d_rqflag, 0, (size_t)count * 4));
+			DEV_ALLOC(sl.d_rq, c->rq_cap); DEV_ALLOC(sl.d_rqn, 8, true); DEV_ALLOC(sl.d_retry, 3 * (size_t)kRetryScans); DEV_ALLOC(sl.d_rqflag, count, true);
+			DEV_ALLOC(sl.d_dq, c->sq_alloc / 2); DEV_ALLOC(sl.d_sq, c->sq_alloc);
+			DEV_ALLOC(sl.d_pq, kPreScans); DEV_CHK(sl.ev_pre.ensure(hipEventDisableTiming));
+			DEV_ALLOC(sl.d_rqbad, count, true);
+			DEV_ALLOC(sl.d_rqflag2, count, true);
+			DEV_CHK(sl.ev_stitch.ensure(hipEventDisableTiming)); DEV_CHK(sl.ev_chk.ensure(hipEventDisableTiming));
 		}
 	}
 
 	Lut4 lut[256]; build_nco_lut(lut);                            // sincosf_lut_init()
-	Tables *tab = new Tables; build_tables(*tab);                 // demod_sync_init(), rs_init(), header tables
+	auto tab = std::make_unique<Tables>(); build_tables(*tab);    // demod_sync_init(), rs_init(), header tables
 	std::vector<WalkState> ws(count);
 	for(auto &w : ws) { memset(&w, 0, sizeof w); walk_state_init(w); }
 	DEV_CHK(hipMemcpy(c->d_bf, &c->bf, sizeof(BlockForm), hipMemcpyHostToDevice));
 	DEV_CHK(hipMemcpy(c->d_qpow, c->bf.Qpow, 64 * sizeof(float4), hipMemcpyHostToDevice));
 	DEV_CHK(hipMemcpy(c->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
-	DEV_CHK(hipMemcpy(c->d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice));
-	delete tab;
+	DEV_CHK(hipMemcpy(c->d_tab, tab.get(), sizeof(Tables), hipMemcpyHostToDevice));
 	DEV_CHK(hipMemcpy(c->d_dphi, c->dphi.data(), 4 * count, hipMemcpyHostToDevice));
 	DEV_CHK(hipMemcpy(c->d_freq, c->freqs.data(), 4 * count, hipMemcpyHostToDevice));
 	{
@@ -1332,14 +1288,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 		std::vector<NfState> nfs(count);
 		for(auto &n : nfs) { memset(&n, 0, sizeof n); nf_state_init(n); }
 		DEV_CHK(hipMemcpy(c->d_nf, nfs.data(), count * sizeof(NfState), hipMemcpyHostToDevice));
-		DEV_CHK(hipMemset(c->d_nfring, 0, (size_t)count * c->nf_ring * 4)); DEV_CHK(hipMemset(c->d_lpbuf, 0, (size_t)count * c->cap_hist * 4));
-		DEV_CHK(hipMemset(c->d_nffeed, 0, count * sizeof(NfFeed)));
 	}
-	DEV_CHK(hipMemset(c->d_y, 0, nring * sizeof(cf32))); DEV_CHK(hipMemset(c->d_pf, 0, nring * sizeof(cf32)));
-	DEV_CHK(hipMemset(c->d_cand, 0, nring / 8)); DEV_CHK(hipMemset(c->d_flag, 0, nring / 8));
-	DEV_CHK(hipMemset(c->d_tcarry[0], 0, count * sizeof(float4))); DEV_CHK(hipMemset(c->d_tcarry[1], 0, count * sizeof(float4)));
-	DEV_CHK(hipMemset(c->d_cnt, 0, 2 * (size_t)count * kNumCounters * 8)); DEV_CHK(hipMemset(c->d_acnt, 0, (size_t)count * kNumAvlcCounters * 8));
-	DEV_CHK(hipMemset(c->d_segend, 0, (size_t)count * c->nseg_cap * sizeof(float4)));
 	// the generic-oversample build may need more than the default dynamic LDS limit (8192: its static LDS is 6 160 bytes; the builds with parked outputs hold 14 352, under tiles of at most 20 800)
 	const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2) + 8192;
 	if(lds > 65536) { vdl2hip_destroy(c); return VDL2HIP_E_INVAL; }
@@ -1364,8 +1313,8 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	const int k = (int)(c->feed_no % kSlots);
 	{ int r = collect_slot(c, c->slot[k]); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
 	if(!c->d_in[k]) {
-		if(hipMalloc((void **)&c->d_in[k], c->in_cap + 16) != hipSuccess) return VDL2HIP_E_NOMEM;
-		HIPCHK(hipEventCreateWithFlags(&c->ev_copied[k], hipEventDisableTiming));
+		if(c->d_in[k].alloc(c->in_cap + 16) != hipSuccess) return VDL2HIP_E_NOMEM;
+		HIPCHK(c->ev_copied[k].ensure(hipEventDisableTiming));
 	}
 	// (In a stream of blocks this copy costs nothing: 200-step regions run at the same 5.51 ms per 256-channel block host-fed and
 	// HBM-resident.  What a short timed region sees is the FIRST copy, which nothing overlaps: 2.6 ms once.  Holding the copy back so that
@@ -1383,9 +1332,9 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 		size_t off = 0;
 		for(int p = 0; p < kColdParts; p++) {
 			const size_t len = p == kColdParts - 1 ? nbytes - off : piece;
-			if(!c->cold.ev[p]) HIPCHK(hipEventCreateWithFlags(&c->cold.ev[p], hipEventDisableTiming));
-			HIPCHK(hipMemcpyAsync(c->d_in[k] + off, (const uint8_t *)buf + off, len, hipMemcpyHostToDevice, c->stream_copy));
-			HIPCHK(hipEventRecord(c->cold.ev[p], c->stream_copy));
+			HIPCHK(c->cold.ev[p].ensure(hipEventDisableTiming));
+			HIPCHK(hipMemcpyAsync(c->d_in[k] + off, (const uint8_t *)buf + off, len, hipMemcpyHostToDevice, c->streams.copy));
+			HIPCHK(hipEventRecord(c->cold.ev[p], c->streams.copy));
 			off += len;
 			c->cold.samples[p] = off / sample_bytes(c->fmt);
 		}
@@ -1400,12 +1349,12 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 		// below (copy stream + event).  The call also waits for whatever else the process has on the legacy default stream.
 		HIPCHK(hipMemcpy(c->d_in[k], buf, nbytes, hipMemcpyHostToDevice));
 	} else {
-		HIPCHK(hipMemcpyAsync(c->d_in[k], buf, nbytes, hipMemcpyHostToDevice, c->stream_copy));
+		HIPCHK(hipMemcpyAsync(c->d_in[k], buf, nbytes, hipMemcpyHostToDevice, c->streams.copy));
 	}
 	if(!wait_copy) {
-		HIPCHK(hipEventRecord(c->ev_copied[k], c->stream_copy));
+		HIPCHK(hipEventRecord(c->ev_copied[k], c->streams.copy));
 		c->pinned_pending = c->ev_copied[k];
-		if(!parts) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_copied[k], 0));
+		if(!parts) HIPCHK(hipStreamWaitEvent(c->streams.front, c->ev_copied[k], 0));
 	}
 	int r = feed_block(c, c->d_in[k], nbytes, parts);
 	if(r == VDL2HIP_E_DEVICE) c->failed = true;          // part of the block's work may be queued, part not: the context is out of step with itself
@@ -1626,318 +1575,13 @@ int vdl2hip_get_stats_sized(vdl2hip_ctx *c, vdl2hip_stats *out, size_t size) {
 }
 int vdl2hip_get_stats(vdl2hip_ctx *c, vdl2hip_stats *out) { return vdl2hip_get_stats_sized(c, out, sizeof(vdl2hip_stats)); }
 
-void *vdl2hip_stream(vdl2hip_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *vdl2hip_stream(vdl2hip_ctx *c) { return c ? (void *)c->streams.front : nullptr; }
 
 int vdl2hip_set_drain_lag(vdl2hip_ctx *c, int lag) {
 	if(!c || lag < 0 || lag > kSlots - 1) return VDL2HIP_E_INVAL;
 	c->drain_lag = lag;
 	return VDL2HIP_OK;
 }
-
-// test hook (not declared in vdl2hip.h; tests/test_gpu_parity.py): "no_fuse" = run the segment-start fix-up as the separate kernel
-// k_fixup instead of inside K1 (bit-identical results); "force_timeout" = make every look-back hand-off fail (producers publish
-// under a wrong epoch), so that the fall-back path is taken by every workgroup and can be tested
-int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
-	if(!c || !name) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	if(strcmp(name, "no_fuse") == 0) { c->fuse_k2 = value == 0; return VDL2HIP_OK; }
-	if(strcmp(name, "force_timeout") == 0) { c->debug_force_timeout = value != 0; return VDL2HIP_OK; }
-	if(strcmp(name, "force_mismatch") == 0) { c->debug_force_mismatch = value != 0; return VDL2HIP_OK; }   // every channel walked again with the next feed's walk already done is taken to have ended differently: the next feed is redone for it
-	if(strcmp(name, "walk_ahead_below") == 0) { c->walk_ahead_below = (double)value; c->walk_ahead_auto = true; return VDL2HIP_OK; }   // (tests: feeds of fewer channel-samples than this let the next walk go ahead)
-	if(strcmp(name, "walk_ahead") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->walk_ahead = (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // 1: the next feed's walk goes ahead of a feed's check, for every feed; 0: a feed's walk waits for the check of the feed before (round 5's schedule)
-	if(strcmp(name, "exact_tier") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->debug_exact_tier = (int)value; return VDL2HIP_OK; }   // 1 (default): the exact sync tier's dense form, k_sync_dense; 0: the word-at-a-time form it replaced, k_sync_exact4 (bit-identical results)
-	if(strcmp(name, "screen_all") == 0) { c->debug_screen_all = value != 0; return VDL2HIP_OK; }   // the screening tier flags every sample (flags are only ever conservative: same frames), so that the exact tier runs at its worst-case density
-	if(strcmp(name, "force_again") == 0) { c->debug_force_again = value != 0; return VDL2HIP_OK; }   // every channel of every long feed is stitched a second time (the referee's walk-again path)
-	if(strcmp(name, "referee") == 0) { if(value && !c->d_refhist) return VDL2HIP_E_INVAL; c->referee = value != 0; return VDL2HIP_OK; }   // (on only where it was on at create: the history ring)
-	if(strcmp(name, "ref_warm") == 0) { if(value < 0 || value > c->ref_T - 4096) return VDL2HIP_E_INVAL; c->ref_warm = value; return VDL2HIP_OK; }
-	return VDL2HIP_E_INVAL;
-}
-
-// test hook (not declared in vdl2hip.h): the referee's scan on [n_lo, n_hi] of one channel, with the raw input the most recent feed could
-// reach - the decimated stream there is then the reference's own, to be read back with vdl2hip_read_decimated().  1: done, 0: refused
-int vdl2hip_debug_exact_window_many(vdl2hip_ctx *c, uint32_t chan, int64_t n_lo, int64_t n_hi, uint32_t count, int64_t stride, float *ms) {
-	if(!c || !c->d_refhist || chan >= (uint32_t)c->C || c->feed_no == 0 || count == 0 || count > 65536) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	int *d_out = nullptr; std::vector<int> h(count, 0);
-	if(hipMalloc((void **)&d_out, 4 * (size_t)count) != hipSuccess) return VDL2HIP_E_NOMEM;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-	if(ok) hipExtLaunchKernelGGL(k_ref_probe, dim3(count), dim3(64), 0, c->stream, e0, e1, 0, c->d_ref[(c->feed_no - 1) % kSlots], (int)chan, c->C, n_lo, n_hi, stride, d_out);
-	ok = ok && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(h.data(), d_out, 4 * (size_t)count, hipMemcpyDeviceToHost) == hipSuccess;
-	float t = 0.f;
-	if(ok && ms) { (void)hipEventElapsedTime(&t, e0, e1); *ms = t; }
-	if(e0) (void)hipEventDestroy(e0);
-	if(e1) (void)hipEventDestroy(e1);
-	(void)hipFree(d_out);
-	if(!ok) return VDL2HIP_E_DEVICE;
-	int n = 0; for(int v : h) n += v;
-	return n;            // stretches done (of `count`)
-}
-// test hook (not declared in vdl2hip.h): the same through k_ref_scan_multi - `count` stretches (chan[i], lo[i], hi[i]) side by side;
-// returns the number of scans run, *ms = the kernels' time.  with_retry: as the product's launches do it - the scans that have not met
-// their witness are listed and run again from ref_retry_mul times further back (without: they are counted as unmet and published)
-int vdl2hip_debug_scan_multi2(vdl2hip_ctx *c, const int32_t *chan, const int64_t *lo, const int64_t *hi, uint32_t count, int with_retry, float *ms) {
-	if(!c || !c->d_refhist || c->feed_no == 0 || count == 0 || count > 65536 || !chan || !lo || !hi) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	std::vector<ScanReq> h(count);
-	for(uint32_t i = 0; i < count; i++) { if(chan[i] < 0 || chan[i] >= c->C) return VDL2HIP_E_INVAL; h[i] = ScanReq{ chan[i], REF_CANDIDATE, lo[i], hi[i] }; }
-	ScanReq *d_sq = nullptr, *d_rt = nullptr; uint32_t *d_n = nullptr;
-	if(hipMalloc((void **)&d_sq, sizeof(ScanReq) * (size_t)count) != hipSuccess || hipMalloc((void **)&d_n, 8) != hipSuccess || hipMalloc((void **)&d_rt, sizeof(ScanReq) * (size_t)kRetryScans) != hipSuccess) {
-		if(d_sq) (void)hipFree(d_sq);
-		if(d_n) (void)hipFree(d_n);
-		return VDL2HIP_E_NOMEM;
-	}
-	uint32_t before[8] = {0}, after[8] = {0};
-	const uint32_t nn[2] = { count, 0u };
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess
-		&& hipMemcpy(d_sq, h.data(), sizeof(ScanReq) * (size_t)count, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_n, nn, 8, hipMemcpyHostToDevice) == hipSuccess
-		&& hipMemcpy(before, c->d_refstats, sizeof before, hipMemcpyDeviceToHost) == hipSuccess;
-	RefChan *ref = c->d_ref[(c->feed_no - 1) % kSlots];
-	if(ok) launch_scans(c, c->stream, ref, 0xfffeu, d_sq, nullptr, d_n, count, c->k_total, with_retry ? d_rt : nullptr, d_n + 1, e0, e1);
-	ok = ok && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(after, c->d_refstats, sizeof after, hipMemcpyDeviceToHost) == hipSuccess;
-	float t = 0.f;
-	if(ok && ms) { (void)hipEventElapsedTime(&t, e0, e1); *ms = t; }
-	if(e0) (void)hipEventDestroy(e0);
-	if(e1) (void)hipEventDestroy(e1);
-	(void)hipFree(d_sq); (void)hipFree(d_n); (void)hipFree(d_rt);
-	return ok ? (int)(after[0] - before[0]) : VDL2HIP_E_DEVICE;
-}
-int vdl2hip_debug_exact_window(vdl2hip_ctx *c, uint32_t chan, int64_t n_lo, int64_t n_hi) { return vdl2hip_debug_exact_window_many(c, chan, n_lo, n_hi, 1, 0, nullptr); }
-
-// test hook (not declared in vdl2hip.h): what the DPP controls the channeliser's scan relies on do on this device
-int vdl2hip_debug_u8_levels(float out[512]) {        // out[0..255]: the channeliser's division-free (i - 127.5) / 127.5, out[256..511]: the division (tests)
-	float *d = nullptr;
-	if(hipMalloc((void **)&d, 512 * sizeof(float)) != hipSuccess) return VDL2HIP_E_NOMEM;
-	hipLaunchKernelGGL(k_u8_level_probe, dim3(1), dim3(256), 0, 0, d);
-	const bool ok = hipMemcpy(out, d, 512 * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	return ok ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
-}
-
-int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
-	float *d_in = nullptr, *d_out = nullptr;
-	if(hipMalloc((void **)&d_in, 64 * 4) != hipSuccess || hipMalloc((void **)&d_out, 256 * 4) != hipSuccess) return VDL2HIP_E_NOMEM;
-	int rc = VDL2HIP_OK;
-	if(hipMemcpy(d_in, in, 64 * 4, hipMemcpyHostToDevice) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	if(rc == VDL2HIP_OK) {
-		hipLaunchKernelGGL(k_dpp_probe, dim3(1), dim3(64), 0, 0, (const float *)d_in, d_out);
-		if(hipMemcpy(out, d_out, 256 * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	(void)hipFree(d_in); (void)hipFree(d_out);
-	return rc;
-}
-
-// test hook (not declared in vdl2hip.h; tests/test_gpu_core_probe.py): the device builds of vdl2_core.h's element-wise pieces on n elements.
-// kind 0 phase_of, 1 phase_fast, 2 mag_of: in (re, im), out 1 float; 3 sync_metric: in 16 phases, out (pherr, slope); 4 sync_metric_screen:
-// in 16 phases in turns, out (16 taps, kScreenEarly taps); 5 slice_symbol: in (phi, prev_phi, vdphi), out int32 (index, neg);
-// 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold); 8 header_to_geometry:
-// in a 25-bit header word (uint32), out uint32 (status, syndrome, tl_bits, want_bits).  Needs no receiver
-int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
-	if(kind < 0 || kind >= PROBE_KINDS || !in || !out || n == 0 || n > (size_t)1 << 26) return VDL2HIP_E_INVAL;
-	const size_t nin = n * (size_t)core_probe_in_words(kind) * 4, nout = n * (size_t)core_probe_out_words(kind) * 4;
-	float *d_in = nullptr, *d_out = nullptr; Tables *d_tab = nullptr;
-	int rc = VDL2HIP_OK;
-	if(hipMalloc((void **)&d_in, nin) != hipSuccess || hipMalloc((void **)&d_out, nout) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess) rc = VDL2HIP_E_NOMEM;
-	if(rc == VDL2HIP_OK) {
-		Tables *tab = new Tables; build_tables(*tab);
-		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice) != hipSuccess
-		   || hipMemset(d_out, 0, nout) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-		delete tab;
-	}
-	if(rc == VDL2HIP_OK) {
-		hipLaunchKernelGGL(k_core_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, (const float *)d_in, (uint32_t)n, d_out, (const Tables *)d_tab);
-		if(hipGetLastError() != hipSuccess || hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(d_in) (void)hipFree(d_in);
-	if(d_out) (void)hipFree(d_out);
-	if(d_tab) (void)hipFree(d_tab);
-	return rc;
-}
-
-// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): the device build of the burst decoder's pieces on n elements, `grid`
-// workgroups of kBurstWaves wavefronts (kernels.h: k_burst_probe_wave, k_burst_probe_rs, k_burst_probe).  Needs no receiver.
-//   kind 0 (wave primitives)  in uint32 [n][64], out uint32 [n][68]: first flag, flag count, 64 scanned values, their total, the minimum
-//   kind 1 (rs_decode_row)    in uint8 [n][256]: 255 octets and npar (0, 2, 4 or 6); out uint8 [n][256]: the row, then int32 [n]: the return value
-//   kind 2 (decode_burst)     in Burst [n], element i on ring y[i][ring_len] (cf32, ring_len a power of two), freq [nchan], referee off.  The output
-//                             control block starts as a feed's does (the counters behind the wavefronts' own shares) with capacities cap_frames and
-//                             cap_pool; behind the records and behind the pool lie guard_frames records and guard_pool octets, everything filled with
-//                             0xA5 beforehand.  Returned: frames [cap_frames + guard_frames], pool [cap_pool + guard_pool], ctl (an OutCtl), cnt
-//                             [nchan][20]; `out` is not used
-int vdl2hip_debug_burst_probe(int kind, const void *in, size_t n, unsigned grid, void *out, const uint32_t *freq, uint32_t nchan, const float *y, uint32_t ring_len,
-		uint32_t cap_frames, uint32_t cap_pool, uint32_t guard_frames, uint32_t guard_pool, void *frames, uint8_t *pool, void *ctl, unsigned long long *cnt) {
-	if(kind < 0 || kind >= BPROBE_KINDS || !in || n == 0 || n > (size_t)1 << 20 || grid == 0 || grid > 1024) return VDL2HIP_E_INVAL;
-	const uint32_t nwaves = grid * (uint32_t)kBurstWaves;
-	size_t nin = 0, nout = 0;
-	if(kind == BPROBE_WAVE) { nin = n * 64 * 4; nout = n * (size_t)kBProbeWaveOut * 4; }
-	else if(kind == BPROBE_RS) {
-		nin = n * (size_t)kBProbeRsStride; nout = n * (size_t)kBProbeRsStride + n * 4;
-		for(size_t i = 0; i < n; i++) { const uint8_t np = ((const uint8_t *)in)[i * kBProbeRsStride + kRsN]; if(np > kRsPar || (np & 1)) return VDL2HIP_E_INVAL; }
-	} else {
-		nin = n * sizeof(Burst);
-		if(!freq || nchan == 0 || !y || ring_len < 64 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || !frames || !pool || !ctl || !cnt) return VDL2HIP_E_INVAL;
-		if(cap_frames > 1u << 20 || cap_pool > 1u << 26 || guard_frames > 1u << 16 || guard_pool > 1u << 20 || n * (size_t)ring_len > (size_t)1 << 26) return VDL2HIP_E_INVAL;
-		for(size_t i = 0; i < n; i++) {
-			const Burst &b = ((const Burst *)in)[i];
-			if(b.chan < 0 || (uint32_t)b.chan >= nchan || b.nsym < 1 || b.nsym > kMaxSyms || b.tl_bits == 0 || b.tl_bits > kMaxTl || b.t_first < 0 || b.prev_n < -2) return VDL2HIP_E_INVAL;
-		}
-	}
-	if(kind != BPROBE_BURST && !out) return VDL2HIP_E_INVAL;
-	const size_t nfr = (size_t)cap_frames + guard_frames, npool = (size_t)cap_pool + guard_pool;
-	void *d_in = nullptr, *d_out = nullptr; Tables *d_tab = nullptr; OutCtl *d_ctl = nullptr;
-	uint32_t *d_freq = nullptr; cf32 *d_y = nullptr; unsigned long long *d_cnt = nullptr; OutFrame *d_frames = nullptr; uint8_t *d_pool = nullptr;
-	int rc = VDL2HIP_OK;
-	if(hipMalloc(&d_in, nin) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess || hipMalloc((void **)&d_ctl, sizeof(OutCtl)) != hipSuccess) rc = VDL2HIP_E_NOMEM;
-	if(rc == VDL2HIP_OK && nout && hipMalloc(&d_out, nout) != hipSuccess) rc = VDL2HIP_E_NOMEM;
-	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
-		if(hipMalloc((void **)&d_freq, (size_t)nchan * 4) != hipSuccess || hipMalloc((void **)&d_y, n * (size_t)ring_len * sizeof(cf32)) != hipSuccess
-		   || hipMalloc((void **)&d_cnt, (size_t)nchan * kNumCounters * 8) != hipSuccess || hipMalloc((void **)&d_frames, (nfr + 1) * sizeof(OutFrame)) != hipSuccess
-		   || hipMalloc((void **)&d_pool, npool + 4) != hipSuccess) rc = VDL2HIP_E_NOMEM;
-	}
-	OutCtl h_ctl; memset(&h_ctl, 0, sizeof h_ctl);
-	h_ctl.cap_frames = cap_frames; h_ctl.cap_pool = cap_pool;
-	h_ctl.nframes = burst_reserve_initial_frames(nwaves); h_ctl.pool_used = burst_reserve_initial_pool(nwaves);     // (kernels.h: reset_out_ctl)
-	if(rc == VDL2HIP_OK) {
-		Tables *tab = new Tables; build_tables(*tab);
-		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice) != hipSuccess
-		   || hipMemcpy(d_ctl, &h_ctl, sizeof h_ctl, hipMemcpyHostToDevice) != hipSuccess || (nout && hipMemset(d_out, 0, nout) != hipSuccess)) rc = VDL2HIP_E_DEVICE;
-		delete tab;
-	}
-	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
-		if(hipMemcpy(d_freq, freq, (size_t)nchan * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_y, y, n * (size_t)ring_len * sizeof(cf32), hipMemcpyHostToDevice) != hipSuccess
-		   || hipMemset(d_cnt, 0, (size_t)nchan * kNumCounters * 8) != hipSuccess || hipMemset(d_frames, 0xA5, (nfr + 1) * sizeof(OutFrame)) != hipSuccess
-		   || hipMemset(d_pool, 0xA5, npool + 4) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(rc == VDL2HIP_OK) {
-		BurstProbeArgs a{ (uint32_t)n, d_tab, d_ctl, (const uint32_t *)d_in, (uint32_t *)d_out, (const uint8_t *)d_in, (uint8_t *)d_out,
-		                  (int32_t *)((uint8_t *)d_out + n * (size_t)kBProbeRsStride), (const Burst *)d_in, d_freq, d_y, ring_len, ring_len - 1, d_cnt, d_frames, d_pool };
-		const unsigned lds = (unsigned)(sizeof(BurstShared) * kBurstWaves);
-		if(kind == BPROBE_WAVE) hipLaunchKernelGGL(k_burst_probe_wave, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
-		else if(kind == BPROBE_RS) hipLaunchKernelGGL(k_burst_probe_rs, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
-		else hipLaunchKernelGGL(k_burst_probe, dim3(grid), dim3(64 * kBurstWaves), lds, 0, a);
-		if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(rc == VDL2HIP_OK && nout && hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	if(rc == VDL2HIP_OK && kind == BPROBE_BURST) {
-		if(hipMemcpy(frames, d_frames, nfr * sizeof(OutFrame), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(pool, d_pool, npool, hipMemcpyDeviceToHost) != hipSuccess
-		   || hipMemcpy(ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cnt, d_cnt, (size_t)nchan * kNumCounters * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(d_in) (void)hipFree(d_in);
-	if(d_out) (void)hipFree(d_out);
-	if(d_tab) (void)hipFree(d_tab);
-	if(d_ctl) (void)hipFree(d_ctl);
-	if(d_freq) (void)hipFree(d_freq);
-	if(d_y) (void)hipFree(d_y);
-	if(d_cnt) (void)hipFree(d_cnt);
-	if(d_frames) (void)hipFree(d_frames);
-	if(d_pool) (void)hipFree(d_pool);
-	return rc;
-}
-
-// test hook (not declared in vdl2hip.h; tests/test_gpu_burst_probe.py): k_frame_finish itself, `grid` workgroups, on the caller's record list
-// (nrec records, tombstones - chan < 0 - among them), octet pool, control block (an OutCtl: nframes, cap_frames; nvalid and pool_out_used zero)
-// and noise-floor rings ring[nchan][ring_len] (ring_len a power of two).  Returned: frames_out [nrec], pool_out [pool_out_cap] (both 0xA5 where
-// nothing was delivered), the whole OutMail (mail_out: sizeof(OutMail) octets, see vdl2hip_debug_sizeof_outmail) and the AVLC counters acnt [nchan][10].
-// Needs no receiver
-int vdl2hip_debug_sizeof_outmail(void) { return (int)sizeof(OutMail); }
-int vdl2hip_debug_frame_finish(unsigned grid, const void *frames_in, uint32_t nrec, const uint8_t *pool, uint32_t pool_len, const void *ctl_in, const float *ring, uint32_t ring_len,
-		uint32_t nchan, void *frames_out, uint8_t *pool_out, uint32_t pool_out_cap, void *mail_out, unsigned long long *acnt) {
-	if(grid == 0 || grid > 1024 || !ctl_in || !ring || ring_len == 0 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || nchan == 0 || nchan > 1024 || !frames_out || !pool_out || !mail_out || !acnt
-	   || nrec > 1u << 20 || pool_len > 1u << 28 || (nrec && !frames_in) || (pool_len && !pool)) return VDL2HIP_E_INVAL;
-	OutCtl h_ctl; memcpy(&h_ctl, ctl_in, sizeof h_ctl);
-	const uint32_t nf = h_ctl.nframes < h_ctl.cap_frames ? h_ctl.nframes : h_ctl.cap_frames;
-	if(nf > nrec || h_ctl.nvalid != 0 || h_ctl.pool_out_used != 0) return VDL2HIP_E_INVAL;
-	size_t need = 0;
-	for(uint32_t i = 0; i < nf; i++) {
-		const OutFrame &f = ((const OutFrame *)frames_in)[i];
-		if(f.chan < 0) continue;
-		if((uint32_t)f.chan >= nchan || f.len > 1u << 20 || (size_t)f.pool_off + f.len > pool_len) return VDL2HIP_E_INVAL;
-		need += ((size_t)f.len + 3) & ~(size_t)3;
-	}
-	if(need > pool_out_cap) return VDL2HIP_E_INVAL;
-	OutFrame *d_frames = nullptr, *d_fout = nullptr; uint8_t *d_pool = nullptr, *d_pout = nullptr; OutMail *d_mail = nullptr; Tables *d_tab = nullptr; float *d_ring = nullptr; unsigned long long *d_acnt = nullptr;
-	int rc = VDL2HIP_OK;
-	const size_t rec_bytes = ((size_t)nrec + 1) * sizeof(OutFrame), ring_bytes = (size_t)nchan * ring_len * 4;
-	if(hipMalloc((void **)&d_frames, rec_bytes) != hipSuccess || hipMalloc((void **)&d_fout, rec_bytes) != hipSuccess || hipMalloc((void **)&d_pool, (size_t)pool_len + 4) != hipSuccess
-	   || hipMalloc((void **)&d_pout, (size_t)pool_out_cap + 4) != hipSuccess || hipMalloc((void **)&d_mail, sizeof(OutMail)) != hipSuccess || hipMalloc((void **)&d_tab, sizeof(Tables)) != hipSuccess
-	   || hipMalloc((void **)&d_ring, ring_bytes) != hipSuccess || hipMalloc((void **)&d_acnt, (size_t)nchan * kNumAvlcCounters * 8) != hipSuccess) rc = VDL2HIP_E_NOMEM;
-	if(rc == VDL2HIP_OK) {
-		Tables *tab = new Tables; build_tables(*tab);
-		OutMail *mail = new OutMail; memset(mail, 0xA5, sizeof *mail); mail->ctl = h_ctl;
-		if(hipMemcpy(d_tab, tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_mail, mail, sizeof(OutMail), hipMemcpyHostToDevice) != hipSuccess
-		   || (nrec && hipMemcpy(d_frames, frames_in, (size_t)nrec * sizeof(OutFrame), hipMemcpyHostToDevice) != hipSuccess) || (pool_len && hipMemcpy(d_pool, pool, pool_len, hipMemcpyHostToDevice) != hipSuccess)
-		   || hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_acnt, 0, (size_t)nchan * kNumAvlcCounters * 8) != hipSuccess
-		   || hipMemset(d_fout, 0xA5, rec_bytes) != hipSuccess || hipMemset(d_pout, 0xA5, (size_t)pool_out_cap + 4) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-		delete tab; delete mail;
-	}
-	if(rc == VDL2HIP_OK) {
-		hipLaunchKernelGGL(k_frame_finish, dim3(grid), dim3(64 * kFrameWaves), 0, 0, d_frames, (const uint8_t *)d_pool, d_mail, (const Tables *)d_tab, d_acnt, (const float *)d_ring, ring_len - 1, d_fout, d_pout);
-		if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(rc == VDL2HIP_OK) {
-		if((nrec && hipMemcpy(frames_out, d_fout, (size_t)nrec * sizeof(OutFrame), hipMemcpyDeviceToHost) != hipSuccess) || (pool_out_cap && hipMemcpy(pool_out, d_pout, pool_out_cap, hipMemcpyDeviceToHost) != hipSuccess)
-		   || hipMemcpy(mail_out, d_mail, sizeof(OutMail), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(acnt, d_acnt, (size_t)nchan * kNumAvlcCounters * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = VDL2HIP_E_DEVICE;
-	}
-	if(d_frames) (void)hipFree(d_frames);
-	if(d_fout) (void)hipFree(d_fout);
-	if(d_pool) (void)hipFree(d_pool);
-	if(d_pout) (void)hipFree(d_pout);
-	if(d_mail) (void)hipFree(d_mail);
-	if(d_tab) (void)hipFree(d_tab);
-	if(d_ring) (void)hipFree(d_ring);
-	if(d_acnt) (void)hipFree(d_acnt);
-	return rc;
-}
-
-#ifdef VDL2_K1_PROF
-int vdl2hip_debug_k1_prof(unsigned long long out[16], int reset) {
-	static unsigned long long h[64][16];
-	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k1_prof), sizeof h) != hipSuccess) return -3;
-	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
-	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k1_prof), h, sizeof h) != hipSuccess) return -3; }
-	return 0;
-}
-#endif
-
-#ifdef VDL2_K3B_PROF
-int vdl2hip_debug_k3b_prof(unsigned long long out[16], int reset) {
-	static unsigned long long h[64][16];
-	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k3b_prof), sizeof h) != hipSuccess) return -3;
-	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
-	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k3b_prof), h, sizeof h) != hipSuccess) return -3; }
-	return 0;
-}
-#endif
-
-#ifdef VDL2_K5_PROF
-int vdl2hip_debug_k5_prof(unsigned long long out[16], int reset) {
-	static unsigned long long h[64][16];
-	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k5_prof), sizeof h) != hipSuccess) return -3;
-	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
-	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k5_prof), h, sizeof h) != hipSuccess) return -3; }
-	return 0;
-}
-int vdl2hip_debug_nf_prof(unsigned long long out[16], int reset) {
-	static unsigned long long h[64][16];
-	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_nf_prof), sizeof h) != hipSuccess) return -3;
-	for(int k = 0; k < 16; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
-	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_nf_prof), h, sizeof h) != hipSuccess) return -3; }
-	return 0;
-}
-int vdl2hip_debug_k4_prof(unsigned long long out[24], int reset) {
-	static unsigned long long h[64][24];
-	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(vdl2_k4_prof), sizeof h) != hipSuccess) return -3;
-	for(int k = 0; k < 24; k++) { out[k] = 0; for(int s = 0; s < 64; s++) out[k] += h[s][k]; }
-	if(reset) { memset(h, 0, sizeof h); if(hipMemcpyToSymbol(HIP_SYMBOL(vdl2_k4_prof), h, sizeof h) != hipSuccess) return -3; }
-	return 0;
-}
-#endif
 
 int vdl2hip_get_lpf(vdl2hip_ctx *c, float A[3], float B[3]) {
 	if(!c) return VDL2HIP_E_INVAL;
@@ -2002,8 +1646,6 @@ int vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t
 	return (int)d.taps.size();
 }
 
-// test hook (not declared in vdl2hip.h): what the sync kernels left for decimated samples first .. first+count-1 of one channel - the tabulated
-// metric {pherr (its sign: the referee's mark), slope} and the candidate bit, one byte per sample
 // ---- the input monitor (vdl2hip.h, "Input monitor"; kernels: spectrum.h) ----
 int vdl2hip_spectrum_window(uint32_t nfft, uint32_t window, float *w, size_t cap) {
 	SpectrumDesign d;
@@ -2021,23 +1663,22 @@ int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	auto &m = c->mon;
 	monitor_free(c);
-	for(auto &sl : c->slot) sl.mon_timed = 0;                        // (what an earlier monitor's launches took is not this one's)
+	for(auto &sl : c->slot) sl.mon_t.n = 0;                          // (what an earlier monitor's launches took is not this one's)
 	if(cfg->nfft == 0) return VDL2HIP_OK;
-	if(!m.ev_last) HIPCHK(hipEventCreateWithFlags(&m.ev_last, hipEventDisableTiming));
-	if(!m.rd) HIPCHK(hipStreamCreateWithFlags(&m.rd, hipStreamNonBlocking));
-	if(!m.h_acc) HIPCHK(hipHostMalloc((void **)&m.h_acc, ((size_t)kSpecMaxN + kSpecLevels) * sizeof(double), hipHostMallocDefault));
+	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
+	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
+	if(!m.tap.land) HIPCHK(m.tap.land.alloc(((size_t)kSpecMaxN + kSpecLevels) * sizeof(double)));
 	const size_t N = cfg->nfft, W = N + kSpecLevels;
-	struct { void **p; size_t bytes; } al[] = { { (void **)&m.d_w, N * sizeof(float) }, { (void **)&m.d_tw, N * sizeof(float2) },
-		{ (void **)&m.d_carry[0], N * sizeof(float2) }, { (void **)&m.d_carry[1], N * sizeof(float2) },
-		{ (void **)&m.d_rows, (size_t)kSpecMaxRows * W * sizeof(double) }, { (void **)&m.d_acc, W * sizeof(double) } };
-	for(auto &x : al) if(hipMalloc(x.p, x.bytes) != hipSuccess) { (void)hipGetLastError(); monitor_free(c); return VDL2HIP_E_NOMEM; }
-	if(hipMemcpy(m.d_w, d.w.data(), N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess
-	   || hipMemcpy(m.d_tw, d.tw.data(), N * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess
-	   || hipMemset(m.d_acc, 0, W * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { monitor_free(c); return VDL2HIP_E_DEVICE; }
+	auto &b = m.buf;
+	if(b.d_w.alloc(N) != hipSuccess || b.d_tw.alloc(N) != hipSuccess || b.d_carry[0].alloc(N) != hipSuccess || b.d_carry[1].alloc(N) != hipSuccess
+	   || b.d_rows.alloc((size_t)kSpecMaxRows * W) != hipSuccess || b.d_acc.alloc(W) != hipSuccess) { monitor_free(c); return VDL2HIP_E_NOMEM; }
+	if(hipMemcpy(b.d_w, d.w.data(), b.d_w.bytes(), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemcpy(b.d_tw, d.tw.data(), b.d_tw.bytes(), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemset(b.d_acc, 0, b.d_acc.bytes()) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { monitor_free(c); return VDL2HIP_E_DEVICE; }
 	m.nfft = cfg->nfft; m.window = cfg->window; m.stride = cfg->stride ? cfg->stride : 1; m.log2n = d.log2n;
 	m.threads = spec_threads(m.nfft); m.lds = spec_lds_bytes(m.nfft);
 	m.sum_w = d.sum_w; m.enbw = d.enbw_bins;
-	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.queued = false;
+	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
 	m.on = true;
 	return VDL2HIP_OK;
 }
@@ -2046,13 +1687,9 @@ int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
 static int monitor_fetch(vdl2hip_ctx *c, std::vector<double> &acc) {
 	auto &m = c->mon;
 	acc.assign((size_t)m.nfft + kSpecLevels, 0.0);
-	if(!m.queued) return VDL2HIP_OK;                                 // nothing has touched them since they were zeroed
-	// on a stream of the monitor's own, behind the event of its last launch: the read waits for nothing else - not for the feeds in
-	// flight, not for what the process has on the default stream
-	HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
-	HIPCHK(hipMemcpyAsync(m.h_acc, m.d_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost, m.rd));
-	HIPCHK(hipStreamSynchronize(m.rd));
-	memcpy(acc.data(), m.h_acc, acc.size() * sizeof(double));
+	if(!m.tap.queued) return VDL2HIP_OK;                             // nothing has touched them since they were zeroed
+	HIPCHK(m.tap.fetch(m.tap.land, m.buf.d_acc, m.buf.d_acc.bytes()));
+	memcpy(acc.data(), m.tap.land, m.buf.d_acc.bytes());
 	return VDL2HIP_OK;
 }
 static void monitor_power(const vdl2hip_ctx *c, const std::vector<double> &acc, double *power) {
@@ -2084,9 +1721,9 @@ int vdl2hip_spectrum_read(vdl2hip_ctx *c, vdl2hip_spectrum_info *info, double *p
 	if(power) monitor_power(c, acc, power);
 	if(reset) {
 		// (on the front stream: behind the launches that are queued, ahead of the next feed's)
-		HIPCHK(hipMemsetAsync(m.d_acc, 0, acc.size() * sizeof(double), c->stream));
-		HIPCHK(hipEventRecord(m.ev_last, c->stream));
-		m.queued = true; m.segments = 0;
+		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
+		HIPCHK(m.tap.mark(c->streams.front));
+		m.segments = 0;
 	}
 	return (int)N;
 }
@@ -2127,56 +1764,6 @@ int vdl2hip_activity_edges(float *edges, size_t cap) {
 	return kActBuckets - 1;
 }
 
-// test hook (not declared in vdl2hip.h; host only): the scan's word step (act_scan_word) over `count` words of nbits[i] <= 64 busy flags
-// each, from an idle start -> out = { transmissions, longest_bins, open, first bin of the open transmission }
-int vdl2hip_debug_activity_words(const uint64_t *busy, const uint32_t *nbits, uint32_t count, uint32_t hang_bins, uint64_t out[4]) {
-	if(!busy || !nbits || !out || hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
-	ActState st{}; uint64_t tx = 0, longest = 0, base = 0;
-	for(uint32_t i = 0; i < count; i++) {
-		if(nbits[i] == 0 || nbits[i] > 64 || (nbits[i] < 64 && (busy[i] >> nbits[i]) != 0)) return VDL2HIP_E_INVAL;
-		act_scan_word(busy[i], nbits[i], hang_bins, base, st, tx, longest);
-		base += nbits[i];
-	}
-	out[0] = tx; out[1] = longest; out[2] = st.open; out[3] = st.open ? st.first : 0;
-	return VDL2HIP_OK;
-}
-
-// test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
-// one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
-// series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.
-int vdl2hip_debug_activity_power(const float *y, uint32_t cap, int64_t k0, uint32_t D, uint32_t B, uint64_t t0, uint32_t run, float carry_in, float *series, uint32_t S, float *carry_out) {
-	if(!y || !series || !carry_out || !cap || (cap & (cap - 1)) || !S || (S & (S - 1)) || B < kActMinBin || B > kActMaxBin || !D || D > cap || !run || k0 < 0 || ((uintptr_t)y & 15)) return VDL2HIP_E_INVAL;
-	const uint64_t m0 = t0 / B, nb = (t0 + D) / B - m0;
-	if(nb > S) return VDL2HIP_E_TOOBIG;
-	ActArgs a{};
-	a.y = (const float2 *)y; a.series = series; a.carry_in = &carry_in; a.carry_out = carry_out; a.k0 = k0; a.m0 = m0;
-	a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = D; a.B = B; a.nbt = (uint32_t)nb + 1; a.run = run; a.cap = cap; a.mask = cap - 1; a.S = S; a.smask = S - 1;
-	// staging arrays with a guard zone of NaNs behind each: a store or a load beyond the kernel's sizes shows
-	constexpr int G = 64;
-	std::vector<float> p(kActLdsP + G), sb(kActMaxSubs + G), gr(kActLdsG + G);
-	bool bad = false;
-	for(uint32_t bx = 0; bx * run < a.nbt; bx++) {
-		uint32_t j = bx * run;
-		const uint32_t jend = j + run < a.nbt ? j + run : a.nbt;
-		int64_t pos = act_run_start(a, j);
-		bool fresh = true;
-		float acc[kActThreads] = {};
-		while(j < jend) {
-			const ActPlan k = act_plan(a, j, jend, pos, fresh);
-			if(k.pos < 0 || k.pos + k.len > D || k.nseg > (uint32_t)kActMaxSegs || k.nsb > (uint32_t)kActMaxSubs || k.ngr > (uint32_t)kActLdsG || act_pad(k.o + k.len) >= (uint32_t)kActLdsP) return VDL2HIP_E_DEVICE;
-			for(auto *v : { &p, &sb, &gr }) std::fill(v->begin(), v->end(), NAN);
-			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<0>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
-			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<1>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
-			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<2>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
-			for(uint32_t l = 0; l < (uint32_t)kActThreads; l++) act_step<3>(a, k, 0, l, p.data(), sb.data(), gr.data(), acc[l]);
-			for(int i = 0; i < G; i++) bad = bad || !std::isnan(p[kActLdsP + i]) || !std::isnan(sb[kActMaxSubs + i]) || !std::isnan(gr[kActLdsG + i]);
-			if(!k.fin0) { pos += kActChunk; fresh = false; }
-			else { j += k.nseg; pos += k.len; fresh = true; }
-		}
-	}
-	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
-}
-
 int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
 	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_activity_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
 	const uint32_t B = cfg->bin_samples ? cfg->bin_samples : 105u;
@@ -2188,22 +1775,19 @@ int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	auto &m = c->act;
 	activity_free(c);
-	for(auto &sl : c->slot) sl.act_timed = 0;                        // (what an earlier monitor's launches took is not this one's)
-	const size_t C = (size_t)c->C, host_bytes = C * (sizeof(ActChan) + sizeof(ActState));
-	if(!m.ev_last) HIPCHK(hipEventCreateWithFlags(&m.ev_last, hipEventDisableTiming));
-	if(!m.rd) HIPCHK(hipStreamCreateWithFlags(&m.rd, hipStreamNonBlocking));
-	if(!m.h_buf) HIPCHK(hipHostMalloc((void **)&m.h_buf, host_bytes, hipHostMallocDefault));
-	struct { void **p; size_t bytes; } al[] = { { (void **)&m.d_series, C * S * sizeof(float) }, { (void **)&m.d_carry[0], C * sizeof(float) },
-		{ (void **)&m.d_carry[1], C * sizeof(float) }, { (void **)&m.d_edges, kActBuckets * sizeof(float) },
-		{ (void **)&m.d_acc, C * sizeof(ActChan) }, { (void **)&m.d_st, C * sizeof(ActState) } };
-	for(auto &x : al) if(hipMalloc(x.p, x.bytes) != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_NOMEM; }
+	for(auto &sl : c->slot) sl.act_t.n = 0;                          // (what an earlier monitor's launches took is not this one's)
+	const size_t C = (size_t)c->C;
+	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
+	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
+	if(!m.tap.land) HIPCHK(m.tap.land.alloc(C * (sizeof(ActChan) + sizeof(ActState))));
+	auto &b = m.buf;
+	for(hipError_t e : { b.d_series.alloc(C * S, true), b.d_carry[0].alloc(C, true), b.d_carry[1].alloc(C, true), b.d_edges.alloc(kActBuckets), b.d_acc.alloc(C, true), b.d_st.alloc(C, true) })
+		if(e != hipSuccess) { activity_free(c); return e == hipErrorOutOfMemory ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; }
 	float edges[kActBuckets] = {};
 	(void)vdl2hip_activity_edges(edges, kActBuckets);
-	bool ok = hipMemcpy(m.d_edges, edges, sizeof edges, hipMemcpyHostToDevice) == hipSuccess;
-	for(auto &x : al) if(x.p != (void **)&m.d_edges) ok = ok && hipMemset(*x.p, 0, x.bytes) == hipSuccess;
-	if(!ok || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_DEVICE; }
+	if(hipMemcpy(b.d_edges, edges, sizeof edges, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_DEVICE; }
 	m.B = B; m.H = cfg->hang_bins; m.S = S; m.thr_dbfs = cfg->threshold_dbfs; m.thr = (float)std::pow(10.0, (double)cfg->threshold_dbfs / 10.0);
-	m.k_on = c->k_total; m.bins = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.queued = false;
+	m.k_on = c->k_total; m.bins = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
 	m.on = true;
 	return VDL2HIP_OK;
 }
@@ -2212,7 +1796,7 @@ int vdl2hip_activity_disable(vdl2hip_ctx *c) {
 	if(!c) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
 	activity_free(c);
-	for(auto &sl : c->slot) sl.act_timed = 0;
+	for(auto &sl : c->slot) sl.act_t.n = 0;
 	return VDL2HIP_OK;
 }
 
@@ -2224,16 +1808,13 @@ int vdl2hip_activity_read(vdl2hip_ctx *c, vdl2hip_activity_info *info, vdl2hip_a
 	OnDevice dev_guard(c);
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	if(chans) {
-		ActState *st = (ActState *)(m.h_buf + C * sizeof(ActChan));
-		if(m.queued) {
-			// on a stream of the monitor's own, behind the event of its last launch: the read waits for nothing else - not for the feeds
-			// in flight, not for what the process has on the default stream
-			HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
-			HIPCHK(hipMemcpyAsync(m.h_buf, m.d_acc, C * sizeof(ActChan), hipMemcpyDeviceToHost, m.rd));
-			HIPCHK(hipMemcpyAsync(st, m.d_st, C * sizeof(ActState), hipMemcpyDeviceToHost, m.rd));
-			HIPCHK(hipStreamSynchronize(m.rd));
-		} else memset(m.h_buf, 0, C * (sizeof(ActChan) + sizeof(ActState)));      // nothing has touched them since they were zeroed
-		memcpy(chans, m.h_buf, C * sizeof(ActChan));
+		uint8_t *land = m.tap.land;
+		ActState *st = (ActState *)(land + C * sizeof(ActChan));
+		if(m.tap.queued) {
+			HIPCHK(m.tap.fetch(land, m.buf.d_acc, m.buf.d_acc.bytes()));
+			HIPCHK(m.tap.fetch(st, m.buf.d_st, m.buf.d_st.bytes()));
+		} else memset(land, 0, m.tap.land.bytes());      // nothing has touched them since they were zeroed
+		memcpy(chans, land, C * sizeof(ActChan));
 		for(size_t i = 0; i < C; i++) { chans[i].open = st[i].open; chans[i].reserved = 0; if(!chans[i].bins) chans[i].max_power = chans[i].min_power = 0.f; }
 	}
 	if(info) {
@@ -2244,9 +1825,8 @@ int vdl2hip_activity_read(vdl2hip_ctx *c, vdl2hip_activity_info *info, vdl2hip_a
 	}
 	if(reset) {
 		// (on the front stream: behind the launches that are queued, ahead of the next feed's; the transmission under way is kept)
-		HIPCHK(hipMemsetAsync(m.d_acc, 0, C * sizeof(ActChan), c->stream));
-		HIPCHK(hipEventRecord(m.ev_last, c->stream));
-		m.queued = true;
+		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
+		HIPCHK(m.tap.mark(c->streams.front));
 	}
 	return chans ? (int)C : 0;
 }
@@ -2260,12 +1840,10 @@ int vdl2hip_activity_series(vdl2hip_ctx *c, uint32_t chan, int64_t first_bin, fl
 	if(!dst) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
 	if(c->failed) return VDL2HIP_E_DEVICE;
-	const float *base = m.d_series + (size_t)(chan - (uint32_t)c->chan_first) * m.S;
+	const float *base = m.buf.d_series + (size_t)(chan - (uint32_t)c->chan_first) * m.S;
 	const size_t p0 = (size_t)((uint64_t)first_bin & (m.S - 1)), n0 = std::min<size_t>(n, m.S - p0);
-	HIPCHK(hipStreamWaitEvent(m.rd, m.ev_last, 0));
-	HIPCHK(hipMemcpyAsync(dst, base + p0, n0 * sizeof(float), hipMemcpyDeviceToHost, m.rd));
-	if(n0 < n) HIPCHK(hipMemcpyAsync(dst + n0, base, (n - n0) * sizeof(float), hipMemcpyDeviceToHost, m.rd));
-	HIPCHK(hipStreamSynchronize(m.rd));
+	HIPCHK(m.tap.fetch(dst, base + p0, n0 * sizeof(float)));
+	if(n0 < n) HIPCHK(m.tap.fetch(dst + n0, base, (n - n0) * sizeof(float)));
 	return (int)n;
 }
 
@@ -2281,14 +1859,13 @@ int vdl2hip_capture_enable(vdl2hip_ctx *c, const vdl2hip_capture_cfg *cfg) {
 	const uint32_t pool = cfg->pool_samples ? cfg->pool_samples : kCapDefPool;
 	const size_t nb = (size_t)c->C * c->cap_bursts_chan;
 	for(auto &sl : c->slot) {
-		bool ok = hipMalloc((void **)&sl.d_cap_hdr, sizeof(CapHdr) + std::max<size_t>(nb, kCapMailRecs) * sizeof(CapRec)) == hipSuccess
-			&& hipMalloc((void **)&sl.d_cap_plan, nb * sizeof(CapPlan)) == hipSuccess && hipMalloc((void **)&sl.d_cap_tot, (size_t)c->C * 8) == hipSuccess
-			&& hipMalloc((void **)&sl.d_cap_pool, (size_t)pool * sizeof(cf32)) == hipSuccess
-			&& hipHostMalloc((void **)&sl.h_cap, kCapMailBytes, hipHostMallocDefault) == hipSuccess;
-		if(!ok) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_NOMEM; }
-		sl.d_cap_rec = reinterpret_cast<CapRec *>(sl.d_cap_hdr + 1);
-		memset(sl.h_cap, 0, kCapMailBytes);
-		if(hipMemset(sl.d_cap_hdr, 0, kCapMailBytes) != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
+		auto &b = sl.cap;
+		const bool ok = b.d_hdr.alloc_bytes(sizeof(CapHdr) + std::max<size_t>(nb, kCapMailRecs) * sizeof(CapRec)) == hipSuccess
+			&& b.d_plan.alloc(nb) == hipSuccess && b.d_tot.alloc((size_t)c->C) == hipSuccess && b.d_pool.alloc(pool) == hipSuccess
+			&& b.h_mail.alloc(kCapMailBytes, true) == hipSuccess;
+		if(!ok) { capture_free(c); return VDL2HIP_E_NOMEM; }
+		b.d_rec = reinterpret_cast<CapRec *>(b.d_hdr.get() + 1);
+		if(hipMemset(b.d_hdr, 0, kCapMailBytes) != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
 	}
 	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
 	m.pre = cfg->pre_samples; m.post = cfg->post_samples; m.flags = cfg->flags; m.pool = pool;
@@ -2332,128 +1909,8 @@ int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, f
 	return (int)n;
 }
 
-// test hooks (not declared in vdl2hip.h; host only, need no GPU): the capture's per-burst steps on the CPU, lane by lane and level by level.
-// A burst as the hooks take it (64 bytes):
-struct CapDebugBurst { int32_t nsym; uint32_t tl_bits; int64_t t_first, sync_sample, end_sample, ord, prev_n; float prev_phi0, vdphi, ppm; uint32_t pad_; };
-static Burst cap_debug_burst(const CapDebugBurst &d) {
-	Burst b{};
-	b.nsym = d.nsym; b.tl_bits = d.tl_bits; b.t_first = d.t_first; b.sync_sample = d.sync_sample; b.end_sample = d.end_sample; b.ord = d.ord; b.prev_n = d.prev_n;
-	b.prev_phi0 = d.prev_phi0; b.vdphi = d.vdphi; b.ppm = d.ppm;
-	return b;
-}
-// One burst over y, a channel's ring of ring_len (re, im) pairs (a power of two, 16-byte aligned), its window placed at pair `off`
-// of a pool: -> the record (iq_off = off) and iq[0 .. iq_count).  VDL2HIP_E_DEVICE if a store went outside the window's place.
-int vdl2hip_debug_capture_burst(const float *y, uint32_t ring_len, const void *burst, uint32_t pre, uint32_t post, int64_t k_end, uint64_t off, uint32_t chan, uint32_t freq,
-		vdl2hip_burst *rec, float *iq, size_t cap_pairs) {
-	if(!y || !burst || !rec || (ring_len & (ring_len - 1)) || ring_len < 2 || ((uintptr_t)y & 15) || pre > kCapMaxPre || post > kCapMaxPost || off > (1u << 24)) return VDL2HIP_E_INVAL;
-	const Burst b = cap_debug_burst(*static_cast<const CapDebugBurst *>(burst));
-	if(b.nsym < 0 || b.sync_sample < 0 || b.end_sample < b.sync_sample || b.end_sample >= k_end || b.t_first < 0 || b.t_first + (int64_t)(b.nsym > 0 ? b.nsym - 1 : 0) * kSpsDec >= k_end) return VDL2HIP_E_INVAL;
-	CapPlan p{};
-	cap_window(b, pre, post, k_end, p.first, p.count);
-	if(iq && p.count > cap_pairs) return VDL2HIP_E_TOOBIG;               // (a window longer than the ring goes round it: the steps mask every index)
-	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
-	constexpr size_t G = 4;                                           // guard pairs of NaN on either side of the window's place
-	const size_t base = (size_t)(off & 1u) + 2 * G;                  // (the pool begins on a 16-byte boundary; the window at a pair of off's parity)
-	std::vector<float4> store((base + p.count + 2 * G + 3) / 2 + 1);
-	cf32 *pool = reinterpret_cast<cf32 *>(store.data());
-	for(size_t i = 0; i < 2 * store.size(); i++) pool[i] = cf32{ NAN, NAN };
-	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_copy(yc, ring_len - 1, p.first, p.count, pool + base, off, l, kCapThreads);
-	bool bad = false;
-	for(size_t i = 0; i < 2 * store.size(); i++) if(i < base || i >= base + p.count) bad = bad || !std::isnan(pool[i].re) || !std::isnan(pool[i].im);
-	std::vector<CapPart> part(kCapThreads);
-	for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) part[l] = cap_quality_run(yc, ring_len - 1, b, l, kCapThreads);
-	for(uint32_t s = kCapThreads / 2; s >= 1; s >>= 1) for(uint32_t l = 0; l < (uint32_t)kCapThreads; l++) cap_tree_step(part.data(), l, s);
-	CapRec r{};
-	cap_record(b, chan, freq, p, off, true, part[0], r);
-	memcpy(rec, &r, sizeof r);
-	if(iq && p.count) memcpy(iq, pool + base, (size_t)p.count * sizeof(cf32));
-	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
-}
-// The offsets of a feed's bursts as the two kernels work them out - bursts[c * cap_bursts_chan + i], i < nb_chan[c]; the scans go in
-// rounds of 64 with a carry as the wavefronts' do (integer sums: their order changes nothing) - and the room decision:
-// -> iq_off, iq_count, flags per burst in record order, hdr = { records, pairs of the pool in use }.  Returns the number of records.
-int vdl2hip_debug_capture_plan(const void *bursts, const uint32_t *nb_chan, uint32_t nchan, uint32_t cap_bursts_chan, uint32_t pre, uint32_t post, int64_t k_end,
-		uint64_t pool_samples, uint64_t *iq_off, uint32_t *iq_count, uint32_t *flags, size_t cap_recs, uint64_t hdr[2]) {
-	if(!bursts || !nb_chan || !hdr || !nchan || nchan > (uint32_t)kCapMaxChan || !cap_bursts_chan || pre > kCapMaxPre || post > kCapMaxPost) return VDL2HIP_E_INVAL;
-	const CapDebugBurst *db = static_cast<const CapDebugBurst *>(bursts);
-	std::vector<CapPlan> plan((size_t)nchan * cap_bursts_chan);
-	std::vector<uint64_t> tot(nchan), bbo(nchan + 1);
-	std::vector<uint32_t> bbn(nchan + 1);
-	for(uint32_t c = 0; c < nchan; c++) {                                // k_capture_plan
-		const uint32_t nb = std::min(nb_chan[c], cap_bursts_chan);
-		uint64_t carry = 0;
-		for(uint32_t w = 0; w < nb; w += 64) {
-			uint32_t inc = 0;
-			for(uint32_t l = 0; l < 64 && w + l < nb; l++) {
-				CapPlan &p = plan[(size_t)c * cap_bursts_chan + w + l];
-				cap_window(cap_debug_burst(db[(size_t)c * cap_bursts_chan + w + l]), pre, post, k_end, p.first, p.count);
-				p.off = carry + inc; inc += p.count;
-			}
-			carry += inc;
-		}
-		tot[c] = carry;
-	}
-	uint32_t total = 0; uint64_t ototal = 0;                             // k_capture_copy: the channels' offsets
-	for(uint32_t c = 0; c < nchan; c++) { bbn[c] = total; bbo[c] = ototal; total += std::min(nb_chan[c], cap_bursts_chan); ototal += tot[c]; }
-	bbn[nchan] = total; bbo[nchan] = ototal;
-	hdr[0] = total; hdr[1] = 0;
-	if((iq_off || iq_count || flags) && cap_recs < total) return VDL2HIP_E_TOOBIG;
-	for(uint32_t g = 0; g < total; g++) {
-		const int c = cap_find_chan(bbn.data(), (int)nchan, g);
-		const uint32_t i = g - bbn[c];
-		const CapPlan &p = plan[(size_t)c * cap_bursts_chan + i];
-		const uint64_t off = bbo[c] + p.off;
-		const bool fits = off + p.count <= pool_samples;
-		if(iq_off) iq_off[g] = fits ? off : 0;
-		if(iq_count) iq_count[g] = fits ? p.count : 0;
-		if(flags) flags[g] = fits ? 0u : kCapNoRoom;
-		if(fits && cap_is_last_fit(bbn.data(), (int)nchan, plan.data(), cap_bursts_chan, g, c, i, off + p.count, pool_samples, total)) hdr[1] = off + p.count;
-	}
-	return (int)total;
-}
-
-int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {
-	if(!c || !pf || !cand || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
-	const size_t n = std::min<size_t>(count, (size_t)(c->k_total - first)), ch = chan - c->chan_first;
-	std::vector<uint64_t> words(c->cap >> 6);
-	HIPCHK(hipMemcpy(words.data(), c->d_cand + ch * (c->cap >> 6), words.size() * 8, hipMemcpyDeviceToHost));
-	for(size_t i = 0; i < n; i++) {
-		const uint32_t slot = (uint32_t)(first + (int64_t)i) & (c->cap - 1);
-		cand[i] = (uint8_t)((words[slot >> 6] >> (slot & 63)) & 1u);
-	}
-	size_t done = 0;
-	while(done < n) {
-		const uint32_t slot = (uint32_t)(first + (int64_t)done) & (c->cap - 1);
-		const size_t m = std::min<size_t>(n - done, c->cap - slot);
-		HIPCHK(hipMemcpy(pf + 2 * done, c->d_pf + ch * c->cap + slot, m * sizeof(cf32), hipMemcpyDeviceToHost));
-		done += m;
-	}
-	return (int)n;
-}
-
-// test hook (not declared in vdl2hip.h; tests/test_gpu_sync_screen.py): the screening tier's verdicts, flag[i] = bit first + i of the d_flag ring
-int vdl2hip_debug_read_flags(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, uint8_t *flag) {
-	if(!c || !flag || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
-	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
-	// (up to the end of the last word: the bits past the last valid sample are the kernel's too, and must be zero)
-	const size_t n = std::min<size_t>(count, (size_t)(((c->k_total + 63) & ~(int64_t)63) - first)), ch = chan - c->chan_first;
-	std::vector<uint64_t> words(c->cap >> 6);
-	HIPCHK(hipMemcpy(words.data(), c->d_flag + ch * (c->cap >> 6), words.size() * 8, hipMemcpyDeviceToHost));
-	for(size_t i = 0; i < n; i++) {
-		const uint32_t slot = (uint32_t)(first + (int64_t)i) & (c->cap - 1);
-		flag[i] = (uint8_t)((words[slot >> 6] >> (slot & 63)) & 1u);
-	}
-	return (int)n;
-}
-
 }  // extern "C"
 
+#include "debug_hooks.inc"   // vdl2hip_debug_*: the test and measurement hooks (needs the statics above)
 #include "group.inc"   // vdl2hip_group_*: one receiver over several GPUs of this process (needs the statics above)
 #include "ubench.inc"  // vdl2hip_debug_ubench(): issue and LDS-gather rates measured on the spot (bench.py's roofline line)

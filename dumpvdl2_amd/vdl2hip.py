@@ -362,6 +362,17 @@ def _capture_read(Lib, ctx, cap_recs: int = 4096, cap_pairs: int = 1 << 20):
     return out, wins
 
 
+def live_resources() -> dict:
+    """Test hook: what the process holds through the library's owning types right now - device buffers, page-locked buffers, events.
+    Needs no receiver and no GPU."""
+    Lib = load_library()
+    out = (C.c_longlong * 3)()
+    r = Lib.vdl2hip_debug_live_resources(out)
+    if r != 0:
+        raise Vdl2HipError(f"vdl2hip_debug_live_resources: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return {"device": out[0], "pinned": out[1], "events": out[2]}
+
+
 class Receiver:
     """One multi-channel VDL2 receiver on one GPU (= the reference's set of demod threads)."""
 
