@@ -102,6 +102,13 @@ int vdl2hip_debug_u8_levels(float out[512]) {        // out[0..255]: the channel
 	return dbg_down(out, d) ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
 }
 
+int vdl2hip_debug_s8_levels(float out[512]) {        // out[0..255]: s8_level() of the byte patterns 0..255, out[256..511]: (float)(int8_t)i / 128.0f the plain way (tests)
+	DevBuf<float> d;
+	if(!hip_ok(d.alloc(512))) return VDL2HIP_E_NOMEM;
+	hipLaunchKernelGGL(k_s8_level_probe, dim3(1), dim3(256), 0, 0, d);
+	return dbg_down(out, d) ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
+}
+
 int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
 	DevBuf<float> d_in, d_out;
 	if(!hip_ok(d_in.alloc(64)) || !hip_ok(d_out.alloc(256))) return VDL2HIP_E_NOMEM;

@@ -111,7 +111,7 @@ int vdl2hip_group_create(const vdl2hip_cfg *cfg_in, const int32_t *devices, uint
 	vdl2hip_group *g = new(std::nothrow) vdl2hip_group();
 	if(!g) return VDL2HIP_E_NOMEM;
 	g->n = (int)ndev; g->dev.assign(devices, devices + ndev);
-	g->in_cap = cfg->max_block_bytes ? cfg->max_block_bytes : 320000u; g->fmt = (int)cfg->sample_fmt;
+	g->in_cap = cfg->max_block_bytes ? cfg->max_block_bytes : 320000u; g->fmt = fmt_code(cfg->sample_fmt);
 	g->ctx.assign(ndev, nullptr); g->xs.assign(ndev, nullptr); g->px.assign(ndev, std::vector<hipStream_t>());
 	for(int k = 0; k < kSlots; k++) {
 		g->blk[k].assign(ndev, nullptr); g->ready[k].assign(ndev, nullptr); g->own[k].assign(ndev, nullptr);

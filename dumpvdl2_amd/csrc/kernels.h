@@ -85,6 +85,9 @@ struct RefChan {
 // (k_ref_scan_multi: q_dphi) multiplies by (sin, cos) = (0, 1) and would turn (+0, -0) into (+0, +0) where the reference leaves it,
 // and atan2 of a silent sample would land on the other side of its branch cut.
 __device__ __forceinline__ float cf32_level(float x) { return x + 0.0f; }
+// S8 input (VDL2HIP_FMT_S8, internal code 3: interleaved I, Q as signed bytes, 2 bytes per complex sample): (float)b / 128.0f, the float
+// process_buf_short() makes of the int16 256 b.  The one conversion of the format, a 16-bit word at a time (defined beside u8_level below)
+__device__ __forceinline__ float2 s8_level(uint32_t w);
 
 // one raw sample as process_buf_short() / process_buf_uchar() convert it (src/demod.c:349-365)
 __device__ __forceinline__ bool ref_raw_sample(const RefChan &r, int64_t s, float &re, float &im) {
@@ -93,6 +96,7 @@ __device__ __forceinline__ bool ref_raw_sample(const RefChan &r, int64_t s, floa
 		if(s >= pc.s0 && s < pc.s0 + pc.n) {
 			if(r.fmt == 2) { const float2 w = ((const float2 *)pc.p)[s - pc.s0]; re = cf32_level(w.x); im = cf32_level(w.y); }
 			else if(r.fmt == 1) { const uint32_t w = ((const uint32_t *)pc.p)[s - pc.s0]; re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
+			else if(r.fmt == 3) { const float2 v = s8_level(((const uint16_t *)pc.p)[s - pc.s0]); re = v.x; im = v.y; }
 			else { const uint16_t w = ((const uint16_t *)pc.p)[s - pc.s0]; re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)(w >> 8) - 127.5f) / 127.5f; }
 			return true;
 		}
@@ -230,7 +234,7 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 			if(j < npiece && s >= ps0[j] && s < ps0[j] + pn[j] && s < s_end) {
 				if(fmt == 2) { const ref_v2u v = ((ref_gu64 *)pp[j])[s - ps0[j]]; w = v.x; w2 = v.y; }
 				else if(fmt == 1) w = ((ref_gu32 *)pp[j])[s - ps0[j]];
-				else w = ((ref_gu16 *)pp[j])[s - ps0[j]];
+				else w = ((ref_gu16 *)pp[j])[s - ps0[j]];                 // (U8 and S8: a 16-bit word)
 			}
 		}
 		const uint32_t phi = ((uint32_t)s * dphi) & 0xffffffu;      // applied, then advanced, from 0 at sample 0 (demod.c:313-316); only the low 24 bits count
@@ -260,6 +264,7 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 		float re, im;
 		if(fmt == 2) { re = cf32_level(__builtin_bit_cast(float, w)); im = cf32_level(__builtin_bit_cast(float, w2)); }
 		else if(fmt == 1) { re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
+		else if(fmt == 3) { const float2 v = s8_level(w); re = v.x; im = v.y; }
 		else { re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
 		if(mix) {
 			const uint32_t phi = ((uint32_t)(sb + lane) * dphi) & 0xffffffu;
@@ -427,9 +432,16 @@ struct K1Args {
 };
 
 // (CF32: the float32 builds of the channeliser - they see no other format, and the other builds never see this one: vdl2hip.hip, launch_chanfir)
-template<bool CF32 = false>
+// (S8, internal code 3: 0 - a build that never sees it (the s16 and u8 builds where S8 has a build of its own: they stay the code they
+// were), 1 - told from a.fmt at run time, 2 - the S8 build, which sees nothing else)
+template<bool CF32 = false, int S8 = 1>
 __device__ __forceinline__ void load_sample(const K1Args &a, int64_t s, float &re, float &im) {
-	if(CF32) {         // the value itself (cf32_level)
+	if(!CF32 && (S8 == 2 || (S8 == 1 && a.fmt == 3))) {   // S8: (float)b / 128.0f (s8_level)
+		const uint16_t *p = (s < (int64_t)a.ncarry) ? (const uint16_t *)a.carry + s : (const uint16_t *)a.in + (s - a.ncarry);
+		const float2 v = s8_level(*p);
+		re = v.x;
+		im = v.y;
+	} else if(CF32) {         // the value itself (cf32_level)
 		const float2 *p = (s < (int64_t)a.ncarry) ? (const float2 *)a.carry + s : (const float2 *)a.in + (s - a.ncarry);
 		const float2 w = *p;
 		re = cf32_level(w.x);
@@ -524,6 +536,16 @@ __device__ __forceinline__ float u8_level(uint32_t i) {
 	return __builtin_fmaf(__builtin_fmaf(-127.5f, q, d), r, q);
 }
 __global__ void k_u8_level_probe(float *out) { const uint32_t i = threadIdx.x; out[i] = u8_level(i); out[256 + i] = ((float)i - 127.5f) / 127.5f; }
+// (float)b / 128.0f of the two signed bytes of a 16-bit word (I in the low byte): one XOR per word turns both bytes into u = b + 128, an
+// unsigned byte converts with a byte-select v_cvt_f32_ubyte*, and fma(u, 2^-7, -1) is exact (u 2^-7 is, and so is the difference: a
+// multiple of 2^-7 in [-1, 1)) - two VALU operations per component where u8_level needs four, and never a negative zero (u = 128 gives
+// 1 - 1 = +0).  Checked on the device for all 256 values: tests/test_gpu_s8.py::test_conversion_is_exact
+__device__ __forceinline__ float2 s8_level(uint32_t w) {
+	const uint32_t u = w ^ 0x8080u;
+	return make_float2(__builtin_fmaf((float)(u & 0xffu), 0.0078125f, -1.0f), __builtin_fmaf((float)((u >> 8) & 0xffu), 0.0078125f, -1.0f));
+}
+// (even patterns through the low byte of the word, odd ones through the high byte)
+__global__ void k_s8_level_probe(float *out) { const uint32_t i = threadIdx.x; out[i] = i & 1 ? s8_level(i << 8).y : s8_level(i).x; out[256 + i] = (float)(int8_t)i / 128.0f; }
 
 // debug kernel (tests/test_gpu_core_probe.py): the DEVICE builds of vdl2_core.h's element-wise pieces, each called as the product calls
 // it, one lane per element, plain loads and stores.  in: core_probe_in_words(kind) 32-bit words per element, out: core_probe_out_words(kind)
@@ -580,8 +602,11 @@ __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, u
 // the s16 build: 3.78 ms per launch): the whole tile ahead under the same cap, at the price of 37 spilled registers (the s16 build: 28), 3.89 ms; the
 // first half of the tile ahead and the second asked for at the top of the staging (3 spills) 3.97; the generic path 4.02; the whole
 // tile ahead with three resident workgroups (148 registers, no spills) 4.08.  Hence the first, which is also the other builds' scheme.
+// S8: the build for signed-byte input (VDL2HIP_FMT_S8: a HackRF's format, the 8-bit wire format of wider radios), where the U8 build is and
+// by its scheme - 16-bit words a tile ahead in pre[], staged without range checks - with s8_level() for u8_level(): a flag beside U8, so
+// that every other instantiation is the code it was.  Everywhere else S8 goes through the generic staging path (load_sample).
 // After the staging the code is the shared code: the tile is float2 whatever the format.
-template<int OS, int R, int CR, bool U8 = false, bool CF32 = false>
+template<int OS, int R, int CR, bool U8 = false, bool CF32 = false, bool S8 = false>
 __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MIN_BLOCKS)) void k_chanfir(K1Args a) {
 	static_assert(64 * R == kFixW || R == 1, "the fused fix-up assumes the fix window is the segment's first tile");
 	static_assert(R >= 1 && R <= 2, "the run's outputs are held in two register pairs");
@@ -619,7 +644,11 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 	constexpr bool kPrefetch = OS != 0 && CR >= 4 && (64 * R * OS + 255) / 256 <= 10 && (64 * R * OS) % 256 == 0;
 	static_assert(!U8 || kPrefetch, "the unsigned-byte build exists where the tile prefetch does");
 	static_assert(!CF32 || !U8, "one format per build");
-	constexpr int kFmt = CF32 ? 2 : U8 ? 0 : 1;               // the sample format this build stages without range checks
+	static_assert(!S8 || (kPrefetch && !U8 && !CF32), "the signed-byte build exists where the unsigned-byte build does, one format per build");
+	constexpr bool kByte = U8 || S8;                          // two bytes per sample: 16-bit words in pre[]
+	constexpr int kFmt = CF32 ? 2 : S8 ? 3 : U8 ? 0 : 1;      // the sample format this build stages without range checks
+	// (S8 reaches a build of oversample 20 or 10 with the tile prefetch only as its own: vdl2hip.hip, launch_chanfir)
+	constexpr int kLoadS8 = S8 ? 2 : (kPrefetch && (OS == 20 || OS == 10)) ? 0 : 1;
 	constexpr int kPre = kPrefetch ? (64 * R * OS) / 256 : 1;
 	constexpr bool kPipeGather = kPrefetch;
 	uint32_t pre[kPre]; bool have_pre = false;
@@ -636,7 +665,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				const float2 *sn = (const float2 *)a.in + (s0 - a.ncarry);
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre2[k] = sn[tid + 256 * k];
-			} else if constexpr(U8) {
+			} else if constexpr(kByte) {
 				const uint16_t *sn = (const uint16_t *)a.in + (s0 - a.ncarry);
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre[k] = sn[tid + 256 * k];
@@ -708,15 +737,16 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				#pragma unroll
 				for(int k = 0; k < kPre; k++) pre2[CF32 ? k : 0] = sn[tid + 256 * k];
 			}
-		} else if(!CF32 && kPrefetch && U8 && fast_now) {
-			// (the unsigned-byte build: the same, two bytes per sample)
+		} else if(!CF32 && kPrefetch && kByte && fast_now) {
+			// (the unsigned-byte and signed-byte builds: the same, two bytes per sample)
 			const uint16_t *src = (const uint16_t *)a.in + (sbase - a.ncarry);
 			#pragma unroll
 			for(int k = 0; k < kPre; k++) {
 				const int t = tid + 256 * k;
 				const uint32_t w = have_pre ? pre[k] : (uint32_t)src[t];
 				const int l = t / run, m = t - l * run;
-				tile[m * 65 + l] = make_float2(u8_level(w & 0xffu), u8_level((w >> 8) & 0xffu));
+				if constexpr(S8) tile[m * 65 + l] = s8_level(w);
+				else tile[m * 65 + l] = make_float2(u8_level(w & 0xffu), u8_level((w >> 8) & 0xffu));
 			}
 			const int64_t snext = sbase + tile_n;
 			have_pre = ts + 1 < a.tiles && (tix + 1) * L < a.D && snext + tile_n <= (int64_t)a.nlogical;
@@ -765,7 +795,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 			for(int t = tid; t < tile_n; t += 256) {
 				const int64_t sidx = sb + t;
 				float re = 0.f, im = 0.f;
-				if(sidx < (int64_t)a.nlogical) load_sample<CF32>(a, sidx, re, im);
+				if(sidx < (int64_t)a.nlogical) load_sample<CF32, kLoadS8>(a, sidx, re, im);
 				const int l = t / run, m = t - l * run;
 				tile[m * 65 + l] = make_float2(re, im);
 			}
@@ -1010,7 +1040,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		for(int t = tid; t < tile_n; t += 256) {
 			const int64_t sidx = sbase + t;
 			float re = 0.f, im = 0.f;
-			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample<CF32>(a, sidx, re, im);
+			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample<CF32, kLoadS8>(a, sidx, re, im);
 			const int l = t / run, m = t - l * run;
 			tile[m * 65 + l] = make_float2(re, im);
 		}
@@ -1140,7 +1170,7 @@ __global__ void k_carry(K1Args a, void *carry_out, uint32_t nrem) {
 	} else if(a.fmt == 1) {
 		const uint32_t *p = (s < (int64_t)a.ncarry) ? (const uint32_t *)a.carry + s : (const uint32_t *)a.in + (s - a.ncarry);
 		((uint32_t *)carry_out)[i] = *p;
-	} else {
+	} else {                                                           // (U8 and S8: two bytes)
 		const uint16_t *p = (s < (int64_t)a.ncarry) ? (const uint16_t *)a.carry + s : (const uint16_t *)a.in + (s - a.ncarry);
 		((uint16_t *)carry_out)[i] = *p;
 	}
@@ -2037,7 +2067,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		constexpr int PF = 4;
 		// (a CF32 sample is two words - the bits of I in wq, of Q in wq2; the other formats leave wq2 alone and it costs them nothing)
 		uint32_t wq[PF][NQ], wq2[PF][NQ];
-		constexpr int SB = FMT == 2 ? 8 : FMT == 1 ? 4 : 2;           // bytes per raw sample
+		constexpr int SB = FMT == 2 ? 8 : FMT == 1 ? 4 : 2;           // bytes per raw sample (U8 and S8: 2)
 		#pragma unroll
 		for(int q = 0; q < NQ; q++) {
 			const int r = pidx + q * kScanProd;
@@ -2111,6 +2141,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 				const uint32_t w = wc[q];
 				if(FMT == 2) { re[q] = cf32_level(__builtin_bit_cast(float, w)); im[q] = cf32_level(__builtin_bit_cast(float, wc2[q])); }
 				else if(FMT == 1) { re[q] = (float)(int16_t)(w & 0xffff) / 32768.0f; im[q] = (float)(int16_t)(w >> 16) / 32768.0f; }
+				else if(FMT == 3) { const float2 v = s8_level(w); re[q] = v.x; im[q] = v.y; }
 				else { re[q] = ((float)(w & 0xff) - 127.5f) / 127.5f; im[q] = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
 				const float F = (float)(phq[q] & 0xffffu);
 				const float sn = eq[q].x + eq[q].z * F, cs = eq[q].y + eq[q].w * F;

@@ -45,6 +45,9 @@ __device__ __forceinline__ float res_u8_level(uint32_t i) {
 	return __builtin_fmaf(__builtin_fmaf(-127.5f, q, d), r, q);
 }
 
+// S8 (FMT 3): (float)b / 128.0f of both bytes of a word, the channeliser's own conversion (kernels.h, included before this file)
+__device__ __forceinline__ float2 s8_level(uint32_t w);
+
 // sample `rel` of the stream relative to the block's first: the tail before it, the block, nothing after it
 template<int FMT>
 __device__ __forceinline__ float2 res_sample(const K0Args &a, int64_t rel) {
@@ -53,6 +56,7 @@ __device__ __forceinline__ float2 res_sample(const K0Args &a, int64_t rel) {
 	if(FMT == 2) { const float2 w = ((const float2 *)a.in)[rel]; return make_float2(w.x + 0.0f, w.y + 0.0f); }      // cf32_level
 	if(FMT == 1) { const uint32_t w = ((const uint32_t *)a.in)[rel]; return make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f); }
 	const uint32_t w = ((const uint16_t *)a.in)[rel];
+	if(FMT == 3) return s8_level(w);
 	return make_float2(res_u8_level(w & 0xff), res_u8_level(w >> 8));
 }
 

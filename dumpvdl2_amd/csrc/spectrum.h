@@ -80,6 +80,7 @@ __device__ __forceinline__ float2 spec_sample(const SpecArgs &a, int64_t rel) {
 	if(FMT == 2) { const float2 v = ((const float2 *)a.in)[rel]; return make_float2(v.x + 0.0f, v.y + 0.0f); }
 	if(FMT == 1) { const uint32_t v = ((const uint32_t *)a.in)[rel]; return make_float2((float)(int16_t)(v & 0xffff) / 32768.0f, (float)(int16_t)(v >> 16) / 32768.0f); }
 	const uint32_t v = ((const uint16_t *)a.in)[rel];
+	if(FMT == 3) return s8_level(v);
 	return make_float2(res_u8_level(v & 0xff), res_u8_level(v >> 8));
 }
 // a component at the rail, stated on the float value (vdl2hip.h)
@@ -87,6 +88,7 @@ template<int FMT>
 __device__ __forceinline__ bool spec_at_rail(float v) {
 	if(FMT == 2) return __builtin_fabsf(v) >= 1.0f;                          // (false for a NaN)
 	if(FMT == 1) return v == -1.0f || v == 32767.0f / 32768.0f;
+	if(FMT == 3) return v == -1.0f || v == 127.0f / 128.0f;                  // (bytes -128 and 127)
 	return __builtin_fabsf(v) == 1.0f;
 }
 

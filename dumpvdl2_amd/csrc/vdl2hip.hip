@@ -255,7 +255,18 @@ struct vdl2hip_ctx {
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) { \
 	fprintf(stderr, "vdl2hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return VDL2HIP_E_DEVICE; } } while(0)
 
-static size_t sample_bytes(int fmt) { return fmt == VDL2HIP_FMT_CF32 ? 8 : fmt == VDL2HIP_FMT_S16LE ? 4 : 2; }
+// The format inside the library (vdl2hip_ctx.fmt / in_fmt, K1Args.fmt, RefChan.fmt, the kernels' template FMT) is a small code: the
+// public value for U8, S16LE and CF32 (0, 1, 2), and 3 for VDL2HIP_FMT_S8, whose public value is 4 (the public 3 is unassigned and
+// refused).  This is the one place that maps one to the other; -1: not a format.
+constexpr int kFmtS8 = 3;
+static int fmt_code(uint32_t sample_fmt) {
+	switch(sample_fmt) {
+		case VDL2HIP_FMT_U8: case VDL2HIP_FMT_S16LE: case VDL2HIP_FMT_CF32: return (int)sample_fmt;
+		case VDL2HIP_FMT_S8: return kFmtS8;
+		default: return -1;
+	}
+}
+static size_t sample_bytes(int fmt) { return fmt == VDL2HIP_FMT_CF32 ? 8 : fmt == VDL2HIP_FMT_S16LE ? 4 : 2; }   // (of a format's code; U8 and S8: 2)
 
 // Every entry point works on the context's own device whatever the calling thread's current device is (a process may hold
 // receivers on several GPUs), and leaves the thread's device as it found it.
@@ -293,6 +304,8 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 		case 4:
 			// (unsigned-byte input where the tile prefetch exists: the build that fetches and converts its tiles the way the s16 build does)
 			if constexpr(OS == 20 || OS == 10) { if(c->fmt == VDL2HIP_FMT_U8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break; } }
+			// (signed-byte input: the same, with a build of its own; everywhere else it takes the generic staging path of the builds below)
+			if constexpr(OS == 20 || OS == 10) { if(c->fmt == kFmtS8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break; } }
 			hipExtLaunchKernelGGL((k_chanfir<OS, R, 4>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
 		case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
 		default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
@@ -624,6 +637,7 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	t.arm(c->profiling >= 2);
 	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, t.e(0), t.e(1));
 	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == kFmtS8) launch_resample<3>(c, a, grid, t.e(0), t.e(1));
 	else launch_resample<0>(c, a, grid, t.e(0), t.e(1));
 	HIPCHK(hipGetLastError());
 	t.launched(1);
@@ -675,6 +689,7 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	t.arm(c->profiling >= 2);
 	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, t.e(0), t.e(1));
 	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == kFmtS8) launch_spectrum<3>(c, a, grid, t.e(0), t.e(1));
 	else launch_spectrum<0>(c, a, grid, t.e(0), t.e(1));
 	if(nseg) {
 		const uint32_t W = m.nfft + kSpecLevels;
@@ -708,6 +723,7 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 #define LAUNCH_SCAN_MULTI(how, ...) do { \
 	if(c->fmt == 2) { if(c->os == 20) how((k_ref_scan_multi<2, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<2, 10>), __VA_ARGS__); else how((k_ref_scan_multi<2, 0>), __VA_ARGS__); } \
 	else if(c->fmt == 1) { if(c->os == 20) how((k_ref_scan_multi<1, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<1, 10>), __VA_ARGS__); else how((k_ref_scan_multi<1, 0>), __VA_ARGS__); } \
+	else if(c->fmt == 3) { if(c->os == 20) how((k_ref_scan_multi<3, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<3, 10>), __VA_ARGS__); else how((k_ref_scan_multi<3, 0>), __VA_ARGS__); } \
 	else { if(c->os == 20) how((k_ref_scan_multi<0, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<0, 10>), __VA_ARGS__); else how((k_ref_scan_multi<0, 0>), __VA_ARGS__); } } while(0)
 // Referee: the listed stretches (`sq`, or the decisions `rq` whose stretches they are; *n of them, at most cap) are made the reference's own,
 // many side by side, and those of them that had not met their witness - a few in ten thousand - are listed in `retry` and scanned again
@@ -1073,7 +1089,8 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	const vdl2hip_cfg *cfg = &cfg_v;
 	if(!cfg->freqs || cfg->nchan == 0) return VDL2HIP_E_INVAL;
 	if(cfg->oversample == 0 || cfg->oversample > (uint32_t)kMaxOversample) return VDL2HIP_E_INVAL;
-	if(cfg->sample_fmt != VDL2HIP_FMT_U8 && cfg->sample_fmt != VDL2HIP_FMT_S16LE && cfg->sample_fmt != VDL2HIP_FMT_CF32) return VDL2HIP_E_INVAL;
+	const int fmt = fmt_code(cfg->sample_fmt);
+	if(fmt < 0) return VDL2HIP_E_INVAL;
 	uint32_t first = cfg->chan_first, count = cfg->chan_count ? cfg->chan_count : cfg->nchan - first;
 	if(first >= cfg->nchan || first + count > cfg->nchan || count > (uint32_t)kK5MaxChan) return VDL2HIP_E_INVAL;
 	// a receiver that resamples: the ratio must be one the resampler takes, and a block must stay a block
@@ -1082,7 +1099,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	uint64_t rs_max_out = 0;
 	if(resample) {
 		if(!design_resampler(cfg->input_rate, (uint32_t)kSymbolRate * kSps * cfg->oversample, rd, false)) return VDL2HIP_E_INVAL;
-		const uint64_t max_in = (cfg->max_block_bytes ? cfg->max_block_bytes : 320000u) / sample_bytes((int)cfg->sample_fmt);
+		const uint64_t max_in = (cfg->max_block_bytes ? cfg->max_block_bytes : 320000u) / sample_bytes(fmt);
 		rs_max_out = (max_in * rd.L + rd.M - 1) / rd.M + 1;
 		if(rs_max_out >= (1ull << 31)) return VDL2HIP_E_INVAL;
 	}
@@ -1098,7 +1115,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	vdl2hip_ctx *c = new(std::nothrow) vdl2hip_ctx();
 	if(!c) return VDL2HIP_E_NOMEM;
 	c->cfg = *cfg; c->cfg.freqs = nullptr;
-	c->C = (int)count; c->chan_first = (int)first; c->os = (int)cfg->oversample; c->fmt = (int)cfg->sample_fmt;
+	c->C = (int)count; c->chan_first = (int)first; c->os = (int)cfg->oversample; c->fmt = fmt;
 	c->in_fmt = c->fmt;
 	if(resample) { c->rs.on = true; c->fmt = VDL2HIP_FMT_CF32; }    // what the channeliser and the referee read is r[]
 	c->freqs.assign(cfg->freqs + first, cfg->freqs + first + count);

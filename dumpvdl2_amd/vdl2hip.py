@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvdl2hip.so")
 
 FMT_U8, FMT_S16LE, FMT_CF32 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_FMT_* (CF32: np.complex64 / interleaved float32, full scale 1.0)
+FMT_S8 = 4                                # signed bytes, interleaved I, Q (np.int8; b / 128: what FMT_S16LE makes of b << 8); 3 is unassigned
 COUNTER_NAMES = [
     "demod.sync.good", "decoder.crc.good", "decoder.crc.bad", "decoder.errors.no_header",
     "decoder.errors.too_long", "decoder.errors.no_fec", "decoder.errors.data_truncated",
@@ -379,7 +380,8 @@ class Receiver:
     def __init__(self, centerfreq: int, freqs: Sequence[int], oversample: int = 20, sample_fmt: int = FMT_S16LE,
                  max_ppm: float = 0.0, device: int = 0, max_block_bytes: int = 320000,
                  chan_first: int = 0, chan_count: int = 0, input_rate: int = 0):
-        """input_rate: the rate of the IQ that will be fed, Hz; 0 = 105000 * oversample.  Any other supported rate is resampled on
+        """sample_fmt: FMT_U8, FMT_S16LE, FMT_CF32 or FMT_S8 (signed bytes: a HackRF's format; the receiver is an FMT_S16LE one fed b << 8).
+        input_rate: the rate of the IQ that will be fed, Hz; 0 = 105000 * oversample.  Any other supported rate is resampled on
         the device ahead of the channeliser (vdl2hip.h, "Resampling")."""
         self.L = load_library()
         self.freqs = list(freqs)
@@ -410,7 +412,7 @@ class Receiver:
 
     def feed(self, raw) -> None:
         """process_buf_uchar()/process_buf_short(): one block of raw IQ from host memory - any array, taken as its bytes (FMT_CF32: np.complex64
-        or interleaved np.float32)."""
+        or interleaved np.float32; FMT_S8: np.int8, interleaved)."""
         a = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
         self._chk(self.L.vdl2hip_feed(self.h, a.ctypes.data, a.size), "vdl2hip_feed")
 
@@ -422,7 +424,7 @@ class Receiver:
         self._chk(self.L.vdl2hip_feed_device(self.h, C.c_void_p(dev_ptr), nbytes), "vdl2hip_feed_device")
 
     def feed_tensor(self, t) -> None:
-        """a block resident on this receiver's device (torch tensor of raw bytes / int16 values / float32 or complex64 values)"""
+        """a block resident on this receiver's device (torch tensor of raw bytes / int8 / int16 values / float32 or complex64 values)"""
         self.feed_device(t.data_ptr(), t.numel() * t.element_size())
 
     def feed_pinned_tensor(self, t) -> None:
@@ -660,6 +662,7 @@ class ReceiverGroup:
         return r
 
     def feed(self, raw) -> None:
+        """one block of raw IQ from host memory - any array, taken as its bytes (FMT_S8: np.int8), as Receiver.feed() takes it"""
         a = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
         self._chk(self.L.vdl2hip_group_feed(self.h, a.ctypes.data, a.size), "vdl2hip_group_feed")
 

@@ -44,7 +44,9 @@ extern "C" {
                                  *    vdl2hip_activity_edges() / _enable() / _disable() / _read() / _series() with vdl2hip_activity_cfg / _info / _chan: the
                                  *    activity monitor, off unless enabled - again new entry points and structures only, so the version stayed
                                  *    vdl2hip_capture_enable() / _disable() / _info_get() / _read() with vdl2hip_capture_cfg / _info and vdl2hip_burst: the
-                                 *    burst capture, off unless enabled - new entry points and structures only once more, so the version stayed */
+                                 *    burst capture, off unless enabled - new entry points and structures only once more, so the version stayed
+                                 *    VDL2HIP_FMT_S8 (4): one more accepted value of vdl2hip_cfg.sample_fmt, as VDL2HIP_FMT_CF32 was - no structure, no
+                                 *    entry point and no result for the other formats changed, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -60,6 +62,16 @@ extern "C" {
  *  - A feed is truncated to whole samples (8 bytes), as it is to 4 or 2 in the other formats; vdl2hip_feed_device() wants an 8-byte
  *    aligned pointer; max_block_bytes stays in bytes (default 320000 = 40000 samples). */
 #define VDL2HIP_FMT_CF32   2
+/* The value 3 is unassigned and refused (VDL2HIP_E_INVAL).
+ * Not in the reference's enum either: signed 8-bit IQ ("CS8", SigMF's ci8 / cs8) - interleaved I, Q as two's-complement int8_t, 2 bytes
+ * per complex sample: a HackRF's only format, the 8-bit wire format of USRPs and of the bladeRF 2.0.
+ *  - The value of a byte b is (float)b / 128.0f, exact for all 256 bytes: -1.0 .. 127 / 128.
+ *  - That is bit for bit the float process_buf_short() makes of the int16 k = 256 b ((float)(256 b) / 32768.0f == b / 128): an S8
+ *    receiver IS a VDL2HIP_FMT_S16LE receiver fed b << 8 - the same frames, metadata, counters, timing and decimated stream, to the bit.
+ *  - A feed is truncated to whole samples (2 bytes); vdl2hip_feed_device() wants a 2-byte aligned pointer; max_block_bytes stays in
+ *    bytes (default 320000 = 160000 samples).
+ *  - The drop-in adapter (vdl2hip_dropin.h) has no entry point for it: the reference has no process_buf_*() of this format to replace. */
+#define VDL2HIP_FMT_S8     4
 
 #define VDL2HIP_OK            0
 #define VDL2HIP_E_INVAL      -1   /* bad argument / configuration */
@@ -143,7 +155,7 @@ typedef struct {
  * 105000 * oversample otherwise - computed on the device from the block the channeliser is about to read.  Off unless enabled; with it
  * off nothing is launched and every result is what it was, to the bit.
  *  - Samples.  x[i] is the float value of input sample i as the formats are converted everywhere else (VDL2HIP_FMT_* above: u8 the
- *    correctly rounded (b - 127.5f) / 127.5f, s16 k / 32768.0f, cf32 the value itself); i counts from the first sample fed after
+ *    correctly rounded (b - 127.5f) / 127.5f, s16 k / 32768.0f, cf32 the value itself, s8 b / 128.0f); i counts from the first sample fed after
  *    vdl2hip_spectrum_enable().
  *  - Segments.  Segment j is x[j N .. (j + 1) N), N = nfft.  It is ANALYSED iff it is complete and j % stride == 0: which segments
  *    are analysed depends on the stream alone, not on how it was cut into feeds (a feed may be one sample, a segment may span many).
@@ -158,7 +170,8 @@ typedef struct {
  *  - nfft: a power of two in 64 .. 4096.  stride 0 means 1.
  *  - Levels, over the samples of the analysed segments, unwindowed: samples = S N; mean_power = mean of re^2 + im^2; dc_i, dc_q = mean
  *    I, mean Q; peak = max over samples of max(|re|, |im|); clipped = samples with a component at the rail, stated on the float value
- *    v:  u8 |v| == 1.0f (bytes 0 and 255);  s16 v == -1.0f or v == 32767 / 32768.0f;  cf32 |v| >= 1.0f (a NaN does not count).
+ *    v:  u8 |v| == 1.0f (bytes 0 and 255);  s16 v == -1.0f or v == 32767 / 32768.0f;  cf32 |v| >= 1.0f (a NaN does not count);
+ *    s8 v == -1.0f or v == 127 / 128.0f (bytes -128 and 127).
  *  - Determinism.  The same sequence of calls gives the same bits (no floating-point atomics anywhere).  The same stream cut
  *    differently gives segments, samples, clipped and peak exactly, and power[], mean_power, dc_* within 1e-12 relative (only the order
  *    of float64 additions moves).

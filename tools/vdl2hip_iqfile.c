@@ -8,8 +8,9 @@
  *                                 samples - 16 s16 blocks at oversample 20, 4 u8 blocks at 10; 1 = the reference's block by block).
  *                                 A block is microseconds of GPU work behind a fixed chain of launches (and, now and then, a 2 ms
  *                                 scan of the referee's): collected blocks give the same frames at 5-7x the rate
- *   --sample-format U8|S16_LE|CF32  (the reference's token is S16_LE, src/dumpvdl2.c:849; CF32 - interleaved float32 I, Q, full scale 1.0,
- *                                 what GNU Radio file sinks and SoapySDR write - is this library's own, VDL2HIP_FMT_CF32)
+ *   --sample-format U8|S16_LE|CF32|S8  (the reference's token is S16_LE, src/dumpvdl2.c:849; CF32 - interleaved float32 I, Q, full scale 1.0,
+ *                                 what GNU Radio file sinks and SoapySDR write - is this library's own, VDL2HIP_FMT_CF32; so is S8 - interleaved
+ *                                 signed bytes, what hackrf_transfer writes and SigMF calls ci8, VDL2HIP_FMT_S8: a byte b counts b / 128)
  *   --sample-rate <Hz>            the rate of the file, where it is not 105000 * oversample (this library's own: the reference sets its
  *                                 radios to that rate and takes files at it).  The receiver resamples on the GPU, vdl2hip_cfg.input_rate;
  *                                 rates it does not take (vdl2hip.h) are refused
@@ -136,6 +137,7 @@ int main(int argc, char **argv) {
 			if(!strcmp(argv[i], "U8")) fmt = VDL2HIP_FMT_U8;
 			else if(!strcmp(argv[i], "S16_LE")) fmt = VDL2HIP_FMT_S16LE;
 			else if(!strcmp(argv[i], "CF32")) fmt = VDL2HIP_FMT_CF32;
+			else if(!strcmp(argv[i], "S8")) fmt = VDL2HIP_FMT_S8;
 			else { fprintf(stderr, "Unknown sample format\n"); return 1; }
 		}
 		else if(!strcmp(a, "--sample-rate")) { NEEDARG(); input_rate = (uint32_t)strtoul(argv[++i], NULL, 10); }
@@ -169,7 +171,7 @@ int main(int argc, char **argv) {
 		else if(nfreq < 1024) freqs[nfreq++] = (uint32_t)strtoul(a, NULL, 10);
 	}
 	(void)fmt_set;
-	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
+	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32|S8] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
 			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] "
@@ -197,7 +199,7 @@ int main(int argc, char **argv) {
 	memset(&cfg, 0, sizeof cfg);
 	cfg.struct_size = sizeof cfg; cfg.centerfreq = centerfreq; cfg.oversample = oversample; cfg.sample_fmt = fmt;
 	if(per_feed == 0) {
-		const uint32_t blk = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_CF32 ? 8u : fmt == VDL2HIP_FMT_S16LE ? 4u : 2u);                   /* samples per block */
+		const uint32_t blk = FILE_BUFSIZE / (fmt == VDL2HIP_FMT_CF32 ? 8u : fmt == VDL2HIP_FMT_S16LE ? 4u : 2u);                   /* samples per block (U8, S8: 2 bytes) */
 		const uint32_t dec = (uint32_t)((uint64_t)blk * (SYMBOL_RATE * 10u) / (input_rate ? input_rate : sample_rate));              /* decimated samples per block */
 		per_feed = dec ? (64000u + dec - 1) / dec : 1;
 	}
