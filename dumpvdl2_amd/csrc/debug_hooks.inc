@@ -244,6 +244,54 @@ int vdl2hip_debug_activity_words(const uint64_t *busy, const uint32_t *nbits, ui
 	return VDL2HIP_OK;
 }
 
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): the transmission log's word steps (txlog.h) for one channel, lane by
+// lane and level by level as k_txlog_emit takes them, over `count` words of nbits[i] <= 64 bins each - p: the bins' powers, one after
+// the other, the first being bin `base`; init: NULL for an idle start, else { open, idle, first bin } of a transmission under way, as
+// k_txlog_init takes it over from the activity monitor.  The records that close go to recs[0 .. cap_recs) with chan and freq 0 and the
+// host's fields as the library delivers a record without frames; k_txlog_plan's count is taken beside and must agree
+// (VDL2HIP_E_DEVICE if not).  Returns the number of records; out = { open, idle, first bin, busy bins so far } of the state behind the last word.
+int vdl2hip_debug_txlog_words(const float *p, const uint32_t *nbits, uint32_t count, float thr, uint32_t hang_bins, uint32_t B, int64_t k_on, uint64_t base,
+		const uint64_t *init, vdl2hip_tx *recs, uint32_t cap_recs, uint64_t out[4]) {
+	if(!p || !nbits || !out || (!recs && cap_recs) || hang_bins > kActMaxHang || !B) return VDL2HIP_E_INVAL;
+	TxState s{}; s.acc = txl_none();
+	if(init && init[0]) { if(init[1] > hang_bins) return VDL2HIP_E_INVAL; s.open = 1u; s.idle = (uint32_t)init[1]; s.first = init[2]; s.flags = kTxPartial; }
+	TxState sp = s;                                                       // (k_txlog_plan's copy)
+	uint32_t nrec = 0, planned = 0;
+	for(uint32_t i = 0; i < count; i++) {
+		const uint32_t n = nbits[i];
+		if(n == 0 || n > 64) return VDL2HIP_E_INVAL;
+		uint64_t busy = 0;
+		for(uint32_t l = 0; l < n; l++) if(p[l] > thr) busy |= 1ull << l;
+		{
+			const TxMasks m = txl_masks(busy, n, hang_bins, sp.open, sp.idle);
+			planned += (uint32_t)__builtin_popcountll(m.closes);
+			txl_next(busy, m, n, hang_bins, base, txl_none(), sp);
+		}
+		const TxMasks m = txl_masks(busy, n, hang_bins, s.open, s.idle);
+		TxPart v[64];
+		for(uint32_t l = 0; l < 64; l++) v[l] = txl_lane(l < n && ((busy >> l) & 1ull), l < n ? p[l] : 0.f, base + l);
+		for(uint32_t d = 1; d < 64; d <<= 1) {
+			TxPart o[64];
+			for(uint32_t l = 0; l < 64; l++) o[l] = v[l >= d ? l - d : l];      // (__shfl_up)
+			for(uint32_t l = 0; l < 64; l++) if(txl_take(m.starts, l, d)) v[l] = txl_combine(o[l], v[l]);
+		}
+		for(uint32_t l = 0; l < 64; l++) if((m.closes >> l) & 1ull) {
+			if(nrec >= cap_recs) return VDL2HIP_E_TOOBIG;
+			vdl2hip_tx r{};
+			TxRec t;
+			txl_record(busy, m, l, base, s, v[l], 0u, 0u, k_on, B, t);
+			memcpy(&r, &t, sizeof t);
+			r.first_burst_ord = -1;
+			recs[nrec++] = r;
+		}
+		txl_next(busy, m, n, hang_bins, base, v[n - 1], s);
+		p += n; base += n;
+	}
+	if(planned != nrec || sp.open != s.open || sp.idle != s.idle) return VDL2HIP_E_DEVICE;
+	out[0] = s.open; out[1] = s.idle; out[2] = s.open ? s.first : 0; out[3] = s.open ? s.acc.cnt : 0;
+	return (int)nrec;
+}
+
 // test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
 // one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
 // series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.

@@ -24,6 +24,7 @@
 #include "spectrum.h"
 #include "spectrum_design.h"
 #include "activity.h"
+#include "txlog.h"
 #include "capture.h"
 #include "tables.h"
 #include "hostmem.h"
@@ -139,12 +140,18 @@ struct OutSlot {
 	Event ev_stitch, ev_chk; DevBuf<uint32_t> d_rqflag2;
 	// profiling level 2, per tap: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
 	// k_activity_power and k_activity_scan (activity monitor) / k_capture_plan and k_capture_copy (burst capture)
-	KernelTimes rs_t, mon_t, act_t, cap_t;
+	// / k_txlog_plan and k_txlog_emit (transmission log)
+	KernelTimes rs_t, mon_t, act_t, cap_t, txl_t;
 	// burst capture (capture.h): the feed's header and records (one allocation: the header and the first records come to the host in one
 	// small copy; d_rec = the records behind the header, not owned), windows and totals, the IQ pool, the small copy's page-locked landing
 	// place.  Given back as one when the capture is disabled (capture_free); cap_on: this feed's back end is followed by the capture's launches
 	struct { DevBuf<CapHdr> d_hdr; CapRec *d_rec = nullptr; DevBuf<CapPlan> d_plan; DevBuf<uint64_t> d_tot; DevBuf<cf32> d_pool; PinnedBuf h_mail; } cap;
 	bool cap_on = false;
+	// transmission log (txlog.h): the feed's header and record pool (one allocation, as the capture's: the header and the first records
+	// come to the host in one small copy; d_rec = the records behind the header, not owned) and that copy's page-locked landing place.
+	// Given back when the log is switched off (txlog_free); txl_on: this feed completed bins and the log's launches followed its scan
+	struct { DevBuf<TxHdr> d_hdr; TxRec *d_rec = nullptr; PinnedBuf h_mail; } txl;
+	bool txl_on = false;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -189,6 +196,16 @@ struct vdl2hip_ctx {
 		PinnedBuf stage;                                       // page-locked landing place of a feed's records and IQ, grown on demand (kept until the receiver goes)
 		std::deque<CapItem> queue;
 	} capt;
+	// Transmission log (txlog.h, vdl2hip_txlog_*): off unless enabled, and only beside the activity monitor.  buf: its per-channel state
+	// and counts, the staging place of a feed with more records than come with the header - given back as one (txlog_free).  queue: the
+	// records of the collected feeds, oldest first; wait: per channel the frames no record has claimed yet (txlog_collect)
+	struct TxFrame { int64_t sync_sample, burst_ord; bool ok; };
+	struct {
+		bool on = false; uint32_t pool = 0, flags = 0;
+		uint64_t transmissions = 0, decoded = 0, dropped = 0, matched = 0, unmatched = 0; double kernel_ms = 0.0;
+		struct { DevBuf<TxState> d_st; DevBuf<uint32_t> d_cnt; PinnedBuf stage; } buf;
+		std::deque<vdl2hip_tx> queue; std::vector<std::deque<TxFrame>> wait;
+	} txl;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
@@ -321,6 +338,7 @@ static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto);
 static bool feed_is_small(const vdl2hip_ctx *c, int64_t D);
 
 static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
+static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
@@ -330,6 +348,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.mon_t.collect(c->mon.kernel_ms);
 	sl.act_t.collect(c->act.kernel_ms);
 	sl.cap_t.collect(c->capt.kernel_ms);
+	sl.txl_t.collect(c->txl.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
 		const Event *ev = sl.ev;
 		float ms = 0.f;
@@ -380,6 +399,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 		}
 	}
 	if(sl.cap_on) { sl.cap_on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
+	if(c->txl.on) { int r = txlog_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	return ctl.overflow ? VDL2HIP_E_OVERFLOW : VDL2HIP_OK;
 }
 
@@ -403,6 +423,7 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0) {
 // scans, on the back streams) waits for an ev_front, which is recorded behind the sync kernels of its feed, and writes nothing at
 // or beyond that feed's last sample (k_ref_scan_multi: n_hi <= in_end / os - 1): what the monitor reads of this feed, [k0, k0 + D),
 // is the channeliser's.  Host bookkeeping: the bin the stream stands in, the bins this feed completes, which carry is current.
+static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb);
 static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
 	auto &m = c->act;
 	const uint64_t B = m.B, t0 = (uint64_t)(k0 - m.k_on), t1 = t0 + (uint64_t)D;
@@ -423,6 +444,9 @@ static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
 		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, sa);
 	}
 	HIPCHK(hipGetLastError());
+	// the transmission log reads the series and the bins this feed completed directly behind the scan (ahead of the mark: whoever waits
+	// for the monitor's last launch waits for the log's too)
+	if(c->txl.on && nb) { int r = txlog_launch(c, sl, m0, (uint32_t)nb); if(r != VDL2HIP_OK) return r; }
 	HIPCHK(m.tap.mark(c->streams.front));
 	t.launched(nb ? 2 : 1);
 	m.bins = m1; m.carry_sel ^= 1;
@@ -472,6 +496,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 
 	sl.ev_valid = false;
 	sl.cap_on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
+	sl.txl_on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
 		// (a cold-start feed launches the channeliser in pieces that wait for the pieces of the copy: not a kernel duration, not timed)
@@ -891,6 +916,9 @@ static_assert(sizeof(vdl2hip_capture_cfg) == 24 && sizeof(vdl2hip_capture_info) 
 static_assert(kCapMaxChan == kK5MaxChan, "k_capture_copy keeps every channel's offsets in LDS");
 constexpr uint32_t kCapMailRecs = 32;      // records that come to the host with the header, in one small copy (most feeds of a live receiver hold a handful of bursts)
 constexpr size_t kCapMailBytes = sizeof(CapHdr) + kCapMailRecs * sizeof(CapRec);
+// the transmission log: records that come to the host with the header; frames per channel that may wait for their record (txlog_collect)
+constexpr uint32_t kTxMailRecs = 32, kTxMaxWait = 4096;
+constexpr size_t kTxMailBytes = sizeof(TxHdr) + kTxMailRecs * sizeof(TxRec);
 
 static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
 	auto &m = c->capt;
@@ -954,6 +982,98 @@ static void capture_free(vdl2hip_ctx *c) {
 	c->capt.queue.clear();
 	c->capt.on = false;
 }
+
+// ---- the transmission log's share of a feed (txlog.h) ----
+static_assert(sizeof(TxRec) == 64 && sizeof(vdl2hip_tx) == 80 && offsetof(vdl2hip_tx, frames) == sizeof(TxRec) && offsetof(vdl2hip_tx, first_burst_ord) == 72
+              && offsetof(TxRec, first_bin) == offsetof(vdl2hip_tx, first_bin) && offsetof(TxRec, peak_bin) == offsetof(vdl2hip_tx, peak_bin)
+              && offsetof(TxRec, first_sample) == offsetof(vdl2hip_tx, first_sample) && offsetof(TxRec, busy_bins) == offsetof(vdl2hip_tx, busy_bins)
+              && offsetof(TxRec, mean_power) == offsetof(vdl2hip_tx, mean_power), "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_txlog_cfg) == 16 && sizeof(vdl2hip_txlog_info) == 64 && sizeof(TxHdr) == 16 && sizeof(TxState) == 48, "vdl2hip.h states these sizes");
+static_assert(kTxMaxChan == kK5MaxChan, "k_txlog_emit keeps every channel's offset in LDS");
+// Behind k_activity_scan of the same feed, on the front stream (activity_feed): the bins m0 .. m0 + nb - 1 the feed completed are in
+// the series ring (S >= the bins of the longest feed + 2) and stay there until the next feed's k_activity_power, which is queued behind.
+static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb) {
+	auto &m = c->txl; const auto &act = c->act;
+	TxArgs a{};
+	a.series = act.buf.d_series; a.freq = c->d_freq; a.st = m.buf.d_st; a.cnt = m.buf.d_cnt; a.rec = sl.txl.d_rec; a.hdr = sl.txl.d_hdr;
+	a.k_on = act.k_on; a.m0 = m0; a.thr = act.thr; a.nb = nb; a.H = act.H; a.B = act.B; a.S = act.S; a.smask = act.S - 1;
+	a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first; a.pool = m.pool;
+	KernelTimes &t = sl.txl_t;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_txlog_plan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
+	hipExtLaunchKernelGGL(k_txlog_emit, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, a);
+	HIPCHK(hipGetLastError());
+	t.launched(2);
+	sl.txl_on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed and the log.  The feed's frames first - all of them, whatever the AVLC filter lets through: they wait, per channel,
+// for the record whose window holds their sync_sample.  Then the feed's records (the first have come with the header): each takes the
+// waiting frames of its window; those before the window are counted as unmatched and dropped (vdl2hip.h, "Transmission log": Outcome).
+static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+	auto &m = c->txl;
+	for(uint32_t i = 0; i < nf; i++) {
+		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
+		auto &w = m.wait[(size_t)fr[i].chan];
+		if(w.size() >= kTxMaxWait) { w.pop_front(); m.unmatched++; }
+		w.push_back(vdl2hip_ctx::TxFrame{ fr[i].sync_sample, fr[i].burst_ord, fr[i].avlc_status == AVLC_OK });
+	}
+	if(!sl.txl_on) return VDL2HIP_OK;
+	sl.txl_on = false;
+	if(!sl.txl.h_mail) return VDL2HIP_OK;
+	const TxHdr h = *sl.txl.h_mail.as<TxHdr>();
+	const uint32_t nrec = std::min(h.nrec, m.pool);
+	m.dropped += h.dropped;
+	if(nrec == 0) return VDL2HIP_OK;
+	const TxRec *rec = reinterpret_cast<const TxRec *>(sl.txl.h_mail + sizeof(TxHdr));
+	if(nrec > kTxMailRecs) {
+		const size_t bytes = sizeof(TxRec) * (size_t)nrec;
+		HIPCHK(m.buf.stage.reserve(bytes));
+		HIPCHK(hipMemcpyAsync(m.buf.stage, sl.txl.d_rec, bytes, hipMemcpyDeviceToHost, c->streams.out));
+		HIPCHK(hipStreamSynchronize(c->streams.out));
+		rec = m.buf.stage.as<TxRec>();
+	}
+	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
+	for(uint32_t i = 0; i < nrec; i++) {
+		vdl2hip_tx r;
+		memcpy(&r, rec + i, sizeof(TxRec));
+		r.frames = r.frames_ok = 0; r.first_burst_ord = -1;
+		const int64_t close_sample = c->act.k_on + ((int64_t)r.last_bin + close_bins) * B;
+		int64_t first_sync = 0;
+		if(r.chan >= (uint32_t)c->chan_first && r.chan < (uint32_t)(c->chan_first + c->C)) {
+			auto &w = m.wait[r.chan - (uint32_t)c->chan_first];
+			size_t keep = 0;
+			for(const auto &f : w) {
+				if(f.sync_sample < r.first_sample) m.unmatched++;
+				else if(f.sync_sample < close_sample) {
+					if(!r.frames || f.sync_sample < first_sync) { first_sync = f.sync_sample; r.first_burst_ord = f.burst_ord; }
+					r.frames++; if(f.ok) r.frames_ok++;
+				} else w[keep++] = f;
+			}
+			w.resize(keep);
+		}
+		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
+		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
+		m.queue.push_back(r);
+	}
+	return VDL2HIP_OK;
+}
+// give the log's buffers back (nothing of it may be in flight: the callers have collected every feed and the front stream has run dry
+// of its launches; the slots' events stay)
+static void txlog_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) { sl.txl = {}; sl.txl_on = false; sl.txl_t.n = 0; }
+	auto &m = c->txl;
+	m.buf = {}; m.queue.clear(); m.wait.clear();
+	m.on = false;
+}
+// switch a running log off: the feeds under way are collected (their copies land in the slots' buffers), then everything goes
+static int txlog_off(vdl2hip_ctx *c) {
+	if(!c->txl.on) return VDL2HIP_OK;
+	if(!c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
+	(void)hipStreamSynchronize(c->streams.front);
+	txlog_free(c);
+	return VDL2HIP_OK;
+}
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const bool small = sl.small;
@@ -1014,6 +1134,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		                   c->d_acnt, (const float *)c->d_nfring, c->nf_ring - 1, sl.d_frames_out, sl.d_pool_out);
 		// the burst capture reads this feed's burst lists and y here: both passes of the burst decoder and its scans are done
 		if(sl.cap_on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		// the transmission log's header and first records of this feed (written on the front stream ahead of the sync kernels: long done)
+		if(sl.txl_on) HIPCHK(hipMemcpyAsync(sl.txl.h_mail, sl.txl.d_hdr, kTxMailBytes, hipMemcpyDeviceToHost, s5_));
 	}
 	// the control block and the first few delivered frames in one copy (collect_slot)
 	HIPCHK(hipMemcpyAsync(sl.h_mail, sl.d_mail, sizeof(OutMail), hipMemcpyDeviceToHost, s5_));
@@ -1790,6 +1912,7 @@ int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
 	uint32_t S = 1; while(S < cfg->series_bins || S < c->dmax / B + 2) S <<= 1;           // a feed's bins never overwrite one another in the ring
 	OnDevice dev_guard(c);
 	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }          // (a transmission log's state would no longer mean anything)
 	auto &m = c->act;
 	activity_free(c);
 	for(auto &sl : c->slot) sl.act_t.n = 0;                          // (what an earlier monitor's launches took is not this one's)
@@ -1812,6 +1935,7 @@ int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
 int vdl2hip_activity_disable(vdl2hip_ctx *c) {
 	if(!c) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
+	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }
 	activity_free(c);
 	for(auto &sl : c->slot) sl.act_t.n = 0;
 	return VDL2HIP_OK;
@@ -1923,6 +2047,61 @@ int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, f
 		q.pop_front();
 	}
 	if(pairs_used) *pairs_used = used;
+	return (int)n;
+}
+
+// ---- the transmission log (vdl2hip.h, "Transmission log"; kernels: txlog.h) ----
+int vdl2hip_txlog_enable(vdl2hip_ctx *c, const vdl2hip_txlog_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txlog_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(!c->act.on || cfg->pool_records > kTxMaxPool || (cfg->flags & ~VDL2HIP_TXLOG_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier log is in flight any more
+	(void)hipStreamSynchronize(c->streams.front);
+	auto &m = c->txl;
+	txlog_free(c);
+	const uint32_t pool = cfg->pool_records ? cfg->pool_records : kTxDefPool;
+	const size_t C = (size_t)c->C;
+	bool ok = m.buf.d_st.alloc(C) == hipSuccess && m.buf.d_cnt.alloc(C, true) == hipSuccess;
+	for(auto &sl : c->slot) {
+		auto &b = sl.txl;
+		ok = ok && b.d_hdr.alloc_bytes(sizeof(TxHdr) + (size_t)std::max(pool, kTxMailRecs) * sizeof(TxRec)) == hipSuccess && b.h_mail.alloc(kTxMailBytes, true) == hipSuccess;
+		if(!ok) break;
+		b.d_rec = reinterpret_cast<TxRec *>(b.d_hdr.get() + 1);
+		ok = hipMemset(b.d_hdr, 0, kTxMailBytes) == hipSuccess;
+	}
+	if(!ok) { (void)hipGetLastError(); txlog_free(c); return VDL2HIP_E_NOMEM; }
+	// the log's state from the monitor's, on the front stream: behind every scan queued so far, ahead of the next feed's
+	hipLaunchKernelGGL(k_txlog_init, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->streams.front, (const ActState *)c->act.buf.d_st.get(), m.buf.d_st.get(), (uint32_t)C);
+	if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txlog_free(c); return VDL2HIP_E_DEVICE; }
+	m.wait.assign(C, {});
+	m.pool = pool; m.flags = cfg->flags;
+	m.transmissions = m.decoded = m.dropped = m.matched = m.unmatched = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_txlog_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	return txlog_off(c);
+}
+
+int vdl2hip_txlog_info_get(vdl2hip_ctx *c, vdl2hip_txlog_info *info) {
+	if(!c || !c->txl.on || !info || info->struct_size != sizeof(vdl2hip_txlog_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->txl;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->pool_records = m.pool; info->flags = m.flags;
+	info->transmissions = m.transmissions; info->decoded = m.decoded; info->dropped = m.dropped;
+	info->frames_matched = m.matched; info->frames_unmatched = m.unmatched; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_txlog_read(vdl2hip_ctx *c, vdl2hip_tx *recs, size_t cap_recs) {
+	if(!c || !c->txl.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
+	auto &q = c->txl.queue;
+	size_t n = 0;
+	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
 	return (int)n;
 }
 

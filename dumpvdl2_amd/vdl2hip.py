@@ -48,7 +48,9 @@ EXPORTS = [
     "vdl2hip_spectrum_window", "vdl2hip_spectrum_enable", "vdl2hip_spectrum_read", "vdl2hip_spectrum_channels",
     "vdl2hip_activity_edges", "vdl2hip_activity_enable", "vdl2hip_activity_disable", "vdl2hip_activity_read", "vdl2hip_activity_series",
     "vdl2hip_capture_enable", "vdl2hip_capture_disable", "vdl2hip_capture_info_get", "vdl2hip_capture_read",
+    "vdl2hip_txlog_enable", "vdl2hip_txlog_disable", "vdl2hip_txlog_info_get", "vdl2hip_txlog_read",
 ]
+TXLOG_UNDECODED_ONLY, TX_PARTIAL = 1, 1     # include/vdl2hip.h: VDL2HIP_TXLOG_UNDECODED_ONLY (cfg.flags), VDL2HIP_TX_PARTIAL (vdl2hip_tx.flags)
 CAPTURE_FAILED_ONLY, BURST_NO_ROOM = 1, 1   # include/vdl2hip.h: VDL2HIP_CAPTURE_FAILED_ONLY (cfg.flags), VDL2HIP_BURST_NO_ROOM (vdl2hip_burst.flags)
 WIN_RECT, WIN_HANN, WIN_BH4 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_WIN_* (the input monitor's analysis windows)
 
@@ -135,6 +137,22 @@ BURST_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("burst_ord", "<i8"), 
                         ("phase_err_rms", "<f4"), ("phase_err_mean", "<f4"), ("phase_err_max", "<f4")])     # vdl2hip_burst, 128 bytes
 
 
+class TxlogCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pool_records", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TxlogInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pool_records", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("transmissions", C.c_uint64), ("decoded", C.c_uint64), ("dropped", C.c_uint64),
+                ("frames_matched", C.c_uint64), ("frames_unmatched", C.c_uint64), ("kernel_ms", C.c_float), ("reserved2", C.c_uint32)]
+
+
+TX_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("last_bin", "<u8"), ("peak_bin", "<u8"),
+                     ("first_sample", "<i8"), ("last_sample", "<i8"), ("busy_bins", "<u4"), ("flags", "<u4"),
+                     ("peak_power", "<f4"), ("mean_power", "<f4"), ("frames", "<u4"), ("frames_ok", "<u4"),
+                     ("first_burst_ord", "<i8")])     # vdl2hip_tx, 80 bytes
+
+
 class PackedFrame(C.Structure):
     _fields_ = [("frame", CFrame), ("octets_off", C.c_uint64)]
 
@@ -205,6 +223,11 @@ def load_library(path: str = None):
         L.vdl2hip_capture_disable.argtypes = [C.c_void_p]
         L.vdl2hip_capture_info_get.argtypes = [C.c_void_p, C.POINTER(CaptureInfo)]
         L.vdl2hip_capture_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "vdl2hip_txlog_enable"):                  # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_txlog_enable.argtypes = [C.c_void_p, C.POINTER(TxlogCfg)]
+        L.vdl2hip_txlog_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_txlog_info_get.argtypes = [C.c_void_p, C.POINTER(TxlogInfo)]
+        L.vdl2hip_txlog_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -361,6 +384,29 @@ def _capture_read(Lib, ctx, cap_recs: int = 4096, cap_pairs: int = 1 << 20):
             wins.append(iq[off:off + cnt].copy().view(np.complex64).reshape(-1))
             out.append(d)
     return out, wins
+
+
+def _txlog_enable(Lib, ctx, undecoded_only, pool_records) -> None:
+    cfg = TxlogCfg(C.sizeof(TxlogCfg), pool_records, TXLOG_UNDECODED_ONLY if undecoded_only else 0, 0)
+    _err(Lib, Lib.vdl2hip_txlog_enable(ctx, C.byref(cfg)), "vdl2hip_txlog_enable")
+
+
+def _txlog_info(Lib, ctx) -> dict:
+    info = TxlogInfo(C.sizeof(TxlogInfo))
+    _err(Lib, Lib.vdl2hip_txlog_info_get(ctx, C.byref(info)), "vdl2hip_txlog_info_get")
+    return {k: getattr(info, k) for k, _ in TxlogInfo._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+
+
+def _txlog_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
+    """vdl2hip_txlog_read() until nothing more comes -> the records as one array of TX_DTYPE (cap_recs: the buffer of one call)"""
+    buf = np.zeros(max(1, cap_recs), dtype=TX_DTYPE)
+    out = []
+    while True:
+        n = _err(Lib, Lib.vdl2hip_txlog_read(ctx, buf.ctypes.data, cap_recs), "vdl2hip_txlog_read")
+        if n == 0:
+            break
+        out.append(buf[:n].copy())
+    return np.concatenate(out) if out else np.zeros(0, dtype=TX_DTYPE)
 
 
 def live_resources() -> dict:
@@ -607,6 +653,23 @@ class Receiver:
         """up to `count` bin powers p[first_bin ...] of channel `chan` (its index in the frequency list), float32"""
         return _activity_series(self.L, self.h, chan, first_bin, count)
 
+    def txlog_enable(self, undecoded_only: bool = False, pool_records: int = 0) -> None:
+        """switch the transmission log on from the next feed (vdl2hip.h, "Transmission log"; needs the activity monitor): one record
+        per transmission the monitor sees, with the frames it yielded.  undecoded_only: deliver only transmissions without a good
+        frame; pool_records: records a feed may log (0: 65 536)."""
+        _txlog_enable(self.L, self.h, undecoded_only, pool_records)
+
+    def txlog_disable(self) -> None:
+        self._chk(self.L.vdl2hip_txlog_disable(self.h), "vdl2hip_txlog_disable")
+
+    def txlog_info(self) -> dict:
+        """the fields of vdl2hip_txlog_info: the configuration in force and the totals of the feeds collected so far"""
+        return _txlog_info(self.L, self.h)
+
+    def txlog_read(self, cap_recs: int = 4096) -> np.ndarray:
+        """the records of the feeds collected so far (sync() or a drain first), oldest first, as an array of TX_DTYPE"""
+        return _txlog_read(self.L, self.h, cap_recs)
+
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """switch the burst capture on from the next feed (vdl2hip.h, "Burst capture"): of every burst handed to the burst decoder the
         decimated IQ from `pre` samples before its sync to `post` after its last symbol, its timing and a phase-error quality figure.
@@ -728,7 +791,7 @@ class ReceiverGroup:
         raise Vdl2HipError("no member owns that channel")
 
     def member(self, i: int):
-        """the context handle of member i (vdl2hip_group_ctx): what the per-context calls take - vdl2hip_spectrum_*, vdl2hip_activity_*"""
+        """the context handle of member i (vdl2hip_group_ctx): what the per-context calls take - vdl2hip_spectrum_*, vdl2hip_activity_*, vdl2hip_capture_*, vdl2hip_txlog_*"""
         return C.c_void_p(self.L.vdl2hip_group_ctx(self.h, i))
 
     def activity_enable(self, bin_samples: int = 105, threshold_dbfs: float = -40.0, hang_bins: int = 0, series_bins: int = 0) -> None:
@@ -752,6 +815,22 @@ class ReceiverGroup:
             if n >= 0:
                 return buf[:n]
         raise Vdl2HipError("no member holds that channel and bin")
+
+    def txlog_enable(self, undecoded_only: bool = False, pool_records: int = 0) -> None:
+        """the transmission log of every member (there is no group call: each member logs its own channels)"""
+        for i in range(self.size()):
+            _txlog_enable(self.L, self.member(i), undecoded_only, pool_records)
+
+    def txlog_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_txlog_disable(self.member(i)), "vdl2hip_txlog_disable")
+
+    def txlog_info(self, member: int) -> dict:
+        return _txlog_info(self.L, self.member(member))
+
+    def txlog_read(self, member: int, cap_recs: int = 4096) -> np.ndarray:
+        """Receiver.txlog_read() of one member: its own channels' transmissions (chan: the index in the group's frequency list)"""
+        return _txlog_read(self.L, self.member(member), cap_recs)
 
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """the burst capture of every member (there is no group call: each member captures its own channels' bursts)"""

@@ -46,7 +46,9 @@ extern "C" {
                                  *    vdl2hip_capture_enable() / _disable() / _info_get() / _read() with vdl2hip_capture_cfg / _info and vdl2hip_burst: the
                                  *    burst capture, off unless enabled - new entry points and structures only once more, so the version stayed
                                  *    VDL2HIP_FMT_S8 (4): one more accepted value of vdl2hip_cfg.sample_fmt, as VDL2HIP_FMT_CF32 was - no structure, no
-                                 *    entry point and no result for the other formats changed, so the version stayed */
+                                 *    entry point and no result for the other formats changed, so the version stayed
+                                 *    vdl2hip_txlog_enable() / _disable() / _info_get() / _read() with vdl2hip_txlog_cfg / _info and vdl2hip_tx: the
+                                 *    transmission log, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -295,6 +297,67 @@ typedef struct {
 	uint32_t reserved2;
 } vdl2hip_capture_info;                        /* 56 bytes */
 
+/* Transmission log (not in the reference): every transmission the activity monitor sees on a channel, one record each - its time,
+ * length and level, and the frames it yielded - so that what was on the air can be set against what was decoded: a collision, a burst
+ * too weak to synchronise, a foreign carrier are records with frames_ok == 0.  It sits on top of the activity monitor and needs it
+ * enabled: it uses the monitor's bins p_c[m], its threshold_power, its hang_bins H and its transmission rule as stated above, and
+ * changes none of them.  Off unless enabled; with it off nothing is launched or allocated and every result is what it was, to the
+ * bit.  On, frames, counters, the decimated stream and everything the activity monitor reports are still exactly what they were: the
+ * log reads the monitor's series and keeps a per-channel state of its own (initialised from the monitor's when it is enabled).
+ *  - Closing.  A transmission with last busy bin l is CLOSED once bin l + H + 1 is complete.  The feed that completes that bin emits
+ *    its record.  Which records exist after N samples depends on the stream alone, not on how it was cut into feeds.  A transmission
+ *    still open when the stream ends is not logged; it shows in vdl2hip_activity_chan.open.
+ *  - Record.  first_bin, last_bin: its first and last BUSY bin, counted from k_on like vdl2hip_activity_series(); peak_bin: the lowest
+ *    bin among those with the largest p; first_sample = k_on + first_bin B, last_sample = k_on + (last_bin + 1) B - 1 (the 105 kS/s
+ *    clock of sync_sample); busy_bins; peak_power = max p (float32 comparison); mean_power = (float)(S / busy_bins), S = the float64
+ *    sum of p over the busy bins.
+ *  - Partial records.  VDL2HIP_TX_PARTIAL marks a transmission that was already open when the log took effect.  Its first_bin is the
+ *    activity monitor's; its busy_bins, peak_* and mean_power cover only bins from the log's first feed on (none of them busy:
+ *    busy_bins, peak_power and mean_power are 0 and peak_bin = first_bin).
+ *  - Accuracy of S.  Summed in float64 in an order fixed by the bins and by where the feeds were cut (no floating-point atomics): the
+ *    same sequence of calls gives the same bytes; against any other order S is within busy_bins 2^-53 relative, every term being
+ *    non-negative, so mean_power is within one float32 ulp (2^-23 relative) of any model.  Every other field is exact.
+ *  - Order.  The records of one feed are ordered by (channel, first_bin); feeds follow one another in feed order.  Per channel the
+ *    sequence of records is independent of the cuts.
+ *  - Room.  Each feed in flight has room for pool_records records (0 means 65 536; above 2^22 is refused).  Offsets are the exclusive
+ *    prefix sum of the channels' counts in record order; records beyond the room are not written and vdl2hip_txlog_info.dropped
+ *    counts them.  Offsets only grow, so what survives is a prefix.
+ *  - Outcome, joined on the host when the feed is collected - the feed's frames first, all of them, independent of
+ *    vdl2hip_set_avlc_filter().  With close_sample = k_on + (last_bin + H + 2) B, a transmission's window is [first_sample,
+ *    close_sample); the windows of consecutive transmissions on a channel are disjoint by construction.  A frame belongs to the record
+ *    whose window holds its sync_sample: frames = the frames attributed, frames_ok = those with avlc_status == VDL2HIP_AVLC_OK,
+ *    first_burst_ord = burst_ord of the attributed frame with the lowest sync_sample, -1 without one.  The host keeps the frames of a
+ *    channel that no record has claimed yet (the newest 4 096 per channel; older ones count as unmatched).  When a record arrives,
+ *    waiting frames with sync_sample < first_sample are counted in frames_unmatched and dropped: they were locked below the threshold,
+ *    or arrived after their window's record had gone.  The latter happens when a burst outlasts its own transmission - a fade below
+ *    the threshold for more than H bins while the decoder runs on - so that its frames come with a later feed than the record: THE
+ *    ONE PLACE WHERE THE OUTCOME DEPENDS ON HOW THE STREAM WAS CUT INTO FEEDS.  Raise hang_bins where that matters.
+ *  - VDL2HIP_TXLOG_UNDECODED_ONLY delivers only the records with frames_ok == 0 (filtered on the host: the device logs everything and
+ *    vdl2hip_txlog_info counts everything).
+ *  - vdl2hip_activity_enable() and vdl2hip_activity_disable() switch a running log off first (the feeds under way are collected, what
+ *    is queued unread is dropped): its state would no longer mean anything.  vdl2hip_activity_read(..., reset) does not touch the log.
+ *  - chan is the index in cfg.freqs.  Groups get no group call: vdl2hip_group_ctx(g, k) is the handle for member k's channels. */
+#define VDL2HIP_TXLOG_UNDECODED_ONLY 1u
+#define VDL2HIP_TX_PARTIAL           1u
+typedef struct { uint32_t struct_size, pool_records, flags, reserved; } vdl2hip_txlog_cfg;      /* 16 bytes; reserved must be 0 */
+typedef struct {
+	uint32_t chan, freq;                  /* index in cfg.freqs, Hz */
+	uint64_t first_bin, last_bin;         /* first and last BUSY bin */
+	uint64_t peak_bin;
+	int64_t  first_sample, last_sample;
+	uint32_t busy_bins, flags;            /* VDL2HIP_TX_* */
+	float    peak_power, mean_power;
+	uint32_t frames, frames_ok;           /* filled in by the host, like first_burst_ord */
+	int64_t  first_burst_ord;
+} vdl2hip_tx;                                  /* 80 bytes: the device writes the first 64 */
+typedef struct {
+	uint32_t struct_size, pool_records, flags, reserved;   /* as in force */
+	uint64_t transmissions, decoded, dropped;  /* of the feeds collected so far: records logged, those with frames_ok > 0, records without room */
+	uint64_t frames_matched, frames_unmatched;
+	float    kernel_ms;                        /* summed HIP-event time of the log's launches at profiling level 2, else 0 */
+	uint32_t reserved2;
+} vdl2hip_txlog_info;                          /* 64 bytes */
+
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
 typedef struct {
@@ -526,9 +589,10 @@ int  vdl2hip_spectrum_channels(vdl2hip_ctx *ctx, float *dbfs, size_t cap);
 int  vdl2hip_activity_edges(float *edges, size_t cap);
 /* Switch the monitor on.  Allowed between feeds; takes effect with the next feed.  Enabling again restarts at the then-current
  * decimated sample with zeroed state.  VDL2HIP_E_INVAL for a bad struct_size, bin_samples, hang_bins, series_bins, threshold or
- * reserved, before anything is allocated or changed: a monitor that was on stays as it was. */
+ * reserved, before anything is allocated or changed: a monitor that was on stays as it was.  A transmission log that is running is
+ * switched off first (vdl2hip_txlog_disable()). */
 int  vdl2hip_activity_enable(vdl2hip_ctx *ctx, const vdl2hip_activity_cfg *cfg);
-/* Switch it off: its buffers are freed, later feeds launch nothing. */
+/* Switch it off: its buffers are freed, later feeds launch nothing.  A transmission log that is running is switched off first. */
 int  vdl2hip_activity_disable(vdl2hip_ctx *ctx);
 /* What the monitor has accumulated.  Waits only for the monitor's own work queued so far (an event behind its last launch), delivers
  * no frames and changes nothing in what vdl2hip_drain() or vdl2hip_sync() later return.  info->struct_size must be set.  chans[i] is
@@ -553,6 +617,21 @@ int  vdl2hip_capture_info_get(vdl2hip_ctx *ctx, vdl2hip_capture_info *info);
  * or their IQ - stays queued for the next call; the call never waits for the device itself.  Returns the number of records written,
  * *pairs_used the pairs (pairs_used may be NULL).  Capture off: VDL2HIP_E_INVAL. */
 int  vdl2hip_capture_read(vdl2hip_ctx *ctx, vdl2hip_burst *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used);
+
+/* ---- Transmission log (see "Transmission log" above) ----
+ * Switch the log on.  Allowed between feeds; takes effect with the next feed: its state is taken from the activity monitor's as it
+ * stands behind the feeds queued so far.  Enabling again collects the feeds under way, drops what is queued unread and starts afresh.
+ * VDL2HIP_E_INVAL if the activity monitor is off, or for a bad struct_size, pool_records, flags or reserved, before anything is
+ * allocated or changed: a log that was on stays as it was. */
+int  vdl2hip_txlog_enable(vdl2hip_ctx *ctx, const vdl2hip_txlog_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_txlog_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Log off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txlog_info_get(vdl2hip_ctx *ctx, vdl2hip_txlog_info *info);
+/* Like vdl2hip_capture_read(): the records of the feeds collected so far (by vdl2hip_sync() or a drain, which respects the drain
+ * lag), oldest first.  What does not fit stays queued for the next call; the call never waits for the device itself.  Returns the
+ * number of records written.  Log off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txlog_read(vdl2hip_ctx *ctx, vdl2hip_tx *recs, size_t cap_recs);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,11 @@
  *   --activity-bin <samples>      bin length in decimated samples, 10 .. 10500 (default 105 = 1 ms)
  *   --activity-threshold <dBFS>   a bin above it is busy (default -40)
  *   --activity-hang <bins>        idle bins a transmission bridges, 0 .. 255 (default 0)
+ *   --tx-out <path>               (this library's own) switch the transmission log on - and with it the activity monitor, which the
+ *                                 --activity-* options above configure - and, at exit, write every transmission the channels carried,
+ *                                 decoded or not: a "# key value" line per field of vdl2hip_txlog_info, then per transmission
+ *                                 "chan freq_hz first_sample length_ms peak_dbfs mean_dbfs frames frames_ok flags", then per channel
+ *                                 "# channel <chan> <freq_hz> transmissions=<n> decoded=<n> ratio=<decoded / transmissions>"
  *   --bursts-out <path>           (this library's own) switch the burst capture on and, at exit, write every burst handed to the burst decoder,
  *                                 decoded or not: a "# key value" line per field of vdl2hip_capture_info, then per burst every field of
  *                                 vdl2hip_burst in the structure's order - "chan freq burst_ord sync_sample end_sample first_symbol nsym
@@ -99,6 +104,25 @@ static int take_bursts(vdl2hip_ctx *rx) {
 	}
 }
 
+/* transmission log: the records so far (written at exit, behind the totals) */
+static vdl2hip_tx *txs;
+static size_t ntxs, cap_txs;
+static int take_tx(vdl2hip_ctx *rx) {
+	enum { RECS = 256 };
+	static vdl2hip_tx rec[RECS];
+	for(;;) {
+		const int n = vdl2hip_txlog_read(rx, rec, RECS);
+		if(n <= 0) return n;
+		if(ntxs + (size_t)n > cap_txs) {
+			cap_txs = 2 * (ntxs + (size_t)n);
+			txs = realloc(txs, cap_txs * sizeof *txs);
+			if(!txs) { perror("realloc"); exit(3); }
+		}
+		memcpy(txs + ntxs, rec, (size_t)n * sizeof *rec);
+		ntxs += (size_t)n;
+	}
+}
+
 static void on_frame(const vdl2hip_frame *f, void *user) {
 	(void)user;
 	nframes++;
@@ -121,7 +145,7 @@ int main(int argc, char **argv) {
 	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
-	const char *bursts_path = NULL, *bursts_iq_path = NULL;
+	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL;
 	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
@@ -161,6 +185,7 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--activity-bin")) { NEEDARG(); activity_bin = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--activity-threshold")) { NEEDARG(); activity_thr = strtof(argv[++i], NULL); }
 		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--tx-out")) { NEEDARG(); tx_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-out")) { NEEDARG(); bursts_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-iq")) { NEEDARG(); bursts_iq_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-failed-only")) bursts_flags |= VDL2HIP_CAPTURE_FAILED_ONLY;
@@ -174,7 +199,7 @@ int main(int argc, char **argv) {
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32|S8] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
-			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] "
+			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] "
 			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
@@ -217,11 +242,15 @@ int main(int argc, char **argv) {
 			fprintf(stderr, "vdl2hip_spectrum_enable: %s\n", vdl2hip_strerror(spectrum_nfft ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
-	if(activity_path) {
+	if(activity_path || tx_path) {
 		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
 		if(activity_bin == 0 || (r = vdl2hip_activity_enable(rx, &ac)) != VDL2HIP_OK) {
 			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
 		}
+	}
+	if(tx_path) {
+		vdl2hip_txlog_cfg tc = { sizeof tc, 0, 0, 0 };
+		if((r = vdl2hip_txlog_enable(rx, &tc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txlog_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
 	if(bursts_path) {
 		vdl2hip_capture_cfg cc = { sizeof cc, bursts_pre, bursts_post, bursts_flags, 0, 0 };
@@ -240,6 +269,7 @@ int main(int argc, char **argv) {
 		if((r = vdl2hip_feed(rx, buf, held)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_feed: %s\n", vdl2hip_strerror(r)); return 3; }
 		if((r = vdl2hip_drain(rx, on_frame, NULL)) < 0) { fprintf(stderr, "vdl2hip_drain: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		held = 0;
 	} while(len == FILE_BUFSIZE);
 	free(buf);
@@ -319,6 +349,30 @@ int main(int argc, char **argv) {
 		}
 		else fprintf(stderr, "bursts not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
 		if(bursts_iq) fclose(bursts_iq);
+	}
+	if(tx_path) {
+		vdl2hip_txlog_info ti;
+		memset(&ti, 0, sizeof ti); ti.struct_size = sizeof ti;
+		r = vdl2hip_txlog_info_get(rx, &ti);
+		FILE *so = r == VDL2HIP_OK ? fopen(tx_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# pool_records %u\n# flags %u\n# transmissions %" PRIu64 "\n# decoded %" PRIu64 "\n# dropped %" PRIu64 "\n", ti.pool_records, ti.flags,
+					ti.transmissions, ti.decoded, ti.dropped);
+			fprintf(so, "# frames_matched %" PRIu64 "\n# frames_unmatched %" PRIu64 "\n# kernel_ms %.6g\n", ti.frames_matched, ti.frames_unmatched, (double)ti.kernel_ms);
+			static uint64_t ch_tx[1024], ch_ok[1024];
+			for(size_t i = 0; i < ntxs; i++) {
+				const vdl2hip_tx *t = &txs[i];
+				fprintf(so, "%u %u %" PRId64 " %.3f %.2f %.2f %u %u %u\n", t->chan, t->freq, t->first_sample,
+						1000.0 * (double)(t->last_sample - t->first_sample + 1) / (SYMBOL_RATE * 10.0), dbfs_of((double)t->peak_power), dbfs_of((double)t->mean_power),
+						t->frames, t->frames_ok, t->flags);
+				if(t->chan < 1024) { ch_tx[t->chan]++; if(t->frames_ok) ch_ok[t->chan]++; }
+			}
+			for(uint32_t c = 0; c < nfreq; c++)
+				fprintf(so, "# channel %u %u transmissions=%" PRIu64 " decoded=%" PRIu64 " ratio=%.4f\n", c, freqs[c], ch_tx[c], ch_ok[c],
+						ch_tx[c] ? (double)ch_ok[c] / (double)ch_tx[c] : 0.0);
+			fclose(so);
+		}
+		else fprintf(stderr, "transmissions not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
