@@ -217,6 +217,93 @@ int vdl2hip_debug_frame_finish(unsigned grid, const void *frames_in, uint32_t nr
 	return VDL2HIP_OK;
 }
 
+// test hook (not declared in vdl2hip.h; tests/test_gpu_nf_probe.py): K4b, the noise-floor replay, on the caller's inputs - one call is one feed
+// of nchan channels.  y [nchan][ring_len] (cf32, ring_len a power of two), the feed's evaluation logs chunks [nchan][cap_log] (EvalChunk) and
+// nlog [nchan], the channels' NfState (nf: nchan * vdl2hip_debug_sizeof_nfstate() octets, in and out) and the history rings ring [nchan][nf_ring]
+// (in and out, nf_ring a power of two).  mode 0: k_nf_prepare, k_nf_replay on dim3(grid, nchan), k_nf_finish, as a long feed launches them;
+// mode 1: k_nf_all, as a short one does (grid is not used).  The dynamic LDS is the product's; cap_comb is the product's cap_log + kNfTail plus
+// a guard of 64 entries behind every channel's row of the two scratch lists.
+// Returned besides: lpbuf [nchan][cap_hist] (0xA5 where nothing was written) and the feed records (NfFeed [nchan]).
+// Refused (VDL2HIP_E_INVAL) is what the product cannot have: nlog > cap_log, a state that does not add up, a feed with more than cap_hist - 1
+// updates, a history ring shorter than cap_hist.  Behind lpbuf, the rings and the two scratch lists lie kNfProbeGuard octets each, and behind every
+// channel's rows of the scratch lists the row guard, all filled with 0xA5 beforehand: VDL2HIP_E_DEVICE if any of it has changed (in lpbuf and
+// the rings a store beyond a channel's own row lands in the next channel's, which the caller sees in what comes back).  Needs no receiver
+int vdl2hip_debug_sizeof_nfstate(void) { return (int)sizeof(NfState); }
+int vdl2hip_debug_sizeof_nffeed(void) { return (int)sizeof(NfFeed); }
+int vdl2hip_debug_nf_probe(int mode, unsigned grid, uint32_t nchan, const float *y, uint32_t ring_len, const void *chunks, const uint32_t *nlog, uint32_t cap_log,
+		void *nf, float *ring, uint32_t nf_ring, uint32_t cap_hist, float *lpbuf, void *feeds) {
+	constexpr size_t kNfProbeGuard = 4096;
+	if(mode < 0 || mode > 1 || grid == 0 || grid > 64 || nchan == 0 || nchan > 1024 || !y || ring_len < 64 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || !chunks || !nlog
+	   || cap_log == 0 || cap_log > 1u << 16 || !nf || !ring || nf_ring == 0 || (nf_ring & (nf_ring - 1)) || nf_ring > 1u << 20 || cap_hist < 2 || cap_hist > nf_ring || !lpbuf || !feeds) return VDL2HIP_E_INVAL;
+	const EvalChunk *hc = static_cast<const EvalChunk *>(chunks);
+	const NfState *hs = static_cast<const NfState *>(nf);
+	for(uint32_t c = 0; c < nchan; c++) {
+		const NfState &s = hs[c];
+		if(nlog[c] > cap_log || s.ntail < 0 || s.ntail > kNfTail || s.evals < 0 || s.tail_ord < 0) return VDL2HIP_E_INVAL;
+		int64_t ord = s.tail_ord;
+		for(int i = 0; i < s.ntail; i++) { if(s.tail[i].count < 1 || s.tail[i].count > (int64_t)1 << 32 || s.tail[i].first < 0) return VDL2HIP_E_INVAL; ord += s.tail[i].count; }
+		if(ord != s.evals) return VDL2HIP_E_INVAL;
+		for(uint32_t i = 0; i < nlog[c]; i++) { const EvalChunk &k = hc[(size_t)c * cap_log + i]; if(k.count < 1 || k.count > (int64_t)1 << 32 || k.first < 0) return VDL2HIP_E_INVAL; ord += k.count; }
+		if(ord / 1000 - s.evals / 1000 > (int64_t)cap_hist - 1) return VDL2HIP_E_INVAL;
+	}
+	// (the scratch lists' rows are cap_comb + 1 long in the kernels: the row guard is part of cap_comb here, which changes nothing else -
+	// cap_comb only bounds ntail + nlog, and that is kNfTail + cap_log at the most)
+	constexpr uint32_t kNfRowGuard = 64;
+	const uint32_t cap_comb = cap_log + (uint32_t)kNfTail + kNfRowGuard;
+	const size_t nsc = (size_t)nchan * (cap_comb + 1), nlp = (size_t)nchan * cap_hist, nring = (size_t)nchan * nf_ring, gw = kNfProbeGuard / 4, gq = kNfProbeGuard / 8;
+	DevBuf<cf32> d_y; DevBuf<NfState> d_nf; DevBuf<EvalChunk> d_log; DevBuf<uint32_t> d_nlog; DevBuf<int64_t> d_scf, d_scc; DevBuf<NfFeed> d_feed; DevBuf<float> d_lp, d_ring;
+	if(!hip_ok(d_y.alloc((size_t)nchan * ring_len)) || !hip_ok(d_nf.alloc(nchan)) || !hip_ok(d_log.alloc((size_t)nchan * cap_log)) || !hip_ok(d_nlog.alloc(nchan)) || !hip_ok(d_scf.alloc(nsc + gq))
+	   || !hip_ok(d_scc.alloc(nsc + gq)) || !hip_ok(d_feed.alloc(nchan)) || !hip_ok(d_lp.alloc(nlp + gw)) || !hip_ok(d_ring.alloc(nring + gw))) return VDL2HIP_E_NOMEM;
+	if(!dbg_up(d_y, y) || !dbg_up(d_nf, nf) || !dbg_up(d_log, chunks) || !dbg_up(d_nlog, nlog) || !dbg_fill(d_scf, 0xA5) || !dbg_fill(d_scc, 0xA5) || !dbg_fill(d_feed, 0xA5) || !dbg_fill(d_lp, 0xA5)
+	   || !dbg_fill(d_ring, 0xA5) || !dbg_up(d_ring, ring, nring * sizeof(float))) return VDL2HIP_E_DEVICE;
+	K4bArgs a{ d_y, d_nf, d_log, d_nlog, d_scf, d_scc, d_feed, d_lp, d_ring, nf_ring - 1, ring_len, ring_len - 1, cap_log, cap_comb, cap_hist, (int32_t)nchan };
+	const unsigned nf_lds = (unsigned)(sizeof(NfShared) * kNfWaves), nf_grid = (unsigned)((nchan + kNfWaves - 1) / kNfWaves);
+	if(mode == 0) {
+		hipLaunchKernelGGL(k_nf_prepare, dim3(nf_grid), dim3(64 * kNfWaves), nf_lds, 0, a);
+		hipLaunchKernelGGL(k_nf_replay, dim3(grid, nchan), dim3(64 * kNfWaves), nf_lds, 0, a);
+		hipLaunchKernelGGL(k_nf_finish, dim3(nf_grid), dim3(64 * kNfWaves), nf_lds, 0, a);
+	} else hipLaunchKernelGGL(k_nf_all, dim3(nf_grid), dim3(64 * kNfWaves), nf_lds, 0, a);
+	if(!hip_ok(hipGetLastError()) || !hip_ok(hipDeviceSynchronize())) return VDL2HIP_E_DEVICE;
+	std::vector<uint8_t> g(4 * kNfProbeGuard);
+	if(!hip_ok(hipMemcpy(g.data(), d_scf.get() + nsc, kNfProbeGuard, hipMemcpyDeviceToHost)) || !hip_ok(hipMemcpy(g.data() + kNfProbeGuard, d_scc.get() + nsc, kNfProbeGuard, hipMemcpyDeviceToHost))
+	   || !hip_ok(hipMemcpy(g.data() + 2 * kNfProbeGuard, d_lp.get() + nlp, kNfProbeGuard, hipMemcpyDeviceToHost))
+	   || !hip_ok(hipMemcpy(g.data() + 3 * kNfProbeGuard, d_ring.get() + nring, kNfProbeGuard, hipMemcpyDeviceToHost))) return VDL2HIP_E_DEVICE;
+	if(!dbg_down(nf, d_nf) || !dbg_down(ring, d_ring, nring * sizeof(float)) || !dbg_down(lpbuf, d_lp, nlp * sizeof(float)) || !dbg_down(feeds, d_feed)) return VDL2HIP_E_DEVICE;
+	for(uint8_t b : g) if(b != 0xA5) return VDL2HIP_E_DEVICE;
+	// every channel's rows of the scratch lists: what lies behind the ncomb + 1 entries the channel has is untouched
+	std::vector<int64_t> hf(nsc), hcm(nsc);
+	if(!dbg_down(hf.data(), d_scf, nsc * sizeof(int64_t)) || !dbg_down(hcm.data(), d_scc, nsc * sizeof(int64_t))) return VDL2HIP_E_DEVICE;
+	const NfFeed *hfd = static_cast<const NfFeed *>(feeds);
+	for(uint32_t c = 0; c < nchan; c++) {
+		if(hfd[c].ncomb > cap_log + (uint32_t)kNfTail) return VDL2HIP_E_DEVICE;
+		for(size_t i = (size_t)hfd[c].ncomb + 1; i <= cap_comb; i++)
+			if(hf[(size_t)c * (cap_comb + 1) + i] != (int64_t)0xA5A5A5A5A5A5A5A5ull || hcm[(size_t)c * (cap_comb + 1) + i] != (int64_t)0xA5A5A5A5A5A5A5A5ull) return VDL2HIP_E_DEVICE;
+	}
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_nf_probe.py): the noise floor as the receiver holds it after everything fed so far -
+// nf[i] = v->mag_nf after first_update + i updates of channel chan, from the history ring (which holds the last nf_ring of them), and
+// *evals = the got_sync() evaluations the replay has accounted for.  Returns the number of entries delivered (fewer than `count` where the
+// channel has had fewer updates)
+int vdl2hip_debug_read_noise_floor(vdl2hip_ctx *c, uint32_t chan, int64_t first_update, size_t count, float *nf, int64_t *evals) {
+	if(!c || !evals || (count && !nf) || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C) || first_update < 0) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	int r = collect_pending(c);
+	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	const size_t ch = chan - c->chan_first;
+	auto st = std::make_unique<NfState>();
+	HIPCHK(hipMemcpy(st.get(), c->d_nf + ch, sizeof(NfState), hipMemcpyDeviceToHost));
+	*evals = st->evals;
+	const int64_t upd = st->evals / 1000;                              // entries 0 .. upd exist; the ring keeps the newest nf_ring of them
+	if(first_update > upd || upd - first_update >= (int64_t)c->nf_ring) return VDL2HIP_E_INVAL;
+	const size_t n = std::min<size_t>(count, (size_t)(upd - first_update + 1));
+	std::vector<float> h(c->nf_ring);
+	HIPCHK(hipMemcpy(h.data(), c->d_nfring + ch * c->nf_ring, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < n; i++) nf[i] = h[(uint32_t)(first_update + (int64_t)i) & (c->nf_ring - 1)];
+	return (int)n;
+}
+
 // Builds with a VDL2_*_PROF switch (kernels.h): the kernels' own counters (prof_read)
 #ifdef VDL2_K1_PROF
 int vdl2hip_debug_k1_prof(unsigned long long out[16], int reset) { return prof_read<16>(HIP_SYMBOL(vdl2_k1_prof), out, reset); }

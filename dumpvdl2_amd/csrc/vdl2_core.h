@@ -1979,12 +1979,17 @@ struct NfScratch { int64_t *first; int64_t *cum; };   // combined (tail + feed) 
 // what the three noise-floor passes of one feed share (per channel)
 struct NfFeed { int64_t ev0, ev1, u0, u1, begin_ord; uint32_t ncomb, pad_; };
 
-// pass 1: combined chunk list = remembered tail + this feed's log, with evaluation ordinals (a prefix sum, 64 chunks at a time)
+// pass 1: combined chunk list = remembered tail + this feed's log (its first chunk joined to the tail's last where it continues it),
+// with evaluation ordinals (a prefix sum, 64 chunks at a time)
 VDL2_HD void nf_prepare(const NfState *g, const EvalLog &lg, const NfScratch &sc, uint32_t cap_comb, NfFeed *fd, NfShared &sh) {
 	int64_t *cnt64 = reinterpret_cast<int64_t *>(&sh.mags[0][0]);   // 64 counts, then 64 running ordinals, then one total
 	const uint32_t nlog = *lg.n;
 	const uint32_t ntail = (uint32_t)g->ntail;
-	uint32_t ntot = ntail + nlog; if(ntot > cap_comb) ntot = cap_comb;
+	// A feed's log starts a new chunk even where its first evaluation continues the grid of the feed before (walk_load): that chunk and the
+	// tail's last are joined here, or feeds of a few samples each would fill the kNfTail remembered chunks with a few evaluations each
+	// and leave fewer than kLpTerms in reach.
+	const uint32_t join = ntail > 0 && nlog > 0 && lg.chunks[0].first == g->tail[ntail - 1].first + 3 * g->tail[ntail - 1].count ? 1u : 0u;
+	uint32_t ntot = ntail + nlog - join; if(ntot > cap_comb) ntot = cap_comb;
 	LANE0
 		cnt64[128] = g->tail_ord;
 	LANE0_END
@@ -1992,7 +1997,8 @@ VDL2_HD void nf_prepare(const NfState *g, const EvalLog &lg, const NfScratch &sc
 		WAVE_FOR(l)
 			const uint32_t k = base + (uint32_t)l;
 			if(k < ntot) {
-				const EvalChunk ch = k < ntail ? g->tail[k] : lg.chunks[k - ntail];
+				EvalChunk ch = k < ntail ? g->tail[k] : lg.chunks[k - ntail + join];
+				if(join && k == ntail - 1) ch.count += lg.chunks[0].count;
 				sc.first[k] = ch.first; cnt64[l] = ch.count;
 			}
 		WAVE_END

@@ -587,6 +587,15 @@ class Receiver:
         n = self._chk(f(self.h, chan, first, count, flag.ctypes.data), "vdl2hip_debug_read_flags")
         return flag[:n]
 
+    def read_noise_floor(self, chan: int, first_update: int = 0, count: int = 1 << 20):
+        """test hook: (nf [n] = mag_nf after first_update + i updates of one channel, from the history ring - entry 0 is the initial 2.0 -,
+        evals = the got_sync() evaluations the noise-floor replay has accounted for)"""
+        f = self.L.vdl2hip_debug_read_noise_floor
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_size_t, C.c_void_p, C.POINTER(C.c_int64)]
+        nf = np.zeros(count, dtype=np.float32); ev = C.c_int64(0)
+        n = self._chk(f(self.h, chan, first_update, count, nf.ctypes.data, C.byref(ev)), "vdl2hip_debug_read_noise_floor")
+        return nf[:n], int(ev.value)
+
     def set_profiling(self, level) -> None:
         """0/False off, 1/True: time the channeliser kernel only, 2: every stage (a few percent slower)"""
         self._chk(self.L.vdl2hip_set_profiling(self.h, int(level)), "vdl2hip_set_profiling")

@@ -89,6 +89,9 @@ def _bind(L):
     L.vdl2o_trace_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.vdl2o_decimated_count.restype = C.c_int64
     L.vdl2o_decimated_count.argtypes = [C.c_void_p, C.c_int]
+    L.vdl2o_trace_noise_floor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.vdl2o_sync_evals.restype = C.c_int64
+    L.vdl2o_sync_evals.argtypes = [C.c_void_p, C.c_int]
     L.vdl2o_rs_decode.restype = C.c_int
     L.vdl2o_rs_decode.argtypes = [C.c_void_p, C.c_int]
     L.vdl2o_rs_encode.argtypes = [C.c_void_p, C.c_void_p]
@@ -153,6 +156,16 @@ class Oracle:
         self._trace_all = np.zeros((len(self.freqs), cap, 2), dtype=np.float32)
         self.L.vdl2o_trace_all(self.h, self._trace_all.ctypes.data, cap)
         return self._trace_all
+
+    def trace_noise_floor(self, cap):
+        """Record mag_nf after each of its updates, every channel: returns array [nchan, cap] (entry i: after i + 1 updates)."""
+        self._trace_nf = np.zeros((len(self.freqs), cap), dtype=np.float32)
+        self.L.vdl2o_trace_noise_floor(self.h, self._trace_nf.ctypes.data, cap)
+        return self._trace_nf
+
+    def sync_evals(self, chan=0):
+        """got_sync() evaluations of the channel so far (every 1000th updates mag_nf)"""
+        return self.L.vdl2o_sync_evals(self.h, chan)
 
     def decimated_count(self, chan=0):
         return self.L.vdl2o_decimated_count(self.h, chan)

@@ -86,6 +86,7 @@ typedef struct {
 	int64_t dsample;            /* decimated samples seen so far - 1 */
 	int64_t sync_sample;
 	int64_t bursts;
+	int64_t nf_upd;             /* mag_nf updates so far (got_sync() evaluations = 1000 * nf_upd + nfcnt) */
 	uint64_t cnt[VDL2O_NUM_COUNTERS];
 	/* frames produced by this channel during the current block */
 	vdl2o_frame *fr; size_t nfr, capfr;
@@ -106,6 +107,7 @@ struct vdl2o_ctx {
 	uint8_t *oct; size_t noct, capoct;
 	int trace_chan; float *trace; size_t trace_cap, trace_n;
 	float *trace_all; size_t trace_all_cap;   /* [nchan][cap] complex, every channel */
+	float *trace_nf; size_t trace_nf_cap;     /* [nchan][cap]: mag_nf after each update, every channel */
 };
 
 /* ======================================================================
@@ -761,6 +763,8 @@ static void chan_demod(const vdl2o_ctx *c, chan_t *v, float re, float im) { /* d
 		if(++v->nfcnt == 1000) {
 			v->nfcnt = 0;
 			v->mag_nf = K_NF_LP * v->mag_nf + (1.0f - K_NF_LP) * fminf(v->mag_lp, v->mag_nf) + 0.0001f;
+			if(c->trace_nf && (size_t)v->nf_upd < c->trace_nf_cap) c->trace_nf[(size_t)(v - c->ch) * c->trace_nf_cap + (size_t)v->nf_upd] = v->mag_nf;
+			v->nf_upd++;
 		}
 		if(chan_try_sync(c, v)) {
 			v->cnt[VDL2O_CNT_SYNC_GOOD]++;
@@ -1012,4 +1016,6 @@ void vdl2o_get_sincos_lut(const vdl2o_ctx *c, float s[257], float co[257]) { mem
 void vdl2o_trace_decimated(vdl2o_ctx *c, int chan, float *dst, size_t cap) { c->trace_chan = chan; c->trace = dst; c->trace_cap = cap; c->trace_n = 0; }
 size_t vdl2o_trace_count(const vdl2o_ctx *c) { return c->trace_n; }
 void vdl2o_trace_all(vdl2o_ctx *c, float *dst, size_t cap_per_chan) { c->trace_all = dst; c->trace_all_cap = cap_per_chan; }
+void vdl2o_trace_noise_floor(vdl2o_ctx *c, float *dst, size_t cap_per_chan) { c->trace_nf = dst; c->trace_nf_cap = cap_per_chan; }
+int64_t vdl2o_sync_evals(const vdl2o_ctx *c, int chan) { return 1000 * c->ch[chan].nf_upd + c->ch[chan].nfcnt; }
 int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].dsample + 1; }

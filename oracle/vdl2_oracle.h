@@ -102,6 +102,11 @@ size_t vdl2o_trace_count(const vdl2o_ctx *c);
 /* trace every channel: dst[chan][cap_per_chan] complex (re,im) */
 void vdl2o_trace_all(vdl2o_ctx *c, float *dst, size_t cap_per_chan);
 int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan);
+/* Optional trace of the noise floor (off by default; one test per 1000 evaluations when off): dst[chan][cap_per_chan] =
+ * v->mag_nf after each of its updates (demod.c:241-243: every 1000th got_sync() evaluation), every channel */
+void vdl2o_trace_noise_floor(vdl2o_ctx *c, float *dst, size_t cap_per_chan);
+/* got_sync() evaluations of a channel so far (1000 * its mag_nf updates + v->nfcnt) */
+int64_t vdl2o_sync_evals(const vdl2o_ctx *c, int chan);
 
 /* Stand-alone pieces, exported for known-answer tests */
 int  vdl2o_rs_decode(uint8_t block[255], int fec_octets);          /* rs.c:32-49 */

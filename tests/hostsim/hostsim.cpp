@@ -507,6 +507,54 @@ int hostsim_decode_burst(const Burst *bursts, int64_t n, uint32_t nwaves, const 
 	}
 	return 0;
 }
+// ---- the noise-floor replay on the inputs of tests/nf_reference.py (the GPU build takes the same ones: vdl2hip_debug_nf_probe) ----
+// one feed of nchan channels: nf_prepare, nf_replay_group for every group, nf_finish per channel, all on ONE NfShared (as a wavefront that
+// takes group after group leaves it); y [nchan][ring_len], chunks [nchan][cap_log], nlog [nchan], nf (NfState [nchan], in and out), ring
+// [nchan][nf_ring] (in and out), lpbuf [nchan][cap_hist] (0xA5 where nothing was written), feeds (NfFeed [nchan]).  Behind every row of the
+// scratch lists and of lpbuf lie guard words: -2 if one has changed, -1 for inputs the product cannot have
+int hostsim_nf_feed(uint32_t nchan, const float *y, uint32_t ring_len, const EvalChunk *chunks, const uint32_t *nlog, uint32_t cap_log, NfState *nf, float *ring, uint32_t nf_ring,
+		uint32_t cap_hist, float *lpbuf, NfFeed *feeds) {
+	if(nchan == 0 || ring_len < 64 || (ring_len & (ring_len - 1)) || cap_log == 0 || nf_ring == 0 || (nf_ring & (nf_ring - 1)) || cap_hist < 2 || cap_hist > nf_ring) return -1;
+	const uint32_t cap_comb = cap_log + (uint32_t)kNfTail;
+	constexpr size_t G = 64;
+	constexpr int64_t kGuard = (int64_t)0xA5A5A5A5A5A5A5A5ull;
+	std::vector<int64_t> scf(cap_comb + 1 + G), scc(cap_comb + 1 + G);
+	std::vector<float> lp(cap_hist + G);
+	static NfShared sh;
+	bool bad = false;
+	for(uint32_t c = 0; c < nchan; c++) {
+		const NfState &s = nf[c];
+		if(nlog[c] > cap_log || s.ntail < 0 || s.ntail > kNfTail) return -1;
+		int64_t ord = s.tail_ord;
+		for(int i = 0; i < s.ntail; i++) ord += s.tail[i].count;
+		if(ord != s.evals) return -1;
+		for(uint32_t i = 0; i < nlog[c]; i++) ord += chunks[(size_t)c * cap_log + i].count;
+		if(ord / 1000 - s.evals / 1000 > (int64_t)cap_hist - 1) return -1;
+		std::fill(scf.begin(), scf.end(), kGuard); std::fill(scc.begin(), scc.end(), kGuard);
+		memset(lp.data(), 0xA5, lp.size() * sizeof(float));
+		uint32_t n = nlog[c];
+		EvalLog lg{ const_cast<EvalChunk *>(chunks) + (size_t)c * cap_log, &n };
+		NfScratch sc{ scf.data(), scc.data() };
+		ChanView v{ reinterpret_cast<const cf32 *>(y) + (size_t)c * ring_len, nullptr, nullptr, ring_len - 1 };
+		NfFeed fd;
+		nf_prepare(&nf[c], lg, sc, cap_comb, &fd, sh);
+		for(int64_t g = 0; fd.u0 + 1 + kNfGroup * g <= fd.u1; g++) nf_replay_group(v, sc, fd, g, lp.data(), cap_hist, sh);
+		nf_finish(&nf[c], sc, fd, lp.data(), ring + (size_t)c * nf_ring, nf_ring - 1, cap_hist, sh);
+		feeds[c] = fd;
+		memcpy(lpbuf + (size_t)c * cap_hist, lp.data(), (size_t)cap_hist * sizeof(float));
+		for(size_t i = 0; i < G; i++) { uint32_t w; memcpy(&w, &lp[cap_hist + i], 4); bad = bad || scf[cap_comb + 1 + i] != kGuard || scc[cap_comb + 1 + i] != kGuard || w != 0xA5A5A5A5u; }
+	}
+	return bad ? -2 : 0;
+}
+// the evaluation log the walker left for the noise-floor replay in the most recent feed: (first, count) per chunk -> the number of chunks
+int64_t hostsim_eval_log(Sim *s, int chan, int64_t *out, int64_t cap) {
+	const int64_t n = s->nlog[chan];
+	for(int64_t i = 0; i < n && i < cap; i++) { out[2 * i] = s->log[(size_t)chan * s->cap_log + i].first; out[2 * i + 1] = s->log[(size_t)chan * s->cap_log + i].count; }
+	return n;
+}
+int hostsim_sizeof_nfstate() { return (int)sizeof(NfState); }
+int hostsim_sizeof_nffeed() { return (int)sizeof(NfFeed); }
+
 int hostsim_sizeof_burst() { return (int)sizeof(Burst); }
 int hostsim_sizeof_outctl() { return (int)sizeof(OutCtl); }
 

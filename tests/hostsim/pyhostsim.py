@@ -29,6 +29,14 @@ def build(reverse_lanes=False):
     return lib
 
 
+def nf_feed(L, nchan, y, chunks, nlog, cap_log, nf, ring, nf_ring, cap_hist, lpbuf, feeds):
+    """hostsim_nf_feed: one feed of the noise-floor replay for nchan channels on the caller's arrays (tests/nf_reference.py lays them out);
+    nf and ring are updated in place, lpbuf and feeds filled.  Returns the library's status (0: good)"""
+    L.hostsim_nf_feed.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    return L.hostsim_nf_feed(nchan, y.ctypes.data, y.shape[1], chunks.ctypes.data, nlog.ctypes.data, cap_log, nf.ctypes.data, ring.ctypes.data, nf_ring, cap_hist,
+                             lpbuf.ctypes.data, feeds.ctypes.data)
+
+
 class HostSim:
     def __init__(self, freqs, max_ppm=0.0, cap_log2=21, reverse_lanes=False):
         self.L = C.CDLL(build(reverse_lanes))
@@ -112,6 +120,14 @@ class HostSim:
         self.L.hostsim_read_sync.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         self.L.hostsim_read_sync(self.h, chan, first, count, pf.ctypes.data, cand.ctypes.data)
         return pf, cand
+
+    def eval_log(self, chan):
+        """the evaluation log of the most recent feed, as the walker handed it to the noise-floor replay: int64 [n, 2] = (first, count)"""
+        a = np.zeros((8192, 2), dtype=np.int64)
+        self.L.hostsim_eval_log.restype = C.c_int64
+        self.L.hostsim_eval_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        n = self.L.hostsim_eval_log(self.h, chan, a.ctypes.data, len(a))
+        return a[:n]
 
     def set_segments(self, seg_min, seg_max=32):
         """walk long feeds in speculative segments, as k_walk_spec / k_walk_stitch do on the device"""
