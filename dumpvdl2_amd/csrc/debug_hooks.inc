@@ -282,6 +282,78 @@ int vdl2hip_debug_nf_probe(int mode, unsigned grid, uint32_t nchan, const float 
 	return VDL2HIP_OK;
 }
 
+// test hook (not declared in vdl2hip.h; tests/test_gpu_walk_probe.py): K4, the walker, on the caller's inputs - one call is one feed [k0, k_end) of
+// nchan channels.  y and pf [nchan][ring_len] (cf32, ring_len a power of two) and cand [nchan][ring_len / 64] as ChanView defines them, the
+// channels' WalkState (ws: nchan * vdl2hip_debug_sizeof_walkstate() octets, in and out) and counters (cnt [nchan][20], in and out).
+// mode 0: k_walk; mode 1: k_walk_spec and k_walk_stitch over nseg segments of seglen samples, with the grids, the blocks and the dynamic LDS of
+// launch_back() / launch_stitch().  The referee is off (no RefChan, no request list, no snapshots).
+// Returned besides: bursts [nchan][cap_bursts_chan] and log [nchan][cap_log] (EvalChunk), both 0xA5 where nothing was written - a store beyond
+// a channel's own row lands in the next channel's, which the caller sees - nb_chan and nlog [nchan], the control block (an OutCtl), and in mode 1
+// seg_stats [nchan][2] and the speculative walks spec [nchan][3 * (nseg - 1)] (SpecOut: vdl2hip_debug_sizeof_specout() octets each).
+// Refused (VDL2HIP_E_INVAL) is what the product cannot have: segments shorter than 64 samples, more than kMaxSeg of them, a segment count
+// that is not the feed's length over seglen rounded up, a feed longer than the ring, a state that is not a walker's.  Behind every output buffer
+// lie kWalkProbeGuard octets filled with 0xA5 beforehand: VDL2HIP_E_DEVICE if any of them has changed.  Needs no receiver
+int vdl2hip_debug_sizeof_walkstate(void) { return (int)sizeof(WalkState); }
+int vdl2hip_debug_sizeof_burst(void) { return (int)sizeof(Burst); }
+int vdl2hip_debug_sizeof_specout(void) { return (int)sizeof(SpecOut); }
+int vdl2hip_debug_walk_probe(int mode, uint32_t nchan, const float *y, const float *pf, const uint64_t *cand, uint32_t ring_len, const uint32_t *freq, float max_ppm,
+		int64_t k0, int64_t k_end, int32_t nseg, int64_t seglen, void *ws, unsigned long long *cnt, uint32_t cap_bursts_chan, uint32_t cap_log,
+		void *bursts, uint32_t *nb_chan, void *log, uint32_t *nlog, void *ctl, uint32_t *seg_stats, void *spec) {
+	constexpr size_t kWalkProbeGuard = 4096;
+	if(mode < 0 || mode > 1 || nchan == 0 || nchan > 1024 || !y || !pf || !cand || ring_len < 64 || (ring_len & (ring_len - 1)) || ring_len > 1u << 20 || !freq || !(max_ppm >= 0.f)
+	   || k0 < 0 || k_end < k0 || k_end - k0 > (int64_t)ring_len || !ws || !cnt || cap_bursts_chan == 0 || cap_bursts_chan > 1u << 16 || cap_log == 0 || cap_log > 1u << 16
+	   || !bursts || !nb_chan || !log || !nlog || !ctl) return VDL2HIP_E_INVAL;
+	const int64_t D = k_end - k0;
+	if(mode == 1 && (!seg_stats || !spec || nseg < 2 || nseg > kMaxSeg || seglen < 64 || (int64_t)(nseg - 1) * seglen >= D || (int64_t)nseg * seglen < D)) return VDL2HIP_E_INVAL;
+	const WalkState *hw = static_cast<const WalkState *>(ws);
+	for(uint32_t c = 0; c < nchan; c++) {
+		const WalkState &s = hw[c];
+		if(s.mode < 0 || s.mode > 2 || s.niv < 0 || s.niv > kNumIv || s.a < 0 || s.evals < 0 || s.bursts < 0) return VDL2HIP_E_INVAL;
+		if(s.mode == 0 && (s.e0 < s.a + 2 || s.e < s.e0 || s.e < k0 || s.e > k0 + 2 || s.a > k0)) return VDL2HIP_E_INVAL;
+		if(s.mode != 0 && (s.pb.sync_sample < 0 || s.pb.sync_sample >= k0 || s.pb.t_first <= s.pb.sync_sample || s.pb.t_first > s.pb.sync_sample + kSpsDec || s.pb.prev_n < -2 || s.pb.prev_n > s.pb.sync_sample)) return VDL2HIP_E_INVAL;
+		if(s.mode == 1 && s.pb.t_first + 8 * kSpsDec < k0) return VDL2HIP_E_INVAL;
+		if(s.mode == 2 && (s.pb.nsym < 1 || s.pb.nsym > kMaxSyms || s.pb.end_sample != s.pb.t_first + (int64_t)(s.pb.nsym - 1) * kSpsDec || s.pb.end_sample < k0)) return VDL2HIP_E_INVAL;
+	}
+	const uint32_t nspec = mode == 1 ? 3u * (uint32_t)(nseg - 1) : 0u;
+	const size_t b_ws = (size_t)nchan * sizeof(WalkState), b_cnt = (size_t)nchan * kNumCounters * sizeof(unsigned long long), b_bursts = (size_t)nchan * cap_bursts_chan * sizeof(Burst),
+	             b_nb = (size_t)nchan * 4, b_log = (size_t)nchan * cap_log * sizeof(EvalChunk), b_ctl = sizeof(OutCtl), b_seg = (size_t)nchan * 8, b_spec = (size_t)nchan * nspec * sizeof(SpecOut);
+	DevBuf<cf32> d_y, d_pf; DevBuf<uint64_t> d_cand; DevBuf<uint32_t> d_freq; DevBuf<float> d_thr; DevBuf<Tables> d_tab;
+	DevBuf<uint8_t> d_ws, d_cnt, d_bursts, d_nb, d_log, d_nlog, d_ctl, d_seg, d_spec;
+	struct Out { DevBuf<uint8_t> *d; size_t used; void *host; };
+	const Out outs[] = { { &d_ws, b_ws, ws }, { &d_cnt, b_cnt, cnt }, { &d_bursts, b_bursts, bursts }, { &d_nb, b_nb, nb_chan }, { &d_log, b_log, log }, { &d_nlog, b_nb, nlog },
+	                     { &d_ctl, b_ctl, ctl }, { &d_seg, b_seg, seg_stats }, { &d_spec, b_spec, spec } };
+	if(!hip_ok(d_y.alloc((size_t)nchan * ring_len)) || !hip_ok(d_pf.alloc((size_t)nchan * ring_len)) || !hip_ok(d_cand.alloc((size_t)nchan * (ring_len >> 6))) || !hip_ok(d_freq.alloc(nchan))
+	   || !hip_ok(d_thr.alloc(nchan)) || !hip_ok(d_tab.alloc(1))) return VDL2HIP_E_NOMEM;
+	for(const Out &o : outs) if(!hip_ok(o.d->alloc(o.used + kWalkProbeGuard))) return VDL2HIP_E_NOMEM;
+	std::vector<float> thr(nchan);
+	for(uint32_t c = 0; c < nchan; c++) thr[c] = ppm_gate_threshold(freq[c], max_ppm);
+	OutCtl h_ctl; memset(&h_ctl, 0, sizeof h_ctl);
+	h_ctl.cap_bursts = nchan * cap_bursts_chan; h_ctl.cap_log = cap_log;
+	if(!dbg_tables(d_tab) || !dbg_up(d_y, y) || !dbg_up(d_pf, pf) || !dbg_up(d_cand, cand) || !dbg_up(d_freq, freq) || !dbg_up(d_thr, thr.data())) return VDL2HIP_E_DEVICE;
+	for(const Out &o : outs) if(!dbg_fill(*o.d, 0xA5)) return VDL2HIP_E_DEVICE;
+	if(!dbg_up(d_ws, ws, b_ws) || !dbg_up(d_cnt, cnt, b_cnt) || !dbg_up(d_ctl, &h_ctl, b_ctl) || !hip_ok(hipMemset(d_seg, 0, b_seg))) return VDL2HIP_E_DEVICE;
+	K4Args k4{};
+	k4.y = d_y; k4.pf = d_pf; k4.cand = d_cand; k4.tab = d_tab; k4.ws = reinterpret_cast<WalkState *>(d_ws.get()); k4.cnt = reinterpret_cast<unsigned long long *>(d_cnt.get());
+	k4.bursts = reinterpret_cast<Burst *>(d_bursts.get()); k4.nb_chan = reinterpret_cast<uint32_t *>(d_nb.get()); k4.cap_bursts_chan = cap_bursts_chan; k4.ctl = reinterpret_cast<OutCtl *>(d_ctl.get());
+	k4.freq = d_freq; k4.log = reinterpret_cast<EvalChunk *>(d_log.get()); k4.nlog = reinterpret_cast<uint32_t *>(d_nlog.get()); k4.cap_log = cap_log; k4.k_end = k_end; k4.max_ppm = max_ppm;
+	k4.cap = ring_len; k4.mask = ring_len - 1; k4.chan_first = 0; k4.nchan = (int32_t)nchan; k4.ppm_thr = d_thr;
+	if(mode == 0) hipLaunchKernelGGL(k_walk, dim3(nchan), dim3(64), 0, 0, k4);
+	else {
+		K4sArgs k4s{ k4, reinterpret_cast<SpecOut *>(d_spec.get()), nspec, nseg, k0, seglen, reinterpret_cast<uint32_t *>(d_seg.get()), 0 };
+		hipLaunchKernelGGL(k_walk_spec, dim3((unsigned)((1 + 3 * (nseg - 1) + kWalkWaves - 1) / kWalkWaves), nchan), dim3(64 * kWalkWaves), 0, 0, k4s);
+		hipLaunchKernelGGL(k_walk_stitch, dim3((unsigned)((nchan + kStitchWaves - 1) / kStitchWaves)), dim3(64 * kStitchWaves), (unsigned)(sizeof(StitchLds) * kStitchWaves), 0, k4s);
+	}
+	if(!hip_ok(hipGetLastError()) || !hip_ok(hipDeviceSynchronize())) return VDL2HIP_E_DEVICE;
+	std::vector<uint8_t> g(kWalkProbeGuard);
+	bool clean = true;
+	for(const Out &o : outs) {
+		if(!hip_ok(hipMemcpy(g.data(), o.d->get() + o.used, kWalkProbeGuard, hipMemcpyDeviceToHost))) return VDL2HIP_E_DEVICE;
+		for(uint8_t b : g) clean = clean && b == 0xA5;
+		if(o.host && o.used && !dbg_down(o.host, *o.d, o.used)) return VDL2HIP_E_DEVICE;
+	}
+	return clean ? VDL2HIP_OK : VDL2HIP_E_DEVICE;
+}
+
 // test hook (not declared in vdl2hip.h; tests/test_gpu_nf_probe.py): the noise floor as the receiver holds it after everything fed so far -
 // nf[i] = v->mag_nf after first_update + i updates of channel chan, from the history ring (which holds the last nf_ring of them), and
 // *evals = the got_sync() evaluations the replay has accounted for.  Returns the number of entries delivered (fewer than `count` where the

@@ -35,6 +35,10 @@ class Frame(C.Structure):
     ]
 
 
+SYNC_EVENT = np.dtype([("sample", "<i8"), ("evals", "<i8"), ("end_sample", "<i8"), ("ppm_error", "<f4"), ("accepted", "<i4"),
+                       ("hdr_status", "<i4"), ("pad_", "<i4")], align=True)      # vdl2_oracle.h: vdl2o_sync_event
+
+
 def build(force=False):
     """Compile the oracle (and oracle/_ref when the reference tree is present)."""
     src_t = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("vdl2_oracle.c", "vdl2_oracle.h", "Makefile"))
@@ -92,6 +96,9 @@ def _bind(L):
     L.vdl2o_trace_noise_floor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.vdl2o_sync_evals.restype = C.c_int64
     L.vdl2o_sync_evals.argtypes = [C.c_void_p, C.c_int]
+    L.vdl2o_trace_sync_events.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.vdl2o_sync_event_count.restype = C.c_size_t
+    L.vdl2o_sync_event_count.argtypes = [C.c_void_p, C.c_int]
     L.vdl2o_rs_decode.restype = C.c_int
     L.vdl2o_rs_decode.argtypes = [C.c_void_p, C.c_int]
     L.vdl2o_rs_encode.argtypes = [C.c_void_p, C.c_void_p]
@@ -162,6 +169,17 @@ class Oracle:
         self._trace_nf = np.zeros((len(self.freqs), cap), dtype=np.float32)
         self.L.vdl2o_trace_noise_floor(self.h, self._trace_nf.ctypes.data, cap)
         return self._trace_nf
+
+    def trace_sync_events(self, cap):
+        """Record every got_sync() success of every channel (vdl2_oracle.h: vdl2o_sync_event); read them with sync_events()."""
+        self._trace_ev = np.zeros((len(self.freqs), cap), dtype=SYNC_EVENT)
+        self.L.vdl2o_trace_sync_events(self.h, self._trace_ev.ctypes.data, cap)
+
+    def sync_events(self, chan):
+        """the channel's events so far, in order: a SYNC_EVENT array"""
+        n = self.L.vdl2o_sync_event_count(self.h, chan)
+        assert n <= self._trace_ev.shape[1], f"channel {chan}: {n} sync events, room for {self._trace_ev.shape[1]}"
+        return self._trace_ev[chan, :n]
 
     def sync_evals(self, chan=0):
         """got_sync() evaluations of the channel so far (every 1000th updates mag_nf)"""

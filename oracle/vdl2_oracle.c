@@ -87,6 +87,7 @@ typedef struct {
 	int64_t sync_sample;
 	int64_t bursts;
 	int64_t nf_upd;             /* mag_nf updates so far (got_sync() evaluations = 1000 * nf_upd + nfcnt) */
+	size_t nev;                 /* got_sync() successes so far (vdl2o_trace_sync_events) */
 	uint64_t cnt[VDL2O_NUM_COUNTERS];
 	/* frames produced by this channel during the current block */
 	vdl2o_frame *fr; size_t nfr, capfr;
@@ -108,6 +109,7 @@ struct vdl2o_ctx {
 	int trace_chan; float *trace; size_t trace_cap, trace_n;
 	float *trace_all; size_t trace_all_cap;   /* [nchan][cap] complex, every channel */
 	float *trace_nf; size_t trace_nf_cap;     /* [nchan][cap]: mag_nf after each update, every channel */
+	vdl2o_sync_event *trace_ev; size_t trace_ev_cap;   /* [nchan][cap]: every got_sync() success, every channel */
 };
 
 /* ======================================================================
@@ -708,6 +710,20 @@ static const float preamble_phase[K_PREAMBLE] = { /* demod.c:107-124 */
 	-3 * M_PI / 4, 4 * M_PI / 4, -2 * M_PI / 4, 3 * M_PI / 4, 1 * M_PI / 4, -2 * M_PI / 4, -3 * M_PI / 4, 0 * M_PI / 4
 };
 
+/* the sync-event trace (vdl2o_trace_sync_events): the record of the channel's most recent got_sync() success, if it is kept */
+static vdl2o_sync_event *chan_last_event(const vdl2o_ctx *c, chan_t *v) {
+	if(!c || !c->trace_ev || v->nev == 0 || v->nev > c->trace_ev_cap) return NULL;
+	return c->trace_ev + (size_t)(v - c->ch) * c->trace_ev_cap + (v->nev - 1);
+}
+static void chan_note_sync(const vdl2o_ctx *c, chan_t *v, int accepted) {
+	if(!c->trace_ev) return;
+	v->nev++;
+	vdl2o_sync_event *e = chan_last_event(c, v);
+	if(!e) return;
+	e->sample = v->dsample; e->evals = 1000 * v->nf_upd + v->nfcnt; e->end_sample = -1;
+	e->ppm_error = v->ppm_error; e->accepted = accepted; e->hdr_status = -1; e->pad_ = 0;
+}
+
 static int chan_try_sync(const vdl2o_ctx *c, chan_t *v) { /* got_sync(), demod.c:105-198 */
 	float e[K_PREAMBLE];
 	float mean = 0.f, unwrap = 0.f;
@@ -741,7 +757,8 @@ static int chan_try_sync(const vdl2o_ctx *c, chan_t *v) { /* got_sync(), demod.c
 		v->slope = v->prev_slope;
 		v->ppm_error = K_SYMRATE * v->slope / (2.0f * M_PI * v->freq) * 1e+6;
 		v->pherr[1] = v->pherr[2] = K_PHERR_BIG;
-		if(c->max_ppm && fabsf(v->ppm_error) > c->max_ppm) { v->cnt[VDL2O_CNT_PPM_REJECT]++; return 0; }
+		if(c->max_ppm && fabsf(v->ppm_error) > c->max_ppm) { v->cnt[VDL2O_CNT_PPM_REJECT]++; chan_note_sync(c, v, 0); return 0; }
+		chan_note_sync(c, v, 1);
 		return 1;
 	}
 	v->pherr[2] = v->pherr[1];
@@ -790,7 +807,16 @@ static void chan_demod(const vdl2o_ctx *c, chan_t *v, float re, float im) { /* d
 	v->prev_phi = phi;
 	if(v->b_end + 3 > K_FIFO_BITS) { chan_demod_reset(v); return; }        /* bitstream_append_msbfirst, bitstream.c:45-56 */
 	for(int j = 2; j >= 0; j--) v->bits[v->b_end++] = (gray[idx] >> j) & 1;
-	if(v->b_end - v->b_start >= v->want_bits) chan_decode_burst(c, v);
+	if(v->b_end - v->b_start >= v->want_bits) {
+		const int was_header = v->decstate == DS_HEADER;
+		const uint64_t bad = v->cnt[VDL2O_CNT_CRC_BAD], lng = v->cnt[VDL2O_CNT_ERR_TOO_LONG], nofec = v->cnt[VDL2O_CNT_ERR_NO_FEC];
+		chan_decode_burst(c, v);
+		vdl2o_sync_event *e = chan_last_event(c, v);
+		if(e) {
+			if(was_header) e->hdr_status = v->cnt[VDL2O_CNT_CRC_BAD] != bad ? 1 : v->cnt[VDL2O_CNT_ERR_TOO_LONG] != lng ? 2 : v->cnt[VDL2O_CNT_ERR_NO_FEC] != nofec ? 3 : 0;
+			if(v->decstate == DS_IDLE) e->end_sample = v->dsample;
+		}
+	}
 }
 
 /* ======================================================================
@@ -1017,5 +1043,7 @@ void vdl2o_trace_decimated(vdl2o_ctx *c, int chan, float *dst, size_t cap) { c->
 size_t vdl2o_trace_count(const vdl2o_ctx *c) { return c->trace_n; }
 void vdl2o_trace_all(vdl2o_ctx *c, float *dst, size_t cap_per_chan) { c->trace_all = dst; c->trace_all_cap = cap_per_chan; }
 void vdl2o_trace_noise_floor(vdl2o_ctx *c, float *dst, size_t cap_per_chan) { c->trace_nf = dst; c->trace_nf_cap = cap_per_chan; }
+void vdl2o_trace_sync_events(vdl2o_ctx *c, vdl2o_sync_event *dst, size_t cap_per_chan) { c->trace_ev = dst; c->trace_ev_cap = cap_per_chan; }
+size_t vdl2o_sync_event_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].nev; }
 int64_t vdl2o_sync_evals(const vdl2o_ctx *c, int chan) { return 1000 * c->ch[chan].nf_upd + c->ch[chan].nfcnt; }
 int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].dsample + 1; }

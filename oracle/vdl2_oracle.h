@@ -107,6 +107,19 @@ int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan);
 void vdl2o_trace_noise_floor(vdl2o_ctx *c, float *dst, size_t cap_per_chan);
 /* got_sync() evaluations of a channel so far (1000 * its mag_nf updates + v->nfcnt) */
 int64_t vdl2o_sync_evals(const vdl2o_ctx *c, int chan);
+/* Optional trace of the sync events (off by default): one record for every got_sync() success of a channel, in the order they
+ * happen.  sample: the decimated sample of the evaluation; evals: got_sync() evaluations of the channel up to and including
+ * it; ppm_error as demod.c:185 leaves it; accepted: 0 dropped by --max-ppm (demod.c:190-192), 1 the channel locked.  For an
+ * accepted one, once the burst is over: hdr_status 0 header good, 1 reserved bits set after correction (decoder.crc.bad),
+ * 2 too long, 3 no FEC (-1 until the ninth symbol has been sliced, and for a dropped one), and end_sample, the sample of the
+ * symbol at which the decoder went idle (the ninth for a refused header; -1 until then).  dst[chan][cap_per_chan] */
+typedef struct {
+	int64_t sample, evals, end_sample;
+	float   ppm_error;
+	int32_t accepted, hdr_status, pad_;
+} vdl2o_sync_event;
+void vdl2o_trace_sync_events(vdl2o_ctx *c, vdl2o_sync_event *dst, size_t cap_per_chan);
+size_t vdl2o_sync_event_count(const vdl2o_ctx *c, int chan);
 
 /* Stand-alone pieces, exported for known-answer tests */
 int  vdl2o_rs_decode(uint8_t block[255], int fec_octets);          /* rs.c:32-49 */

@@ -546,6 +546,64 @@ int hostsim_nf_feed(uint32_t nchan, const float *y, uint32_t ring_len, const Eva
 	}
 	return bad ? -2 : 0;
 }
+// ---- the walker on the inputs of tests/walk_reference.py (the GPU build takes the same ones, argument for argument: vdl2hip_debug_walk_probe) ----
+// one feed [k0, k_end) of nchan channels: mode 0 walk_channel, mode 1 spec_walk for every (segment, grid phase) and stitch_channel, channel after
+// channel on ONE WalkShared / StitchShared.  Outputs as the device hook's: bursts [nchan][cap_bursts_chan], log [nchan][cap_log] (0xA5 where
+// nothing was written), nb_chan, nlog, the control block, seg_stats [nchan][2], spec [nchan][3 * (nseg - 1)].  -1 for inputs the product cannot
+// have, -2 if the guard words behind the burst list, the log or the speculative walks have changed
+int hostsim_walk_probe(int mode, uint32_t nchan, const float *y, const float *pf, const uint64_t *cand, uint32_t ring_len, const uint32_t *freq, float max_ppm,
+		int64_t k0, int64_t k_end, int32_t nseg, int64_t seglen, void *ws, unsigned long long *cnt, uint32_t cap_bursts_chan, uint32_t cap_log,
+		void *bursts, uint32_t *nb_chan, void *log, uint32_t *nlog, void *ctl, uint32_t *seg_stats, void *spec) {
+	static Tables T; static bool init = false;
+	if(!init) { build_tables(T); init = true; }
+	if(mode < 0 || mode > 1 || nchan == 0 || !y || !pf || !cand || ring_len < 64 || (ring_len & (ring_len - 1)) || !freq || !(max_ppm >= 0.f) || k0 < 0 || k_end < k0 || k_end - k0 > (int64_t)ring_len
+	   || !ws || !cnt || cap_bursts_chan == 0 || cap_log == 0 || !bursts || !nb_chan || !log || !nlog || !ctl) return -1;
+	const int64_t D = k_end - k0;
+	if(mode == 1 && (!seg_stats || !spec || nseg < 2 || nseg > kMaxSeg || seglen < 64 || (int64_t)(nseg - 1) * seglen >= D || (int64_t)nseg * seglen < D)) return -1;
+	WalkState *hw = static_cast<WalkState *>(ws);
+	for(uint32_t c = 0; c < nchan; c++) {
+		const WalkState &s = hw[c];
+		if(s.mode < 0 || s.mode > 2 || s.niv < 0 || s.niv > kNumIv || s.a < 0 || s.evals < 0 || s.bursts < 0) return -1;
+		if(s.mode == 0 && (s.e0 < s.a + 2 || s.e < s.e0 || s.e < k0 || s.e > k0 + 2 || s.a > k0)) return -1;
+		if(s.mode != 0 && (s.pb.sync_sample < 0 || s.pb.sync_sample >= k0 || s.pb.t_first <= s.pb.sync_sample || s.pb.t_first > s.pb.sync_sample + kSpsDec || s.pb.prev_n < -2 || s.pb.prev_n > s.pb.sync_sample)) return -1;
+		if(s.mode == 1 && s.pb.t_first + 8 * kSpsDec < k0) return -1;
+		if(s.mode == 2 && (s.pb.nsym < 1 || s.pb.nsym > kMaxSyms || s.pb.end_sample != s.pb.t_first + (int64_t)(s.pb.nsym - 1) * kSpsDec || s.pb.end_sample < k0)) return -1;
+	}
+	constexpr size_t G = 4096;
+	const uint32_t nspec = mode == 1 ? 3u * (uint32_t)(nseg - 1) : 0u;
+	const size_t b_bursts = (size_t)nchan * cap_bursts_chan * sizeof(Burst), b_log = (size_t)nchan * cap_log * sizeof(EvalChunk), b_spec = (size_t)nchan * nspec * sizeof(SpecOut);
+	std::vector<uint8_t> vb(b_bursts + G, 0xA5), vl(b_log + G, 0xA5), vs(b_spec + G, 0xA5);
+	Burst *hb = reinterpret_cast<Burst *>(vb.data()); EvalChunk *hl = reinterpret_cast<EvalChunk *>(vl.data()); SpecOut *hs = reinterpret_cast<SpecOut *>(vs.data());
+	OutCtl h_ctl; memset(&h_ctl, 0, sizeof h_ctl);
+	h_ctl.cap_bursts = nchan * cap_bursts_chan; h_ctl.cap_log = cap_log;
+	static WalkShared sh; static StitchShared ss;
+	for(uint32_t c = 0; c < nchan; c++) {
+		ChanView v{ reinterpret_cast<const cf32 *>(y) + (size_t)c * ring_len, reinterpret_cast<const cf32 *>(pf) + (size_t)c * ring_len, cand + (size_t)c * (ring_len >> 6), ring_len - 1 };
+		EvalLog lg{ hl + (size_t)c * cap_log, nlog + c };
+		const float thr = ppm_gate_threshold(freq[c], max_ppm);
+		nb_chan[c] = 0xA5A5A5A5u; nlog[c] = 0xA5A5A5A5u;
+		if(mode == 0) walk_channel((int)c, freq[c], max_ppm, thr, k_end, T, v, &hw[c], cnt + (size_t)c * kNumCounters, hb + (size_t)c * cap_bursts_chan, cap_bursts_chan, nb_chan + c, &h_ctl, lg, sh);
+		else {
+			SpecOut *sp = hs + (size_t)c * nspec;
+			for(int x = 1; x < 1 + 3 * (nseg - 1); x++) {                 // (k_walk_spec)
+				const int seg = 1 + (x - 1) / 3, r = (x - 1) % 3;
+				const int64_t b = k0 + (int64_t)seg * seglen, kn = seg + 1 < nseg ? b + seglen : k_end;
+				spec_walk((int)c, freq[c], max_ppm, thr, b, r, kn, T, v, sp + (x - 1), sh);
+			}
+			seg_stats[2 * c] = seg_stats[2 * c + 1] = 0;
+			stitch_channel((int)c, freq[c], max_ppm, thr, k0, seglen, nseg, k_end, T, v, &hw[c], cnt + (size_t)c * kNumCounters, hb + (size_t)c * cap_bursts_chan, cap_bursts_chan, nb_chan + c,
+			               &h_ctl, lg, sp, sh, ss, seg_stats + 2 * c);
+		}
+	}
+	bool bad = false;
+	for(size_t i = 0; i < G; i++) bad = bad || vb[b_bursts + i] != 0xA5 || vl[b_log + i] != 0xA5 || vs[b_spec + i] != 0xA5;
+	memcpy(bursts, vb.data(), b_bursts); memcpy(log, vl.data(), b_log); memcpy(ctl, &h_ctl, sizeof h_ctl);
+	if(b_spec) memcpy(spec, vs.data(), b_spec);
+	return bad ? -2 : 0;
+}
+int hostsim_sizeof_walkstate() { return (int)sizeof(WalkState); }
+int hostsim_sizeof_specout() { return (int)sizeof(SpecOut); }
+
 // the evaluation log the walker left for the noise-floor replay in the most recent feed: (first, count) per chunk -> the number of chunks
 int64_t hostsim_eval_log(Sim *s, int chan, int64_t *out, int64_t cap) {
 	const int64_t n = s->nlog[chan];
