@@ -44,6 +44,7 @@ int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
 	if(strcmp(name, "force_timeout") == 0) { c->debug_force_timeout = value != 0; return VDL2HIP_OK; }
 	if(strcmp(name, "force_mismatch") == 0) { c->debug_force_mismatch = value != 0; return VDL2HIP_OK; }   // every channel walked again with the next feed's walk already done is taken to have ended differently: the next feed is redone for it
 	if(strcmp(name, "walk_ahead_below") == 0) { c->walk_ahead_below = (double)value; c->walk_ahead_auto = true; return VDL2HIP_OK; }   // (tests: feeds of fewer channel-samples than this let the next walk go ahead)
+	if(strcmp(name, "mark_cap") == 0) { if(value < 0 || value > (long long)kDeferScansMax) return VDL2HIP_E_INVAL; c->debug_mark_cap = (uint32_t)value; return VDL2HIP_OK; }   // the list of pieces marked ahead of the check (k_burst_mark) holds at most this many (0: as sized): what runs over goes the burst decoder's own list-and-second-pass way
 	if(strcmp(name, "walk_ahead") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->walk_ahead = (int)value; c->walk_ahead_auto = false; return VDL2HIP_OK; }   // 1: the next feed's walk goes ahead of a feed's check, for every feed; 0: a feed's walk waits for the check of the feed before (round 5's schedule)
 	if(strcmp(name, "exact_tier") == 0) { if(value != 0 && value != 1) return VDL2HIP_E_INVAL; c->debug_exact_tier = (int)value; return VDL2HIP_OK; }   // 1 (default): the exact sync tier's dense form, k_sync_dense; 0: the word-at-a-time form it replaced, k_sync_exact4 (bit-identical results)
 	if(strcmp(name, "screen_all") == 0) { c->debug_screen_all = value != 0; return VDL2HIP_OK; }   // the screening tier flags every sample (flags are only ever conservative: same frames), so that the exact tier runs at its worst-case density

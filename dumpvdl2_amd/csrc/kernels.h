@@ -1327,7 +1327,7 @@ __device__ unsigned long long vdl2_k3b_prof[64][16];
 // FULL: sync_metric_ref()'s `full` (receivers that scan ahead of the walk; a template so that the other form is the old code exactly)
 template<bool FULL>
 __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
-	if(blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { reset_out_ctl(a.ctl, a.k5_waves); if(a.ref) *a.ref = a.refv; if(a.rq_n) { a.rq_n[0] = 0u; a.rq_n[1] = 0u; a.rq_n[2] = 0u; a.rq_n[4] = 0u; a.rq_n[5] = 0u; a.rq_n[6] = 0u; } }   // (rq_n[1], [2]: the burst decoder's lists, BurstDefer)
+	if(blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { reset_out_ctl(a.ctl, a.k5_waves); if(a.ref) *a.ref = a.refv; if(a.rq_n) { a.rq_n[0] = 0u; a.rq_n[1] = 0u; a.rq_n[2] = 0u; a.rq_n[4] = 0u; a.rq_n[5] = 0u; a.rq_n[6] = 0u; a.rq_n[7] = 0u; } }   // (rq_n[1], [2]: the burst decoder's lists, BurstDefer; [7]: k_burst_mark's)
 	if(blockIdx.x == 0 && threadIdx.x == 0 && a.rq_flag) { a.rq_flag[blockIdx.y] = 0u; a.rq_bad[blockIdx.y].n = 0u; if(a.rq_flag2) a.rq_flag2[blockIdx.y] = 0u; }
 	constexpr int kBack = 160, kSpan = kBack + 64;        // staged samples: base - 160 .. base + 63
 	// [wave][6 + bit]: metric of sample word*64 + bit (entries 0..5 = the six samples before the word), its slope, and - for the
@@ -1496,7 +1496,7 @@ static_assert(kK3dEvals >= 70 && kK3dEvals <= 512 && kK3dList * 70 < (1 << 20) &
 #define K3D_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while(0)
 template<bool FULL>
 __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
-	if(blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { reset_out_ctl(a.ctl, a.k5_waves); if(a.ref) *a.ref = a.refv; if(a.rq_n) { a.rq_n[0] = 0u; a.rq_n[1] = 0u; a.rq_n[2] = 0u; a.rq_n[4] = 0u; a.rq_n[5] = 0u; a.rq_n[6] = 0u; } }   // (rq_n[1], [2]: the burst decoder's lists, BurstDefer)
+	if(blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { reset_out_ctl(a.ctl, a.k5_waves); if(a.ref) *a.ref = a.refv; if(a.rq_n) { a.rq_n[0] = 0u; a.rq_n[1] = 0u; a.rq_n[2] = 0u; a.rq_n[4] = 0u; a.rq_n[5] = 0u; a.rq_n[6] = 0u; a.rq_n[7] = 0u; } }   // (rq_n[1], [2]: the burst decoder's lists, BurstDefer; [7]: k_burst_mark's)
 	if(blockIdx.x == 0 && threadIdx.x == 0 && a.rq_flag) { a.rq_flag[blockIdx.y] = 0u; a.rq_bad[blockIdx.y].n = 0u; if(a.rq_flag2) a.rq_flag2[blockIdx.y] = 0u; }
 	// the list: word (index within the workgroup), work mask, the six before it, the number of evaluations up to and including the
 	// word, and what the decide step gathers for it: candidate bits, marked candidates
@@ -1936,7 +1936,7 @@ constexpr int kScanWaves = VDL2_SCAN_WAVES;   // wavefronts launched per workgro
 struct ScanShared {
 	alignas(16) float buf[2][2][kScanLanes][kScanRow];   // [block parity][component][request][sample] feed-forward values
 	int64_t s_beg[kScanLanes], len[kScanLanes], n_lo[kScanLanes], n_hi[kScanLanes];
-	uint32_t dphi[kScanLanes]; int32_t chan[kScanLanes], kind[kScanLanes]; uint32_t flags[kScanLanes];   // flags: 1 mix, 2 shortened run-up
+	uint32_t dphi[kScanLanes]; int32_t chan[kScanLanes], kind[kScanLanes]; uint32_t flags[kScanLanes];   // flags: 1 mix, 2 shortened run-up, 4 of the second list
 	int64_t lmax, smin;
 	v4f lut[256];                                // the NCO table
 };
@@ -1947,12 +1947,14 @@ struct ScanShared {
 // steps are straight-line code with the outputs at fixed places: a compare + branch per step cost as much as the arithmetic), else 0
 template<int FMT, int OS>
 __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp, uint32_t launch, const ScanReq *sq, const RefReq *rq, const uint32_t *n_ptr, uint32_t cap, int64_t k_end,
-                      ScanReq *retry_q, uint32_t *retry_n, uint32_t retry_cap, int32_t warm_mul) {
+                      ScanReq *retry_q, uint32_t *retry_n, uint32_t retry_cap, int32_t warm_mul, const ScanReq *sq2, const uint32_t *n2_ptr, uint32_t cap2) {
 #if VDL2_DEVICE_PASS
 	#pragma clang fp contract(off)
 	__shared__ ScanShared sh;
 	constexpr int BLK = OS ? (kScanBlock / (OS ? OS : 1)) * OS : kScanBlock;    // input samples per block
-	const uint32_t ntot = *n_ptr < cap ? *n_ptr : cap;
+	// (sq2: a second list served by the same launch - request n1 + i is its i-th; the pieces k_burst_mark has listed, behind the check's noted decisions)
+	const uint32_t n1 = *n_ptr < cap ? *n_ptr : cap;
+	const uint32_t ntot = n1 + (sq2 ? (*n2_ptr < cap2 ? *n2_ptr : cap2) : 0u);
 	const uint32_t base = blockIdx.x * (uint32_t)kScanLanes;
 	if(base >= ntot) return;
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1972,7 +1974,8 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		const int r = threadIdx.x & (kScanLanes - 1), part = threadIdx.x >> 4;
 		int64_t n_lo = 0, n_hi = -1, s_beg = 0, len = 0; int c = 0, kind = 0; uint32_t fl = 0;
 		if(base + r < ntot && npiece > 0) {
-			if(sq) { const ScanReq q = sq[base + r]; c = q.chan; kind = q.kind; n_lo = q.lo; n_hi = q.hi; }
+			if(base + r >= n1) { const ScanReq q = sq2[base + r - n1]; c = q.chan; kind = q.kind; n_lo = q.lo; n_hi = q.hi; fl |= 4u; }
+			else if(sq) { const ScanReq q = sq[base + r]; c = q.chan; kind = q.kind; n_lo = q.lo; n_hi = q.hi; }
 			else { const RefReq q = rq[base + r]; c = q.chan; kind = q.kind; ref_request_window(q, k_end, n_lo, n_hi); }
 			const int64_t in_end = ps0[npiece - 1] + pn[npiece - 1];
 			if(n_lo < 0) n_lo = 0;
@@ -2290,9 +2293,10 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		if(len >= 0) __hip_atomic_store(rp->done + (size_t)c * kRefCache + (i % (uint32_t)kRefCache), ((unsigned long long)(n_lo >> 8) << 32) | ((unsigned long long)len << 16) | (unsigned long long)(launch & 0xffffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		atomicAdd(stats + 0, 1u); atomicAdd(stats + 4 + sh.kind[r], 1u);
 		if(sh.flags[r] & 2u) atomicAdd(stats + 3, 1u);
+		if(sh.flags[r] & 4u) atomicAdd(stats + 11, 1u);              // (vdl2hip_stats.referee_symbol_pieces_ahead)
 	}
 #else
-	(void)rp; (void)launch; (void)sq; (void)rq; (void)n_ptr; (void)cap; (void)k_end;
+	(void)rp; (void)launch; (void)sq; (void)rq; (void)n_ptr; (void)cap; (void)k_end; (void)sq2; (void)n2_ptr; (void)cap2;
 #endif
 }
 
@@ -2364,6 +2368,30 @@ __global__ __launch_bounds__(64 * kBurstWaves) void k_burst_probe_rs(BurstProbeA
 	}
 }
 
+// Which burst is a wavefront's?  Every wavefront turns the per-channel burst counts into offsets for itself, in LDS (one load per
+// lane and 64 channels, one scan): finding a burst's channel is then a search in LDS, not eight dependent trips to memory per burst -
+// and no kernel of its own has to run between the walker and this one.  bb[c]: bursts of the channels before c, bb[nchan] = the
+// feed's (returned).  Shared by k_burst and k_burst_mark: the two index a feed's bursts the same way.
+__device__ __forceinline__ uint32_t burst_offsets(const uint32_t *nb_chan, int nchan, uint32_t *bb, int lane) {
+	uint32_t total = 0;
+	for(int c0 = 0; c0 < nchan; c0 += 64) {
+		const uint32_t v = c0 + lane < nchan ? nb_chan[c0 + lane] : 0u;
+		uint32_t inc = v;
+		#pragma unroll
+		for(int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d); if(lane >= d) inc += o; }
+		if(c0 + lane < nchan) bb[c0 + lane] = total + inc - v;
+		total += __shfl(inc, 63);
+	}
+	if(lane == 0) bb[nchan] = total;
+	return total;
+}
+// channel c with bb[c] <= g < bb[c+1]
+__device__ __forceinline__ int burst_chan_of(const uint32_t *bb, int nchan, uint32_t g) {
+	int lo = 0, hi = nchan;
+	while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(bb[mid] <= g) lo = mid; else hi = mid; }
+	return lo;
+}
+
 // (the LDS is dynamic so that the compiler does not see its size: it would size the register budget by the LDS-limited occupancy
 // and take 169, more than a channeliser wave leaves)
 // (the body of k_burst: `block` of `nblocks` workgroups of kBurstWaves wavefronts)
@@ -2373,19 +2401,8 @@ __device__ __forceinline__ void burst_body(const K5Args &a, unsigned char *k5_ld
 	uint32_t *bb = reinterpret_cast<uint32_t *>(k5_lds + sizeof(BurstShared) * kBurstWaves) + (size_t)(threadIdx.x >> 6) * (kK5MaxChan + 1);
 	const int lane = threadIdx.x & 63;
 	const uint32_t wave_id = block * kBurstWaves + (threadIdx.x >> 6);
-	// Every wavefront turns the per-channel burst counts into offsets for itself, in LDS (one load per lane and 64 channels, one scan):
-	// finding a burst's channel is then a search in LDS, not eight dependent trips to memory per burst - and no kernel of its own has to
-	// run between the walker and this one.
-	uint32_t total = 0;
-	for(int c0 = 0; c0 < a.nchan; c0 += 64) {
-		const uint32_t v = c0 + lane < a.nchan ? a.nb_chan[c0 + lane] : 0u;
-		uint32_t inc = v;
-		#pragma unroll
-		for(int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d); if(lane >= d) inc += o; }
-		if(c0 + lane < a.nchan) bb[c0 + lane] = total + inc - v;
-		total += __shfl(inc, 63);
-	}
-	if(lane == 0) { bb[a.nchan] = total; if(wave_id == 0 && a.df.pass != 2) a.ctl->nbursts = total; }
+	const uint32_t total = burst_offsets(a.nb_chan, a.nchan, bb, lane);
+	if(lane == 0 && wave_id == 0 && a.df.pass != 2) a.ctl->nbursts = total;
 	WAVE_SYNC();
 	if(a.df.pass == 2) {
 		// the bursts the first pass has listed; its wavefronts own the initial shares of the output, this pass's go to the counters
@@ -2394,9 +2411,7 @@ __device__ __forceinline__ void burst_body(const K5Args &a, unsigned char *k5_ld
 		burst_shared_init(*a.tab, wave_id, a.ctl, sh, true);
 		for(uint32_t i = wave_id; i < nd; i += nblocks * kBurstWaves) {
 			const uint32_t g = a.df.dq[i];
-			int lo = 0, hi = a.nchan;
-			while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(bb[mid] <= g) lo = mid; else hi = mid; }
-			const int c = lo;
+			const int c = burst_chan_of(bb, a.nchan, g);
 			const Burst b = a.bursts[(size_t)c * a.cap_bursts_chan + (g - bb[c])];
 			ChanView v{ a.y + (size_t)c * a.cap, nullptr, nullptr, a.mask, a.ref, c, a.ref_launch };
 			decode_burst(b, a.freq[c], *a.tab, v, a.cnt + (size_t)c * kNumCounters, a.frames, a.pool, a.ctl, sh, &a.df, g);
@@ -2413,9 +2428,7 @@ __device__ __forceinline__ void burst_body(const K5Args &a, unsigned char *k5_ld
 	}
 	burst_shared_init(*a.tab, wave_id, a.ctl, sh);
 	for(uint32_t g = wave_id; g < total; g += nblocks * kBurstWaves) {
-		int lo = 0, hi = a.nchan;                       // channel c with bb[c] <= g < bb[c+1]
-		while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(bb[mid] <= g) lo = mid; else hi = mid; }
-		const int c = lo;
+		const int c = burst_chan_of(bb, a.nchan, g);
 		const Burst b = a.bursts[(size_t)c * a.cap_bursts_chan + (g - bb[c])];
 		ChanView v{ a.y + (size_t)c * a.cap, nullptr, nullptr, a.mask, a.ref, c, a.ref_launch };
 		decode_burst(b, a.freq[c], *a.tab, v, a.cnt + (size_t)c * kNumCounters, a.frames, a.pool, a.ctl, sh, a.df.pass ? &a.df : nullptr, g);
@@ -2427,6 +2440,56 @@ __device__ __forceinline__ void burst_body(const K5Args &a, unsigned char *k5_ld
 __global__ __launch_bounds__(256, 4) void k_burst(K5Args a) {
 	extern __shared__ __align__(16) unsigned char k5_lds[];       // BurstShared[kBurstWaves], then the per-channel burst offsets
 	burst_body(a, k5_lds, blockIdx.x, gridDim.x);
+}
+
+// Referee: which pieces will the burst decoder want exact?  The answer needs the burst descriptors - written by the feed's first
+// walk - and y, nothing the check decides: this kernel runs right behind the walk, a wavefront per burst as in k_burst, takes the
+// decoder's own marking step (burst_mark) and lists the pieces in `mq`, which the check's scan launch serves together with the noted
+// decisions.  The burst decoder's first pass then finds them done and the feed's chain holds one scan round, not two.  A piece a
+// visible launch has made already is not listed; what finds no room is left to the decoder's own list (pass 1 -> pass 2).
+// Writes nothing but the list and its count: no frames, no counters, no OutCtl.
+struct K5mArgs {
+	const cf32 *y; const Burst *bursts; const uint32_t *nb_chan; uint32_t cap_bursts_chan; int32_t nchan;
+	uint32_t cap, mask; RefChan *ref; uint32_t ref_launch;        // ref_launch: the scan launch's that will serve the list - what that one believes done is done for it
+	ScanReq *mq; uint32_t *mq_n; uint32_t mq_cap;
+};
+__global__ __launch_bounds__(256, 4) void k_burst_mark(K5mArgs a) {
+	extern __shared__ __align__(16) unsigned char k5_lds[];       // as k_burst's
+	if((threadIdx.x >> 6) >= kBurstWaves) return;
+	BurstShared &sh = reinterpret_cast<BurstShared *>(k5_lds)[threadIdx.x >> 6];
+	uint32_t *bb = reinterpret_cast<uint32_t *>(k5_lds + sizeof(BurstShared) * kBurstWaves) + (size_t)(threadIdx.x >> 6) * (kK5MaxChan + 1);
+	const int lane = threadIdx.x & 63;
+	const uint32_t wave_id = blockIdx.x * kBurstWaves + (threadIdx.x >> 6);
+	const uint32_t total = burst_offsets(a.nb_chan, a.nchan, bb, lane);
+	WAVE_SYNC();
+	for(uint32_t g = wave_id; g < total; g += gridDim.x * kBurstWaves) {
+		const int c = burst_chan_of(bb, a.nchan, g);
+		const Burst b = a.bursts[(size_t)c * a.cap_bursts_chan + (g - bb[c])];
+		ChanView v{ a.y + (size_t)c * a.cap, nullptr, nullptr, a.mask, a.ref, c, a.ref_launch };
+		BurstMarks mk;
+		burst_mark(b, v, sh, mk);
+		if(mk.mfirst != 0xffffffffu) {
+			uint32_t pm[4] = { sh.u_pm[0], sh.u_pm[1], sh.u_pm[2], sh.u_pm[3] };
+			for(int q = 0; q < 128; q++) {
+				if(!((pm[q >> 5] >> (q & 31)) & 1u)) continue;
+				int64_t lo_, hi_;
+				burst_piece_range(mk, q, q, lo_, hi_);
+				if(ref_window_done(v, lo_, hi_)) pm[q >> 5] &= ~(1u << (q & 31));
+			}
+			if(lane == 0) {
+				const uint32_t np = (uint32_t)(popc32(pm[0]) + popc32(pm[1]) + popc32(pm[2]) + popc32(pm[3]));
+				uint32_t j = np ? atomicAdd(a.mq_n, np) : 0u;
+				for(int q = 0; q < 128; q++) {
+					if(!((pm[q >> 5] >> (q & 31)) & 1u)) continue;
+					int64_t lo_, hi_;
+					burst_piece_range(mk, q, q, lo_, hi_);
+					if(j < a.mq_cap) a.mq[j] = ScanReq{ c, REF_SYMBOLS, lo_, hi_ };
+					j++;
+				}
+			}
+		}
+		WAVE_SYNC();
+	}
 }
 
 // Short feeds: the noise floor (needs the walker's evaluation log) and the burst decoder (needs its burst lists) do not need each other,

@@ -2513,32 +2513,33 @@ VDL2_HD void burst_shared_init(const Tables &T, uint32_t wave, const OutCtl *ctl
 // them all at once, a wavefront each, and a second pass decodes the listed bursts (pass 2: every stretch it asks for is then done).
 constexpr int kRefPieceBits = 10;           // a burst's stretches are asked for in pieces of 2^10 decimated samples, each scanned on its own (a scan is its run-up, 2^17 input samples, plus its stretch: with pieces of 2^12 - 82 000 input samples - a listed burst's scans took 2.2 ms instead of 1.6)
 struct ScanReq { int32_t chan, kind; int64_t lo, hi; };
-struct BurstDefer { uint32_t *dq, *dq_n; uint32_t dq_cap; ScanReq *sq; uint32_t *sq_n; uint32_t sq_cap; int32_t pass; };
+struct BurstDefer { uint32_t *dq, *dq_n; uint32_t dq_cap; ScanReq *sq; uint32_t *sq_n; uint32_t sq_cap; int32_t pass; uint32_t *late_n = nullptr; };   // late_n: counts the pieces pass 1 lists (statistics)
 
-// decode_vdl2_burst() DEC_DATA branch + decode_frame(): decode.c:259-380, 173-194.  burst_shared_init() first.
-// (df, tag: see BurstDefer - tag is what pass 1 lists the burst as)
-VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_t freq, const Tables &T, const ChanView &v, unsigned long long *cnt,
-		OutFrame *frames, uint8_t *pool, OutCtl *ctl, BurstShared &sh, const BurstDefer *df = nullptr, uint32_t tag = 0) {
-	// geometry again from TL (decode.c:233-256)
-	const uint32_t octets = b.tl_bits / 8 + (b.tl_bits % 8 != 0);
-	uint32_t nblk = octets / kRsK, last = octets % kRsK;
-	uint32_t fec = nblk * kRsPar;
-	if(last != 0) nblk++;
-	fec += (uint32_t)fec_octets_for(last);
-	if(last == 0) last = kRsK;
-	const int npar_last = fec_octets_for(last);
+// What the marking step (burst_mark) leaves besides sh.sym, sh.u_pwr and sh.u_negs: the first and last marked symbol (mfirst
+// 0xffffffff: none - nothing else is set then) and, in sh.u_pm, the pieces of 2^kRefPieceBits samples that hold a marked symbol's two
+// samples or the slope's taps, counted from piece P0; w_lo / hi: the first and last sample anybody asks for (wide: all of it as one stretch).
+struct BurstMarks { uint32_t mfirst, mlast; bool redo_slope, wide; int64_t w_lo, hi, P0; };
+// pieces q .. q1 of the mask as one stretch
+VDL2_HD void burst_piece_range(const BurstMarks &mk, int q, int q1, int64_t &lo_, int64_t &hi_) {
+	lo_ = (mk.P0 + q) << kRefPieceBits; hi_ = ((mk.P0 + q1 + 1) << kRefPieceBits) - 1;
+	if(mk.wide) { lo_ = mk.w_lo; hi_ = mk.hi; }
+	if(lo_ < mk.w_lo) lo_ = mk.w_lo;
+	if(hi_ > mk.hi) hi_ = mk.hi;                                   // (the slope's taps lie before the burst's first symbol: below hi)
+}
+// Step 1 of decode_burst(), which needs the burst's descriptor and the channel's y and nothing else of the decoder: the burst decoder
+// calls it, and so does k_burst_mark (kernels.h), which lists the pieces for the check's scan launch before the burst decoder runs.
+VDL2_HD __attribute__((always_inline)) void burst_mark(const Burst &b, const ChanView &v, BurstShared &sh, BurstMarks &mk) {
 	const int nsym = b.nsym;
-	K5_BEGIN();
-
 	// 1. slice every symbol (demod.c:252-274); decisions are independent because prev_phi is the raw phase.  A lane takes
 	//    a run of consecutive symbols, so that the phase of a symbol (one double-precision atan2, evaluated here: there is no
 	//    stored phase stream) also serves as the next symbol's prev_phi.
 	//    Referee: a symbol whose decision is within the margin of the stream's error is marked (bit 7 of its entry) and sliced
-	//    again below, on the reference's own samples.
+	//    again by decode_burst(), on the reference's own samples.
 	const int per_lane = (nsym + 63) / 64;
 	const bool ref_on = v.ref != nullptr;
-	float vdphi = b.vdphi, ppm = b.ppm;
+	const float vdphi = b.vdphi;
 	const float verr = fabsf(b.vdphi_err);
+	mk.mfirst = 0xffffffffu; mk.mlast = 0u; mk.redo_slope = false; mk.wide = false; mk.w_lo = 0; mk.hi = -1; mk.P0 = 0;
 	WAVE_FOR(l)
 		float pw = 0.f; int neg = 0; float qmin = kRefBig;
 		const int m0 = l * per_lane, m1 = m0 + per_lane < nsym ? m0 + per_lane : nsym;
@@ -2611,7 +2612,6 @@ VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_
 		const uint32_t mfirst = wave_min64(sh.lanek), mlast = ~wave_min64(sh.lanet);
 		WAVE_SYNC();
 		if(mfirst != 0xffffffffu) {
-			// ---- referee: the marked symbols (and, if it is not the reference's yet, the carrier slope) on the reference's own samples ----
 			// A scan costs its run-up (2^17 input samples) plus the stretch, so not the whole burst is asked for but the pieces of it
 			// that hold a marked symbol's two samples or the slope's taps (which lie before the burst).
 			const bool redo_slope = b.vdphi_err > 0.f;
@@ -2621,7 +2621,7 @@ VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_
 			const int64_t w_lo = (redo_slope && s_lo < t_lo) ? (s_lo < 0 ? 0 : s_lo) : t_lo;
 			const int64_t P0 = w_lo >> kRefPieceBits;
 			const bool wide = (hi >> kRefPieceBits) - P0 >= 128;             // (longer than any burst of the bench workloads: one stretch then)
-			const int pass = df ? df->pass : 0;
+			mk.mfirst = mfirst; mk.mlast = mlast; mk.redo_slope = redo_slope; mk.wide = wide; mk.w_lo = w_lo; mk.hi = hi; mk.P0 = P0;
 			LANE0
 				uint32_t pm[4] = { 0u, 0u, 0u, 0u };
 				if(wide) pm[0] = 1u;
@@ -2636,8 +2636,48 @@ VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_
 					}
 				}
 				for(int i = 0; i < 4; i++) sh.u_pm[i] = pm[i];
+			LANE0_END
+		}
+	}
+}
+
+// decode_vdl2_burst() DEC_DATA branch + decode_frame(): decode.c:259-380, 173-194.  burst_shared_init() first.
+// (df, tag: see BurstDefer - tag is what pass 1 lists the burst as)
+VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_t freq, const Tables &T, const ChanView &v, unsigned long long *cnt,
+		OutFrame *frames, uint8_t *pool, OutCtl *ctl, BurstShared &sh, const BurstDefer *df = nullptr, uint32_t tag = 0) {
+	// geometry again from TL (decode.c:233-256)
+	const uint32_t octets = b.tl_bits / 8 + (b.tl_bits % 8 != 0);
+	uint32_t nblk = octets / kRsK, last = octets % kRsK;
+	uint32_t fec = nblk * kRsPar;
+	if(last != 0) nblk++;
+	fec += (uint32_t)fec_octets_for(last);
+	if(last == 0) last = kRsK;
+	const int npar_last = fec_octets_for(last);
+	K5_BEGIN();
+
+	// 1. every symbol sliced, those within the referee's margin marked, the pieces that hold them in sh.u_pm
+	float vdphi = b.vdphi, ppm = b.ppm;
+	BurstMarks mk;
+	burst_mark(b, v, sh, mk);
+	{
+		const uint32_t mfirst = mk.mfirst, mlast = mk.mlast;
+		if(mfirst != 0xffffffffu) {
+			// ---- referee: the marked symbols (and, if it is not the reference's yet, the carrier slope) on the reference's own samples ----
+			const bool redo_slope = mk.redo_slope;
+			const int pass = df ? df->pass : 0;
+			// Pass 1: the pieces have been listed ahead (k_burst_mark) and scanned in the check's launch - all but always every one of them is
+			// exact by now, and the burst is decoded here.  Not so after a second stitch that changed the channel's bursts, a mark list that
+			// ran over or a refused scan: the burst and its pieces are listed for pass 2.
+			bool ahead = pass == 1;
+			for(int q = 0; q < 128 && ahead; q++) {
+				if(!((sh.u_pm[q >> 5] >> (q & 31)) & 1u)) continue;
+				int64_t lo_, hi_;
+				burst_piece_range(mk, q, q, lo_, hi_);
+				ahead = ref_window_done(v, lo_, hi_);
+			}
+			LANE0
 				sh.u_defer = 0;
-				if(pass == 1) {
+				if(pass == 1 && !ahead) {
 					// list the burst and its pieces; a burst that does not get on the list is done here and now
 #if VDL2_DEVICE_PASS
 					const uint32_t i = atomicAdd(df->dq_n, 1u);
@@ -2647,18 +2687,18 @@ VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_
 					if(i < df->dq_cap) {
 						df->dq[i] = tag; sh.u_defer = 1;
 						uint32_t np = 0;
-						for(int q = 0; q < 4; q++) np += (uint32_t)popc32(pm[q]);
+						for(int q = 0; q < 4; q++) np += (uint32_t)popc32(sh.u_pm[q]);
 #if VDL2_DEVICE_PASS
 						uint32_t j = atomicAdd(df->sq_n, np);
+						if(df->late_n) atomicAdd(df->late_n, np);
 #else
 						uint32_t j = *df->sq_n; *df->sq_n += np;
+						if(df->late_n) *df->late_n += np;
 #endif
 						for(int q = 0; q < 128; q++) {
-							if(!((pm[q >> 5] >> (q & 31)) & 1u)) continue;
-							int64_t lo_ = (P0 + q) << kRefPieceBits, hi_ = ((P0 + q + 1) << kRefPieceBits) - 1;
-							if(wide) { lo_ = w_lo; hi_ = hi; }
-							if(lo_ < w_lo) lo_ = w_lo;
-							if(hi_ > hi) hi_ = hi;                                   // (the slope's taps lie before the burst's first symbol: below hi)
+							if(!((sh.u_pm[q >> 5] >> (q & 31)) & 1u)) continue;
+							int64_t lo_, hi_;
+							burst_piece_range(mk, q, q, lo_, hi_);
 							if(j < df->sq_cap) df->sq[j] = ScanReq{ v.ref_chan, REF_SYMBOLS, lo_, hi_ };      // (a piece that finds no room is scanned by pass 2 itself)
 							j++;
 						}
@@ -2668,15 +2708,13 @@ VDL2_HD __attribute__((always_inline)) void decode_burst(const Burst &b, uint32_
 			if(sh.u_defer) { K5_END(); return; }
 			bool ok = true;
 			{
-				// runs of pieces: one stretch each (pass 2: piece by piece, as they were made)
-				for(int q = 0; q < 128 && ok; ) {
+				// runs of pieces: one stretch each (pass 2: piece by piece, as they were made; pieces made ahead: nothing to ask for)
+				for(int q = 0; q < 128 && ok && !ahead; ) {
 					if(!((sh.u_pm[q >> 5] >> (q & 31)) & 1u)) { q++; continue; }
 					int q1 = q;
 					if(pass != 2) while(q1 + 1 < 128 && ((sh.u_pm[(q1 + 1) >> 5] >> ((q1 + 1) & 31)) & 1u)) q1++;
-					int64_t lo_ = (P0 + q) << kRefPieceBits, hi_ = ((P0 + q1 + 1) << kRefPieceBits) - 1;
-					if(wide) { lo_ = w_lo; hi_ = hi; }
-					if(lo_ < w_lo) lo_ = w_lo;
-					if(hi_ > hi) hi_ = hi;
+					int64_t lo_, hi_;
+					burst_piece_range(mk, q, q1, lo_, hi_);
 					ok = ref_exact_window(v, lo_, hi_, sh.xw, REF_SYMBOLS);
 					q = q1 + 1;
 				}

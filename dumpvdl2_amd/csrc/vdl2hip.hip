@@ -123,6 +123,7 @@ struct OutSlot {
 	DevBuf<OutFrame> d_frames_out; DevBuf<uint8_t> d_pool_out;    // what k_frame_finish delivers (no tombstones, no holes): what the host copies
 	DevBuf<EvalChunk> d_log; DevBuf<uint32_t> d_nlog;   // the walker's evaluation log of this feed (read by K4b)
 	DevBuf<uint32_t> d_dq; DevBuf<ScanReq> d_sq;      // referee, long feeds: the bursts that wait for a scan, the stretches they wait for (counts: d_rqn[1], d_rqn[2])
+	DevBuf<ScanReq> d_mq;               // referee: the pieces k_burst_mark lists behind the walk for the check's scan launch (count: d_rqn[7])
 	DevBuf<RefReq> d_rq; DevBuf<uint32_t> d_rqn, d_rqflag; DevBuf<RefBad> d_rqbad;
 	DevBuf<ScanReq> d_retry;            // [3][kRetryScans]: the unmet scans of the scans ahead of the walk / of the check / of the burst decoder (counts: d_rqn[4..6])
 	DevBuf<ScanReq> d_pq; Event ev_pre;      // referee: the stretches around marked candidates, made exact between the front and the walk (count: d_rqn[3])
@@ -258,7 +259,7 @@ struct vdl2hip_ctx {
 	bool referee = true; bool ref_prescan = false;   /* VDL2HIP_REF_PRESCAN=1: the stretches around marked candidates are made exact ahead of the walk - a rank-sized shard 4.05 -> 2.88 ms per step, 256 channels 7.2 -> 7.85: for receivers of few channels */ int64_t ref_warm = 3 << 16 /* 196 608: kernels.h */, ref_T = 0; DevBuf<uint8_t> d_refhist; uint64_t ref_cap = 0, ref_wp = 0;
 	struct HistPiece { int64_t s0, n; uint64_t pos; }; std::vector<HistPiece> ref_pieces;
 	DevBuf<WalkState> d_ws_snap[2], d_ws_tmp; DevBuf<unsigned long long> d_cnt_snap[2], d_cnt_tmp; uint32_t rq_cap = 8192; uint32_t sq_alloc = 8192;
-	int walk_ahead = 1; bool walk_ahead_auto = true; double walk_ahead_below = 1.1e8; int debug_force_mismatch = 0;   // launch_back(): the walk of the next feed does not (1) / does (0) wait for this feed's check
+	int walk_ahead = 1; bool walk_ahead_auto = true; double walk_ahead_below = 1.1e8; int debug_force_mismatch = 0; uint32_t debug_mark_cap = 0;   // launch_back(): the walk of the next feed does not (1) / does (0) wait for this feed's check
 	int ref_retry_mul = 2;                 // a scan that has not met its witness is run again from this many times further back (0: not at all; VDL2HIP_REF_RETRY)
 	DevBuf<RefChan> d_ref[kSlots]; DevBuf<unsigned long long> d_refdone; DevBuf<uint32_t> d_refdonen, d_refstats; DevBuf<uint8_t> d_mix;
 	std::vector<uint64_t> statsd_prev;
@@ -755,12 +756,13 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 // from ref_retry_mul times further back (no list, or ref_retry_mul 0: they are published as they are, counted).  e0 / e1: the first
 // kernel's start and the last one's stop (the test hook's timing).
 static void launch_scans(vdl2hip_ctx *c, hipStream_t st, RefChan *ref, uint32_t launch, const ScanReq *sq, const RefReq *rq, const uint32_t *n, uint32_t cap, int64_t k_end,
-                         ScanReq *retry, uint32_t *retry_n, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+                         ScanReq *retry, uint32_t *retry_n, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, const ScanReq *sq2 = nullptr, const uint32_t *n2 = nullptr, uint32_t cap2 = 0) {
 	const int rty = retry ? c->ref_retry_mul : 0;
-	LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3((cap + kScanLanes - 1) / kScanLanes), dim3(64 * kScanWaves), 0, st, e0, rty ? (hipEvent_t) nullptr : e1, 0, ref, launch,
-	                  sq, rq, n, cap, k_end, rty ? retry : (ScanReq *) nullptr, retry_n, kRetryScans, 1);
+	// (sq2: a second list - *n2 of them, at most cap2 - served by the same launch, behind the first; the grid covers both)
+	LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3((cap + (sq2 ? cap2 : 0u) + kScanLanes - 1) / kScanLanes), dim3(64 * kScanWaves), 0, st, e0, rty ? (hipEvent_t) nullptr : e1, 0, ref, launch,
+	                  sq, rq, n, cap, k_end, rty ? retry : (ScanReq *) nullptr, retry_n, kRetryScans, 1, sq2, n2, sq2 ? cap2 : 0u);
 	if(rty) LAUNCH_SCAN_MULTI(hipExtLaunchKernelGGL, dim3(kRetryScans / kScanLanes), dim3(64 * kScanWaves), 0, st, (hipEvent_t) nullptr, e1, 0, ref, launch,
-	                  (const ScanReq *)retry, (const RefReq *) nullptr, (const uint32_t *)retry_n, kRetryScans, k_end, (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty);
+	                  (const ScanReq *)retry, (const RefReq *) nullptr, (const uint32_t *)retry_n, kRetryScans, k_end, (ScanReq *) nullptr, (uint32_t *) nullptr, 0u, rty, (const ScanReq *) nullptr, (const uint32_t *) nullptr, 0u);
 }
 // The walk of feed i + 1 does not wait for the check of feed i ("walk ahead").  walk(i + 1) needs the state walk(i) leaves, and that
 // state is final only when the decisions walk(i) noted have been checked - behind a scan of 1.5 ms that no hardware shortens; with a
@@ -866,8 +868,21 @@ static int launch_back(vdl2hip_ctx *c, OutSlot &sl) {
 			// of its own it cost the 256-channel receiver 0.6 ms per step, profiles/r06_walk_ahead_ab.txt)
 			sl.has_chk = true;
 			hipStream_t sc_ = wa ? sp_ : sb_;
+			// ... and with them, in the same launch, the pieces the burst decoder will want exact: which they are depends on the burst
+			// descriptors this walk has written and on y, on nothing the check decides - k_burst_mark lists them here, right behind the
+			// walk, and the burst decoder's first pass finds them done (a channel stitched again, a list that ran over, a refused scan:
+			// the decoder's own list and second pass, as before).  One scan round in a feed's chain instead of two.
+			uint32_t mq_cap = small ? kDeferScans / 16 : std::min(c->sq_alloc, defer_scans_for(D, c->C));
+			if(c->debug_mark_cap) mq_cap = std::min(mq_cap, c->debug_mark_cap);
+			// (on the walk stream, ahead of the hand-over to the check's stream: the kernels that rewrite this feed's burst rows later - the
+			// second stitch, the feed once more after a corrected start - follow on this stream, so it reads the rows the first walk wrote)
+			{
+				K5mArgs k5m{ c->d_y, sl.d_bursts, sl.d_nbchan, c->cap_bursts_chan, c->C, c->cap, c->cap - 1, k4.ref, k4.ref_launch - 1u, sl.d_mq, sl.d_rqn + 7, mq_cap };
+				const unsigned k5_lds = (unsigned)((sizeof(BurstShared) + 4 * (kK5MaxChan + 1)) * kBurstWaves);
+				hipLaunchKernelGGL(k_burst_mark, dim3(sl.k5_waves / kBurstWaves), dim3(64 * kBurstWaves), k5_lds, sb_, k5m);
+			}
 			if(sc_ != sb_) { HIPCHK(hipEventRecord(sl.ev_stitch, sb_)); HIPCHK(hipStreamWaitEvent(sc_, sl.ev_stitch, 0)); }
-			launch_scans(c, sc_, k4.ref, k4.ref_launch - 1u, nullptr, k4.rq, k4.rq_n, rq_cap, k1, sl.d_retry + kRetryScans, sl.d_rqn + 5);
+			launch_scans(c, sc_, k4.ref, k4.ref_launch - 1u, nullptr, k4.rq, k4.rq_n, rq_cap, k1, sl.d_retry + kRetryScans, sl.d_rqn + 5, nullptr, nullptr, sl.d_mq, sl.d_rqn + 7, mq_cap);
 			hipLaunchKernelGGL(k_ref_verify, dim3(small ? 64 : 1024), dim3(64), 0, sc_, k4);
 			HIPCHK(hipEventRecord(sl.ev_chk, sc_));
 		}
@@ -1117,7 +1132,7 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		// block for 22 ms, profiles/r06_weak_bursts.txt; their lists and the grids that serve them are a sixteenth of a long feed's.)
 		const bool defer5 = c->referee;
 		const uint32_t sq_cap = small ? kDeferScans / 16 : std::min(c->sq_alloc, defer_scans_for(D, c->C)), dq_cap = sq_cap / 2;
-		if(defer5) k5.df = BurstDefer{ sl.d_dq, sl.d_rqn + 1, dq_cap, sl.d_sq, sl.d_rqn + 2, sq_cap, 1 };
+		if(defer5) k5.df = BurstDefer{ sl.d_dq, sl.d_rqn + 1, dq_cap, sl.d_sq, sl.d_rqn + 2, sq_cap, 1, c->d_refstats + 12 };
 		const unsigned k5_lds = (unsigned)((sizeof(BurstShared) + 4 * (kK5MaxChan + 1)) * kBurstWaves);
 		hipEvent_t ev_last5 = defer5 ? (hipEvent_t) nullptr : EV(11);
 		if(small) hipExtLaunchKernelGGL(k_nf_burst, dim3(nf_grid + sl.k5_waves / kBurstWaves), dim3(64 * kNfWaves), std::max(nf_lds, k5_lds), s5_, EV(8), ev_last5, 0, k4b, k5, (uint32_t)nf_grid);
@@ -1399,7 +1414,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 		c->sq_alloc = defer_scans_for((int64_t)dmax, (int)count);
 		for(auto &sl : c->slot) {
 			DEV_ALLOC(sl.d_rq, c->rq_cap); DEV_ALLOC(sl.d_rqn, 8, true); DEV_ALLOC(sl.d_retry, 3 * (size_t)kRetryScans); DEV_ALLOC(sl.d_rqflag, count, true);
-			DEV_ALLOC(sl.d_dq, c->sq_alloc / 2); DEV_ALLOC(sl.d_sq, c->sq_alloc);
+			DEV_ALLOC(sl.d_dq, c->sq_alloc / 2); DEV_ALLOC(sl.d_sq, c->sq_alloc); DEV_ALLOC(sl.d_mq, c->sq_alloc);
 			DEV_ALLOC(sl.d_pq, kPreScans); DEV_CHK(sl.ev_pre.ensure(hipEventDisableTiming));
 			DEV_ALLOC(sl.d_rqbad, count, true);
 			DEV_ALLOC(sl.d_rqflag2, count, true);
@@ -1704,10 +1719,11 @@ int vdl2hip_get_stats_sized(vdl2hip_ctx *c, vdl2hip_stats *out, size_t size) {
 		for(int i = 0; i < c->C; i++) { c->stats.seg_adopted += ss[2 * i]; c->stats.seg_walked += ss[2 * i + 1]; }
 	}
 	if(c->d_refstats) {
-		uint32_t rs[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		uint32_t rs[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		if(hipMemcpy(rs, c->d_refstats, sizeof rs, hipMemcpyDeviceToHost) != hipSuccess) return VDL2HIP_E_DEVICE;
 		c->stats.referee_scans = rs[0]; c->stats.referee_cached = rs[1]; c->stats.referee_refused = rs[2]; c->stats.referee_short = rs[3];
 		c->stats.referee_candidate_scans = rs[4]; c->stats.referee_header_scans = rs[5]; c->stats.referee_symbol_scans = rs[6]; c->stats.referee_rewalks = rs[7]; c->stats.referee_redone_next = rs[8]; c->stats.referee_unmet = rs[9]; c->stats.referee_retried = rs[10];
+		c->stats.referee_symbol_pieces_ahead = rs[11]; c->stats.referee_symbol_pieces_late = rs[12];
 	}
 	memcpy(out, &c->stats, std::min(size, sizeof c->stats));
 	return (r == VDL2HIP_E_OVERFLOW || c->failed) ? VDL2HIP_OK : r;

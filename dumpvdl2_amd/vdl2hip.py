@@ -81,7 +81,8 @@ class Stats(C.Structure):
                 ("referee_scans", C.c_uint64), ("referee_cached", C.c_uint64), ("referee_refused", C.c_uint64), ("referee_short", C.c_uint64), ("referee_rewalks", C.c_uint64),
                 ("referee_candidate_scans", C.c_uint64), ("referee_header_scans", C.c_uint64), ("referee_symbol_scans", C.c_uint64),
                 ("referee_redone_next", C.c_uint64), ("referee_unmet", C.c_uint64), ("referee_retried", C.c_uint64),
-                ("resampled_samples", C.c_uint64), ("resample_ms", C.c_double)]
+                ("resampled_samples", C.c_uint64), ("resample_ms", C.c_double),
+                ("referee_symbol_pieces_ahead", C.c_uint64), ("referee_symbol_pieces_late", C.c_uint64)]
 
 
 class SpectrumCfg(C.Structure):

@@ -48,7 +48,9 @@ extern "C" {
                                  *    VDL2HIP_FMT_S8 (4): one more accepted value of vdl2hip_cfg.sample_fmt, as VDL2HIP_FMT_CF32 was - no structure, no
                                  *    entry point and no result for the other formats changed, so the version stayed
                                  *    vdl2hip_txlog_enable() / _disable() / _info_get() / _read() with vdl2hip_txlog_cfg / _info and vdl2hip_tx: the
-                                 *    transmission log, off unless enabled - new entry points and structures only, so the version stayed */
+                                 *    transmission log, off unless enabled - new entry points and structures only, so the version stayed
+                                 *    vdl2hip_stats.referee_symbol_pieces_ahead / _late (at its end, as resampled_samples was: a caller built against the
+                                 *    shorter structure goes through vdl2hip_get_stats_sized() or never reads them), so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -443,6 +445,11 @@ typedef struct {
 	uint64_t referee_retried;   /* ABI 6.  ... and those that were: listed and scanned again from twice as far back (VDL2HIP_REF_RETRY) */
 	uint64_t resampled_samples; /* receivers with cfg.input_rate: samples of the resampled stream r[] made so far (0 otherwise) */
 	double   resample_ms;       /* ... and the summed HIP-event time of the resampler's launches (profiling level 2, like the other stages) */
+	uint64_t referee_symbol_pieces_ahead;   /* ABI 6 (at the structure's end).  Pieces of bursts (1 024 decimated samples each) that hold a symbol within the
+	                             * margin, listed right behind the feed's walk and scanned in the same launch as the walk's noted decisions: the
+	                             * burst decoder then finds them done and a feed's chain holds one round of scans, not two */
+	uint64_t referee_symbol_pieces_late;    /* ... and those the burst decoder's first pass still had to list for a scan round and a second pass of its own:
+	                             * bursts of a channel that the check had stitched again, what a full list left over, refused scans */
 } vdl2hip_stats;
 
 int  vdl2hip_abi_version(void);
