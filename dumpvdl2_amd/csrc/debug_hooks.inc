@@ -452,6 +452,41 @@ int vdl2hip_debug_txlog_words(const float *p, const uint32_t *nbits, uint32_t co
 	return (int)nrec;
 }
 
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): the preamble search's per-piece steps (txsearch.h) for one record,
+// lane by lane and level by level as k_txsearch_piece and k_txsearch_reduce take them - y: the channel's ring of ring_len (re, im)
+// pairs (a power of two), the record's first_sample and last_sample, its frequency -> rec: a vdl2hip_tx_search with chan, first_bin
+// and the host's fields 0.  The staging arrays have a guard zone of NaNs behind each: VDL2HIP_E_DEVICE if a store went beyond a piece's sizes.
+int vdl2hip_debug_txsearch_range(const float *y, uint32_t ring_len, int64_t first, int64_t last, uint32_t freq, void *rec) {
+	if(!y || !rec || ring_len < 2 || (ring_len & (ring_len - 1)) || first < 0 || last < first || !freq) return VDL2HIP_E_INVAL;
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	auto tab = std::make_unique<Tables>(); build_tables(*tab);
+	int64_t sf; uint32_t fl;
+	txs_range(first, last, sf, fl);
+	const uint32_t np = txs_pieces(sf, last);
+	if(np == 0 || np > (uint32_t)(kTxsSpan / kTxsPiece)) return VDL2HIP_E_DEVICE;
+	constexpr int G = 16;
+	std::vector<float> phi(kTxsPhi + G), p(kTxsP + G);
+	std::vector<TxsPart> part(kTxsThreads), piece(np);
+	bool bad = false;
+	for(uint32_t g = 0; g < np; g++) {
+		const int64_t n0 = sf + (int64_t)g * (int64_t)kTxsPiece, left = last - n0 + 1;
+		const uint32_t cnt = left < (int64_t)kTxsPiece ? (uint32_t)left : kTxsPiece;
+		std::fill(phi.begin(), phi.end(), NAN); std::fill(p.begin(), p.end(), NAN);
+		for(uint32_t l = 0; l < (uint32_t)kTxsThreads; l++) txs_phase_step(yc, ring_len - 1, n0, cnt, l, kTxsThreads, phi.data());
+		for(uint32_t l = 0; l < (uint32_t)kTxsThreads; l++) { part[l] = txs_none(); txs_metric_step(phi.data(), *tab, n0, cnt, l, kTxsThreads, p.data(), part[l]); }
+		for(uint32_t l = 0; l < (uint32_t)kTxsThreads; l++) txs_lock_step(p.data(), n0, cnt, sf, l, kTxsThreads, part[l]);
+		for(uint32_t s = kTxsThreads / 2; s >= 1; s >>= 1) for(uint32_t l = 0; l < (uint32_t)kTxsThreads; l++) txs_tree_step(part.data(), l, s);
+		piece[g] = part[0];
+		for(int i = 0; i < G; i++) bad = bad || !std::isnan(phi[kTxsPhi + i]) || !std::isnan(p[kTxsP + i]);
+	}
+	TxsPart t = txs_none();
+	for(uint32_t g = 0; g < np; g++) txs_combine(t, piece[g]);
+	TxsRec r;
+	txs_record(0u, freq, 0ull, 0u, sf, last, fl, t, r);
+	memcpy(rec, &r, sizeof r);
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+
 // test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
 // one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
 // series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.

@@ -25,6 +25,7 @@
 #include "spectrum_design.h"
 #include "activity.h"
 #include "txlog.h"
+#include "txsearch.h"
 #include "capture.h"
 #include "tables.h"
 #include "hostmem.h"
@@ -141,8 +142,8 @@ struct OutSlot {
 	Event ev_stitch, ev_chk; DevBuf<uint32_t> d_rqflag2;
 	// profiling level 2, per tap: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
 	// k_activity_power and k_activity_scan (activity monitor) / k_capture_plan and k_capture_copy (burst capture)
-	// / k_txlog_plan and k_txlog_emit (transmission log)
-	KernelTimes rs_t, mon_t, act_t, cap_t, txl_t;
+	// / k_txlog_plan and k_txlog_emit (transmission log) / k_txsearch_plan .. k_txsearch_reduce (preamble search: one pair round the three)
+	KernelTimes rs_t, mon_t, act_t, cap_t, txl_t, txs_t;
 	// burst capture (capture.h): the feed's header and records (one allocation: the header and the first records come to the host in one
 	// small copy; d_rec = the records behind the header, not owned), windows and totals, the IQ pool, the small copy's page-locked landing
 	// place.  Given back as one when the capture is disabled (capture_free); cap_on: this feed's back end is followed by the capture's launches
@@ -153,6 +154,11 @@ struct OutSlot {
 	// Given back when the log is switched off (txlog_free); txl_on: this feed completed bins and the log's launches followed its scan
 	struct { DevBuf<TxHdr> d_hdr; TxRec *d_rec = nullptr; PinnedBuf h_mail; } txl;
 	bool txl_on = false;
+	// preamble search (txsearch.h): the feed's header and records (one allocation, as the log's; d_rec = the records behind the header,
+	// not owned), the records' piece offsets, the pieces' partial results, the small copy's page-locked landing place.  Given back when
+	// the search is switched off (txsearch_free); txs_on: the search's launches followed this feed's frame finisher
+	struct { DevBuf<TxsHdr> d_hdr; TxsRec *d_rec = nullptr; DevBuf<uint32_t> d_off; DevBuf<TxsPart> d_part; PinnedBuf h_mail; } txs;
+	bool txs_on = false;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -207,6 +213,14 @@ struct vdl2hip_ctx {
 		struct { DevBuf<TxState> d_st; DevBuf<uint32_t> d_cnt; PinnedBuf stage; } buf;
 		std::deque<vdl2hip_tx> queue; std::vector<std::deque<TxFrame>> wait;
 	} txl;
+	// Preamble search (txsearch.h, vdl2hip_txsearch_*): off unless enabled, and only beside the transmission log.  piece_cap: the
+	// pieces a feed's records can have at the most (txsearch_piece_cap); stage: the landing place of a feed with more records than come
+	// with the header; queue: the records of the collected feeds, oldest first
+	struct {
+		bool on = false; uint32_t flags = 0, piece_cap = 0;
+		uint64_t records = 0, samples = 0, clipped = 0; double kernel_ms = 0.0;
+		PinnedBuf stage; std::deque<vdl2hip_tx_search> queue;
+	} txs;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
@@ -340,6 +354,8 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D);
 
 static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
 static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
+static int txsearch_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st);
+static void txsearch_free(vdl2hip_ctx *c);
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
@@ -350,6 +366,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.act_t.collect(c->act.kernel_ms);
 	sl.cap_t.collect(c->capt.kernel_ms);
 	sl.txl_t.collect(c->txl.kernel_ms);
+	sl.txs_t.collect(c->txs.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
 		const Event *ev = sl.ev;
 		float ms = 0.f;
@@ -498,6 +515,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	sl.ev_valid = false;
 	sl.cap_on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
 	sl.txl_on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
+	sl.txs_on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
 		// (a cold-start feed launches the channeliser in pieces that wait for the pieces of the copy: not a kernel duration, not timed)
@@ -998,6 +1016,82 @@ static void capture_free(vdl2hip_ctx *c) {
 	c->capt.on = false;
 }
 
+// ---- the preamble search's share of a feed (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
+// The ring behind the range.  The search of feed i reads y from search_first - 153 on (the taps of p(search_first - 3)), under the
+// burst capture's conditions (above): what the ring keeps behind feed i's first sample k0 is kHistory + 1024 samples.  A record is
+// emitted by the feed that completes bin last_bin + H + 1, so that bin ends at or after k0 and last_sample >= k0 - (H + 1) B
+// >= k0 - kTxsMaxBack (vdl2hip_txsearch_enable refuses a monitor beyond that); search_first >= last_sample - (kTxsSpan - 1).
+static_assert(kTxsMaxBack + (kTxsSpan - 1) + kTxsLead < kHistory + 1024, "a range and its taps begin inside what the ring keeps behind a feed");
+static_assert(sizeof(TxsRec) == sizeof(vdl2hip_tx_search) && sizeof(vdl2hip_tx_search) == 96 && offsetof(TxsRec, first_bin) == offsetof(vdl2hip_tx_search, first_bin)
+              && offsetof(TxsRec, first_lock) == offsetof(vdl2hip_tx_search, first_lock) && offsetof(TxsRec, best_pherr) == offsetof(vdl2hip_tx_search, best_pherr)
+              && offsetof(TxsRec, best_ppm) == offsetof(vdl2hip_tx_search, best_ppm) && offsetof(TxsRec, lock_points) == offsetof(vdl2hip_tx_search, lock_points)
+              && offsetof(TxsRec, flags) == offsetof(vdl2hip_tx_search, flags) && offsetof(vdl2hip_tx_search, flags) == 72 && offsetof(TxsRec, frames) == offsetof(vdl2hip_tx_search, frames)
+              && offsetof(TxsRec, why) == offsetof(vdl2hip_tx_search, why) && offsetof(vdl2hip_tx_search, why) == 84, "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_txsearch_cfg) == 16 && sizeof(vdl2hip_txsearch_info) == 40 && sizeof(TxsHdr) == 16 && sizeof(TxsPart) == 40, "vdl2hip.h states these sizes");
+static_assert(VDL2HIP_TXS_CLIPPED == kTxsClipped && VDL2HIP_TX_PARTIAL == kTxPartial && (kTxsClipped & kTxPartial) == 0, "the two flags share a word");
+constexpr uint32_t kTxsMailRecs = 32;      // records that come to the host with the header
+constexpr size_t kTxsMailBytes = sizeof(TxsHdr) + kTxsMailRecs * sizeof(TxsRec);
+// The pieces one feed's records can have at the most.  The transmissions of a channel are disjoint and the ranges of those a feed
+// closes lie in [k0 - kTxsMaxBack - kTxsSpan, k0 + dmax): their lengths add up to less than dmax + kTxsMaxBack + kTxsSpan per channel,
+// and a range of L samples has at most L / kTxsPiece + 1 pieces; the records are at most `pool`.
+static uint64_t txsearch_piece_cap(const vdl2hip_ctx *c, uint32_t pool) {
+	return (uint64_t)c->C * ((c->dmax + kTxsMaxBack + (uint64_t)kTxsSpan) / kTxsPiece + 1) + pool;
+}
+static int txsearch_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->txs;
+	TxsArgs a{};
+	a.y = c->d_y; a.tab = c->d_tab; a.txhdr = sl.txl.d_hdr; a.txrec = sl.txl.d_rec;
+	a.off = sl.txs.d_off; a.part = sl.txs.d_part; a.rec = sl.txs.d_rec; a.hdr = sl.txs.d_hdr;
+	a.pool = c->txl.pool; a.piece_cap = m.piece_cap; a.cap = c->cap; a.mask = c->cap - 1; a.chan_first = (uint32_t)c->chan_first;
+	KernelTimes &t = sl.txs_t;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_txsearch_plan, dim3(1), dim3(kTxsThreads), 0u, st, t.e(0), (hipEvent_t) nullptr, 0, a);
+	// a workgroup per piece, grid-stride: a piece per kTxsPiece channel-samples of the feed would be every sample busy - a quarter of that, 16 .. 2048
+	const unsigned grid = (unsigned)std::min<uint64_t>(2048, std::max<uint64_t>(16, (uint64_t)sl.back_D * (uint64_t)c->C / (4 * kTxsPiece)));
+	hipLaunchKernelGGL(k_txsearch_piece, dim3(grid), dim3(kTxsThreads), 0, st, a);
+	hipExtLaunchKernelGGL(k_txsearch_reduce, dim3(std::min(256u, (c->txl.pool + 63) / 64)), dim3(64), 0u, st, (hipEvent_t) nullptr, t.e(1), 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(sl.txs.h_mail, sl.txs.d_hdr, kTxsMailBytes, hipMemcpyDeviceToHost, st));
+	t.launched(1);
+	sl.txs_on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed's search records, index for index beside the log's nrec records (the first have come with the header)
+static int txsearch_fetch(vdl2hip_ctx *c, OutSlot &sl, uint32_t nrec, const TxsRec *&srec) {
+	auto &m = c->txs;
+	srec = nullptr;
+	if(!m.on || !sl.txs.h_mail) return VDL2HIP_OK;
+	const TxsHdr h = *sl.txs.h_mail.as<TxsHdr>();
+	if(h.nrec != nrec) return VDL2HIP_E_DEVICE;                       // (never: both are the log's header of this feed)
+	srec = reinterpret_cast<const TxsRec *>(sl.txs.h_mail + sizeof(TxsHdr));
+	if(nrec > kTxsMailRecs) {
+		const size_t bytes = sizeof(TxsRec) * (size_t)nrec;
+		HIPCHK(m.stage.reserve(bytes));
+		HIPCHK(hipMemcpyAsync(m.stage, sl.txs.d_rec, bytes, hipMemcpyDeviceToHost, c->streams.out));
+		HIPCHK(hipStreamSynchronize(c->streams.out));
+		srec = m.stage.as<TxsRec>();
+	}
+	return VDL2HIP_OK;
+}
+// ... one of them, with the outcome the log has joined to its record
+static void txsearch_take(vdl2hip_ctx *c, const TxsRec &s, const vdl2hip_tx &tx) {
+	auto &m = c->txs;
+	vdl2hip_tx_search r;
+	memcpy(&r, &s, sizeof r);
+	r.frames = tx.frames; r.frames_ok = tx.frames_ok; r.reserved = r.reserved2 = 0;
+	r.why = tx.frames_ok ? VDL2HIP_TXS_DECODED : tx.frames ? VDL2HIP_TXS_FRAMES_BAD : r.lock_points ? VDL2HIP_TXS_LOCK_NO_FRAME : VDL2HIP_TXS_NO_PREAMBLE;
+	m.records++; if(r.search_last >= r.search_first) m.samples += (uint64_t)(r.search_last - r.search_first + 1); if(r.flags & VDL2HIP_TXS_CLIPPED) m.clipped++;
+	if((m.flags & VDL2HIP_TXSEARCH_UNDECODED_ONLY) && r.frames_ok != 0) return;
+	m.queue.push_back(r);
+}
+// give the search's buffers back (nothing of it may be in flight: the callers have collected every feed), the
+// staging buffer included; the slots' events stay)
+static void txsearch_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) { sl.txs = {}; sl.txs_on = false; sl.txs_t.n = 0; }
+	c->txs.stage = {}; c->txs.queue.clear();
+	c->txs.on = false;
+}
+
 // ---- the transmission log's share of a feed (txlog.h) ----
 static_assert(sizeof(TxRec) == 64 && sizeof(vdl2hip_tx) == 80 && offsetof(vdl2hip_tx, frames) == sizeof(TxRec) && offsetof(vdl2hip_tx, first_burst_ord) == 72
               && offsetof(TxRec, first_bin) == offsetof(vdl2hip_tx, first_bin) && offsetof(TxRec, peak_bin) == offsetof(vdl2hip_tx, peak_bin)
@@ -1035,11 +1129,11 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 	}
 	if(!sl.txl_on) return VDL2HIP_OK;
 	sl.txl_on = false;
-	if(!sl.txl.h_mail) return VDL2HIP_OK;
+	if(!sl.txl.h_mail) { sl.txs_on = false; return VDL2HIP_OK; }
 	const TxHdr h = *sl.txl.h_mail.as<TxHdr>();
 	const uint32_t nrec = std::min(h.nrec, m.pool);
 	m.dropped += h.dropped;
-	if(nrec == 0) return VDL2HIP_OK;
+	if(nrec == 0) { sl.txs_on = false; return VDL2HIP_OK; }
 	const TxRec *rec = reinterpret_cast<const TxRec *>(sl.txl.h_mail + sizeof(TxHdr));
 	if(nrec > kTxMailRecs) {
 		const size_t bytes = sizeof(TxRec) * (size_t)nrec;
@@ -1048,6 +1142,8 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 		HIPCHK(hipStreamSynchronize(c->streams.out));
 		rec = m.buf.stage.as<TxRec>();
 	}
+	const TxsRec *srec = nullptr;
+	if(sl.txs_on) { sl.txs_on = false; int r = txsearch_fetch(c, sl, nrec, srec); if(r != VDL2HIP_OK) return r; }
 	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
 	for(uint32_t i = 0; i < nrec; i++) {
 		vdl2hip_tx r;
@@ -1068,6 +1164,7 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 			w.resize(keep);
 		}
 		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
+		if(srec) txsearch_take(c, srec[i], r);
 		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
 		m.queue.push_back(r);
 	}
@@ -1086,6 +1183,7 @@ static int txlog_off(vdl2hip_ctx *c) {
 	if(!c->txl.on) return VDL2HIP_OK;
 	if(!c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
 	(void)hipStreamSynchronize(c->streams.front);
+	txsearch_free(c);                                                // (a search reads the log's records: it goes first)
 	txlog_free(c);
 	return VDL2HIP_OK;
 }
@@ -1151,6 +1249,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		if(sl.cap_on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 		// the transmission log's header and first records of this feed (written on the front stream ahead of the sync kernels: long done)
 		if(sl.txl_on) HIPCHK(hipMemcpyAsync(sl.txl.h_mail, sl.txl.d_hdr, kTxMailBytes, hipMemcpyDeviceToHost, s5_));
+		// the preamble search reads the log's records of this feed (the same ordering) and y here, like the capture
+		if(sl.txl_on && c->txs.on) { int r = txsearch_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 	}
 	// the control block and the first few delivered frames in one copy (collect_slot)
 	HIPCHK(hipMemcpyAsync(sl.h_mail, sl.d_mail, sizeof(OutMail), hipMemcpyDeviceToHost, s5_));
@@ -2075,6 +2175,7 @@ int vdl2hip_txlog_enable(vdl2hip_ctx *c, const vdl2hip_txlog_cfg *cfg) {
 	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier log is in flight any more
 	(void)hipStreamSynchronize(c->streams.front);
 	auto &m = c->txl;
+	txsearch_free(c);                                                // (a search that was running goes with the log it read)
 	txlog_free(c);
 	const uint32_t pool = cfg->pool_records ? cfg->pool_records : kTxDefPool;
 	const size_t C = (size_t)c->C;
@@ -2116,6 +2217,60 @@ int vdl2hip_txlog_info_get(vdl2hip_ctx *c, vdl2hip_txlog_info *info) {
 int vdl2hip_txlog_read(vdl2hip_ctx *c, vdl2hip_tx *recs, size_t cap_recs) {
 	if(!c || !c->txl.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
 	auto &q = c->txl.queue;
+	size_t n = 0;
+	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
+	return (int)n;
+}
+
+// ---- the preamble search (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
+int vdl2hip_txsearch_enable(vdl2hip_ctx *c, const vdl2hip_txsearch_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txsearch_cfg) || cfg->reserved[0] != 0 || cfg->reserved[1] != 0) return VDL2HIP_E_INVAL;
+	if(!c->txl.on || !c->act.on || (cfg->flags & ~VDL2HIP_TXSEARCH_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
+	if(((uint64_t)c->act.H + 1) * c->act.B > kTxsMaxBack) return VDL2HIP_E_INVAL;
+	const uint64_t piece_cap = txsearch_piece_cap(c, c->txl.pool);
+	if(piece_cap > 0x7fffffffull) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier search is in flight any more
+	auto &m = c->txs;
+	txsearch_free(c);
+	const uint32_t pool = c->txl.pool;
+	bool ok = true;
+	for(auto &sl : c->slot) {
+		auto &b = sl.txs;
+		ok = ok && b.d_hdr.alloc_bytes(sizeof(TxsHdr) + (size_t)std::max(pool, kTxsMailRecs) * sizeof(TxsRec)) == hipSuccess && b.d_off.alloc((size_t)pool + 1) == hipSuccess
+			&& b.d_part.alloc((size_t)piece_cap) == hipSuccess && b.h_mail.alloc(kTxsMailBytes, true) == hipSuccess;
+		if(!ok) break;
+		b.d_rec = reinterpret_cast<TxsRec *>(b.d_hdr.get() + 1);
+		ok = hipMemset(b.d_hdr, 0, kTxsMailBytes) == hipSuccess;
+	}
+	if(!ok || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txsearch_free(c); return ok ? VDL2HIP_E_DEVICE : VDL2HIP_E_NOMEM; }
+	m.flags = cfg->flags; m.piece_cap = (uint32_t)piece_cap;
+	m.records = m.samples = m.clipped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_txsearch_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->txs.on && !c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
+	txsearch_free(c);
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_txsearch_info_get(vdl2hip_ctx *c, vdl2hip_txsearch_info *info) {
+	if(!c || !c->txs.on || !info || info->struct_size != sizeof(vdl2hip_txsearch_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->txs;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->flags = m.flags;
+	info->records = m.records; info->samples_searched = m.samples; info->clipped = m.clipped; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+
+int vdl2hip_txsearch_read(vdl2hip_ctx *c, vdl2hip_tx_search *recs, size_t cap_recs) {
+	if(!c || !c->txs.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
+	auto &q = c->txs.queue;
 	size_t n = 0;
 	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
 	return (int)n;

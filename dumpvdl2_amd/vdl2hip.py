@@ -49,7 +49,11 @@ EXPORTS = [
     "vdl2hip_activity_edges", "vdl2hip_activity_enable", "vdl2hip_activity_disable", "vdl2hip_activity_read", "vdl2hip_activity_series",
     "vdl2hip_capture_enable", "vdl2hip_capture_disable", "vdl2hip_capture_info_get", "vdl2hip_capture_read",
     "vdl2hip_txlog_enable", "vdl2hip_txlog_disable", "vdl2hip_txlog_info_get", "vdl2hip_txlog_read",
+    "vdl2hip_txsearch_enable", "vdl2hip_txsearch_disable", "vdl2hip_txsearch_info_get", "vdl2hip_txsearch_read",
 ]
+# include/vdl2hip.h: VDL2HIP_TXSEARCH_UNDECODED_ONLY (cfg.flags), VDL2HIP_TXS_CLIPPED (vdl2hip_tx_search.flags, beside TX_PARTIAL), VDL2HIP_TXS_* (why)
+TXSEARCH_UNDECODED_ONLY, TXS_CLIPPED = 1, 2
+TXS_DECODED, TXS_FRAMES_BAD, TXS_LOCK_NO_FRAME, TXS_NO_PREAMBLE = 0, 1, 2, 3
 TXLOG_UNDECODED_ONLY, TX_PARTIAL = 1, 1     # include/vdl2hip.h: VDL2HIP_TXLOG_UNDECODED_ONLY (cfg.flags), VDL2HIP_TX_PARTIAL (vdl2hip_tx.flags)
 CAPTURE_FAILED_ONLY, BURST_NO_ROOM = 1, 1   # include/vdl2hip.h: VDL2HIP_CAPTURE_FAILED_ONLY (cfg.flags), VDL2HIP_BURST_NO_ROOM (vdl2hip_burst.flags)
 WIN_RECT, WIN_HANN, WIN_BH4 = 0, 1, 2     # include/vdl2hip.h: VDL2HIP_WIN_* (the input monitor's analysis windows)
@@ -154,6 +158,21 @@ TX_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("l
                      ("first_burst_ord", "<i8")])     # vdl2hip_tx, 80 bytes
 
 
+class TxsearchCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TxsearchInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("records", C.c_uint64), ("samples_searched", C.c_uint64),
+                ("clipped", C.c_uint64), ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+TXS_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("search_first", "<i8"), ("search_last", "<i8"),
+                      ("best_sample", "<i8"), ("first_lock", "<i8"), ("best_pherr", "<f4"), ("best_slope", "<f4"), ("best_ppm", "<f4"),
+                      ("lock_points", "<u4"), ("below_thr", "<u4"), ("lock_phases", "<u4"), ("flags", "<u4"),
+                      ("frames", "<u4"), ("frames_ok", "<u4"), ("why", "<u4"), ("reserved", "<u4"), ("reserved2", "<u4")])     # vdl2hip_tx_search, 96 bytes
+
+
 class PackedFrame(C.Structure):
     _fields_ = [("frame", CFrame), ("octets_off", C.c_uint64)]
 
@@ -229,6 +248,11 @@ def load_library(path: str = None):
         L.vdl2hip_txlog_disable.argtypes = [C.c_void_p]
         L.vdl2hip_txlog_info_get.argtypes = [C.c_void_p, C.POINTER(TxlogInfo)]
         L.vdl2hip_txlog_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_txsearch_enable"):
+        L.vdl2hip_txsearch_enable.argtypes = [C.c_void_p, C.POINTER(TxsearchCfg)]
+        L.vdl2hip_txsearch_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_txsearch_info_get.argtypes = [C.c_void_p, C.POINTER(TxsearchInfo)]
+        L.vdl2hip_txsearch_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -408,6 +432,29 @@ def _txlog_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
             break
         out.append(buf[:n].copy())
     return np.concatenate(out) if out else np.zeros(0, dtype=TX_DTYPE)
+
+
+def _txsearch_enable(Lib, ctx, undecoded_only) -> None:
+    cfg = TxsearchCfg(C.sizeof(TxsearchCfg), TXSEARCH_UNDECODED_ONLY if undecoded_only else 0)
+    _err(Lib, Lib.vdl2hip_txsearch_enable(ctx, C.byref(cfg)), "vdl2hip_txsearch_enable")
+
+
+def _txsearch_info(Lib, ctx) -> dict:
+    info = TxsearchInfo(C.sizeof(TxsearchInfo))
+    _err(Lib, Lib.vdl2hip_txsearch_info_get(ctx, C.byref(info)), "vdl2hip_txsearch_info_get")
+    return {k: getattr(info, k) for k, _ in TxsearchInfo._fields_ if k not in ("struct_size", "reserved")}
+
+
+def _txsearch_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
+    """vdl2hip_txsearch_read() until nothing more comes -> the records as one array of TXS_DTYPE (cap_recs: the buffer of one call)"""
+    buf = np.zeros(max(1, cap_recs), dtype=TXS_DTYPE)
+    out = []
+    while True:
+        n = _err(Lib, Lib.vdl2hip_txsearch_read(ctx, buf.ctypes.data, cap_recs), "vdl2hip_txsearch_read")
+        if n == 0:
+            break
+        out.append(buf[:n].copy())
+    return np.concatenate(out) if out else np.zeros(0, dtype=TXS_DTYPE)
 
 
 def live_resources() -> dict:
@@ -680,6 +727,22 @@ class Receiver:
         """the records of the feeds collected so far (sync() or a drain first), oldest first, as an array of TX_DTYPE"""
         return _txlog_read(self.L, self.h, cap_recs)
 
+    def txsearch_enable(self, undecoded_only: bool = False) -> None:
+        """Switch the preamble search on (include/vdl2hip.h, "Preamble search"): it needs the transmission log, takes effect with the
+        next feed, and searches every transmission the log closes for the reference's preamble metric"""
+        _txsearch_enable(self.L, self.h, undecoded_only)
+
+    def txsearch_disable(self) -> None:
+        self._chk(self.L.vdl2hip_txsearch_disable(self.h), "vdl2hip_txsearch_disable")
+
+    def txsearch_info(self) -> dict:
+        """the fields of vdl2hip_txsearch_info: the flags in force and the totals of the feeds collected so far"""
+        return _txsearch_info(self.L, self.h)
+
+    def txsearch_read(self, cap_recs: int = 4096) -> np.ndarray:
+        """the records of the feeds collected so far (sync() or a drain first), oldest first, as an array of TXS_DTYPE"""
+        return _txsearch_read(self.L, self.h, cap_recs)
+
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """switch the burst capture on from the next feed (vdl2hip.h, "Burst capture"): of every burst handed to the burst decoder the
         decimated IQ from `pre` samples before its sync to `post` after its last symbol, its timing and a phase-error quality figure.
@@ -841,6 +904,22 @@ class ReceiverGroup:
     def txlog_read(self, member: int, cap_recs: int = 4096) -> np.ndarray:
         """Receiver.txlog_read() of one member: its own channels' transmissions (chan: the index in the group's frequency list)"""
         return _txlog_read(self.L, self.member(member), cap_recs)
+
+    def txsearch_enable(self, undecoded_only: bool = False) -> None:
+        """Receiver.txsearch_enable() on every member"""
+        for i in range(self.size()):
+            _txsearch_enable(self.L, self.member(i), undecoded_only)
+
+    def txsearch_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_txsearch_disable(self.member(i)), "vdl2hip_txsearch_disable")
+
+    def txsearch_info(self, member: int) -> dict:
+        return _txsearch_info(self.L, self.member(member))
+
+    def txsearch_read(self, member: int, cap_recs: int = 4096) -> np.ndarray:
+        """Receiver.txsearch_read() of one member: its own channels' transmissions"""
+        return _txsearch_read(self.L, self.member(member), cap_recs)
 
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """the burst capture of every member (there is no group call: each member captures its own channels' bursts)"""

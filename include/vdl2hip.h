@@ -50,7 +50,9 @@ extern "C" {
                                  *    vdl2hip_txlog_enable() / _disable() / _info_get() / _read() with vdl2hip_txlog_cfg / _info and vdl2hip_tx: the
                                  *    transmission log, off unless enabled - new entry points and structures only, so the version stayed
                                  *    vdl2hip_stats.referee_symbol_pieces_ahead / _late (at its end, as resampled_samples was: a caller built against the
-                                 *    shorter structure goes through vdl2hip_get_stats_sized() or never reads them), so the version stayed */
+                                 *    shorter structure goes through vdl2hip_get_stats_sized() or never reads them), so the version stayed
+                                 *    vdl2hip_txsearch_enable() / _disable() / _info_get() / _read() with vdl2hip_txsearch_cfg / _info and
+                                 *    vdl2hip_tx_search: the preamble search, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -360,6 +362,64 @@ typedef struct {
 	uint32_t reserved2;
 } vdl2hip_txlog_info;                          /* 64 bytes */
 
+/* Preamble search (not in the reference): for every transmission the transmission log closes, was there a VDL2 preamble in it, and how
+ * far was it from locking?  An opt-in pass on the GPU that evaluates the reference's own preamble metric - got_sync() of
+ * src/demod.c:129-171, float for float - at EVERY decimated sample of the transmission, where the receiver itself evaluates it only
+ * where its screening tier lets it and keeps nothing.  It sits on top of the transmission log and needs it enabled.  Off unless
+ * enabled; with it off nothing is launched or allocated and every result is what it was, to the bit.  On, frames, counters, the
+ * decimated stream, the activity monitor, the log and the burst capture are still exactly what they were.
+ *  - Metric.  Phi(n) = the phase of y_c[n] (atan2 in float64, narrowed to float32) for n >= 0, and 0 for n < 0.  (p(n), s(n)) =
+ *    the reference's phase-error sum and slope over the 16 phases Phi(n - 150 + 10 i), i = 0 .. 15: what got_sync() computes at n on
+ *    a phase ring that holds the 160 most recent samples.
+ *  - Samples.  y_c is taken as it stands when the burst decoder of the feed that closes the transmission has finished (the burst
+ *    capture's placement and its caveat about a later feed's referee).  With the referee off, or with a single feed, it is what
+ *    vdl2hip_read_decimated() returns after vdl2hip_sync().
+ *  - Range.  search_last = the log record's last_sample; search_first = max(first_sample, search_last - 57 343): at most 57 344
+ *    samples, more than the longest burst (56 090).  VDL2HIP_TXS_CLIPPED is set in flags if the maximum took the second term.  The
+ *    range depends on the stream alone, not on how it was cut into feeds.  So that the range lies inside what the ring holds behind
+ *    a feed, vdl2hip_txsearch_enable() refuses an activity monitor with (hang_bins + 1) * bin_samples > 4096.
+ *  - Results, over n in [search_first, search_last]:
+ *      best_pherr   the smallest p(n): a float32 <, taken in ascending n, starting from +infinity; a NaN is never the best
+ *      best_sample  the lowest n that has best_pherr; -1 if none
+ *      best_slope   s(best_sample): what the reference's v->dphi would be (0 if none);  best_ppm: the reference's ppm figure of it
+ *      below_thr    #{ n : p(n) < 4.0f }
+ *      lock points  n is one iff n - 3 >= search_first and p(n - 3) < 4.0f && p(n) > p(n - 3): the condition under which the
+ *                   reference locks if its grid of every third sample evaluates at n (src/demod.c:39,173).  lock_points: their
+ *                   number; first_lock: the lowest, -1 if none; lock_phases: bit r set iff some lock point has n mod 3 == r -
+ *                   7: a reference in DM_INIT would have locked whatever its grid's phase, 0: none could.
+ *    Every field is exact: the same y_c gives the same bytes however it is cut and however the kernel splits the range.  (What the
+ *    search inherits: without the referee the channeliser's y_c itself depends, in its last bits, on how the input was cut into feeds.)
+ *  - flags: VDL2HIP_TXS_CLIPPED, and VDL2HIP_TX_PARTIAL passed on from the log's record.
+ *  - why, from the log's join: VDL2HIP_TXS_DECODED (frames_ok > 0), _FRAMES_BAD (frames > 0, none good), _LOCK_NO_FRAME (no frame,
+ *    lock_points > 0), _NO_PREAMBLE (no frame, no lock point).  frames and frames_ok are the log record's.
+ *  - Records and order.  One record per record the log wrote to its pool (a transmission the log dropped for lack of room gets none),
+ *    in the log's order, feed by feed; first_bin with chan is the join key with vdl2hip_tx.
+ *  - VDL2HIP_TXSEARCH_UNDECODED_ONLY delivers only the records with frames_ok == 0 (filtered on the host, like the log's).
+ *  - vdl2hip_txlog_enable(), vdl2hip_txlog_disable(), vdl2hip_activity_enable() and vdl2hip_activity_disable() switch a running
+ *    search off first.  Groups get no group call: vdl2hip_group_ctx(g, k) is the handle. */
+#define VDL2HIP_TXSEARCH_UNDECODED_ONLY 1u
+#define VDL2HIP_TXS_CLIPPED         2u         /* (bit 0 of vdl2hip_tx_search.flags is VDL2HIP_TX_PARTIAL) */
+#define VDL2HIP_TXS_DECODED         0u
+#define VDL2HIP_TXS_FRAMES_BAD      1u
+#define VDL2HIP_TXS_LOCK_NO_FRAME   2u
+#define VDL2HIP_TXS_NO_PREAMBLE     3u
+typedef struct { uint32_t struct_size, flags, reserved[2]; } vdl2hip_txsearch_cfg;      /* 16 bytes; reserved must be 0 */
+typedef struct {
+	uint32_t chan, freq;                  /* as in vdl2hip_tx */
+	uint64_t first_bin;                   /* the join key with vdl2hip_tx */
+	int64_t  search_first, search_last, best_sample, first_lock;
+	float    best_pherr, best_slope, best_ppm;
+	uint32_t lock_points, below_thr, lock_phases, flags;   /* flags: VDL2HIP_TXS_CLIPPED | VDL2HIP_TX_PARTIAL */
+	uint32_t frames, frames_ok, why;      /* filled in by the host from the log's join; why: VDL2HIP_TXS_DECODED ... _NO_PREAMBLE */
+	uint32_t reserved, reserved2;
+} vdl2hip_tx_search;                           /* 96 bytes */
+typedef struct {
+	uint32_t struct_size, flags;               /* as in force */
+	uint64_t records, samples_searched, clipped;   /* of the feeds collected so far: records, the sum of their range lengths, records with VDL2HIP_TXS_CLIPPED */
+	float    kernel_ms;                        /* summed HIP-event time of the search's launches at profiling level 2, else 0 */
+	uint32_t reserved;
+} vdl2hip_txsearch_info;                       /* 40 bytes */
+
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
 typedef struct {
@@ -639,6 +699,20 @@ int  vdl2hip_txlog_info_get(vdl2hip_ctx *ctx, vdl2hip_txlog_info *info);
  * lag), oldest first.  What does not fit stays queued for the next call; the call never waits for the device itself.  Returns the
  * number of records written.  Log off: VDL2HIP_E_INVAL. */
 int  vdl2hip_txlog_read(vdl2hip_ctx *ctx, vdl2hip_tx *recs, size_t cap_recs);
+
+/* ---- Preamble search (see "Preamble search" above) ----
+ * Switch the search on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way, drops
+ * what is queued unread and starts afresh.  VDL2HIP_E_INVAL if the transmission log is off, for a bad struct_size or flags, a reserved
+ * word that is not 0, or an activity monitor with (hang_bins + 1) * bin_samples > 4096, before anything is allocated or changed: a
+ * search that was on stays as it was. */
+int  vdl2hip_txsearch_enable(vdl2hip_ctx *ctx, const vdl2hip_txsearch_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_txsearch_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Search off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txsearch_info_get(vdl2hip_ctx *ctx, vdl2hip_txsearch_info *info);
+/* Like vdl2hip_txlog_read(): the records of the feeds collected so far, oldest first.  What does not fit stays queued for the next
+ * call; the call never waits for the device itself.  Returns the number of records written.  Search off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txsearch_read(vdl2hip_ctx *ctx, vdl2hip_tx_search *recs, size_t cap_recs);
 
 #ifdef __cplusplus
 }

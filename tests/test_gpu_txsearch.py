@@ -1,0 +1,511 @@
+"""The preamble search on the GPU (include/vdl2hip.h, "Preamble search"; kernels: dumpvdl2_amd/csrc/txsearch.h): for every
+transmission the transmission log closes, the reference's own sync metric at every decimated sample of it.
+
+Records are held to the model (tests/txsearch_model.py) run on the device's OWN decimated stream, read back with read_decimated()
+behind every feed: with the referee off that is the stream the search read.  Every comparison is exact, floats by their bits.
+Oversample 10 and at most 4 channels where the stream is made here, captures of 1 s at the most, the referee off unless stated."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cases
+import txsearch_model as tm
+from util import assert_frames_equal
+
+pytestmark = pytest.mark.gpu
+CF = 136975000
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WAV = os.path.join(ROOT, "tests", "golden", "vdl2_model_16b_1050kHz.wav")
+E_INVAL = -1
+
+
+@pytest.fixture(scope="module")
+def vh():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from dumpvdl2_amd import vdl2hip
+    vdl2hip.load_library()
+    return vdl2hip
+
+
+# ---------------------------------------------------------------- running a stream
+def cut_sizes(n, sizes):
+    out, k, i = [], 0, 0
+    while k < n:
+        d = min(sizes[i % len(sizes)], n - k)
+        out.append(d)
+        k += d
+        i += 1
+    return out
+
+
+def run(vh, raw, freqs, sizes, os_=10, act=(105, -40.0, 0), referee=0, search=True, log=True, undecoded=False, pool=0, block=None, read_y=True,
+        cf=CF, max_ppm=0.0, cap_recs=4096, **kw):
+    """raw: int16 (n, 2), fed in pieces of `sizes` samples with a sync() behind each; behind every feed the new decimated samples of
+    every channel are read back (the ring may be short) -> dict"""
+    rx = vh.Receiver(cf, freqs, os_, vh.FMT_S16LE, max_ppm, max_block_bytes=4 * (block or max(sizes)), **kw)
+    rx.debug_option("referee", referee)
+    if act:
+        rx.activity_enable(act[0], act[1], act[2], 0)
+    if log:
+        rx.txlog_enable(pool_records=pool)
+    if search:
+        rx.txsearch_enable(undecoded_only=undecoded)
+    chans = range(rx.chan_first, rx.chan_first + rx.chan_count)
+    y = {c: [] for c in chans}
+    frames, tx, txs, per_feed = [], [], [], []
+    k = made = 0
+    for d in sizes:
+        rx.feed(raw[k:k + d])
+        k += d
+        if read_y or d == sizes[-1]:
+            rx.sync()
+        frames += rx.drain()
+        if log:
+            tx.append(rx.txlog_read())
+        if search:
+            per_feed.append(rx.txsearch_read(cap_recs))
+        now = k // os_
+        if read_y and now > made:
+            for c in chans:
+                y[c].append(rx.read_decimated(c, made, now - made))
+            made = now
+    rx.sync()
+    frames += rx.drain()
+    if log:
+        tx.append(rx.txlog_read())
+    if search:
+        per_feed.append(rx.txsearch_read(cap_recs))
+    out = dict(frames=frames, tx=np.concatenate(tx) if log else None, txs=np.concatenate(per_feed) if search else None, per_feed=per_feed,
+               info=rx.txsearch_info() if search else None, loginfo=rx.txlog_info() if log else None,
+               counters=[[list(rx.counters(c).values()), list(rx.avlc_counters(c).values())] for c in chans],
+               stats=rx.stats(), act=rx.activity() if act else None, freqs=freqs, chan_first=rx.chan_first,
+               y={c: np.concatenate(v).view(np.complex64).reshape(-1) for c, v in y.items()} if read_y else None)
+    rx.close()
+    return out
+
+
+def check_model(res, y=None, label=""):
+    """every search record beside the log's record of the same index: the join key, the device's fields against the model on the
+    stream, the host's fields against the log's -> the number of records"""
+    tx, txs = res["tx"], res["txs"]
+    y = y or res["y"]
+    assert len(tx) == len(txs), (label, len(tx), len(txs))
+    samples = clipped = 0
+    for i, (t, s) in enumerate(zip(tx, txs)):
+        assert (int(s["chan"]), int(s["freq"]), int(s["first_bin"])) == (int(t["chan"]), int(t["freq"]), int(t["first_bin"])), (label, i)
+        want, _ = tm.search(tm.stream_get(y[int(t["chan"])]), int(t["first_sample"]), int(t["last_sample"]), int(t["freq"]), int(t["flags"]))
+        tm.check(s, want, (label, i))
+        assert (int(s["frames"]), int(s["frames_ok"])) == (int(t["frames"]), int(t["frames_ok"])), (label, i)
+        assert int(s["why"]) == tm.why(int(t["frames"]), int(t["frames_ok"]), want["lock_points"]) and int(s["reserved"]) == 0 == int(s["reserved2"])
+        samples += want["search_last"] - want["search_first"] + 1
+        clipped += bool(want["flags"] & tm.CLIPPED)
+    info = res["info"]
+    assert (info["records"], info["samples_searched"], info["clipped"], info["flags"]) == (len(txs), samples, clipped, 0), (label, info)
+    return len(txs)
+
+
+def same_across_cuts(a, b, label=""):
+    """Two runs of one input, cut differently.  The records are put in an order that does not depend on the cut (a feed's are ordered
+    by (channel, first_bin), feeds follow one another), and the host's join is left out, the one thing in them that may depend on it
+    (vdl2hip.h, "Transmission log": Outcome).  Which records exist and their ranges must be identical.  The search is a function of
+    the decimated stream, and WITHOUT THE REFEREE THE CHANNELISER'S STREAM ITSELF DEPENDS ON THE CUT in its last bits (its filter scan
+    starts afresh from a carried state at every feed: config2 cut in two, 46 337 of channel 0's 52 500 samples behind the cut differ by
+    an ulp or two) - so a record must be identical, byte for byte, wherever the two runs' streams are over its range and its taps,
+    which is every record ahead of the first cut; each run is held to the model on its own stream beside this (check_model).
+    -> the number of records compared byte for byte"""
+    ra, rb = (np.sort(r["txs"], order=["chan", "first_bin"]) for r in (a, b))
+    assert len(ra) == len(rb), (label, len(ra), len(rb))
+    exact = 0
+    for x, y in zip(ra, rb):
+        for k in ("chan", "freq", "first_bin", "search_first", "search_last", "flags"):
+            assert x[k] == y[k], (label, k, x, y)
+        lo, hi, c = max(0, int(x["search_first"]) - 153), int(x["search_last"]) + 1, int(x["chan"])
+        if np.array_equal(a["y"][c][lo:hi].view(np.uint64), b["y"][c][lo:hi].view(np.uint64)):
+            assert all(x[k].tobytes() == y[k].tobytes() for k in tm.DEVICE_FIELDS), (label, x, y)
+            exact += 1
+    print(f"{label}: {len(ra)} records, {exact} over identical samples and identical byte for byte")
+    return exact
+
+
+# ---------------------------------------------------------------- 1. the reference's test vector
+def wav_run(vh, wav, search, log=True):
+    return run(vh, wav.view("<i2").reshape(-1, 2), [CF], cut_sizes(wav.size // 4, [80000]), act=(105, -30.0, 0) if log else None, log=log, search=search)
+
+
+def test_reference_wav(vh, golden_wav):
+    on = wav_run(vh, golden_wav, True)
+    assert check_model(on, label="wav") == 1
+    s, fr = on["txs"][0], on["frames"]
+    assert len(fr) == 2 and int(s["why"]) == vh.TXS_DECODED and int(s["frames"]) == 2 and int(s["flags"]) == 0
+    # the walker's lock sample: got_sync() succeeds at the evaluation n with p(n - 3) < 4 and p(n) > p(n - 3), and the walker takes
+    # sync_sample = n (vdl2_core.h, the success branch: st.pb.sync_sample = n) and the slope of the evaluation BEFORE it, s(n - 3),
+    # as the burst's (vdphi = u_prevd).  So sync_sample is itself a lock point, on the grid phase the walker was on
+    sync = fr[0]["sync_sample"]
+    want, (p, sl) = tm.search(tm.stream_get(on["y"][0]), int(on["tx"][0]["first_sample"]), int(on["tx"][0]["last_sample"]), CF)
+    i = sync - want["search_first"]
+    assert i >= 3 and p[i - 3] < 4.0 and p[i] > p[i - 3], "sync_sample is a lock point of the model"
+    assert int(s["first_lock"]) <= sync <= int(s["search_last"]) and int(s["lock_phases"]) >> (sync % 3) & 1 and int(s["lock_points"]) >= 1
+    assert tm.same_bits(tm.cr.ppm_of(sl[i - 3], CF), np.float32(fr[0]["ppm_error"])), "the burst's slope is s(sync_sample - 3)"
+    assert float(s["best_pherr"]) <= float(p[i - 3]) < 4.0 and int(s["lock_phases"]) == 7
+    # frames and counters are the golden file's with the search on: those of a run without it, and of one without the log
+    off = wav_run(vh, golden_wav, False)
+    bare = wav_run(vh, golden_wav, False, log=False)
+    for other in (off, bare):
+        assert_frames_equal(other["frames"], fr, label="search on")
+        assert other["counters"] == on["counters"]
+    assert off["tx"].tobytes() == on["tx"].tobytes()
+    for k, v in off["act"].items():
+        assert k == "kernel_ms" or np.array_equal(np.asarray(v), np.asarray(on["act"][k])), k
+    for k, v in bare["stats"].items():
+        assert k.endswith("_ms") or v == on["stats"][k], k
+    assert np.array_equal(off["y"][0].view(np.uint32), on["y"][0].view(np.uint32))
+
+
+# ---------------------------------------------------------------- 2. the cut does not matter
+@functools.lru_cache(maxsize=1)
+def config2():
+    cfg, iq, _, _ = cases.load("config2_1s")
+    return cfg, np.asarray(iq).reshape(-1, 2)
+
+
+def run_config2(vh, sizes, read_y=True):
+    cfg, raw = config2()
+    return run(vh, raw, list(cfg.freqs), sizes, os_=cfg.oversample, cf=cfg.centerfreq, max_ppm=cfg.rx_max_ppm, act=(105, -40.0, 1), block=raw.shape[0],
+               read_y=read_y)
+
+
+@pytest.fixture(scope="module")
+def config2_whole(vh):
+    res = run_config2(vh, [config2()[1].shape[0]])
+    assert check_model(res, label="config2 whole") >= 8
+    return res
+
+
+@pytest.mark.parametrize("pieces", [2, 7])
+def test_config2_pieces(vh, config2_whole, pieces):
+    n = config2()[1].shape[0]
+    res = run_config2(vh, cut_sizes(n, [-(-n // pieces)]))
+    assert len(res["per_feed"]) == pieces + 1
+    check_model(res, label=f"config2 in {pieces}")
+    exact = same_across_cuts(res, config2_whole, f"config2 in {pieces}")
+    assert exact >= 1 or pieces == 7          # (half a second holds several whole transmissions; a seventh of one holds none of config2's)
+
+
+def test_config2_small_feeds(vh, config2_whole):
+    """a feed every 4 096 bytes: 2 051 of them; most close nothing, and a record's range begins many feeds back"""
+    n = config2()[1].shape[0]
+    res = run_config2(vh, cut_sizes(n, [1024]))
+    assert len(res["per_feed"]) == 2052
+    check_model(res, label="config2 every 4096 bytes")
+    same_across_cuts(res, config2_whole, "config2 every 4096 bytes")
+
+
+# ---------------------------------------------------------------- 3. one channel carrying three things
+THREE_N = 900000
+THREE_SEED = 18
+
+
+@functools.lru_cache(maxsize=1)
+def three_things():
+    """-> int16 (n, 2) at 1.05 MS/s, the channel at the centre: a burst of one AVLC frame at 50 ms (-20 dBFS), an unmodulated carrier
+    from 250 to 350 ms (-26 dBFS), a burst of a 600-octet frame at 500 ms whose power is half the channel's noise power"""
+    from dumpvdl2_amd import synth
+    rng = np.random.default_rng(THREE_SEED)
+    x = 0.0005 * (rng.standard_normal(THREE_N) + 1j * rng.standard_normal(THREE_N))
+    marks = {}
+    for name, start_s, amp, payload in (("strong", 0.05, 0.1, 100), ("weak", 0.5, WEAK_AMPLITUDE, 600)):
+        bb = synth.build_burst([synth.make_avlc_frame(bytes(rng.integers(0, 256, size=payload, dtype=np.uint8)))])
+        wave = synth.modulate(bb.symbols, synth.SPS * 10, start_phase=float(rng.uniform(0, 2 * np.pi)))
+        k = int(start_s * 1050000)
+        x[k:k + wave.size] += amp * wave
+        marks[name] = (k // 10, (k + wave.size) // 10)
+    k0, k1 = int(0.25 * 1050000), int(0.35 * 1050000)
+    x[k0:k1] += 0.05 * np.exp(1j * 0.3)
+    marks["carrier"] = (k0 // 10, k1 // 10)
+    iq = np.stack([x.real, x.imag], axis=1)
+    return np.clip(np.rint(32768.0 * iq), -32768, 32767).astype("<i2"), marks
+
+
+# The noise of 0.0005 per component at 1.05 MS/s leaves 8.8e-9 (-80.55 dBFS) in the channel's decimated stream, and a burst of
+# amplitude a a mean power of 0.85 a^2 (both measured on the reference's own channeliser, and the ratio again by the test below on
+# the device's stream): a = 7.2e-5 puts the burst 3 dB below the noise.  Bins of 1 000 samples (9.5 ms) average the noise to within
+# +-0.6 dB of its floor; the threshold of -79.7 dBFS lies 0.85 dB above the floor, and noise + the weak burst 1.76 dB above it.
+WEAK_AMPLITUDE = 7.2e-5
+THREE_ACT = (1000, -79.7, 2)
+
+
+def test_three_things(vh):
+    raw, marks = three_things()
+    res = run(vh, raw, [CF], cut_sizes(THREE_N, [300000]), act=THREE_ACT)
+    y = res["y"][0]
+    noise = float(np.mean(np.abs(y[500:4000].astype(np.complex128)) ** 2))
+    weak = float(np.mean(np.abs(y[marks["weak"][0] + 100:marks["weak"][1] - 100].astype(np.complex128)) ** 2)) - noise
+    print(f"noise {10 * np.log10(noise):.2f} dBFS, weak burst {10 * np.log10(weak / noise):.2f} dB relative to it")
+    assert -3.5 <= 10 * np.log10(weak / noise) <= -2.5
+    assert check_model(res, label="three") == 3
+    tx, txs = res["tx"], res["txs"]
+    for t, name in zip(tx, ("strong", "carrier", "weak")):
+        assert abs(int(t["first_sample"]) - marks[name][0]) <= 2000 and abs(int(t["last_sample"]) - marks[name][1]) <= 2000, name
+    # what the model says of this seed (worked out on the CPU beforehand, on the reference's channeliser: best_pherr 2.85 and three
+    # lock points for the weak burst, where seven other seeds gave 5.3 .. 7.8 and none; asserted here on the device's stream through
+    # check_model): the strong burst decodes, the carrier never comes near a preamble, and the weak burst does come within the
+    # threshold - the reference would have locked - and yields nothing
+    assert [int(w) for w in txs["why"]] == [vh.TXS_DECODED, vh.TXS_NO_PREAMBLE, vh.TXS_LOCK_NO_FRAME]
+    assert [int(f) for f in txs["frames"]] == [1, 0, 0]
+    p = [float(v) for v in txs["best_pherr"]]
+    assert p[0] < p[2] < 4.0 < p[1] and len(set(p)) == 3
+    assert int(txs[0]["lock_phases"]) == 7 and int(txs[1]["lock_points"]) == 0 and int(txs[1]["below_thr"]) == 0
+
+
+# ---------------------------------------------------------------- 4. a long carrier, a transmission at the stream's start
+def carrier_stream(n_in, spans, seed, amp=0.05):
+    rng = np.random.default_rng(seed)
+    x = 0.0005 * (rng.standard_normal(n_in) + 1j * rng.standard_normal(n_in))
+    for a, b in spans:
+        x[a:b] += amp * np.exp(1j * 0.3)
+    iq = np.stack([x.real, x.imag], axis=1)
+    return np.clip(np.rint(32768.0 * iq), -32768, 32767).astype("<i2")
+
+
+def test_clipped(vh):
+    """a carrier of 0.6 s: 63 000 samples, more than the longest range"""
+    n = 800000
+    raw = carrier_stream(n, [(50000, 680000)], 5)
+    res = run(vh, raw, [CF], cut_sizes(n, [250000]))
+    assert check_model(res, label="clipped") == 1
+    s, t = res["txs"][0], res["tx"][0]
+    assert int(t["last_sample"]) - int(t["first_sample"]) + 1 > 57344
+    assert int(s["flags"]) == vh.TXS_CLIPPED and int(s["search_first"]) == int(s["search_last"]) - 57343 and int(s["search_last"]) == int(t["last_sample"])
+    assert res["info"]["clipped"] == 1 and res["info"]["samples_searched"] == 57344
+    assert int(s["why"]) == vh.TXS_NO_PREAMBLE
+
+
+def test_stream_start(vh):
+    """a transmission inside the first 150 samples: its windows reach before the stream, where the phase is 0"""
+    n = 60000
+    raw = carrier_stream(n, [(0, 600)], 6)
+    res = run(vh, raw, [CF], [n])
+    assert check_model(res, label="start") == 1
+    s = res["txs"][0]
+    assert int(s["search_first"]) == 0 and int(s["search_last"]) in (104, 209)      # (its last busy bin of 105: bin 0, or bin 1 with the filter's tail)
+
+
+# ---------------------------------------------------------------- 5. the ring wraps
+def test_ring_wraps(vh):
+    """small blocks make the decimated ring small (2^17 samples: 6 feeds of 10 001 + 65 536 + 1 024); over 4 s it wraps three times,
+    with ranges across the wrap"""
+    from dumpvdl2_amd import synth
+    cfg = synth.SynthConfig(freqs=synth.channel_plan(3, spacing=100000), duration_s=4.0, mean_gap_s=0.08, max_payload=600, seed=4242)
+    iq, _ = synth.synthesize(cfg)
+    raw = np.asarray(iq).reshape(-1, 2)
+    blk = 200000                                                 # samples: 10 000 decimated per feed
+    res = run(vh, raw, list(cfg.freqs), cut_sizes(raw.shape[0], [blk]), os_=cfg.oversample, cf=cfg.centerfreq, act=(105, -40.0, 1))
+    assert raw.shape[0] // 20 > 3 * (1 << 17)
+    assert check_model(res, label="ring") >= 30
+    txs = res["txs"]
+    across = [s for s in txs if (int(s["search_first"]) - 153) >> 17 != int(s["search_last"]) >> 17]
+    assert len(across) >= 1, "no range lay across the ring's end"
+    assert np.count_nonzero(txs["why"] == vh.TXS_DECODED) >= 20
+
+
+# ---------------------------------------------------------------- 6. room, filtering, reading
+def keyed(n_in, seed, count=9):
+    """`count` short carriers of 5 ms, 30 ms apart"""
+    return carrier_stream(n_in, [(40000 + 31500 * i, 40000 + 31500 * i + 5250) for i in range(count)], seed)
+
+
+def test_small_pool(vh):
+    n = 400000
+    raw = keyed(n, 7)
+    full = run(vh, raw, [CF], [n])
+    tight = run(vh, raw, [CF], [n], pool=1)
+    assert check_model(full, label="full") == 9
+    assert len(tight["txs"]) == 1 == len(tight["tx"]) and tight["txs"].tobytes() == full["txs"][:1].tobytes()
+    assert tight["loginfo"]["dropped"] == 8 and tight["info"]["records"] == 1 and full["loginfo"]["dropped"] == 0
+
+
+def test_undecoded_only(vh, golden_wav):
+    """the decoded burst of the golden file is counted and not delivered; undecoded carriers are delivered"""
+    raw = golden_wav.view("<i2").reshape(-1, 2)
+    res = run(vh, raw, [CF], cut_sizes(raw.shape[0], [80000]), act=(105, -30.0, 0), undecoded=True)
+    assert len(res["tx"]) == 1 and len(res["txs"]) == 0 and res["info"]["records"] == 1 and res["info"]["flags"] == vh.TXSEARCH_UNDECODED_ONLY
+    n = 400000
+    res = run(vh, keyed(n, 7), [CF], [n], undecoded=True)
+    assert len(res["txs"]) == 9 == res["info"]["records"] and np.all(res["txs"]["frames_ok"] == 0)
+
+
+def test_read_one_at_a_time(vh):
+    n = 400000
+    raw = keyed(n, 7)
+    full = run(vh, raw, [CF], [n])
+    one = run(vh, raw, [CF], [n], cap_recs=1)
+    assert one["txs"].tobytes() == full["txs"].tobytes() and len(one["txs"]) == 9
+
+
+# ---------------------------------------------------------------- 7. arguments and switching
+def test_arguments_and_switching(vh):
+    n = 400000
+    raw = keyed(n, 7)
+    rx = vh.Receiver(CF, [CF], 10, vh.FMT_S16LE, max_block_bytes=4 * n)
+    rx.debug_option("referee", 0)
+    L = rx.L
+    good = dict(struct_size=16, flags=0)
+    cfg = lambda **kw: C.byref(vh.TxsearchCfg(**{**good, **kw}))
+    info = vh.TxsearchInfo(C.sizeof(vh.TxsearchInfo))
+    one = np.zeros(1, dtype=vh.TXS_DTYPE)
+    off = lambda: L.vdl2hip_txsearch_info_get(rx.h, C.byref(info)) == E_INVAL and L.vdl2hip_txsearch_read(rx.h, one.ctypes.data, 1) == E_INVAL
+    # the log is off (and the monitor): refused, and nothing to ask of a search that is off
+    assert L.vdl2hip_txsearch_enable(rx.h, cfg()) == E_INVAL and off()
+    assert L.vdl2hip_txsearch_disable(rx.h) == 0
+    rx.activity_enable(105, -40.0, 0, 0)
+    assert L.vdl2hip_txsearch_enable(rx.h, cfg()) == E_INVAL and off()
+    rx.txlog_enable()
+    for k in range(0, 120000, 20000):                             # (a slot's input buffer and copy event are made on the slot's first feed)
+        rx.feed(raw[k:k + 20000])
+        rx.sync()
+    rx.txlog_read()
+    with_log = vh.live_resources()
+    rx.txsearch_enable()
+    assert vh.live_resources()["device"] > with_log["device"] and vh.live_resources()["pinned"] > with_log["pinned"]
+    rx.feed(raw[120000:250000])
+    rx.sync()
+    s0 = rx.txsearch_info()
+    assert s0["records"] >= 3
+    two = (C.c_uint32 * 2)
+    for bad in (dict(struct_size=12), dict(struct_size=20), dict(flags=2), dict(flags=3), dict(reserved=two(1, 0)), dict(reserved=two(0, 1))):
+        assert L.vdl2hip_txsearch_enable(rx.h, cfg(**bad)) == E_INVAL, bad
+        assert {k: v for k, v in rx.txsearch_info().items() if k != "kernel_ms"} == {k: v for k, v in s0.items() if k != "kernel_ms"}, bad
+    assert L.vdl2hip_txsearch_enable(rx.h, None) == E_INVAL and L.vdl2hip_txsearch_enable(None, cfg()) == E_INVAL
+    assert L.vdl2hip_txsearch_info_get(rx.h, C.byref(vh.TxsearchInfo(32))) == E_INVAL and L.vdl2hip_txsearch_read(rx.h, None, 1) == E_INVAL
+    assert L.vdl2hip_txsearch_read(rx.h, None, 0) == 0 and L.vdl2hip_txsearch_read(rx.h, one.ctypes.data, 1) == 1
+    assert len(rx.txsearch_read()) == s0["records"] - 1
+    # the log's own flags = 2 stays refused, and a refused call leaves the search as it was
+    assert L.vdl2hip_txlog_enable(rx.h, C.byref(vh.TxlogCfg(16, 0, 2, 0))) == E_INVAL
+    assert rx.txsearch_info()["records"] == s0["records"]
+    # enabling again starts afresh
+    rx.txsearch_enable()
+    assert rx.txsearch_info()["records"] == 0
+    # switched off by txlog_disable(), txlog_enable(), activity_enable() and activity_disable(); everything of it given back
+    rx.txlog_disable()
+    assert off()
+    rx.txlog_enable(); rx.txsearch_enable(); rx.txlog_enable()
+    assert off() and vh.live_resources() == with_log
+    rx.txsearch_enable(); rx.activity_enable(105, -40.0, 0, 0)
+    assert off() and L.vdl2hip_txlog_read(rx.h, one.ctypes.data, 1) == E_INVAL
+    rx.txlog_enable(); rx.txsearch_enable(); rx.activity_disable()
+    assert off()
+    # a hang time that reaches further back than the ring is sure to hold: (40 + 1) * 105 = 4 305 > 4 096 is refused, 38 is not
+    rx.activity_enable(105, -40.0, 40, 0); rx.txlog_enable()
+    base = vh.live_resources()
+    assert L.vdl2hip_txsearch_enable(rx.h, cfg()) == E_INVAL and off() and vh.live_resources() == base
+    rx.activity_enable(105, -40.0, 38, 0); rx.txlog_enable()
+    rx.txsearch_enable()
+    rx.txsearch_disable()
+    assert off() and vh.live_resources() == base
+    rx.txsearch_enable()                                          # destroyed with the search on
+    rx.feed(raw[250000:])
+    rx.close()
+
+
+def test_off_is_off(vh):
+    """with the search never enabled: frames, counters, the log's records and what the process holds are those of a run that never
+    heard of it - and with it on, the log's records are still those"""
+    n = 400000
+    raw = keyed(n, 7)
+    base = vh.live_resources()
+    held = []
+
+    def one(search):
+        rx = vh.Receiver(CF, [CF], 10, vh.FMT_S16LE, max_block_bytes=4 * 100000)
+        rx.debug_option("referee", 0)
+        rx.activity_enable(105, -40.0, 0, 0)
+        rx.txlog_enable()
+        if search:
+            rx.txsearch_enable()
+        for k in range(0, n, 100000):
+            rx.feed(raw[k:k + 100000])
+        rx.sync()
+        held.append(vh.live_resources())
+        out = (rx.drain(), rx.txlog_read().tobytes(), list(rx.counters(0).values()), rx.read_decimated(0, 0, n // 10).tobytes())
+        rx.close()
+        return out
+    a, b, c = one(False), one(False), one(True)
+    assert a == b == c and len(a[1]) == 9 * vh.TX_DTYPE.itemsize
+    assert held[0] == held[1] and held[2]["device"] > held[0]["device"]
+    assert vh.live_resources() == base
+
+
+# ---------------------------------------------------------------- 8. shards and groups
+def test_shards_and_group(vh):
+    from test_gpu_txlog import make_stream
+    n = 525013
+    raw, freqs, _ = make_stream(4, n, 77, step=100000)
+    sizes = cut_sizes(n, [200000])
+    full = run(vh, raw, freqs, sizes, act=(105, -40.0, 1))
+    assert check_model(full, label="full") >= 20
+    shard = run(vh, raw, freqs, sizes, act=(105, -40.0, 1), chan_first=1, chan_count=2)
+    check_model(shard, label="shard")
+    assert set(shard["txs"]["chan"].tolist()) == {1, 2}
+    pick = lambda r, c: r[r["chan"] == c].tobytes()
+    for c in (1, 2):
+        assert pick(shard["txs"], c) == pick(full["txs"], c)
+    # a group of two on one device: vdl2hip_group_ctx(g, k) is the handle of member k's channels
+    g = vh.ReceiverGroup(CF, freqs, [0, 0], 10, vh.FMT_S16LE, max_block_bytes=4 * 200000)
+    for i in range(g.size()):
+        assert g.L.vdl2hip_debug_option(g.member(i), b"referee", 0) == 0
+    g.activity_enable(105, -40.0, 1, 0)
+    g.txlog_enable()
+    g.txsearch_enable()
+    k = 0
+    for d in sizes:
+        g.feed(raw[k:k + d])
+        k += d
+    g.sync()
+    seen = 0
+    for i in range(2):
+        recs = g.txsearch_read(i)
+        assert set(recs["chan"].tolist()) == {2 * i, 2 * i + 1} and g.txsearch_info(i)["records"] == len(recs) == len(g.txlog_read(i))
+        for c in (2 * i, 2 * i + 1):
+            assert pick(recs, c) == pick(full["txs"], c)
+        seen += len(recs)
+    assert seen == len(full["txs"])
+    g.txsearch_disable()
+    g.close()
+
+
+# ---------------------------------------------------------------- 9. the tool
+def test_tool(vh, tmp_path, golden_wav):
+    from dumpvdl2_amd import build
+    exe = build.build_cli(str(tmp_path / "vdl2hip_iqfile"))
+    out, txo = str(tmp_path / "txs.txt"), str(tmp_path / "tx.txt")
+    base = [exe, "--iq-file", WAV, "--sample-format", "S16_LE"]
+    p0 = subprocess.run(base + ["--tx-out", txo, "--activity-threshold", "-30"], check=True, capture_output=True, text=True, timeout=120)
+    tx0 = open(txo).read()
+    p1 = subprocess.run(base + ["--tx-out", txo, "--tx-search-out", out, "--activity-threshold", "-30"], check=True, capture_output=True, text=True, timeout=120)
+    assert p0.stdout == p1.stdout and p0.stdout.count("[S:") == 2 and p0.stderr == p1.stderr
+    strip = lambda s: [l for l in s.splitlines() if not l.startswith("# kernel_ms")]
+    assert strip(open(txo).read()) == strip(tx0), "--tx-out's file does not change"
+    p2 = subprocess.run(base + ["--tx-search-out", out + "2", "--activity-threshold", "-30"], check=True, capture_output=True, text=True, timeout=120)
+    assert p2.stdout == p0.stdout and open(out + "2").read().splitlines()[1:] == open(out).read().splitlines()[1:]
+    lines = open(out).read().splitlines()
+    head = lines[0].split()
+    rows = [l.split() for l in lines[1:]]
+    # the tool gathers the file's 320 000-byte blocks into one feed (eight blocks a feed; the file has five), with the referee on
+    raw = golden_wav.view("<i2").reshape(-1, 2)
+    want = run(vh, raw, [CF], [raw.shape[0]], act=(105, -30.0, 0), referee=1)
+    info, r = want["info"], want["txs"][0]
+    assert head[0] == "#" and dict(zip(head[1::2], head[2::2])).keys() == {"flags", "records", "samples_searched", "clipped", "kernel_ms"}
+    hd = dict(zip(head[1::2], head[2::2]))
+    assert [int(hd[k]) for k in ("flags", "records", "samples_searched", "clipped")] == [info[k] for k in ("flags", "records", "samples_searched", "clipped")]
+    names = [k for k in vh.TXS_DTYPE.names if k not in ("reserved", "reserved2")]
+    assert len(rows) == 1 and len(rows[0]) == len(names) == 17
+    for k, v in zip(names, rows[0]):
+        if k in ("best_pherr", "best_slope", "best_ppm"):
+            assert tm.same_bits(np.float32(float(v)), r[k]), k      # (%.9g brings a float32 back exactly)
+        else:
+            assert int(v) == int(r[k]), k

@@ -38,6 +38,12 @@
  *                                 decoded or not: a "# key value" line per field of vdl2hip_txlog_info, then per transmission
  *                                 "chan freq_hz first_sample length_ms peak_dbfs mean_dbfs frames frames_ok flags", then per channel
  *                                 "# channel <chan> <freq_hz> transmissions=<n> decoded=<n> ratio=<decoded / transmissions>"
+ *   --tx-search-out <path>        (this library's own) switch the preamble search on - and with it the transmission log and the activity
+ *                                 monitor, as --tx-out does - and, at exit, write to a file of its own what the search found in every
+ *                                 transmission: one line "# flags <f> records <n> samples_searched <n> clipped <n> kernel_ms <x>", then per
+ *                                 transmission the fields of vdl2hip_tx_search in the structure's order - "chan freq first_bin search_first
+ *                                 search_last best_sample first_lock best_pherr best_slope best_ppm lock_points below_thr lock_phases
+ *                                 flags frames frames_ok why"
  *   --bursts-out <path>           (this library's own) switch the burst capture on and, at exit, write every burst handed to the burst decoder,
  *                                 decoded or not: a "# key value" line per field of vdl2hip_capture_info, then per burst every field of
  *                                 vdl2hip_burst in the structure's order - "chan freq burst_ord sync_sample end_sample first_symbol nsym
@@ -123,6 +129,30 @@ static int take_tx(vdl2hip_ctx *rx) {
 	}
 }
 
+/* preamble search: the records so far (written at exit, behind the totals) */
+static vdl2hip_tx_search *txss;
+static size_t ntxss, cap_txss;
+static int take_tx_search(vdl2hip_ctx *rx) {
+	enum { RECS = 256 };
+	static vdl2hip_tx_search rec[RECS];
+	for(;;) {
+		const int n = vdl2hip_txsearch_read(rx, rec, RECS);
+		if(n <= 0) return n;
+		if(ntxss + (size_t)n > cap_txss) {
+			cap_txss = 2 * (ntxss + (size_t)n);
+			txss = realloc(txss, cap_txss * sizeof *txss);
+			if(!txss) { perror("realloc"); exit(3); }
+		}
+		memcpy(txss + ntxss, rec, (size_t)n * sizeof *rec);
+		ntxss += (size_t)n;
+	}
+}
+/* ... without --tx-out the log's own records are read and let go, so that they do not pile up */
+static int drop_tx(vdl2hip_ctx *rx) {
+	static vdl2hip_tx rec[256];
+	for(;;) { const int n = vdl2hip_txlog_read(rx, rec, 256); if(n <= 0) return n; }
+}
+
 static void on_frame(const vdl2hip_frame *f, void *user) {
 	(void)user;
 	nframes++;
@@ -145,7 +175,7 @@ int main(int argc, char **argv) {
 	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
-	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL;
+	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL, *tx_search_path = NULL;
 	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
@@ -186,6 +216,7 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--activity-threshold")) { NEEDARG(); activity_thr = strtof(argv[++i], NULL); }
 		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--tx-out")) { NEEDARG(); tx_path = argv[++i]; }
+		else if(!strcmp(a, "--tx-search-out")) { NEEDARG(); tx_search_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-out")) { NEEDARG(); bursts_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-iq")) { NEEDARG(); bursts_iq_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-failed-only")) bursts_flags |= VDL2HIP_CAPTURE_FAILED_ONLY;
@@ -199,7 +230,7 @@ int main(int argc, char **argv) {
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32|S8] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
-			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] "
+			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] "
 			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
@@ -242,15 +273,19 @@ int main(int argc, char **argv) {
 			fprintf(stderr, "vdl2hip_spectrum_enable: %s\n", vdl2hip_strerror(spectrum_nfft ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
-	if(activity_path || tx_path) {
+	if(activity_path || tx_path || tx_search_path) {
 		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
 		if(activity_bin == 0 || (r = vdl2hip_activity_enable(rx, &ac)) != VDL2HIP_OK) {
 			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
-	if(tx_path) {
+	if(tx_path || tx_search_path) {
 		vdl2hip_txlog_cfg tc = { sizeof tc, 0, 0, 0 };
 		if((r = vdl2hip_txlog_enable(rx, &tc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txlog_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+	}
+	if(tx_search_path) {
+		vdl2hip_txsearch_cfg sc = { sizeof sc, 0, { 0, 0 } };
+		if((r = vdl2hip_txsearch_enable(rx, &sc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txsearch_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
 	if(bursts_path) {
 		vdl2hip_capture_cfg cc = { sizeof cc, bursts_pre, bursts_post, bursts_flags, 0, 0 };
@@ -270,6 +305,8 @@ int main(int argc, char **argv) {
 		if((r = vdl2hip_drain(rx, on_frame, NULL)) < 0) { fprintf(stderr, "vdl2hip_drain: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(tx_search_path && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(tx_search_path && (r = take_tx_search(rx)) < 0) { fprintf(stderr, "vdl2hip_txsearch_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		held = 0;
 	} while(len == FILE_BUFSIZE);
 	free(buf);
@@ -373,6 +410,24 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "transmissions not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+	}
+	if(tx_search_path) {
+		vdl2hip_txsearch_info si;
+		memset(&si, 0, sizeof si); si.struct_size = sizeof si;
+		r = vdl2hip_txsearch_info_get(rx, &si);
+		FILE *so = r == VDL2HIP_OK ? fopen(tx_search_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# flags %u records %" PRIu64 " samples_searched %" PRIu64 " clipped %" PRIu64 " kernel_ms %.6g\n", si.flags, si.records, si.samples_searched,
+					si.clipped, (double)si.kernel_ms);
+			for(size_t i = 0; i < ntxss; i++) {
+				const vdl2hip_tx_search *t = &txss[i];
+				fprintf(so, "%u %u %" PRIu64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %.9g %.9g %.9g %u %u %u %u %u %u %u\n", t->chan, t->freq, t->first_bin,
+						t->search_first, t->search_last, t->best_sample, t->first_lock, (double)t->best_pherr, (double)t->best_slope, (double)t->best_ppm,
+						t->lock_points, t->below_thr, t->lock_phases, t->flags, t->frames, t->frames_ok, t->why);
+			}
+			fclose(so);
+		}
+		else fprintf(stderr, "preamble search not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
