@@ -7,7 +7,6 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvdl2hip.so")
-SOURCES = ["vdl2hip.hip", "hostmem.h", "debug_hooks.inc", "group.inc", "ubench.inc", "kernels.h", "resample.h", "resample_design.h", "spectrum.h", "spectrum_design.h", "activity.h", "capture.h", "txlog.h", "vdl2_core.h", "design.h", "tables.h"]
 # -ffp-contract=off: the walker/burst code must keep the reference's mul/add sequence;
 # the channeliser asks for FMAs explicitly where it wants them.
 # -fno-slp-vectorize: packed FP32 issues at half rate on CDNA4, so a v_pk_add the SLP vectoriser glues together from two scalar
@@ -27,7 +26,8 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(os.path.dirname(HERE), "include", "vdl2hip.h")]
+    # what the library is built from: every header, include and source of csrc/ (no list to keep), and the public header
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))] + [os.path.join(os.path.dirname(HERE), "include", "vdl2hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

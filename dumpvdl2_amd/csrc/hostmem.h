@@ -85,4 +85,40 @@ public:
 	operator hipEvent_t() const { return e_; }
 };
 
+// The mailbox of a tap that delivers records, one per feed in flight.  The device side is one allocation: a header, the records behind
+// it.  The host side is a page-locked landing place for the header and the first kMailRecs records: post() brings them in one small
+// copy queued behind the tap's kernels, which is all most feeds of a live receiver need.  A feed with more records has all of them
+// fetched into a staging buffer of the caller's, who may have more to copy into it (the burst capture: its IQ) before the one wait.
+constexpr uint32_t kMailRecs = 32;
+template<typename Hdr, typename Rec>
+class RecordMail {
+	DevBuf<Hdr> d_; PinnedBuf h_;
+public:
+	static constexpr size_t kMailBytes = sizeof(Hdr) + kMailRecs * sizeof(Rec);
+	// room for `cap` records; the mail's share of the device side and the landing place start zeroed (an error with the mail
+	// standing - operator bool - is the clearing's, any other an allocation's)
+	hipError_t alloc(size_t cap) {
+		hipError_t e = d_.alloc_bytes(sizeof(Hdr) + std::max<size_t>(cap, kMailRecs) * sizeof(Rec));
+		if(e == hipSuccess) e = h_.alloc(kMailBytes, true);
+		if(e == hipSuccess && (e = hipMemset(d_, 0, kMailBytes)) != hipSuccess) (void)hipGetLastError();
+		return e;
+	}
+	explicit operator bool() const { return h_.bytes() != 0; }
+	Hdr *d_hdr() const { return d_; }
+	Rec *d_rec() const { return reinterpret_cast<Rec *>(d_.get() + 1); }
+	hipError_t post(hipStream_t st) const { return hipMemcpyAsync(h_, d_, kMailBytes, hipMemcpyDeviceToHost, st); }
+	// once the feed is done: the header as post() brought it ...
+	const Hdr &hdr() const { return *h_.template as<Hdr>(); }
+	// ... and its `nrec` records: in the landing place, or - staged(nrec) bytes - at the start of `stage`, copied there on `out` and
+	// waited for.  extra: the caller copies as many bytes behind them on `out` and then waits itself, if there is anything to wait for
+	static size_t staged(uint32_t nrec) { return nrec > kMailRecs ? sizeof(Rec) * (size_t)nrec : 0; }
+	hipError_t fetch(uint32_t nrec, PinnedBuf &stage, hipStream_t out, const Rec *&rec, bool wait = true, size_t extra = 0) const {
+		const size_t bytes = staged(nrec);
+		hipError_t e = stage.reserve(bytes + extra);
+		rec = bytes ? stage.as<Rec>() : reinterpret_cast<const Rec *>(h_ + sizeof(Hdr));
+		if(e == hipSuccess && bytes) e = hipMemcpyAsync(stage, d_rec(), bytes, hipMemcpyDeviceToHost, out);
+		return e == hipSuccess && bytes && wait ? hipStreamSynchronize(out) : e;
+	}
+};
+
 }  // namespace hostmem

@@ -1,0 +1,690 @@
+// taps.inc - the receiver's five optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h,
+// capture.h, txsearch.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
+// (collect), what gives its buffers back (free), then its entry points of vdl2hip.h.  A tap stands behind those it calls into: the
+// log hands its records to the search, the activity monitor launches the log and switches it off.
+// Three of them deliver records - capture, search, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
+// (hostmem.h), per context the totals, a queue of collected records and the staging buffer of a feed with more records than come
+// with the header.  Their enable is: validate, collect what is in flight, free the old, allocate per slot, zero the totals, on.
+// (The entry points have C linkage from their declarations in vdl2hip.h.)
+
+// vdl2hip_<tap>_read of a tap whose records go out as they are queued
+template<typename R>
+static int pop_records(std::deque<R> &q, R *recs, size_t cap_recs) {
+	size_t n = 0;
+	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
+	return (int)n;
+}
+
+// ---- the input monitor (vdl2hip.h, "Input monitor"; kernels: spectrum.h) ----
+// Its share of a feed: on the front stream ahead of everything else that reads the block, so it is ordered with the copy into
+// d_in[k], with that buffer's reuse and with a caller's device buffer exactly as the channeliser is.
+// Host bookkeeping: the stream position (64 bits), the segments this feed completes, which of them are analysed, what is carried.
+template<int FMT>
+static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->streams.front, e0, e1, 0, a)
+	switch(c->mon.nfft / c->mon.threads) {                           // samples per lane (spec_threads(): 1, 2, 4 up to N = 1024, 8, 16)
+		case 1: SPEC_LAUNCH(1); break;
+		case 2: SPEC_LAUNCH(2); break;
+		case 4: SPEC_LAUNCH(4); break;
+		case 8: SPEC_LAUNCH(8); break;
+		default: SPEC_LAUNCH(16); break;
+	}
+	#undef SPEC_LAUNCH
+}
+static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
+	auto &m = c->mon;
+	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
+	if(nin == 0) return VDL2HIP_OK;
+	if(nin >= (1ull << 32)) return VDL2HIP_E_TOOBIG;
+	const uint64_t N = m.nfft, pos0 = m.pos, pos1 = pos0 + nin;
+	const uint64_t j0 = pos0 / N, j1 = pos1 / N;                          // the segments the stream stands in before and after: [j0, j1) are completed
+	const uint64_t ja = (j0 + m.stride - 1) / m.stride * m.stride;        // the first of them that is analysed
+	const uint64_t nseg = ja < j1 ? (j1 - 1 - ja) / m.stride + 1 : 0;
+	const uint32_t o1 = (uint32_t)(pos1 % N);
+	const uint32_t ncarry_out = j1 % m.stride == 0 ? o1 : 0;               // (a segment that stride skips is not kept)
+	m.pos = pos1;
+	if(nseg == 0 && ncarry_out == 0) { m.ncarry = 0; return VDL2HIP_OK; }
+	SpecArgs a{};
+	a.in = dev_in; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1]; a.w = m.buf.d_w; a.tw = m.buf.d_tw; a.rows = m.buf.d_rows;
+	a.rel0 = (int64_t)(ja * N) - (int64_t)pos0; a.carry_rel = (int64_t)(j1 * N) - (int64_t)pos0; a.seg_step = (uint64_t)m.stride * N;
+	a.nin = (uint32_t)nin; a.ncarry = m.ncarry; a.ncarry_out = ncarry_out; a.nseg = (uint32_t)nseg;
+	a.run = (uint32_t)std::max<uint64_t>(1, (nseg + kSpecMaxRows - 1) / kSpecMaxRows); a.N = m.nfft; a.log2n = m.log2n;
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nseg + a.run - 1) / a.run);      // (no segment: workgroup 0 still moves the carry on)
+	if(grid > kSpecMaxRows || (int64_t)a.ncarry + a.rel0 < 0) return VDL2HIP_E_INVAL;       // (never)
+	OutSlot &sl = c->slot[c->feed_no % kSlots];
+	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
+	KernelTimes &t = sl.mon_t;
+	t.arm(c->profiling >= 2);
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, t.e(0), t.e(1));
+	else if(c->in_fmt == kFmtS8) launch_spectrum<3>(c, a, grid, t.e(0), t.e(1));
+	else launch_spectrum<0>(c, a, grid, t.e(0), t.e(1));
+	if(nseg) {
+		const uint32_t W = m.nfft + kSpecLevels;
+		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), t.e(3), 0,
+		                      (const double *)m.buf.d_rows, m.buf.d_acc.get(), (uint32_t)grid, m.nfft);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(m.tap.mark(c->streams.front));
+	t.launched(nseg ? 2 : 1);
+	m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
+	return VDL2HIP_OK;
+}
+// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap;
+// what its launches took of the slots' feeds is not a later monitor's)
+static void monitor_free(vdl2hip_ctx *c) {
+	auto &m = c->mon;
+	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
+	m.buf = {};
+	for(auto &sl : c->slot) sl.mon_t.n = 0;
+	m.on = false; m.tap.queued = false; m.nfft = 0;
+}
+// the accumulators as they stand once everything the monitor has queued is done: [nfft] sums of |X|^2, then the level sums
+static int monitor_fetch(vdl2hip_ctx *c, std::vector<double> &acc) {
+	auto &m = c->mon;
+	acc.assign((size_t)m.nfft + kSpecLevels, 0.0);
+	if(!m.tap.queued) return VDL2HIP_OK;                             // nothing has touched them since they were zeroed
+	HIPCHK(m.tap.fetch(m.tap.land, m.buf.d_acc, m.buf.d_acc.bytes()));
+	memcpy(acc.data(), m.tap.land, m.buf.d_acc.bytes());
+	return VDL2HIP_OK;
+}
+static void monitor_power(const vdl2hip_ctx *c, const std::vector<double> &acc, double *power) {
+	const auto &m = c->mon;
+	const double scale = m.segments ? 1.0 / ((double)m.segments * m.sum_w * m.sum_w) : 0.0;
+	for(uint32_t i = 0; i < m.nfft; i++) power[i] = acc[i] * scale;
+}
+int vdl2hip_spectrum_window(uint32_t nfft, uint32_t window, float *w, size_t cap) {
+	SpectrumDesign d;
+	if(!design_spectrum(nfft, window, d, false)) return VDL2HIP_E_INVAL;
+	if(!w || cap < nfft) return VDL2HIP_E_TOOBIG;
+	memcpy(w, d.w.data(), (size_t)nfft * sizeof(float));
+	return (int)nfft;
+}
+int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_spectrum_cfg)) return VDL2HIP_E_INVAL;
+	SpectrumDesign d;
+	if(cfg->nfft != 0 && !design_spectrum(cfg->nfft, cfg->window, d)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	auto &m = c->mon;
+	monitor_free(c);
+	if(cfg->nfft == 0) return VDL2HIP_OK;
+	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
+	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
+	if(!m.tap.land) HIPCHK(m.tap.land.alloc(((size_t)kSpecMaxN + kSpecLevels) * sizeof(double)));
+	const size_t N = cfg->nfft, W = N + kSpecLevels;
+	auto &b = m.buf;
+	if(b.d_w.alloc(N) != hipSuccess || b.d_tw.alloc(N) != hipSuccess || b.d_carry[0].alloc(N) != hipSuccess || b.d_carry[1].alloc(N) != hipSuccess
+	   || b.d_rows.alloc((size_t)kSpecMaxRows * W) != hipSuccess || b.d_acc.alloc(W) != hipSuccess) { monitor_free(c); return VDL2HIP_E_NOMEM; }
+	if(hipMemcpy(b.d_w, d.w.data(), b.d_w.bytes(), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemcpy(b.d_tw, d.tw.data(), b.d_tw.bytes(), hipMemcpyHostToDevice) != hipSuccess
+	   || hipMemset(b.d_acc, 0, b.d_acc.bytes()) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { monitor_free(c); return VDL2HIP_E_DEVICE; }
+	m.nfft = cfg->nfft; m.window = cfg->window; m.stride = cfg->stride ? cfg->stride : 1; m.log2n = d.log2n;
+	m.threads = spec_threads(m.nfft); m.lds = spec_lds_bytes(m.nfft);
+	m.sum_w = d.sum_w; m.enbw = d.enbw_bins;
+	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_spectrum_read(vdl2hip_ctx *c, vdl2hip_spectrum_info *info, double *power, size_t cap, int reset) {
+	if(!c || !c->mon.on || (info && info->struct_size != sizeof(vdl2hip_spectrum_info))) return VDL2HIP_E_INVAL;
+	auto &m = c->mon;
+	if(power && cap < m.nfft) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	std::vector<double> acc;
+	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
+	const uint32_t N = m.nfft;
+	if(info) {
+		memset(info, 0, sizeof *info);
+		info->struct_size = sizeof *info; info->nfft = N; info->window = m.window; info->stride = m.stride;
+		info->sample_rate = c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample;
+		info->centerfreq = c->cfg.centerfreq;
+		info->segments = m.segments; info->samples = m.segments * N; info->clipped = (uint64_t)acc[N + 3];
+		info->enbw_bins = m.enbw;
+		if(info->samples) { const double n = (double)info->samples; info->mean_power = acc[N] / n; info->dc_i = acc[N + 1] / n; info->dc_q = acc[N + 2] / n; }
+		info->peak = (float)acc[N + 4];
+		info->kernel_ms = (float)m.kernel_ms;
+	}
+	if(power) monitor_power(c, acc, power);
+	if(reset) {
+		// (on the front stream: behind the launches that are queued, ahead of the next feed's)
+		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
+		HIPCHK(m.tap.mark(c->streams.front));
+		m.segments = 0;
+	}
+	return (int)N;
+}
+int vdl2hip_spectrum_channels(vdl2hip_ctx *c, float *dbfs, size_t cap) {
+	if(!c || !c->mon.on || !dbfs) return VDL2HIP_E_INVAL;
+	auto &m = c->mon;
+	const size_t nchan = c->all_freqs.size();
+	if(cap < nchan) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	std::vector<double> acc;
+	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
+	const uint32_t N = m.nfft;
+	std::vector<double> power(N);
+	monitor_power(c, acc, power.data());
+	const double fs = (double)(c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample), cf = (double)c->cfg.centerfreq;
+	for(size_t ch = 0; ch < nchan; ch++) {
+		const double f = (double)c->all_freqs[ch];
+		double sum = 0.0, best = 0.0; bool any = false; uint32_t nearest = 0;
+		for(uint32_t i = 0; i < N; i++) {
+			const double d = std::fabs(cf + ((double)i - (double)(N / 2)) * fs / (double)N - f);
+			if(d <= 12500.0) { sum += power[i]; any = true; }
+			if(i == 0 || d < best) { best = d; nearest = i; }
+		}
+		if(!any) sum = power[nearest];
+		dbfs[ch] = sum > 0.0 ? (float)(10.0 * std::log10(sum / m.enbw)) : -INFINITY;
+	}
+	return (int)nchan;
+}
+
+// ---- the burst capture (vdl2hip.h, "Burst capture"; kernels: capture.h) ----
+// The ring behind the window.  The capture of feed i reads y from iq_first >= sync_sample - kCapMaxPre on, while the channelisers
+// of up to kSlots - 1 later feeds may be writing (feed i + kSlots takes feed i's slot, and collect_slot() has waited for feed i
+// before that).  They write [k_end, k_end + (kSlots - 1) dmax), which in a ring of `cap` >= kSlots dmax + kHistory + 1024 samples
+// (vdl2hip_create) lands on samples older than k_end - dmax - kHistory - 1024 <= k0 - kHistory - 1024, k0 being feed i's first
+// sample.  A burst is handed over in the feed that brings its last symbol, so end_sample >= k0; the longest burst is 56 320 samples
+// from its first symbol to its last and its sync lies a unique word before that: iq_first > k0 - 56 320 - 200 - 4 096 = k0 - 60 616
+// > k0 - kHistory - 1024 = k0 - 66 560.  The 5 944 samples between the two are why pre stops at 4 096.  A window is at most
+// 4 096 + 56 520 + 1 024 < 2^16 pairs long.
+static_assert(kCapMaxPre + 56320 + 200 < kHistory + 1024, "a window begins inside what the ring keeps behind a feed");
+static_assert(sizeof(CapRec) == sizeof(vdl2hip_burst) && sizeof(vdl2hip_burst) == 128 && offsetof(CapRec, iq_first) == offsetof(vdl2hip_burst, iq_first)
+              && offsetof(CapRec, frames) == offsetof(vdl2hip_burst, frames) && offsetof(CapRec, mean_power) == offsetof(vdl2hip_burst, mean_power)
+              && offsetof(CapRec, phase_err_max) == offsetof(vdl2hip_burst, phase_err_max), "the host copies the device's records as they are");
+static_assert(sizeof(vdl2hip_capture_cfg) == 24 && sizeof(vdl2hip_capture_info) == 56 && sizeof(CapHdr) == 16, "vdl2hip.h states these sizes");
+static_assert(kCapMaxChan == kK5MaxChan, "k_capture_copy keeps every channel's offsets in LDS");
+
+// Its share of a feed (launch_rest): behind the frame finisher on the feed's burst stream, where both passes of the burst decoder are done
+static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->capt;
+	CapArgs a{};
+	a.y = c->d_y; a.bursts = sl.d_bursts; a.nb_chan = sl.d_nbchan; a.freq = c->d_freq;
+	a.plan = sl.cap.d_plan; a.tot = sl.cap.d_tot; a.rec = sl.cap.mail.d_rec(); a.pool = sl.cap.d_pool; a.hdr = sl.cap.mail.d_hdr();
+	a.k_end = sl.back_k0 + sl.back_D; a.pool_samples = m.pool; a.cap_bursts_chan = c->cap_bursts_chan; a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first;
+	a.cap = c->cap; a.mask = c->cap - 1; a.pre = m.pre; a.post = m.post;
+	KernelTimes &t = sl.cap.times;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_capture_plan, dim3((unsigned)c->C), dim3(64), 0u, st, t.e(0), t.e(1), 0, a);
+	// a workgroup per burst, bounded like the burst decoder's wavefronts (16 .. 2048 of them, by the feed's size): 8 .. 512
+	const unsigned grid = std::min(512u, std::max(8u, sl.k5_waves / 4));
+	hipExtLaunchKernelGGL(k_capture_copy, dim3(grid), dim3(kCapThreads), 0u, st, t.e(2), t.e(3), 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(sl.cap.mail.post(st));
+	t.launched(2);
+	return VDL2HIP_OK;
+}
+// A collected feed's records and the used part of its IQ pool - one staging buffer, one wait - joined with the feed's frames - all of
+// them, whatever the AVLC filter lets through - and appended to the queue.
+static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+	auto &m = c->capt;
+	if(!m.on || !sl.cap.mail) return VDL2HIP_OK;
+	const CapHdr h = sl.cap.mail.hdr();
+	const uint32_t nrec = (uint32_t)std::min<uint64_t>(h.nrec, (uint64_t)c->C * c->cap_bursts_chan);
+	const uint64_t pairs = std::min<uint64_t>(h.pairs, m.pool);
+	if(nrec == 0) return VDL2HIP_OK;
+	const CapRec *rec = nullptr;
+	const size_t rec_bytes = sl.cap.mail.staged(nrec), iq_bytes = (size_t)pairs * sizeof(cf32);
+	HIPCHK(sl.cap.mail.fetch(nrec, m.stage, c->streams.out, rec, false, iq_bytes));
+	if(pairs) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.cap.d_pool, iq_bytes, hipMemcpyDeviceToHost, c->streams.out));
+	if(rec_bytes + iq_bytes) HIPCHK(hipStreamSynchronize(c->streams.out));
+	const float *iqp = reinterpret_cast<const float *>(m.stage + rec_bytes);
+	auto iq = pairs ? std::make_shared<std::vector<float>>(iqp, iqp + 2 * (size_t)pairs) : std::make_shared<std::vector<float>>();
+	struct Join { uint32_t frames = 0, ok = 0; int32_t fec = -1, last_idx = -1; };
+	std::map<std::pair<int32_t, int64_t>, Join> join;
+	for(uint32_t i = 0; i < nf; i++) {
+		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
+		Join &j = join[{ fr[i].chan + c->chan_first, fr[i].burst_ord }];
+		j.frames++; if(fr[i].avlc_status == AVLC_OK) j.ok++;
+		if(fr[i].idx >= j.last_idx) { j.last_idx = fr[i].idx; j.fec = fr[i].num_fec_corrections; }
+	}
+	for(uint32_t i = 0; i < nrec; i++) {
+		vdl2hip_burst r;
+		memcpy(&r, rec + i, sizeof r);
+		if(r.iq_off + r.iq_count > pairs) { r.iq_count = 0; r.iq_off = 0; r.flags |= VDL2HIP_BURST_NO_ROOM; }      // (never)
+		m.bursts++; m.iq_samples += r.iq_count; if(r.flags & VDL2HIP_BURST_NO_ROOM) m.iq_dropped++;
+		auto it = join.find({ (int32_t)r.chan, r.burst_ord });
+		if(it != join.end()) { r.frames = it->second.frames; r.frames_ok = it->second.ok; r.fec_corrections = it->second.fec; }
+		if((m.flags & VDL2HIP_CAPTURE_FAILED_ONLY) && r.frames_ok != 0) continue;
+		m.queue.push_back(vdl2hip_ctx::CapItem{ r, iq });
+	}
+	return VDL2HIP_OK;
+}
+// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed)
+static void capture_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.cap.reset();
+	c->capt.queue.clear();
+	c->capt.on = false;
+}
+int vdl2hip_capture_enable(vdl2hip_ctx *c, const vdl2hip_capture_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_capture_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(cfg->pre_samples > kCapMaxPre || cfg->post_samples > kCapMaxPost || (cfg->flags & ~VDL2HIP_CAPTURE_FAILED_ONLY) || cfg->pool_samples > kCapMaxPool) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier capture is in flight any more
+	auto &m = c->capt;
+	capture_free(c);
+	const uint32_t pool = cfg->pool_samples ? cfg->pool_samples : kCapDefPool;
+	const size_t nb = (size_t)c->C * c->cap_bursts_chan;
+	for(auto &sl : c->slot) {
+		auto &b = sl.cap;
+		const hipError_t mail = b.mail.alloc(nb);
+		const bool ok = mail == hipSuccess && b.d_plan.alloc(nb) == hipSuccess && b.d_tot.alloc((size_t)c->C) == hipSuccess && b.d_pool.alloc(pool) == hipSuccess;
+		// (a mail that stands and still reports an error: its allocations succeeded, clearing it did not)
+		if(!ok) { const bool cleared = mail == hipSuccess || !b.mail; capture_free(c); return cleared ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; }
+	}
+	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
+	m.pre = cfg->pre_samples; m.post = cfg->post_samples; m.flags = cfg->flags; m.pool = pool;
+	m.bursts = m.iq_samples = m.iq_dropped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_capture_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->capt.on && !c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	capture_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_capture_info_get(vdl2hip_ctx *c, vdl2hip_capture_info *info) {
+	if(!c || !c->capt.on || !info || info->struct_size != sizeof(vdl2hip_capture_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->capt;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->pre_samples = m.pre; info->post_samples = m.post; info->flags = m.flags; info->pool_samples = m.pool;
+	info->bursts = m.bursts; info->iq_samples = m.iq_samples; info->iq_dropped = m.iq_dropped; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+// (its own: a record goes out with its IQ, packed behind the IQ of the records before it)
+int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used) {
+	if(!c || !c->capt.on || (!recs && cap_recs) || (!iq && cap_pairs)) return VDL2HIP_E_INVAL;
+	auto &q = c->capt.queue;
+	size_t n = 0, used = 0;
+	while(!q.empty() && n < cap_recs) {
+		const vdl2hip_ctx::CapItem &it = q.front();
+		if(used + it.r.iq_count > cap_pairs) break;
+		recs[n] = it.r;
+		recs[n].iq_off = used;
+		if(it.r.iq_count) memcpy(iq + 2 * used, it.iq->data() + 2 * it.r.iq_off, (size_t)it.r.iq_count * 2 * sizeof(float));
+		used += it.r.iq_count;
+		n++;
+		q.pop_front();
+	}
+	if(pairs_used) *pairs_used = used;
+	return (int)n;
+}
+
+// ---- the preamble search (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
+// The ring behind the range.  The search of feed i reads y from search_first - 153 on (the taps of p(search_first - 3)), under the
+// burst capture's conditions (above): what the ring keeps behind feed i's first sample k0 is kHistory + 1024 samples.  A record is
+// emitted by the feed that completes bin last_bin + H + 1, so that bin ends at or after k0 and last_sample >= k0 - (H + 1) B
+// >= k0 - kTxsMaxBack (vdl2hip_txsearch_enable refuses a monitor beyond that); search_first >= last_sample - (kTxsSpan - 1).
+static_assert(kTxsMaxBack + (kTxsSpan - 1) + kTxsLead < kHistory + 1024, "a range and its taps begin inside what the ring keeps behind a feed");
+static_assert(sizeof(TxsRec) == sizeof(vdl2hip_tx_search) && sizeof(vdl2hip_tx_search) == 96 && offsetof(TxsRec, first_bin) == offsetof(vdl2hip_tx_search, first_bin)
+              && offsetof(TxsRec, first_lock) == offsetof(vdl2hip_tx_search, first_lock) && offsetof(TxsRec, best_pherr) == offsetof(vdl2hip_tx_search, best_pherr)
+              && offsetof(TxsRec, best_ppm) == offsetof(vdl2hip_tx_search, best_ppm) && offsetof(TxsRec, lock_points) == offsetof(vdl2hip_tx_search, lock_points)
+              && offsetof(TxsRec, flags) == offsetof(vdl2hip_tx_search, flags) && offsetof(vdl2hip_tx_search, flags) == 72 && offsetof(TxsRec, frames) == offsetof(vdl2hip_tx_search, frames)
+              && offsetof(TxsRec, why) == offsetof(vdl2hip_tx_search, why) && offsetof(vdl2hip_tx_search, why) == 84, "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_txsearch_cfg) == 16 && sizeof(vdl2hip_txsearch_info) == 40 && sizeof(TxsHdr) == 16 && sizeof(TxsPart) == 40, "vdl2hip.h states these sizes");
+static_assert(VDL2HIP_TXS_CLIPPED == kTxsClipped && VDL2HIP_TX_PARTIAL == kTxPartial && (kTxsClipped & kTxPartial) == 0, "the two flags share a word");
+// The pieces one feed's records can have at the most.  The transmissions of a channel are disjoint and the ranges of those a feed
+// closes lie in [k0 - kTxsMaxBack - kTxsSpan, k0 + dmax): their lengths add up to less than dmax + kTxsMaxBack + kTxsSpan per channel,
+// and a range of L samples has at most L / kTxsPiece + 1 pieces; the records are at most `pool`.
+static uint64_t txsearch_piece_cap(const vdl2hip_ctx *c, uint32_t pool) {
+	return (uint64_t)c->C * ((c->dmax + kTxsMaxBack + (uint64_t)kTxsSpan) / kTxsPiece + 1) + pool;
+}
+// Its share of a feed (launch_rest): behind the frame finisher and the copy of the log's records, which it reads, like the capture
+static int txsearch_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->txs;
+	TxsArgs a{};
+	a.y = c->d_y; a.tab = c->d_tab; a.txhdr = sl.txl.mail.d_hdr(); a.txrec = sl.txl.mail.d_rec();
+	a.off = sl.txs.d_off; a.part = sl.txs.d_part; a.rec = sl.txs.mail.d_rec(); a.hdr = sl.txs.mail.d_hdr();
+	a.pool = c->txl.pool; a.piece_cap = m.piece_cap; a.cap = c->cap; a.mask = c->cap - 1; a.chan_first = (uint32_t)c->chan_first;
+	KernelTimes &t = sl.txs.times;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_txsearch_plan, dim3(1), dim3(kTxsThreads), 0u, st, t.e(0), (hipEvent_t) nullptr, 0, a);
+	// a workgroup per piece, grid-stride: a piece per kTxsPiece channel-samples of the feed would be every sample busy - a quarter of that, 16 .. 2048
+	const unsigned grid = (unsigned)std::min<uint64_t>(2048, std::max<uint64_t>(16, (uint64_t)sl.back_D * (uint64_t)c->C / (4 * kTxsPiece)));
+	hipLaunchKernelGGL(k_txsearch_piece, dim3(grid), dim3(kTxsThreads), 0, st, a);
+	hipExtLaunchKernelGGL(k_txsearch_reduce, dim3(std::min(256u, (c->txl.pool + 63) / 64)), dim3(64), 0u, st, (hipEvent_t) nullptr, t.e(1), 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(sl.txs.mail.post(st));
+	t.launched(1);
+	sl.txs.on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed's search records, index for index beside the log's nrec records
+static int txsearch_fetch(vdl2hip_ctx *c, OutSlot &sl, uint32_t nrec, const TxsRec *&srec) {
+	auto &m = c->txs;
+	srec = nullptr;
+	if(!m.on || !sl.txs.mail) return VDL2HIP_OK;
+	if(sl.txs.mail.hdr().nrec != nrec) return VDL2HIP_E_DEVICE;      // (never: both are the log's header of this feed)
+	HIPCHK(sl.txs.mail.fetch(nrec, m.stage, c->streams.out, srec));
+	return VDL2HIP_OK;
+}
+// ... one of them, with the outcome the log has joined to its record
+static void txsearch_take(vdl2hip_ctx *c, const TxsRec &s, const vdl2hip_tx &tx) {
+	auto &m = c->txs;
+	vdl2hip_tx_search r;
+	memcpy(&r, &s, sizeof r);
+	r.frames = tx.frames; r.frames_ok = tx.frames_ok; r.reserved = r.reserved2 = 0;
+	r.why = tx.frames_ok ? VDL2HIP_TXS_DECODED : tx.frames ? VDL2HIP_TXS_FRAMES_BAD : r.lock_points ? VDL2HIP_TXS_LOCK_NO_FRAME : VDL2HIP_TXS_NO_PREAMBLE;
+	m.records++; if(r.search_last >= r.search_first) m.samples += (uint64_t)(r.search_last - r.search_first + 1); if(r.flags & VDL2HIP_TXS_CLIPPED) m.clipped++;
+	if((m.flags & VDL2HIP_TXSEARCH_UNDECODED_ONLY) && r.frames_ok != 0) return;
+	m.queue.push_back(r);
+}
+// give the search's buffers back (nothing of it may be in flight: the callers have collected every feed)
+static void txsearch_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.txs.reset();
+	c->txs.queue.clear();
+	c->txs.on = false;
+}
+int vdl2hip_txsearch_enable(vdl2hip_ctx *c, const vdl2hip_txsearch_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txsearch_cfg) || cfg->reserved[0] != 0 || cfg->reserved[1] != 0) return VDL2HIP_E_INVAL;
+	if(!c->txl.on || !c->act.on || (cfg->flags & ~VDL2HIP_TXSEARCH_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
+	if(((uint64_t)c->act.H + 1) * c->act.B > kTxsMaxBack) return VDL2HIP_E_INVAL;
+	const uint64_t piece_cap = txsearch_piece_cap(c, c->txl.pool);
+	if(piece_cap > 0x7fffffffull) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier search is in flight any more
+	auto &m = c->txs;
+	txsearch_free(c);
+	const uint32_t pool = c->txl.pool;
+	for(auto &sl : c->slot) {
+		auto &b = sl.txs;
+		const bool ok = b.mail.alloc(pool) == hipSuccess && b.d_off.alloc((size_t)pool + 1) == hipSuccess && b.d_part.alloc((size_t)piece_cap) == hipSuccess;
+		if(!ok) { txsearch_free(c); return VDL2HIP_E_NOMEM; }
+	}
+	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txsearch_free(c); return VDL2HIP_E_DEVICE; }
+	m.flags = cfg->flags; m.piece_cap = (uint32_t)piece_cap;
+	m.records = m.samples = m.clipped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_txsearch_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->txs.on && !c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	txsearch_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_txsearch_info_get(vdl2hip_ctx *c, vdl2hip_txsearch_info *info) {
+	if(!c || !c->txs.on || !info || info->struct_size != sizeof(vdl2hip_txsearch_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->txs;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->flags = m.flags;
+	info->records = m.records; info->samples_searched = m.samples; info->clipped = m.clipped; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+int vdl2hip_txsearch_read(vdl2hip_ctx *c, vdl2hip_tx_search *recs, size_t cap_recs) {
+	if(!c || !c->txs.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
+	return pop_records(c->txs.queue, recs, cap_recs);
+}
+
+// ---- the transmission log (vdl2hip.h, "Transmission log"; kernels: txlog.h) ----
+static_assert(sizeof(TxRec) == 64 && sizeof(vdl2hip_tx) == 80 && offsetof(vdl2hip_tx, frames) == sizeof(TxRec) && offsetof(vdl2hip_tx, first_burst_ord) == 72
+              && offsetof(TxRec, first_bin) == offsetof(vdl2hip_tx, first_bin) && offsetof(TxRec, peak_bin) == offsetof(vdl2hip_tx, peak_bin)
+              && offsetof(TxRec, first_sample) == offsetof(vdl2hip_tx, first_sample) && offsetof(TxRec, busy_bins) == offsetof(vdl2hip_tx, busy_bins)
+              && offsetof(TxRec, mean_power) == offsetof(vdl2hip_tx, mean_power), "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_txlog_cfg) == 16 && sizeof(vdl2hip_txlog_info) == 64 && sizeof(TxHdr) == 16 && sizeof(TxState) == 48, "vdl2hip.h states these sizes");
+static_assert(kTxMaxChan == kK5MaxChan, "k_txlog_emit keeps every channel's offset in LDS");
+constexpr uint32_t kTxMaxWait = 4096;      // frames per channel that may wait for their record (txlog_collect)
+// Its share of a feed: behind k_activity_scan of the same feed, on the front stream (activity_feed): the bins m0 .. m0 + nb - 1 the feed
+// completed are in the series ring (S >= the bins of the longest feed + 2) and stay there until the next feed's k_activity_power, which
+// is queued behind.  (The copy of the header and the first records follows the feed's frame finisher: launch_rest.)
+static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb) {
+	auto &m = c->txl; const auto &act = c->act;
+	TxArgs a{};
+	a.series = act.buf.d_series; a.freq = c->d_freq; a.st = m.buf.d_st; a.cnt = m.buf.d_cnt; a.rec = sl.txl.mail.d_rec(); a.hdr = sl.txl.mail.d_hdr();
+	a.k_on = act.k_on; a.m0 = m0; a.thr = act.thr; a.nb = nb; a.H = act.H; a.B = act.B; a.S = act.S; a.smask = act.S - 1;
+	a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first; a.pool = m.pool;
+	KernelTimes &t = sl.txl.times;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_txlog_plan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
+	hipExtLaunchKernelGGL(k_txlog_emit, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, a);
+	HIPCHK(hipGetLastError());
+	t.launched(2);
+	sl.txl.on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed and the log.  The feed's frames first - all of them, whatever the AVLC filter lets through: they wait, per channel,
+// for the record whose window holds their sync_sample.  Then the feed's records: each takes the waiting frames of its window; those
+// before the window are counted as unmatched and dropped (vdl2hip.h, "Transmission log": Outcome).
+static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+	auto &m = c->txl;
+	for(uint32_t i = 0; i < nf; i++) {
+		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
+		auto &w = m.wait[(size_t)fr[i].chan];
+		if(w.size() >= kTxMaxWait) { w.pop_front(); m.unmatched++; }
+		w.push_back(vdl2hip_ctx::TxFrame{ fr[i].sync_sample, fr[i].burst_ord, fr[i].avlc_status == AVLC_OK });
+	}
+	if(!sl.txl.on) return VDL2HIP_OK;
+	sl.txl.on = false;
+	if(!sl.txl.mail) { sl.txs.on = false; return VDL2HIP_OK; }
+	const TxHdr h = sl.txl.mail.hdr();
+	const uint32_t nrec = std::min(h.nrec, m.pool);
+	m.dropped += h.dropped;
+	if(nrec == 0) { sl.txs.on = false; return VDL2HIP_OK; }
+	const TxRec *rec = nullptr;
+	HIPCHK(sl.txl.mail.fetch(nrec, m.stage, c->streams.out, rec));
+	const TxsRec *srec = nullptr;
+	if(sl.txs.on) { sl.txs.on = false; int r = txsearch_fetch(c, sl, nrec, srec); if(r != VDL2HIP_OK) return r; }
+	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
+	for(uint32_t i = 0; i < nrec; i++) {
+		vdl2hip_tx r;
+		memcpy(&r, rec + i, sizeof(TxRec));
+		r.frames = r.frames_ok = 0; r.first_burst_ord = -1;
+		const int64_t close_sample = c->act.k_on + ((int64_t)r.last_bin + close_bins) * B;
+		int64_t first_sync = 0;
+		if(r.chan >= (uint32_t)c->chan_first && r.chan < (uint32_t)(c->chan_first + c->C)) {
+			auto &w = m.wait[r.chan - (uint32_t)c->chan_first];
+			size_t keep = 0;
+			for(const auto &f : w) {
+				if(f.sync_sample < r.first_sample) m.unmatched++;
+				else if(f.sync_sample < close_sample) {
+					if(!r.frames || f.sync_sample < first_sync) { first_sync = f.sync_sample; r.first_burst_ord = f.burst_ord; }
+					r.frames++; if(f.ok) r.frames_ok++;
+				} else w[keep++] = f;
+			}
+			w.resize(keep);
+		}
+		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
+		if(srec) txsearch_take(c, srec[i], r);
+		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
+		m.queue.push_back(r);
+	}
+	return VDL2HIP_OK;
+}
+// give the log's buffers back (nothing of it may be in flight: the callers have collected every feed and the front stream has run dry
+// of its launches)
+static void txlog_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.txl.reset();
+	auto &m = c->txl;
+	m.buf = {}; m.queue.clear(); m.wait.clear();
+	m.on = false;
+}
+// switch a running log off: the feeds under way are collected (their copies land in the slots' buffers), then everything goes
+static int txlog_off(vdl2hip_ctx *c) {
+	if(!c->txl.on) return VDL2HIP_OK;
+	if(!c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	(void)hipStreamSynchronize(c->streams.front);
+	txsearch_free(c);                                                // (a search reads the log's records: it goes first)
+	txlog_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_txlog_enable(vdl2hip_ctx *c, const vdl2hip_txlog_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txlog_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(!c->act.on || cfg->pool_records > kTxMaxPool || (cfg->flags & ~VDL2HIP_TXLOG_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier log is in flight any more
+	(void)hipStreamSynchronize(c->streams.front);
+	auto &m = c->txl;
+	txsearch_free(c);                                                // (a search that was running goes with the log it read)
+	txlog_free(c);
+	const uint32_t pool = cfg->pool_records ? cfg->pool_records : kTxDefPool;
+	const size_t C = (size_t)c->C;
+	bool ok = m.buf.d_st.alloc(C) == hipSuccess && m.buf.d_cnt.alloc(C, true) == hipSuccess;
+	for(auto &sl : c->slot) ok = ok && sl.txl.mail.alloc(pool) == hipSuccess;
+	if(!ok) { txlog_free(c); return VDL2HIP_E_NOMEM; }
+	// the log's state from the monitor's, on the front stream: behind every scan queued so far, ahead of the next feed's
+	hipLaunchKernelGGL(k_txlog_init, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->streams.front, (const ActState *)c->act.buf.d_st.get(), m.buf.d_st.get(), (uint32_t)C);
+	if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txlog_free(c); return VDL2HIP_E_DEVICE; }
+	m.wait.assign(C, {});
+	m.pool = pool; m.flags = cfg->flags;
+	m.transmissions = m.decoded = m.dropped = m.matched = m.unmatched = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_txlog_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	return txlog_off(c);
+}
+int vdl2hip_txlog_info_get(vdl2hip_ctx *c, vdl2hip_txlog_info *info) {
+	if(!c || !c->txl.on || !info || info->struct_size != sizeof(vdl2hip_txlog_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->txl;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->pool_records = m.pool; info->flags = m.flags;
+	info->transmissions = m.transmissions; info->decoded = m.decoded; info->dropped = m.dropped;
+	info->frames_matched = m.matched; info->frames_unmatched = m.unmatched; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+int vdl2hip_txlog_read(vdl2hip_ctx *c, vdl2hip_tx *recs, size_t cap_recs) {
+	if(!c || !c->txl.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
+	return pop_records(c->txl.queue, recs, cap_recs);
+}
+
+// ---- the activity monitor (vdl2hip.h, "Activity monitor"; kernels: activity.h) ----
+static_assert(sizeof(ActChan) == sizeof(vdl2hip_activity_chan) && offsetof(ActChan, hist) == offsetof(vdl2hip_activity_chan, hist), "the host copies the device's accumulators as they are");
+// Its share of a feed: on the front stream directly behind the channeliser - k_chanfir, every piece of a cold-start feed, k_fixup
+// where it is not fused - and ahead of the sync kernels.  Everything that rewrites y (the referee's scans, on the back streams)
+// waits for an ev_front, which is recorded behind the sync kernels of its feed, and writes nothing at or beyond that feed's last
+// sample (k_ref_scan_multi: n_hi <= in_end / os - 1): what the monitor reads of this feed, [k0, k0 + D), is the channeliser's.
+// Host bookkeeping: the bin the stream stands in, the bins this feed completes, which carry is current.
+static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
+	auto &m = c->act;
+	const uint64_t B = m.B, t0 = (uint64_t)(k0 - m.k_on), t1 = t0 + (uint64_t)D;
+	const uint64_t m0 = t0 / B, m1 = t1 / B, nb = m1 - m0;
+	ActArgs a{};
+	a.y = (const float2 *)c->d_y.get(); a.series = m.buf.d_series; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1];
+	a.k0 = k0; a.m0 = m0; a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = (uint32_t)D; a.B = m.B; a.nbt = (uint32_t)nb + 1;
+	a.cap = c->cap; a.mask = c->cap - 1; a.S = m.S; a.smask = m.S - 1;
+	// bins per workgroup: some 4096 workgroups over the channels, each with one to eight chunks' worth of samples
+	const uint64_t per = std::min<uint64_t>(8 * kActChunk, std::max<uint64_t>(kActChunk, (uint64_t)D * (uint64_t)c->C / 4096));
+	a.run = (uint32_t)std::max<uint64_t>(1, per / B);
+	const unsigned gx = (a.nbt + a.run - 1) / a.run;
+	KernelTimes &t = sl.act_t;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_activity_power, dim3(gx, (unsigned)c->C), dim3(kActThreads), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
+	if(nb) {
+		ActScanArgs sa{ m.buf.d_series, m.buf.d_acc, m.buf.d_st, m.buf.d_edges, m.thr, m0, (uint32_t)nb, m.H, m.S, m.S - 1 };
+		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, sa);
+	}
+	HIPCHK(hipGetLastError());
+	// the transmission log reads the series and the bins this feed completed directly behind the scan (ahead of the mark: whoever waits
+	// for the monitor's last launch waits for the log's too)
+	if(c->txl.on && nb) { int r = txlog_launch(c, sl, m0, (uint32_t)nb); if(r != VDL2HIP_OK) return r; }
+	HIPCHK(m.tap.mark(c->streams.front));
+	t.launched(nb ? 2 : 1);
+	m.bins = m1; m.carry_sel ^= 1;
+	return VDL2HIP_OK;
+}
+// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap;
+// what its launches took of the slots' feeds is not a later monitor's)
+static void activity_free(vdl2hip_ctx *c) {
+	auto &m = c->act;
+	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
+	m.buf = {};
+	for(auto &sl : c->slot) sl.act_t.n = 0;
+	m.on = false; m.tap.queued = false;
+}
+static float activity_edge(int i) { return (float)std::pow(10.0, (double)(-120 + 2 * i) / 10.0); }
+
+int vdl2hip_activity_edges(float *edges, size_t cap) {
+	if(!edges || cap < (size_t)kActBuckets - 1) return VDL2HIP_E_TOOBIG;
+	for(int i = 0; i < kActBuckets - 1; i++) edges[i] = activity_edge(i);
+	return kActBuckets - 1;
+}
+int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_activity_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	const uint32_t B = cfg->bin_samples ? cfg->bin_samples : 105u;
+	if(B < kActMinBin || B > kActMaxBin || cfg->hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
+	if(cfg->series_bins > kActMaxSeries || (cfg->series_bins & (cfg->series_bins - 1)) != 0) return VDL2HIP_E_INVAL;
+	if(std::isnan(cfg->threshold_dbfs)) return VDL2HIP_E_INVAL;
+	uint32_t S = 1; while(S < cfg->series_bins || S < c->dmax / B + 2) S <<= 1;           // a feed's bins never overwrite one another in the ring
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }          // (a transmission log's state would no longer mean anything)
+	auto &m = c->act;
+	activity_free(c);
+	const size_t C = (size_t)c->C;
+	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
+	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
+	if(!m.tap.land) HIPCHK(m.tap.land.alloc(C * (sizeof(ActChan) + sizeof(ActState))));
+	auto &b = m.buf;
+	for(hipError_t e : { b.d_series.alloc(C * S, true), b.d_carry[0].alloc(C, true), b.d_carry[1].alloc(C, true), b.d_edges.alloc(kActBuckets), b.d_acc.alloc(C, true), b.d_st.alloc(C, true) })
+		if(e != hipSuccess) { activity_free(c); return e == hipErrorOutOfMemory ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; }
+	float edges[kActBuckets] = {};
+	(void)vdl2hip_activity_edges(edges, kActBuckets);
+	if(hipMemcpy(b.d_edges, edges, sizeof edges, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_DEVICE; }
+	m.B = B; m.H = cfg->hang_bins; m.S = S; m.thr_dbfs = cfg->threshold_dbfs; m.thr = (float)std::pow(10.0, (double)cfg->threshold_dbfs / 10.0);
+	m.k_on = c->k_total; m.bins = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_activity_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }
+	activity_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_activity_read(vdl2hip_ctx *c, vdl2hip_activity_info *info, vdl2hip_activity_chan *chans, size_t cap_chans, int reset) {
+	if(!c || !c->act.on || (info && info->struct_size != sizeof(vdl2hip_activity_info))) return VDL2HIP_E_INVAL;
+	auto &m = c->act;
+	const size_t C = (size_t)c->C;
+	if(chans && cap_chans < C) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	if(chans) {
+		uint8_t *land = m.tap.land;
+		ActState *st = (ActState *)(land + C * sizeof(ActChan));
+		if(m.tap.queued) {
+			HIPCHK(m.tap.fetch(land, m.buf.d_acc, m.buf.d_acc.bytes()));
+			HIPCHK(m.tap.fetch(st, m.buf.d_st, m.buf.d_st.bytes()));
+		} else memset(land, 0, m.tap.land.bytes());      // nothing has touched them since they were zeroed
+		memcpy(chans, land, C * sizeof(ActChan));
+		for(size_t i = 0; i < C; i++) { chans[i].open = st[i].open; chans[i].reserved = 0; if(!chans[i].bins) chans[i].max_power = chans[i].min_power = 0.f; }
+	}
+	if(info) {
+		memset(info, 0, sizeof *info);
+		info->struct_size = sizeof *info; info->bin_samples = m.B; info->hang_bins = m.H; info->series_bins = m.S;
+		info->threshold_dbfs = m.thr_dbfs; info->threshold_power = m.thr; info->first_sample = m.k_on; info->bins = m.bins;
+		info->kernel_ms = (float)m.kernel_ms;
+	}
+	if(reset) {
+		// (on the front stream: behind the launches that are queued, ahead of the next feed's; the transmission under way is kept)
+		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
+		HIPCHK(m.tap.mark(c->streams.front));
+	}
+	return chans ? (int)C : 0;
+}
+int vdl2hip_activity_series(vdl2hip_ctx *c, uint32_t chan, int64_t first_bin, float *dst, size_t cap) {
+	if(!c || !c->act.on || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
+	auto &m = c->act;
+	if(first_bin < 0 || (uint64_t)first_bin > m.bins || m.bins - (uint64_t)first_bin > m.S) return VDL2HIP_E_INVAL;
+	const size_t n = std::min<size_t>(cap, (size_t)(m.bins - (uint64_t)first_bin));
+	if(n == 0) return 0;
+	if(!dst) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	const float *base = m.buf.d_series + (size_t)(chan - (uint32_t)c->chan_first) * m.S;
+	const size_t p0 = (size_t)((uint64_t)first_bin & (m.S - 1)), n0 = std::min<size_t>(n, m.S - p0);
+	HIPCHK(m.tap.fetch(dst, base + p0, n0 * sizeof(float)));
+	if(n0 < n) HIPCHK(m.tap.fetch(dst + n0, base, (n - n0) * sizeof(float)));
+	return (int)n;
+}

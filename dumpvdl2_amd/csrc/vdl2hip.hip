@@ -31,7 +31,7 @@
 #include "hostmem.h"
 
 using namespace vdl2;
-using hostmem::DevBuf; using hostmem::PinnedBuf; using hostmem::Event;
+using hostmem::DevBuf; using hostmem::PinnedBuf; using hostmem::Event; using hostmem::RecordMail;
 
 static_assert(VDL2HIP_NUM_COUNTERS == kNumCounters, "counter enum out of sync");
 
@@ -117,6 +117,15 @@ struct TapRead {
 	}
 };
 
+// A record tap's share of a slot: whether the slot's feed carries the tap's launches, what they took (profiling level 2), and the
+// tap's per-feed buffers B, whose first records come to the host through a RecordMail (hostmem.h).  reset(): the tap is switched off -
+// the buffers go as one, the timing events stay with the slot ("Ownership").
+template<typename B>
+struct TapSlot : B {
+	bool on = false; KernelTimes times;
+	void reset() { static_cast<B &>(*this) = B{}; on = false; times.n = 0; }
+};
+
 struct OutSlot {
 	DevBuf<Burst> d_bursts; DevBuf<uint32_t> d_nbchan;
 	DevBuf<OutFrame> d_frames; DevBuf<uint8_t> d_pool;
@@ -140,25 +149,21 @@ struct OutSlot {
 	// has_chk: the walk noted decisions to a list that is checked
 	bool rest_pending = false, has_chk = false; int nseg = 1; int64_t seglen = 0; K4Args k4{}; SpecOut *d_spec_of = nullptr;
 	Event ev_stitch, ev_chk; DevBuf<uint32_t> d_rqflag2;
-	// profiling level 2, per tap: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
-	// k_activity_power and k_activity_scan (activity monitor) / k_capture_plan and k_capture_copy (burst capture)
-	// / k_txlog_plan and k_txlog_emit (transmission log) / k_txsearch_plan .. k_txsearch_reduce (preamble search: one pair round the three)
-	KernelTimes rs_t, mon_t, act_t, cap_t, txl_t, txs_t;
-	// burst capture (capture.h): the feed's header and records (one allocation: the header and the first records come to the host in one
-	// small copy; d_rec = the records behind the header, not owned), windows and totals, the IQ pool, the small copy's page-locked landing
-	// place.  Given back as one when the capture is disabled (capture_free); cap_on: this feed's back end is followed by the capture's launches
-	struct { DevBuf<CapHdr> d_hdr; CapRec *d_rec = nullptr; DevBuf<CapPlan> d_plan; DevBuf<uint64_t> d_tot; DevBuf<cf32> d_pool; PinnedBuf h_mail; } cap;
-	bool cap_on = false;
-	// transmission log (txlog.h): the feed's header and record pool (one allocation, as the capture's: the header and the first records
-	// come to the host in one small copy; d_rec = the records behind the header, not owned) and that copy's page-locked landing place.
-	// Given back when the log is switched off (txlog_free); txl_on: this feed completed bins and the log's launches followed its scan
-	struct { DevBuf<TxHdr> d_hdr; TxRec *d_rec = nullptr; PinnedBuf h_mail; } txl;
-	bool txl_on = false;
-	// preamble search (txsearch.h): the feed's header and records (one allocation, as the log's; d_rec = the records behind the header,
-	// not owned), the records' piece offsets, the pieces' partial results, the small copy's page-locked landing place.  Given back when
-	// the search is switched off (txsearch_free); txs_on: the search's launches followed this feed's frame finisher
-	struct { DevBuf<TxsHdr> d_hdr; TxsRec *d_rec = nullptr; DevBuf<uint32_t> d_off; DevBuf<TxsPart> d_part; PinnedBuf h_mail; } txs;
-	bool txs_on = false;
+	// profiling level 2: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
+	// k_activity_power and k_activity_scan (activity monitor)
+	KernelTimes rs_t, mon_t, act_t;
+	// burst capture (capture.h): the feed's records, windows and totals, the IQ pool.  on: this feed's back end is followed by the
+	// capture's launches; times: k_capture_plan and k_capture_copy
+	struct CapBufs { RecordMail<CapHdr, CapRec> mail; DevBuf<CapPlan> d_plan; DevBuf<uint64_t> d_tot; DevBuf<cf32> d_pool; };
+	TapSlot<CapBufs> cap;
+	// transmission log (txlog.h): the feed's records.  on: this feed completed bins and the log's launches followed its scan; times:
+	// k_txlog_plan and k_txlog_emit
+	struct TxlBufs { RecordMail<TxHdr, TxRec> mail; };
+	TapSlot<TxlBufs> txl;
+	// preamble search (txsearch.h): the feed's records, their piece offsets, the pieces' partial results.  on: the search's launches
+	// followed this feed's frame finisher; times: k_txsearch_plan .. k_txsearch_reduce (one pair round the three)
+	struct TxsBufs { RecordMail<TxsHdr, TxsRec> mail; DevBuf<uint32_t> d_off; DevBuf<TxsPart> d_part; };
+	TapSlot<TxsBufs> txs;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -195,27 +200,27 @@ struct vdl2hip_ctx {
 		int carry_sel = 0; TapRead tap; double kernel_ms = 0.0;
 	} act;
 	// Burst capture (capture.h, vdl2hip_capture_*): off unless enabled.  queue: the records of the collected feeds, oldest first, each
-	// with the IQ of its feed (one allocation per feed, shared by its records; iq_off: where the record's window begins in it)
+	// with the IQ of its feed (one allocation per feed, shared by its records; iq_off: where the record's window begins in it).
+	// stage (here and in the two taps below): the page-locked staging buffer of a feed with more records than come with the header -
+	// the capture's takes the feed's IQ too - grown on demand and kept, whatever the tap does, until the receiver goes
 	struct CapItem { vdl2hip_burst r; std::shared_ptr<std::vector<float>> iq; };
 	struct {
 		bool on = false; uint32_t pre = 0, post = 0, flags = 0, pool = 0;
 		uint64_t bursts = 0, iq_samples = 0, iq_dropped = 0; double kernel_ms = 0.0;
-		PinnedBuf stage;                                       // page-locked landing place of a feed's records and IQ, grown on demand (kept until the receiver goes)
-		std::deque<CapItem> queue;
+		PinnedBuf stage; std::deque<CapItem> queue;
 	} capt;
 	// Transmission log (txlog.h, vdl2hip_txlog_*): off unless enabled, and only beside the activity monitor.  buf: its per-channel state
-	// and counts, the staging place of a feed with more records than come with the header - given back as one (txlog_free).  queue: the
-	// records of the collected feeds, oldest first; wait: per channel the frames no record has claimed yet (txlog_collect)
+	// and counts, given back as one (txlog_free).  queue: the records of the collected feeds, oldest first; wait: per channel the frames
+	// no record has claimed yet (txlog_collect)
 	struct TxFrame { int64_t sync_sample, burst_ord; bool ok; };
 	struct {
 		bool on = false; uint32_t pool = 0, flags = 0;
 		uint64_t transmissions = 0, decoded = 0, dropped = 0, matched = 0, unmatched = 0; double kernel_ms = 0.0;
-		struct { DevBuf<TxState> d_st; DevBuf<uint32_t> d_cnt; PinnedBuf stage; } buf;
-		std::deque<vdl2hip_tx> queue; std::vector<std::deque<TxFrame>> wait;
+		struct { DevBuf<TxState> d_st; DevBuf<uint32_t> d_cnt; } buf;
+		PinnedBuf stage; std::deque<vdl2hip_tx> queue; std::vector<std::deque<TxFrame>> wait;
 	} txl;
 	// Preamble search (txsearch.h, vdl2hip_txsearch_*): off unless enabled, and only beside the transmission log.  piece_cap: the
-	// pieces a feed's records can have at the most (txsearch_piece_cap); stage: the landing place of a feed with more records than come
-	// with the header; queue: the records of the collected feeds, oldest first
+	// pieces a feed's records can have at the most (txsearch_piece_cap); queue: the records of the collected feeds, oldest first
 	struct {
 		bool on = false; uint32_t flags = 0, piece_cap = 0;
 		uint64_t records = 0, samples = 0, clipped = 0; double kernel_ms = 0.0;
@@ -344,18 +349,47 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 	}
 }
 
+// The front's picks among the builds of its kernel templates (channeliser, exact sync tier, resampler).  They stand here, ahead of
+// taps.inc, for ONE reason: the compiler emits the builds of kernel templates in the order the host code first names them, and the
+// input monitor's k_spectrum, named in taps.inc, must come out behind these as it always did - the device assembly stays the same
+// file, diffable against any earlier build.  Nothing else depends on the three launchers; the order of the names inside them counts too.
+static void launch_k1(vdl2hip_ctx *c, const K1Args &a, size_t lds, hipEvent_t e0, hipEvent_t e1) {
+	if(c->specialised && c->os == 20) launch_chanfir<20, kRun>(c, a, c->cr, lds, e0, e1);
+	else if(c->specialised && c->os == 13) launch_chanfir<13, kRun>(c, a, c->cr, lds, e0, e1);
+	else if(c->specialised) launch_chanfir<10, kRun>(c, a, c->cr, lds, e0, e1);
+	else launch_chanfir<0, kRunGeneric>(c, a, c->cr, lds, e0, e1);
+}
+// (the exact sync tier, its stop event the feed's ev_front: feed_common)
+static void launch_k3b(vdl2hip_ctx *c, const K3Args &k3, dim3 grid, hipEvent_t ev_front) {
+	const bool pre = c->referee && c->ref_prescan;
+	if(c->debug_exact_tier) { if(pre) LAUNCH_EV(k_sync_dense<true>, grid, dim3(256), c->streams.front, (hipEvent_t) nullptr, ev_front, k3); else LAUNCH_EV(k_sync_dense<false>, grid, dim3(256), c->streams.front, (hipEvent_t) nullptr, ev_front, k3); }
+	else { if(pre) LAUNCH_EV(k_sync_exact4<true>, grid, dim3(256), c->streams.front, (hipEvent_t) nullptr, ev_front, k3); else LAUNCH_EV(k_sync_exact4<false>, grid, dim3(256), c->streams.front, (hipEvent_t) nullptr, ev_front, k3); }
+}
+template<int FMT>
+static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
+	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
+}
+static void launch_k0(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, e0, e1);
+	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, e0, e1);
+	else if(c->in_fmt == kFmtS8) launch_resample<3>(c, a, grid, e0, e1);
+	else launch_resample<0>(c, a, grid, e0, e1);
+}
+
 static int launch_back(vdl2hip_ctx *c, OutSlot &sl);
-static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st);
-static void capture_free(vdl2hip_ctx *c);
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, struct OutSlot *succ);
 static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto);
 // A short feed (fewer than two walk segments' worth of samples; the reference's own 320 000-byte blocks are 4 000): launch_back()
 static bool feed_is_small(const vdl2hip_ctx *c, int64_t D);
+static int collect_slot(vdl2hip_ctx *c, OutSlot &sl);
+static int collect_pending(vdl2hip_ctx *c, int keep = 0);
+// what is in flight is collected, as a tap's enable and disable need it before they touch its buffers: an output buffer that ran over
+// on the way is the drain's to report, not theirs
+static int collect_all(vdl2hip_ctx *c) { const int r = collect_pending(c); return r == VDL2HIP_E_OVERFLOW ? VDL2HIP_OK : r; }
 
-static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
-static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf);
-static int txsearch_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st);
-static void txsearch_free(vdl2hip_ctx *c);
+#include "taps.inc"   // the five taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
+
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
 	if(sl.rest_pending) { int r = flush_rest(c, &sl); if(r != VDL2HIP_OK) return r; }   // nothing followed this feed: no walk that its second walks could have been queued behind (it and what is older, oldest first)
@@ -364,9 +398,9 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.rs_t.collect(c->stats.resample_ms);
 	sl.mon_t.collect(c->mon.kernel_ms);
 	sl.act_t.collect(c->act.kernel_ms);
-	sl.cap_t.collect(c->capt.kernel_ms);
-	sl.txl_t.collect(c->txl.kernel_ms);
-	sl.txs_t.collect(c->txs.kernel_ms);
+	sl.cap.times.collect(c->capt.kernel_ms);
+	sl.txl.times.collect(c->txl.kernel_ms);
+	sl.txs.times.collect(c->txs.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
 		const Event *ev = sl.ev;
 		float ms = 0.f;
@@ -416,13 +450,13 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 			if(!c->avlc_filter || fr[i].avlc_status == AVLC_OK) c->queue.push_back(HostFrame{ fr[i], pool });
 		}
 	}
-	if(sl.cap_on) { sl.cap_on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
+	if(sl.cap.on) { sl.cap.on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	if(c->txl.on) { int r = txlog_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	return ctl.overflow ? VDL2HIP_E_OVERFLOW : VDL2HIP_OK;
 }
 
 // collect every feed except the `keep` most recent ones, oldest first
-static int collect_pending(vdl2hip_ctx *c, int keep = 0) {
+static int collect_pending(vdl2hip_ctx *c, int keep) {
 	int rc = VDL2HIP_OK;
 	for(int pass = 0; pass < kSlots; pass++) {
 		OutSlot *oldest = nullptr;
@@ -434,48 +468,6 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0) {
 		if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
 	}
 	return rc;
-}
-
-// The activity monitor's share of a feed (activity.h): on the front stream directly behind the channeliser - k_chanfir, every piece
-// of a cold-start feed, k_fixup where it is not fused - and ahead of the sync kernels.  Everything that rewrites y (the referee's
-// scans, on the back streams) waits for an ev_front, which is recorded behind the sync kernels of its feed, and writes nothing at
-// or beyond that feed's last sample (k_ref_scan_multi: n_hi <= in_end / os - 1): what the monitor reads of this feed, [k0, k0 + D),
-// is the channeliser's.  Host bookkeeping: the bin the stream stands in, the bins this feed completes, which carry is current.
-static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb);
-static int activity_feed(vdl2hip_ctx *c, OutSlot &sl, int64_t k0, int64_t D) {
-	auto &m = c->act;
-	const uint64_t B = m.B, t0 = (uint64_t)(k0 - m.k_on), t1 = t0 + (uint64_t)D;
-	const uint64_t m0 = t0 / B, m1 = t1 / B, nb = m1 - m0;
-	ActArgs a{};
-	a.y = (const float2 *)c->d_y.get(); a.series = m.buf.d_series; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1];
-	a.k0 = k0; a.m0 = m0; a.off = (int32_t)((int64_t)(m0 * B) - (int64_t)t0); a.D = (uint32_t)D; a.B = m.B; a.nbt = (uint32_t)nb + 1;
-	a.cap = c->cap; a.mask = c->cap - 1; a.S = m.S; a.smask = m.S - 1;
-	// bins per workgroup: some 4096 workgroups over the channels, each with one to eight chunks' worth of samples
-	const uint64_t per = std::min<uint64_t>(8 * kActChunk, std::max<uint64_t>(kActChunk, (uint64_t)D * (uint64_t)c->C / 4096));
-	a.run = (uint32_t)std::max<uint64_t>(1, per / B);
-	const unsigned gx = (a.nbt + a.run - 1) / a.run;
-	KernelTimes &t = sl.act_t;
-	t.arm(c->profiling >= 2);
-	hipExtLaunchKernelGGL(k_activity_power, dim3(gx, (unsigned)c->C), dim3(kActThreads), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
-	if(nb) {
-		ActScanArgs sa{ m.buf.d_series, m.buf.d_acc, m.buf.d_st, m.buf.d_edges, m.thr, m0, (uint32_t)nb, m.H, m.S, m.S - 1 };
-		hipExtLaunchKernelGGL(k_activity_scan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, sa);
-	}
-	HIPCHK(hipGetLastError());
-	// the transmission log reads the series and the bins this feed completed directly behind the scan (ahead of the mark: whoever waits
-	// for the monitor's last launch waits for the log's too)
-	if(c->txl.on && nb) { int r = txlog_launch(c, sl, m0, (uint32_t)nb); if(r != VDL2HIP_OK) return r; }
-	HIPCHK(m.tap.mark(c->streams.front));
-	t.launched(nb ? 2 : 1);
-	m.bins = m1; m.carry_sel ^= 1;
-	return VDL2HIP_OK;
-}
-// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap)
-static void activity_free(vdl2hip_ctx *c) {
-	auto &m = c->act;
-	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
-	m.buf = {};
-	m.on = false; m.tap.queued = false;
 }
 
 static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
@@ -513,9 +505,9 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	}
 
 	sl.ev_valid = false;
-	sl.cap_on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
-	sl.txl_on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
-	sl.txs_on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
+	sl.cap.on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
+	sl.txl.on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
+	sl.txs.on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
 		// (a cold-start feed launches the channeliser in pieces that wait for the pieces of the copy: not a kernel duration, not timed)
@@ -523,18 +515,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		if(cold) c->stats.cold_start_feeds++;
 		sl.k1_timed = prof && !cold;
 		hipEvent_t e0 = sl.k1_timed ? (hipEvent_t)ev[0] : nullptr, e1 = sl.k1_timed ? (hipEvent_t)ev[1] : nullptr;
-		auto launch = [&](int seg0, int seg1, hipEvent_t s_ev, hipEvent_t p_ev) {
-			a.seg0 = seg0; a.seg1 = seg1;
-			if(c->specialised) {
-				switch(c->os) {
-					case 20: launch_chanfir<20, kRun>(c, a, c->cr, lds, s_ev, p_ev); break;
-					case 13: launch_chanfir<13, kRun>(c, a, c->cr, lds, s_ev, p_ev); break;
-					default: launch_chanfir<10, kRun>(c, a, c->cr, lds, s_ev, p_ev); break;
-				}
-			} else {
-				launch_chanfir<0, kRunGeneric>(c, a, c->cr, lds, s_ev, p_ev);
-			}
-		};
+		auto launch = [&](int seg0, int seg1, hipEvent_t s_ev, hipEvent_t p_ev) { a.seg0 = seg0; a.seg1 = seg1; launch_k1(c, a, lds, s_ev, p_ev); };
 		if(!in_parts || c->cold.n <= 1) launch(0, a.nseg, e0, e1);
 		else {
 			// cold start: piece p of the block is on the device when cold.ev[p] fires; the workgroup segments whose input lies in the
@@ -625,13 +606,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 		// (receivers that scan ahead of the walk work out the windows with one or two unwrap decisions within the margin: sync_metric_ref)
 		// (debug_exact_tier 0: the word-at-a-time form the dense one replaced, kept as its yardstick - same grid, same arguments)
 		const dim3 k3b_grid((unsigned)((nwords + wpb - 1) / wpb), (unsigned)c->C);
-		if(c->debug_exact_tier) {
-			if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_dense<true>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
-			else LAUNCH_EV(k_sync_dense<false>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
-		} else {
-			if(c->referee && c->ref_prescan) LAUNCH_EV(k_sync_exact4<true>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
-			else LAUNCH_EV(k_sync_exact4<false>, k3b_grid, dim3(256), st, (hipEvent_t) nullptr, sl.ev_front, k3);
-		}
+		launch_k3b(c, k3, k3b_grid, sl.ev_front);
 	}
 	if(D <= 0) HIPCHK(hipEventRecord(sl.ev_front, st));
 	if(D > 0) { sl.ev_valid = prof; sl.ev_level = c->profiling; sl.fused = a.fuse != 0; if(sl.k1_timed) c->stats.chan_samples += (uint64_t)D * c->os * c->C; } else sl.k1_timed = false;
@@ -649,12 +624,6 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 // (cfg.input_rate) turns it into this feed's block of r[] first - K0, k_resample, on the front stream into the buffer of the feed's
 // slot, which stays as it is until the slot comes round again: the referee reads it as it reads any block - and is a CF32 receiver
 // fed that block from there on.
-template<int FMT>
-static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
-	if(c->rs.taps_lds) hipExtLaunchKernelGGL((k_resample<FMT, true>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
-	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
-}
-static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes);
 static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
 	// (the monitor sees a block once nothing can refuse it any more, and ahead of everything else that reads it)
 	if(c->failed) return VDL2HIP_E_DEVICE;
@@ -679,10 +648,7 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nout + per - 1) / per);       // (no output: workgroup 0 still moves the tail on)
 	KernelTimes &t = sl.rs_t;
 	t.arm(c->profiling >= 2);
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == kFmtS8) launch_resample<3>(c, a, grid, t.e(0), t.e(1));
-	else launch_resample<0>(c, a, grid, t.e(0), t.e(1));
+	launch_k0(c, a, grid, t.e(0), t.e(1));
 	HIPCHK(hipGetLastError());
 	t.launched(1);
 	rs.tail_sel ^= 1; rs.first[k] = n0; rs.count[k] = nout; rs.n_in = N1; rs.n_out = n1;
@@ -690,68 +656,6 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	c->stats.input_samples += nin - nout;                           // (feed_common counted the block it saw) the caller's samples
 	c->stats.resampled_samples += nout;
 	return r;
-}
-
-// The input monitor's share of a feed (spectrum.h): on the front stream ahead of everything else that reads the block, so it is
-// ordered with the copy into d_in[k], with that buffer's reuse and with a caller's device buffer exactly as the channeliser is.
-// Host bookkeeping: the stream position (64 bits), the segments this feed completes, which of them are analysed, what is carried.
-template<int FMT>
-static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
-	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->streams.front, e0, e1, 0, a)
-	switch(c->mon.nfft / c->mon.threads) {                           // samples per lane (spec_threads(): 1, 2, 4 up to N = 1024, 8, 16)
-		case 1: SPEC_LAUNCH(1); break;
-		case 2: SPEC_LAUNCH(2); break;
-		case 4: SPEC_LAUNCH(4); break;
-		case 8: SPEC_LAUNCH(8); break;
-		default: SPEC_LAUNCH(16); break;
-	}
-	#undef SPEC_LAUNCH
-}
-static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
-	auto &m = c->mon;
-	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
-	if(nin == 0) return VDL2HIP_OK;
-	if(nin >= (1ull << 32)) return VDL2HIP_E_TOOBIG;
-	const uint64_t N = m.nfft, pos0 = m.pos, pos1 = pos0 + nin;
-	const uint64_t j0 = pos0 / N, j1 = pos1 / N;                          // the segments the stream stands in before and after: [j0, j1) are completed
-	const uint64_t ja = (j0 + m.stride - 1) / m.stride * m.stride;        // the first of them that is analysed
-	const uint64_t nseg = ja < j1 ? (j1 - 1 - ja) / m.stride + 1 : 0;
-	const uint32_t o1 = (uint32_t)(pos1 % N);
-	const uint32_t ncarry_out = j1 % m.stride == 0 ? o1 : 0;               // (a segment that stride skips is not kept)
-	m.pos = pos1;
-	if(nseg == 0 && ncarry_out == 0) { m.ncarry = 0; return VDL2HIP_OK; }
-	SpecArgs a{};
-	a.in = dev_in; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1]; a.w = m.buf.d_w; a.tw = m.buf.d_tw; a.rows = m.buf.d_rows;
-	a.rel0 = (int64_t)(ja * N) - (int64_t)pos0; a.carry_rel = (int64_t)(j1 * N) - (int64_t)pos0; a.seg_step = (uint64_t)m.stride * N;
-	a.nin = (uint32_t)nin; a.ncarry = m.ncarry; a.ncarry_out = ncarry_out; a.nseg = (uint32_t)nseg;
-	a.run = (uint32_t)std::max<uint64_t>(1, (nseg + kSpecMaxRows - 1) / kSpecMaxRows); a.N = m.nfft; a.log2n = m.log2n;
-	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nseg + a.run - 1) / a.run);      // (no segment: workgroup 0 still moves the carry on)
-	if(grid > kSpecMaxRows || (int64_t)a.ncarry + a.rel0 < 0) return VDL2HIP_E_INVAL;       // (never)
-	OutSlot &sl = c->slot[c->feed_no % kSlots];
-	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
-	KernelTimes &t = sl.mon_t;
-	t.arm(c->profiling >= 2);
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == kFmtS8) launch_spectrum<3>(c, a, grid, t.e(0), t.e(1));
-	else launch_spectrum<0>(c, a, grid, t.e(0), t.e(1));
-	if(nseg) {
-		const uint32_t W = m.nfft + kSpecLevels;
-		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), t.e(3), 0,
-		                      (const double *)m.buf.d_rows, m.buf.d_acc.get(), (uint32_t)grid, m.nfft);
-	}
-	HIPCHK(hipGetLastError());
-	HIPCHK(m.tap.mark(c->streams.front));
-	t.launched(nseg ? 2 : 1);
-	m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
-	return VDL2HIP_OK;
-}
-// wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap)
-static void monitor_free(vdl2hip_ctx *c) {
-	auto &m = c->mon;
-	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
-	m.buf = {};
-	m.on = false; m.tap.queued = false; m.nfft = 0;
 }
 
 // The burst-rate back end of one feed (K4 walk, K4b noise floor, K5 burst decoder, frame finish), on three streams of its own so
@@ -932,261 +836,6 @@ static int flush_rest(vdl2hip_ctx *c, const OutSlot *upto) {
 	}
 }
 
-// ---- the burst capture's share of a feed (vdl2hip.h, "Burst capture"; kernels: capture.h) ----
-// The ring behind the window.  The capture of feed i reads y from iq_first >= sync_sample - kCapMaxPre on, while the channelisers
-// of up to kSlots - 1 later feeds may be writing (feed i + kSlots takes feed i's slot, and collect_slot() has waited for feed i
-// before that).  They write [k_end, k_end + (kSlots - 1) dmax), which in a ring of `cap` >= kSlots dmax + kHistory + 1024 samples
-// (vdl2hip_create) lands on samples older than k_end - dmax - kHistory - 1024 <= k0 - kHistory - 1024, k0 being feed i's first
-// sample.  A burst is handed over in the feed that brings its last symbol, so end_sample >= k0; the longest burst is 56 320 samples
-// from its first symbol to its last and its sync lies a unique word before that: iq_first > k0 - 56 320 - 200 - 4 096 = k0 - 60 616
-// > k0 - kHistory - 1024 = k0 - 66 560.  The 5 944 samples between the two are why pre stops at 4 096.  A window is at most
-// 4 096 + 56 520 + 1 024 < 2^16 pairs long.
-static_assert(kCapMaxPre + 56320 + 200 < kHistory + 1024, "a window begins inside what the ring keeps behind a feed");
-static_assert(sizeof(CapRec) == sizeof(vdl2hip_burst) && sizeof(vdl2hip_burst) == 128 && offsetof(CapRec, iq_first) == offsetof(vdl2hip_burst, iq_first)
-              && offsetof(CapRec, frames) == offsetof(vdl2hip_burst, frames) && offsetof(CapRec, mean_power) == offsetof(vdl2hip_burst, mean_power)
-              && offsetof(CapRec, phase_err_max) == offsetof(vdl2hip_burst, phase_err_max), "the host copies the device's records as they are");
-static_assert(sizeof(vdl2hip_capture_cfg) == 24 && sizeof(vdl2hip_capture_info) == 56 && sizeof(CapHdr) == 16, "vdl2hip.h states these sizes");
-static_assert(kCapMaxChan == kK5MaxChan, "k_capture_copy keeps every channel's offsets in LDS");
-constexpr uint32_t kCapMailRecs = 32;      // records that come to the host with the header, in one small copy (most feeds of a live receiver hold a handful of bursts)
-constexpr size_t kCapMailBytes = sizeof(CapHdr) + kCapMailRecs * sizeof(CapRec);
-// the transmission log: records that come to the host with the header; frames per channel that may wait for their record (txlog_collect)
-constexpr uint32_t kTxMailRecs = 32, kTxMaxWait = 4096;
-constexpr size_t kTxMailBytes = sizeof(TxHdr) + kTxMailRecs * sizeof(TxRec);
-
-static int capture_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
-	auto &m = c->capt;
-	CapArgs a{};
-	a.y = c->d_y; a.bursts = sl.d_bursts; a.nb_chan = sl.d_nbchan; a.freq = c->d_freq;
-	a.plan = sl.cap.d_plan; a.tot = sl.cap.d_tot; a.rec = sl.cap.d_rec; a.pool = sl.cap.d_pool; a.hdr = sl.cap.d_hdr;
-	a.k_end = sl.back_k0 + sl.back_D; a.pool_samples = m.pool; a.cap_bursts_chan = c->cap_bursts_chan; a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first;
-	a.cap = c->cap; a.mask = c->cap - 1; a.pre = m.pre; a.post = m.post;
-	KernelTimes &t = sl.cap_t;
-	t.arm(c->profiling >= 2);
-	hipExtLaunchKernelGGL(k_capture_plan, dim3((unsigned)c->C), dim3(64), 0u, st, t.e(0), t.e(1), 0, a);
-	// a workgroup per burst, bounded like the burst decoder's wavefronts (16 .. 2048 of them, by the feed's size): 8 .. 512
-	const unsigned grid = std::min(512u, std::max(8u, sl.k5_waves / 4));
-	hipExtLaunchKernelGGL(k_capture_copy, dim3(grid), dim3(kCapThreads), 0u, st, t.e(2), t.e(3), 0, a);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(sl.cap.h_mail, sl.cap.d_hdr, kCapMailBytes, hipMemcpyDeviceToHost, st));
-	t.launched(2);
-	return VDL2HIP_OK;
-}
-// A collected feed's records (the first have come with the header) and the used part of its IQ pool, joined with the feed's frames -
-// all of them, whatever the AVLC filter lets through - and appended to the queue.
-static int capture_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
-	auto &m = c->capt;
-	if(!m.on || !sl.cap.h_mail) return VDL2HIP_OK;
-	const CapHdr h = *sl.cap.h_mail.as<CapHdr>();
-	const uint32_t nrec = (uint32_t)std::min<uint64_t>(h.nrec, (uint64_t)c->C * c->cap_bursts_chan);
-	const uint64_t pairs = std::min<uint64_t>(h.pairs, m.pool);
-	if(nrec == 0) return VDL2HIP_OK;
-	const CapRec *rec = reinterpret_cast<const CapRec *>(sl.cap.h_mail + sizeof(CapHdr));
-	const size_t rec_bytes = nrec > kCapMailRecs ? sizeof(CapRec) * (size_t)nrec : 0, need = rec_bytes + (size_t)pairs * sizeof(cf32);
-	HIPCHK(m.stage.reserve(need));
-	if(rec_bytes) { HIPCHK(hipMemcpyAsync(m.stage, sl.cap.d_rec, rec_bytes, hipMemcpyDeviceToHost, c->streams.out)); rec = m.stage.as<CapRec>(); }
-	if(pairs) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.cap.d_pool, (size_t)pairs * sizeof(cf32), hipMemcpyDeviceToHost, c->streams.out));
-	if(need) HIPCHK(hipStreamSynchronize(c->streams.out));
-	const float *iqp = reinterpret_cast<const float *>(m.stage + rec_bytes);
-	auto iq = pairs ? std::make_shared<std::vector<float>>(iqp, iqp + 2 * (size_t)pairs) : std::make_shared<std::vector<float>>();
-	struct Join { uint32_t frames = 0, ok = 0; int32_t fec = -1, last_idx = -1; };
-	std::map<std::pair<int32_t, int64_t>, Join> join;
-	for(uint32_t i = 0; i < nf; i++) {
-		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
-		Join &j = join[{ fr[i].chan + c->chan_first, fr[i].burst_ord }];
-		j.frames++; if(fr[i].avlc_status == AVLC_OK) j.ok++;
-		if(fr[i].idx >= j.last_idx) { j.last_idx = fr[i].idx; j.fec = fr[i].num_fec_corrections; }
-	}
-	for(uint32_t i = 0; i < nrec; i++) {
-		vdl2hip_burst r;
-		memcpy(&r, rec + i, sizeof r);
-		if(r.iq_off + r.iq_count > pairs) { r.iq_count = 0; r.iq_off = 0; r.flags |= VDL2HIP_BURST_NO_ROOM; }      // (never)
-		m.bursts++; m.iq_samples += r.iq_count; if(r.flags & VDL2HIP_BURST_NO_ROOM) m.iq_dropped++;
-		auto it = join.find({ (int32_t)r.chan, r.burst_ord });
-		if(it != join.end()) { r.frames = it->second.frames; r.frames_ok = it->second.ok; r.fec_corrections = it->second.fec; }
-		if((m.flags & VDL2HIP_CAPTURE_FAILED_ONLY) && r.frames_ok != 0) continue;
-		m.queue.push_back(vdl2hip_ctx::CapItem{ r, iq });
-	}
-	return VDL2HIP_OK;
-}
-// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed; the slots' events and the
-// context's staging buffer stay)
-static void capture_free(vdl2hip_ctx *c) {
-	for(auto &sl : c->slot) { sl.cap = {}; sl.cap_on = false; sl.cap_t.n = 0; }
-	c->capt.queue.clear();
-	c->capt.on = false;
-}
-
-// ---- the preamble search's share of a feed (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
-// The ring behind the range.  The search of feed i reads y from search_first - 153 on (the taps of p(search_first - 3)), under the
-// burst capture's conditions (above): what the ring keeps behind feed i's first sample k0 is kHistory + 1024 samples.  A record is
-// emitted by the feed that completes bin last_bin + H + 1, so that bin ends at or after k0 and last_sample >= k0 - (H + 1) B
-// >= k0 - kTxsMaxBack (vdl2hip_txsearch_enable refuses a monitor beyond that); search_first >= last_sample - (kTxsSpan - 1).
-static_assert(kTxsMaxBack + (kTxsSpan - 1) + kTxsLead < kHistory + 1024, "a range and its taps begin inside what the ring keeps behind a feed");
-static_assert(sizeof(TxsRec) == sizeof(vdl2hip_tx_search) && sizeof(vdl2hip_tx_search) == 96 && offsetof(TxsRec, first_bin) == offsetof(vdl2hip_tx_search, first_bin)
-              && offsetof(TxsRec, first_lock) == offsetof(vdl2hip_tx_search, first_lock) && offsetof(TxsRec, best_pherr) == offsetof(vdl2hip_tx_search, best_pherr)
-              && offsetof(TxsRec, best_ppm) == offsetof(vdl2hip_tx_search, best_ppm) && offsetof(TxsRec, lock_points) == offsetof(vdl2hip_tx_search, lock_points)
-              && offsetof(TxsRec, flags) == offsetof(vdl2hip_tx_search, flags) && offsetof(vdl2hip_tx_search, flags) == 72 && offsetof(TxsRec, frames) == offsetof(vdl2hip_tx_search, frames)
-              && offsetof(TxsRec, why) == offsetof(vdl2hip_tx_search, why) && offsetof(vdl2hip_tx_search, why) == 84, "the host copies the device's records as they are and fills in the rest");
-static_assert(sizeof(vdl2hip_txsearch_cfg) == 16 && sizeof(vdl2hip_txsearch_info) == 40 && sizeof(TxsHdr) == 16 && sizeof(TxsPart) == 40, "vdl2hip.h states these sizes");
-static_assert(VDL2HIP_TXS_CLIPPED == kTxsClipped && VDL2HIP_TX_PARTIAL == kTxPartial && (kTxsClipped & kTxPartial) == 0, "the two flags share a word");
-constexpr uint32_t kTxsMailRecs = 32;      // records that come to the host with the header
-constexpr size_t kTxsMailBytes = sizeof(TxsHdr) + kTxsMailRecs * sizeof(TxsRec);
-// The pieces one feed's records can have at the most.  The transmissions of a channel are disjoint and the ranges of those a feed
-// closes lie in [k0 - kTxsMaxBack - kTxsSpan, k0 + dmax): their lengths add up to less than dmax + kTxsMaxBack + kTxsSpan per channel,
-// and a range of L samples has at most L / kTxsPiece + 1 pieces; the records are at most `pool`.
-static uint64_t txsearch_piece_cap(const vdl2hip_ctx *c, uint32_t pool) {
-	return (uint64_t)c->C * ((c->dmax + kTxsMaxBack + (uint64_t)kTxsSpan) / kTxsPiece + 1) + pool;
-}
-static int txsearch_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
-	auto &m = c->txs;
-	TxsArgs a{};
-	a.y = c->d_y; a.tab = c->d_tab; a.txhdr = sl.txl.d_hdr; a.txrec = sl.txl.d_rec;
-	a.off = sl.txs.d_off; a.part = sl.txs.d_part; a.rec = sl.txs.d_rec; a.hdr = sl.txs.d_hdr;
-	a.pool = c->txl.pool; a.piece_cap = m.piece_cap; a.cap = c->cap; a.mask = c->cap - 1; a.chan_first = (uint32_t)c->chan_first;
-	KernelTimes &t = sl.txs_t;
-	t.arm(c->profiling >= 2);
-	hipExtLaunchKernelGGL(k_txsearch_plan, dim3(1), dim3(kTxsThreads), 0u, st, t.e(0), (hipEvent_t) nullptr, 0, a);
-	// a workgroup per piece, grid-stride: a piece per kTxsPiece channel-samples of the feed would be every sample busy - a quarter of that, 16 .. 2048
-	const unsigned grid = (unsigned)std::min<uint64_t>(2048, std::max<uint64_t>(16, (uint64_t)sl.back_D * (uint64_t)c->C / (4 * kTxsPiece)));
-	hipLaunchKernelGGL(k_txsearch_piece, dim3(grid), dim3(kTxsThreads), 0, st, a);
-	hipExtLaunchKernelGGL(k_txsearch_reduce, dim3(std::min(256u, (c->txl.pool + 63) / 64)), dim3(64), 0u, st, (hipEvent_t) nullptr, t.e(1), 0, a);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(sl.txs.h_mail, sl.txs.d_hdr, kTxsMailBytes, hipMemcpyDeviceToHost, st));
-	t.launched(1);
-	sl.txs_on = true;
-	return VDL2HIP_OK;
-}
-// A collected feed's search records, index for index beside the log's nrec records (the first have come with the header)
-static int txsearch_fetch(vdl2hip_ctx *c, OutSlot &sl, uint32_t nrec, const TxsRec *&srec) {
-	auto &m = c->txs;
-	srec = nullptr;
-	if(!m.on || !sl.txs.h_mail) return VDL2HIP_OK;
-	const TxsHdr h = *sl.txs.h_mail.as<TxsHdr>();
-	if(h.nrec != nrec) return VDL2HIP_E_DEVICE;                       // (never: both are the log's header of this feed)
-	srec = reinterpret_cast<const TxsRec *>(sl.txs.h_mail + sizeof(TxsHdr));
-	if(nrec > kTxsMailRecs) {
-		const size_t bytes = sizeof(TxsRec) * (size_t)nrec;
-		HIPCHK(m.stage.reserve(bytes));
-		HIPCHK(hipMemcpyAsync(m.stage, sl.txs.d_rec, bytes, hipMemcpyDeviceToHost, c->streams.out));
-		HIPCHK(hipStreamSynchronize(c->streams.out));
-		srec = m.stage.as<TxsRec>();
-	}
-	return VDL2HIP_OK;
-}
-// ... one of them, with the outcome the log has joined to its record
-static void txsearch_take(vdl2hip_ctx *c, const TxsRec &s, const vdl2hip_tx &tx) {
-	auto &m = c->txs;
-	vdl2hip_tx_search r;
-	memcpy(&r, &s, sizeof r);
-	r.frames = tx.frames; r.frames_ok = tx.frames_ok; r.reserved = r.reserved2 = 0;
-	r.why = tx.frames_ok ? VDL2HIP_TXS_DECODED : tx.frames ? VDL2HIP_TXS_FRAMES_BAD : r.lock_points ? VDL2HIP_TXS_LOCK_NO_FRAME : VDL2HIP_TXS_NO_PREAMBLE;
-	m.records++; if(r.search_last >= r.search_first) m.samples += (uint64_t)(r.search_last - r.search_first + 1); if(r.flags & VDL2HIP_TXS_CLIPPED) m.clipped++;
-	if((m.flags & VDL2HIP_TXSEARCH_UNDECODED_ONLY) && r.frames_ok != 0) return;
-	m.queue.push_back(r);
-}
-// give the search's buffers back (nothing of it may be in flight: the callers have collected every feed), the
-// staging buffer included; the slots' events stay)
-static void txsearch_free(vdl2hip_ctx *c) {
-	for(auto &sl : c->slot) { sl.txs = {}; sl.txs_on = false; sl.txs_t.n = 0; }
-	c->txs.stage = {}; c->txs.queue.clear();
-	c->txs.on = false;
-}
-
-// ---- the transmission log's share of a feed (txlog.h) ----
-static_assert(sizeof(TxRec) == 64 && sizeof(vdl2hip_tx) == 80 && offsetof(vdl2hip_tx, frames) == sizeof(TxRec) && offsetof(vdl2hip_tx, first_burst_ord) == 72
-              && offsetof(TxRec, first_bin) == offsetof(vdl2hip_tx, first_bin) && offsetof(TxRec, peak_bin) == offsetof(vdl2hip_tx, peak_bin)
-              && offsetof(TxRec, first_sample) == offsetof(vdl2hip_tx, first_sample) && offsetof(TxRec, busy_bins) == offsetof(vdl2hip_tx, busy_bins)
-              && offsetof(TxRec, mean_power) == offsetof(vdl2hip_tx, mean_power), "the host copies the device's records as they are and fills in the rest");
-static_assert(sizeof(vdl2hip_txlog_cfg) == 16 && sizeof(vdl2hip_txlog_info) == 64 && sizeof(TxHdr) == 16 && sizeof(TxState) == 48, "vdl2hip.h states these sizes");
-static_assert(kTxMaxChan == kK5MaxChan, "k_txlog_emit keeps every channel's offset in LDS");
-// Behind k_activity_scan of the same feed, on the front stream (activity_feed): the bins m0 .. m0 + nb - 1 the feed completed are in
-// the series ring (S >= the bins of the longest feed + 2) and stay there until the next feed's k_activity_power, which is queued behind.
-static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb) {
-	auto &m = c->txl; const auto &act = c->act;
-	TxArgs a{};
-	a.series = act.buf.d_series; a.freq = c->d_freq; a.st = m.buf.d_st; a.cnt = m.buf.d_cnt; a.rec = sl.txl.d_rec; a.hdr = sl.txl.d_hdr;
-	a.k_on = act.k_on; a.m0 = m0; a.thr = act.thr; a.nb = nb; a.H = act.H; a.B = act.B; a.S = act.S; a.smask = act.S - 1;
-	a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first; a.pool = m.pool;
-	KernelTimes &t = sl.txl_t;
-	t.arm(c->profiling >= 2);
-	hipExtLaunchKernelGGL(k_txlog_plan, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(0), t.e(1), 0, a);
-	hipExtLaunchKernelGGL(k_txlog_emit, dim3((unsigned)c->C), dim3(64), 0u, c->streams.front, t.e(2), t.e(3), 0, a);
-	HIPCHK(hipGetLastError());
-	t.launched(2);
-	sl.txl_on = true;
-	return VDL2HIP_OK;
-}
-// A collected feed and the log.  The feed's frames first - all of them, whatever the AVLC filter lets through: they wait, per channel,
-// for the record whose window holds their sync_sample.  Then the feed's records (the first have come with the header): each takes the
-// waiting frames of its window; those before the window are counted as unmatched and dropped (vdl2hip.h, "Transmission log": Outcome).
-static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
-	auto &m = c->txl;
-	for(uint32_t i = 0; i < nf; i++) {
-		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
-		auto &w = m.wait[(size_t)fr[i].chan];
-		if(w.size() >= kTxMaxWait) { w.pop_front(); m.unmatched++; }
-		w.push_back(vdl2hip_ctx::TxFrame{ fr[i].sync_sample, fr[i].burst_ord, fr[i].avlc_status == AVLC_OK });
-	}
-	if(!sl.txl_on) return VDL2HIP_OK;
-	sl.txl_on = false;
-	if(!sl.txl.h_mail) { sl.txs_on = false; return VDL2HIP_OK; }
-	const TxHdr h = *sl.txl.h_mail.as<TxHdr>();
-	const uint32_t nrec = std::min(h.nrec, m.pool);
-	m.dropped += h.dropped;
-	if(nrec == 0) { sl.txs_on = false; return VDL2HIP_OK; }
-	const TxRec *rec = reinterpret_cast<const TxRec *>(sl.txl.h_mail + sizeof(TxHdr));
-	if(nrec > kTxMailRecs) {
-		const size_t bytes = sizeof(TxRec) * (size_t)nrec;
-		HIPCHK(m.buf.stage.reserve(bytes));
-		HIPCHK(hipMemcpyAsync(m.buf.stage, sl.txl.d_rec, bytes, hipMemcpyDeviceToHost, c->streams.out));
-		HIPCHK(hipStreamSynchronize(c->streams.out));
-		rec = m.buf.stage.as<TxRec>();
-	}
-	const TxsRec *srec = nullptr;
-	if(sl.txs_on) { sl.txs_on = false; int r = txsearch_fetch(c, sl, nrec, srec); if(r != VDL2HIP_OK) return r; }
-	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
-	for(uint32_t i = 0; i < nrec; i++) {
-		vdl2hip_tx r;
-		memcpy(&r, rec + i, sizeof(TxRec));
-		r.frames = r.frames_ok = 0; r.first_burst_ord = -1;
-		const int64_t close_sample = c->act.k_on + ((int64_t)r.last_bin + close_bins) * B;
-		int64_t first_sync = 0;
-		if(r.chan >= (uint32_t)c->chan_first && r.chan < (uint32_t)(c->chan_first + c->C)) {
-			auto &w = m.wait[r.chan - (uint32_t)c->chan_first];
-			size_t keep = 0;
-			for(const auto &f : w) {
-				if(f.sync_sample < r.first_sample) m.unmatched++;
-				else if(f.sync_sample < close_sample) {
-					if(!r.frames || f.sync_sample < first_sync) { first_sync = f.sync_sample; r.first_burst_ord = f.burst_ord; }
-					r.frames++; if(f.ok) r.frames_ok++;
-				} else w[keep++] = f;
-			}
-			w.resize(keep);
-		}
-		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
-		if(srec) txsearch_take(c, srec[i], r);
-		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
-		m.queue.push_back(r);
-	}
-	return VDL2HIP_OK;
-}
-// give the log's buffers back (nothing of it may be in flight: the callers have collected every feed and the front stream has run dry
-// of its launches; the slots' events stay)
-static void txlog_free(vdl2hip_ctx *c) {
-	for(auto &sl : c->slot) { sl.txl = {}; sl.txl_on = false; sl.txl_t.n = 0; }
-	auto &m = c->txl;
-	m.buf = {}; m.queue.clear(); m.wait.clear();
-	m.on = false;
-}
-// switch a running log off: the feeds under way are collected (their copies land in the slots' buffers), then everything goes
-static int txlog_off(vdl2hip_ctx *c) {
-	if(!c->txl.on) return VDL2HIP_OK;
-	if(!c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
-	(void)hipStreamSynchronize(c->streams.front);
-	txsearch_free(c);                                                // (a search reads the log's records: it goes first)
-	txlog_free(c);
-	return VDL2HIP_OK;
-}
 static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 	const int64_t D = sl.back_D, k0 = sl.back_k0;
 	const bool small = sl.small;
@@ -1246,11 +895,11 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		hipLaunchKernelGGL(k_frame_finish, dim3(ff_grid), dim3(64 * kFrameWaves), 0, s5_, sl.d_frames, (const uint8_t *)sl.d_pool, sl.d_mail, (const Tables *)c->d_tab,
 		                   c->d_acnt, (const float *)c->d_nfring, c->nf_ring - 1, sl.d_frames_out, sl.d_pool_out);
 		// the burst capture reads this feed's burst lists and y here: both passes of the burst decoder and its scans are done
-		if(sl.cap_on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		if(sl.cap.on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 		// the transmission log's header and first records of this feed (written on the front stream ahead of the sync kernels: long done)
-		if(sl.txl_on) HIPCHK(hipMemcpyAsync(sl.txl.h_mail, sl.txl.d_hdr, kTxMailBytes, hipMemcpyDeviceToHost, s5_));
+		if(sl.txl.on) HIPCHK(sl.txl.mail.post(s5_));
 		// the preamble search reads the log's records of this feed (the same ordering) and y here, like the capture
-		if(sl.txl_on && c->txs.on) { int r = txsearch_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		if(sl.txl.on && c->txs.on) { int r = txsearch_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 	}
 	// the control block and the first few delivered frames in one copy (collect_slot)
 	HIPCHK(hipMemcpyAsync(sl.h_mail, sl.d_mail, sizeof(OutMail), hipMemcpyDeviceToHost, s5_));
@@ -1726,8 +1375,7 @@ int vdl2hip_pack_raw_frame(const vdl2hip_frame *f, const char *station_id, int64
 int vdl2hip_counters(vdl2hip_ctx *c, uint32_t chan, uint64_t out[VDL2HIP_NUM_COUNTERS]) {
 	if(!c || !out || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	uint64_t w[kNumCounters];
 	HIPCHK(hipMemcpy(out, c->d_cnt + (size_t)(chan - c->chan_first) * kNumCounters, 8 * kNumCounters, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(w, c->d_wcnt + (size_t)(chan - c->chan_first) * kNumCounters, 8 * kNumCounters, hipMemcpyDeviceToHost));
@@ -1738,8 +1386,7 @@ int vdl2hip_counters(vdl2hip_ctx *c, uint32_t chan, uint64_t out[VDL2HIP_NUM_COU
 int vdl2hip_avlc_counters(vdl2hip_ctx *c, uint32_t chan, uint64_t out[VDL2HIP_NUM_AVLC_COUNTERS]) {
 	if(!c || !out || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	HIPCHK(hipMemcpy(out, c->d_acnt + (size_t)(chan - c->chan_first) * kNumAvlcCounters, 8 * kNumAvlcCounters, hipMemcpyDeviceToHost));
 	return VDL2HIP_OK;
 }
@@ -1765,8 +1412,7 @@ static const char *const kAvlcCounterNames[VDL2HIP_NUM_AVLC_COUNTERS] = {
 int vdl2hip_statsd_lines(vdl2hip_ctx *c, const char *ns, char *out, size_t cap) {
 	if(!c || !ns || !out) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	const size_t per = VDL2HIP_NUM_COUNTERS + VDL2HIP_NUM_AVLC_COUNTERS;
 	std::vector<uint64_t> now((size_t)c->C * per);
 	{
@@ -1853,8 +1499,7 @@ int vdl2hip_get_nco_step(vdl2hip_ctx *c, uint32_t chan, uint32_t *dphi) {
 int vdl2hip_read_decimated(vdl2hip_ctx *c, uint32_t chan, int64_t first, float *dst, size_t cap) {
 	if(!c || !dst || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	if(first < 0 || first > c->k_total || c->k_total - first > (int64_t)c->cap) return VDL2HIP_E_INVAL;
 	size_t n = std::min<size_t>(cap, (size_t)(c->k_total - first));
 	const cf32 *base = c->d_y + (size_t)(chan - c->chan_first) * c->cap;
@@ -1871,8 +1516,7 @@ int vdl2hip_read_decimated(vdl2hip_ctx *c, uint32_t chan, int64_t first, float *
 int vdl2hip_read_resampled(vdl2hip_ctx *c, int64_t first, float *dst, size_t cap) {
 	if(!c || !dst || !c->rs.on) return VDL2HIP_E_INVAL;
 	OnDevice dev_guard(c);
-	int r = collect_pending(c);
-	if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	if(first < 0 || (uint64_t)first > c->rs.n_out) return VDL2HIP_E_INVAL;
 	size_t done = 0;
 	const size_t n = (size_t)std::min<uint64_t>(cap, c->rs.n_out - (uint64_t)first);
@@ -1899,381 +1543,6 @@ int vdl2hip_resampler_design(uint32_t input_rate, uint32_t output_rate, uint32_t
 	if(!design_resampler(input_rate, output_rate, d)) return VDL2HIP_E_INVAL;
 	memcpy(taps, d.taps.data(), d.taps.size() * sizeof(float));
 	return (int)d.taps.size();
-}
-
-// ---- the input monitor (vdl2hip.h, "Input monitor"; kernels: spectrum.h) ----
-int vdl2hip_spectrum_window(uint32_t nfft, uint32_t window, float *w, size_t cap) {
-	SpectrumDesign d;
-	if(!design_spectrum(nfft, window, d, false)) return VDL2HIP_E_INVAL;
-	if(!w || cap < nfft) return VDL2HIP_E_TOOBIG;
-	memcpy(w, d.w.data(), (size_t)nfft * sizeof(float));
-	return (int)nfft;
-}
-
-int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
-	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_spectrum_cfg)) return VDL2HIP_E_INVAL;
-	SpectrumDesign d;
-	if(cfg->nfft != 0 && !design_spectrum(cfg->nfft, cfg->window, d)) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	auto &m = c->mon;
-	monitor_free(c);
-	for(auto &sl : c->slot) sl.mon_t.n = 0;                          // (what an earlier monitor's launches took is not this one's)
-	if(cfg->nfft == 0) return VDL2HIP_OK;
-	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
-	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
-	if(!m.tap.land) HIPCHK(m.tap.land.alloc(((size_t)kSpecMaxN + kSpecLevels) * sizeof(double)));
-	const size_t N = cfg->nfft, W = N + kSpecLevels;
-	auto &b = m.buf;
-	if(b.d_w.alloc(N) != hipSuccess || b.d_tw.alloc(N) != hipSuccess || b.d_carry[0].alloc(N) != hipSuccess || b.d_carry[1].alloc(N) != hipSuccess
-	   || b.d_rows.alloc((size_t)kSpecMaxRows * W) != hipSuccess || b.d_acc.alloc(W) != hipSuccess) { monitor_free(c); return VDL2HIP_E_NOMEM; }
-	if(hipMemcpy(b.d_w, d.w.data(), b.d_w.bytes(), hipMemcpyHostToDevice) != hipSuccess
-	   || hipMemcpy(b.d_tw, d.tw.data(), b.d_tw.bytes(), hipMemcpyHostToDevice) != hipSuccess
-	   || hipMemset(b.d_acc, 0, b.d_acc.bytes()) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { monitor_free(c); return VDL2HIP_E_DEVICE; }
-	m.nfft = cfg->nfft; m.window = cfg->window; m.stride = cfg->stride ? cfg->stride : 1; m.log2n = d.log2n;
-	m.threads = spec_threads(m.nfft); m.lds = spec_lds_bytes(m.nfft);
-	m.sum_w = d.sum_w; m.enbw = d.enbw_bins;
-	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
-	m.on = true;
-	return VDL2HIP_OK;
-}
-
-// the accumulators as they stand once everything the monitor has queued is done: [nfft] sums of |X|^2, then the level sums
-static int monitor_fetch(vdl2hip_ctx *c, std::vector<double> &acc) {
-	auto &m = c->mon;
-	acc.assign((size_t)m.nfft + kSpecLevels, 0.0);
-	if(!m.tap.queued) return VDL2HIP_OK;                             // nothing has touched them since they were zeroed
-	HIPCHK(m.tap.fetch(m.tap.land, m.buf.d_acc, m.buf.d_acc.bytes()));
-	memcpy(acc.data(), m.tap.land, m.buf.d_acc.bytes());
-	return VDL2HIP_OK;
-}
-static void monitor_power(const vdl2hip_ctx *c, const std::vector<double> &acc, double *power) {
-	const auto &m = c->mon;
-	const double scale = m.segments ? 1.0 / ((double)m.segments * m.sum_w * m.sum_w) : 0.0;
-	for(uint32_t i = 0; i < m.nfft; i++) power[i] = acc[i] * scale;
-}
-
-int vdl2hip_spectrum_read(vdl2hip_ctx *c, vdl2hip_spectrum_info *info, double *power, size_t cap, int reset) {
-	if(!c || !c->mon.on || (info && info->struct_size != sizeof(vdl2hip_spectrum_info))) return VDL2HIP_E_INVAL;
-	auto &m = c->mon;
-	if(power && cap < m.nfft) return VDL2HIP_E_TOOBIG;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	std::vector<double> acc;
-	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
-	const uint32_t N = m.nfft;
-	if(info) {
-		memset(info, 0, sizeof *info);
-		info->struct_size = sizeof *info; info->nfft = N; info->window = m.window; info->stride = m.stride;
-		info->sample_rate = c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample;
-		info->centerfreq = c->cfg.centerfreq;
-		info->segments = m.segments; info->samples = m.segments * N; info->clipped = (uint64_t)acc[N + 3];
-		info->enbw_bins = m.enbw;
-		if(info->samples) { const double n = (double)info->samples; info->mean_power = acc[N] / n; info->dc_i = acc[N + 1] / n; info->dc_q = acc[N + 2] / n; }
-		info->peak = (float)acc[N + 4];
-		info->kernel_ms = (float)m.kernel_ms;
-	}
-	if(power) monitor_power(c, acc, power);
-	if(reset) {
-		// (on the front stream: behind the launches that are queued, ahead of the next feed's)
-		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
-		HIPCHK(m.tap.mark(c->streams.front));
-		m.segments = 0;
-	}
-	return (int)N;
-}
-
-int vdl2hip_spectrum_channels(vdl2hip_ctx *c, float *dbfs, size_t cap) {
-	if(!c || !c->mon.on || !dbfs) return VDL2HIP_E_INVAL;
-	auto &m = c->mon;
-	const size_t nchan = c->all_freqs.size();
-	if(cap < nchan) return VDL2HIP_E_TOOBIG;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	std::vector<double> acc;
-	{ int r = monitor_fetch(c, acc); if(r != VDL2HIP_OK) return r; }
-	const uint32_t N = m.nfft;
-	std::vector<double> power(N);
-	monitor_power(c, acc, power.data());
-	const double fs = (double)(c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample), cf = (double)c->cfg.centerfreq;
-	for(size_t ch = 0; ch < nchan; ch++) {
-		const double f = (double)c->all_freqs[ch];
-		double sum = 0.0, best = 0.0; bool any = false; uint32_t nearest = 0;
-		for(uint32_t i = 0; i < N; i++) {
-			const double d = std::fabs(cf + ((double)i - (double)(N / 2)) * fs / (double)N - f);
-			if(d <= 12500.0) { sum += power[i]; any = true; }
-			if(i == 0 || d < best) { best = d; nearest = i; }
-		}
-		if(!any) sum = power[nearest];
-		dbfs[ch] = sum > 0.0 ? (float)(10.0 * std::log10(sum / m.enbw)) : -INFINITY;
-	}
-	return (int)nchan;
-}
-
-// ---- the activity monitor (vdl2hip.h, "Activity monitor"; kernels: activity.h) ----
-static_assert(sizeof(ActChan) == sizeof(vdl2hip_activity_chan) && offsetof(ActChan, hist) == offsetof(vdl2hip_activity_chan, hist), "the host copies the device's accumulators as they are");
-static float activity_edge(int i) { return (float)std::pow(10.0, (double)(-120 + 2 * i) / 10.0); }
-int vdl2hip_activity_edges(float *edges, size_t cap) {
-	if(!edges || cap < (size_t)kActBuckets - 1) return VDL2HIP_E_TOOBIG;
-	for(int i = 0; i < kActBuckets - 1; i++) edges[i] = activity_edge(i);
-	return kActBuckets - 1;
-}
-
-int vdl2hip_activity_enable(vdl2hip_ctx *c, const vdl2hip_activity_cfg *cfg) {
-	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_activity_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
-	const uint32_t B = cfg->bin_samples ? cfg->bin_samples : 105u;
-	if(B < kActMinBin || B > kActMaxBin || cfg->hang_bins > kActMaxHang) return VDL2HIP_E_INVAL;
-	if(cfg->series_bins > kActMaxSeries || (cfg->series_bins & (cfg->series_bins - 1)) != 0) return VDL2HIP_E_INVAL;
-	if(std::isnan(cfg->threshold_dbfs)) return VDL2HIP_E_INVAL;
-	uint32_t S = 1; while(S < cfg->series_bins || S < c->dmax / B + 2) S <<= 1;           // a feed's bins never overwrite one another in the ring
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }          // (a transmission log's state would no longer mean anything)
-	auto &m = c->act;
-	activity_free(c);
-	for(auto &sl : c->slot) sl.act_t.n = 0;                          // (what an earlier monitor's launches took is not this one's)
-	const size_t C = (size_t)c->C;
-	HIPCHK(m.tap.last.ensure(hipEventDisableTiming));
-	if(!m.tap.rd) HIPCHK(hipStreamCreateWithFlags(&m.tap.rd, hipStreamNonBlocking));
-	if(!m.tap.land) HIPCHK(m.tap.land.alloc(C * (sizeof(ActChan) + sizeof(ActState))));
-	auto &b = m.buf;
-	for(hipError_t e : { b.d_series.alloc(C * S, true), b.d_carry[0].alloc(C, true), b.d_carry[1].alloc(C, true), b.d_edges.alloc(kActBuckets), b.d_acc.alloc(C, true), b.d_st.alloc(C, true) })
-		if(e != hipSuccess) { activity_free(c); return e == hipErrorOutOfMemory ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; }
-	float edges[kActBuckets] = {};
-	(void)vdl2hip_activity_edges(edges, kActBuckets);
-	if(hipMemcpy(b.d_edges, edges, sizeof edges, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); activity_free(c); return VDL2HIP_E_DEVICE; }
-	m.B = B; m.H = cfg->hang_bins; m.S = S; m.thr_dbfs = cfg->threshold_dbfs; m.thr = (float)std::pow(10.0, (double)cfg->threshold_dbfs / 10.0);
-	m.k_on = c->k_total; m.bins = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
-	m.on = true;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_activity_disable(vdl2hip_ctx *c) {
-	if(!c) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	{ int r = txlog_off(c); if(r != VDL2HIP_OK) return r; }
-	activity_free(c);
-	for(auto &sl : c->slot) sl.act_t.n = 0;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_activity_read(vdl2hip_ctx *c, vdl2hip_activity_info *info, vdl2hip_activity_chan *chans, size_t cap_chans, int reset) {
-	if(!c || !c->act.on || (info && info->struct_size != sizeof(vdl2hip_activity_info))) return VDL2HIP_E_INVAL;
-	auto &m = c->act;
-	const size_t C = (size_t)c->C;
-	if(chans && cap_chans < C) return VDL2HIP_E_TOOBIG;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	if(chans) {
-		uint8_t *land = m.tap.land;
-		ActState *st = (ActState *)(land + C * sizeof(ActChan));
-		if(m.tap.queued) {
-			HIPCHK(m.tap.fetch(land, m.buf.d_acc, m.buf.d_acc.bytes()));
-			HIPCHK(m.tap.fetch(st, m.buf.d_st, m.buf.d_st.bytes()));
-		} else memset(land, 0, m.tap.land.bytes());      // nothing has touched them since they were zeroed
-		memcpy(chans, land, C * sizeof(ActChan));
-		for(size_t i = 0; i < C; i++) { chans[i].open = st[i].open; chans[i].reserved = 0; if(!chans[i].bins) chans[i].max_power = chans[i].min_power = 0.f; }
-	}
-	if(info) {
-		memset(info, 0, sizeof *info);
-		info->struct_size = sizeof *info; info->bin_samples = m.B; info->hang_bins = m.H; info->series_bins = m.S;
-		info->threshold_dbfs = m.thr_dbfs; info->threshold_power = m.thr; info->first_sample = m.k_on; info->bins = m.bins;
-		info->kernel_ms = (float)m.kernel_ms;
-	}
-	if(reset) {
-		// (on the front stream: behind the launches that are queued, ahead of the next feed's; the transmission under way is kept)
-		HIPCHK(hipMemsetAsync(m.buf.d_acc, 0, m.buf.d_acc.bytes(), c->streams.front));
-		HIPCHK(m.tap.mark(c->streams.front));
-	}
-	return chans ? (int)C : 0;
-}
-
-int vdl2hip_activity_series(vdl2hip_ctx *c, uint32_t chan, int64_t first_bin, float *dst, size_t cap) {
-	if(!c || !c->act.on || chan < (uint32_t)c->chan_first || chan >= (uint32_t)(c->chan_first + c->C)) return VDL2HIP_E_INVAL;
-	auto &m = c->act;
-	if(first_bin < 0 || (uint64_t)first_bin > m.bins || m.bins - (uint64_t)first_bin > m.S) return VDL2HIP_E_INVAL;
-	const size_t n = std::min<size_t>(cap, (size_t)(m.bins - (uint64_t)first_bin));
-	if(n == 0) return 0;
-	if(!dst) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	const float *base = m.buf.d_series + (size_t)(chan - (uint32_t)c->chan_first) * m.S;
-	const size_t p0 = (size_t)((uint64_t)first_bin & (m.S - 1)), n0 = std::min<size_t>(n, m.S - p0);
-	HIPCHK(m.tap.fetch(dst, base + p0, n0 * sizeof(float)));
-	if(n0 < n) HIPCHK(m.tap.fetch(dst + n0, base, (n - n0) * sizeof(float)));
-	return (int)n;
-}
-
-// ---- the burst capture (vdl2hip.h, "Burst capture"; kernels: capture.h) ----
-int vdl2hip_capture_enable(vdl2hip_ctx *c, const vdl2hip_capture_cfg *cfg) {
-	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_capture_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
-	if(cfg->pre_samples > kCapMaxPre || cfg->post_samples > kCapMaxPost || (cfg->flags & ~VDL2HIP_CAPTURE_FAILED_ONLY) || cfg->pool_samples > kCapMaxPool) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier capture is in flight any more
-	auto &m = c->capt;
-	capture_free(c);
-	const uint32_t pool = cfg->pool_samples ? cfg->pool_samples : kCapDefPool;
-	const size_t nb = (size_t)c->C * c->cap_bursts_chan;
-	for(auto &sl : c->slot) {
-		auto &b = sl.cap;
-		const bool ok = b.d_hdr.alloc_bytes(sizeof(CapHdr) + std::max<size_t>(nb, kCapMailRecs) * sizeof(CapRec)) == hipSuccess
-			&& b.d_plan.alloc(nb) == hipSuccess && b.d_tot.alloc((size_t)c->C) == hipSuccess && b.d_pool.alloc(pool) == hipSuccess
-			&& b.h_mail.alloc(kCapMailBytes, true) == hipSuccess;
-		if(!ok) { capture_free(c); return VDL2HIP_E_NOMEM; }
-		b.d_rec = reinterpret_cast<CapRec *>(b.d_hdr.get() + 1);
-		if(hipMemset(b.d_hdr, 0, kCapMailBytes) != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
-	}
-	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); capture_free(c); return VDL2HIP_E_DEVICE; }
-	m.pre = cfg->pre_samples; m.post = cfg->post_samples; m.flags = cfg->flags; m.pool = pool;
-	m.bursts = m.iq_samples = m.iq_dropped = 0; m.kernel_ms = 0.0;
-	m.on = true;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_capture_disable(vdl2hip_ctx *c) {
-	if(!c) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->capt.on && !c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
-	capture_free(c);
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_capture_info_get(vdl2hip_ctx *c, vdl2hip_capture_info *info) {
-	if(!c || !c->capt.on || !info || info->struct_size != sizeof(vdl2hip_capture_info)) return VDL2HIP_E_INVAL;
-	const auto &m = c->capt;
-	memset(info, 0, sizeof *info);
-	info->struct_size = sizeof *info; info->pre_samples = m.pre; info->post_samples = m.post; info->flags = m.flags; info->pool_samples = m.pool;
-	info->bursts = m.bursts; info->iq_samples = m.iq_samples; info->iq_dropped = m.iq_dropped; info->kernel_ms = (float)m.kernel_ms;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used) {
-	if(!c || !c->capt.on || (!recs && cap_recs) || (!iq && cap_pairs)) return VDL2HIP_E_INVAL;
-	auto &q = c->capt.queue;
-	size_t n = 0, used = 0;
-	while(!q.empty() && n < cap_recs) {
-		const vdl2hip_ctx::CapItem &it = q.front();
-		if(used + it.r.iq_count > cap_pairs) break;
-		recs[n] = it.r;
-		recs[n].iq_off = used;
-		if(it.r.iq_count) memcpy(iq + 2 * used, it.iq->data() + 2 * it.r.iq_off, (size_t)it.r.iq_count * 2 * sizeof(float));
-		used += it.r.iq_count;
-		n++;
-		q.pop_front();
-	}
-	if(pairs_used) *pairs_used = used;
-	return (int)n;
-}
-
-// ---- the transmission log (vdl2hip.h, "Transmission log"; kernels: txlog.h) ----
-int vdl2hip_txlog_enable(vdl2hip_ctx *c, const vdl2hip_txlog_cfg *cfg) {
-	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txlog_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
-	if(!c->act.on || cfg->pool_records > kTxMaxPool || (cfg->flags & ~VDL2HIP_TXLOG_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier log is in flight any more
-	(void)hipStreamSynchronize(c->streams.front);
-	auto &m = c->txl;
-	txsearch_free(c);                                                // (a search that was running goes with the log it read)
-	txlog_free(c);
-	const uint32_t pool = cfg->pool_records ? cfg->pool_records : kTxDefPool;
-	const size_t C = (size_t)c->C;
-	bool ok = m.buf.d_st.alloc(C) == hipSuccess && m.buf.d_cnt.alloc(C, true) == hipSuccess;
-	for(auto &sl : c->slot) {
-		auto &b = sl.txl;
-		ok = ok && b.d_hdr.alloc_bytes(sizeof(TxHdr) + (size_t)std::max(pool, kTxMailRecs) * sizeof(TxRec)) == hipSuccess && b.h_mail.alloc(kTxMailBytes, true) == hipSuccess;
-		if(!ok) break;
-		b.d_rec = reinterpret_cast<TxRec *>(b.d_hdr.get() + 1);
-		ok = hipMemset(b.d_hdr, 0, kTxMailBytes) == hipSuccess;
-	}
-	if(!ok) { (void)hipGetLastError(); txlog_free(c); return VDL2HIP_E_NOMEM; }
-	// the log's state from the monitor's, on the front stream: behind every scan queued so far, ahead of the next feed's
-	hipLaunchKernelGGL(k_txlog_init, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->streams.front, (const ActState *)c->act.buf.d_st.get(), m.buf.d_st.get(), (uint32_t)C);
-	if(hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txlog_free(c); return VDL2HIP_E_DEVICE; }
-	m.wait.assign(C, {});
-	m.pool = pool; m.flags = cfg->flags;
-	m.transmissions = m.decoded = m.dropped = m.matched = m.unmatched = 0; m.kernel_ms = 0.0;
-	m.on = true;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_txlog_disable(vdl2hip_ctx *c) {
-	if(!c) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	return txlog_off(c);
-}
-
-int vdl2hip_txlog_info_get(vdl2hip_ctx *c, vdl2hip_txlog_info *info) {
-	if(!c || !c->txl.on || !info || info->struct_size != sizeof(vdl2hip_txlog_info)) return VDL2HIP_E_INVAL;
-	const auto &m = c->txl;
-	memset(info, 0, sizeof *info);
-	info->struct_size = sizeof *info; info->pool_records = m.pool; info->flags = m.flags;
-	info->transmissions = m.transmissions; info->decoded = m.decoded; info->dropped = m.dropped;
-	info->frames_matched = m.matched; info->frames_unmatched = m.unmatched; info->kernel_ms = (float)m.kernel_ms;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_txlog_read(vdl2hip_ctx *c, vdl2hip_tx *recs, size_t cap_recs) {
-	if(!c || !c->txl.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
-	auto &q = c->txl.queue;
-	size_t n = 0;
-	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
-	return (int)n;
-}
-
-// ---- the preamble search (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
-int vdl2hip_txsearch_enable(vdl2hip_ctx *c, const vdl2hip_txsearch_cfg *cfg) {
-	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txsearch_cfg) || cfg->reserved[0] != 0 || cfg->reserved[1] != 0) return VDL2HIP_E_INVAL;
-	if(!c->txl.on || !c->act.on || (cfg->flags & ~VDL2HIP_TXSEARCH_UNDECODED_ONLY)) return VDL2HIP_E_INVAL;
-	if(((uint64_t)c->act.H + 1) * c->act.B > kTxsMaxBack) return VDL2HIP_E_INVAL;
-	const uint64_t piece_cap = txsearch_piece_cap(c, c->txl.pool);
-	if(piece_cap > 0x7fffffffull) return VDL2HIP_E_TOOBIG;
-	OnDevice dev_guard(c);
-	if(c->failed) return VDL2HIP_E_DEVICE;
-	{ int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }      // nothing of an earlier search is in flight any more
-	auto &m = c->txs;
-	txsearch_free(c);
-	const uint32_t pool = c->txl.pool;
-	bool ok = true;
-	for(auto &sl : c->slot) {
-		auto &b = sl.txs;
-		ok = ok && b.d_hdr.alloc_bytes(sizeof(TxsHdr) + (size_t)std::max(pool, kTxsMailRecs) * sizeof(TxsRec)) == hipSuccess && b.d_off.alloc((size_t)pool + 1) == hipSuccess
-			&& b.d_part.alloc((size_t)piece_cap) == hipSuccess && b.h_mail.alloc(kTxsMailBytes, true) == hipSuccess;
-		if(!ok) break;
-		b.d_rec = reinterpret_cast<TxsRec *>(b.d_hdr.get() + 1);
-		ok = hipMemset(b.d_hdr, 0, kTxsMailBytes) == hipSuccess;
-	}
-	if(!ok || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txsearch_free(c); return ok ? VDL2HIP_E_DEVICE : VDL2HIP_E_NOMEM; }
-	m.flags = cfg->flags; m.piece_cap = (uint32_t)piece_cap;
-	m.records = m.samples = m.clipped = 0; m.kernel_ms = 0.0;
-	m.on = true;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_txsearch_disable(vdl2hip_ctx *c) {
-	if(!c) return VDL2HIP_E_INVAL;
-	OnDevice dev_guard(c);
-	if(c->txs.on && !c->failed) { int r = collect_pending(c); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
-	txsearch_free(c);
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_txsearch_info_get(vdl2hip_ctx *c, vdl2hip_txsearch_info *info) {
-	if(!c || !c->txs.on || !info || info->struct_size != sizeof(vdl2hip_txsearch_info)) return VDL2HIP_E_INVAL;
-	const auto &m = c->txs;
-	memset(info, 0, sizeof *info);
-	info->struct_size = sizeof *info; info->flags = m.flags;
-	info->records = m.records; info->samples_searched = m.samples; info->clipped = m.clipped; info->kernel_ms = (float)m.kernel_ms;
-	return VDL2HIP_OK;
-}
-
-int vdl2hip_txsearch_read(vdl2hip_ctx *c, vdl2hip_tx_search *recs, size_t cap_recs) {
-	if(!c || !c->txs.on || (!recs && cap_recs)) return VDL2HIP_E_INVAL;
-	auto &q = c->txs.queue;
-	size_t n = 0;
-	while(!q.empty() && n < cap_recs) { recs[n++] = q.front(); q.pop_front(); }
-	return (int)n;
 }
 
 }  // extern "C"

@@ -422,16 +422,22 @@ def _txlog_info(Lib, ctx) -> dict:
     return {k: getattr(info, k) for k, _ in TxlogInfo._fields_ if k not in ("struct_size", "reserved", "reserved2")}
 
 
-def _txlog_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
-    """vdl2hip_txlog_read() until nothing more comes -> the records as one array of TX_DTYPE (cap_recs: the buffer of one call)"""
-    buf = np.zeros(max(1, cap_recs), dtype=TX_DTYPE)
+def _read_records(Lib, ctx, name: str, dtype, cap_recs: int) -> np.ndarray:
+    """A record tap's read (`name`: vdl2hip_txlog_read, vdl2hip_txsearch_read) until nothing more comes -> the records as one array
+    of `dtype` (cap_recs: the buffer of one call)"""
+    fn = getattr(Lib, name)
+    buf = np.zeros(max(1, cap_recs), dtype=dtype)
     out = []
     while True:
-        n = _err(Lib, Lib.vdl2hip_txlog_read(ctx, buf.ctypes.data, cap_recs), "vdl2hip_txlog_read")
+        n = _err(Lib, fn(ctx, buf.ctypes.data, cap_recs), name)
         if n == 0:
             break
         out.append(buf[:n].copy())
-    return np.concatenate(out) if out else np.zeros(0, dtype=TX_DTYPE)
+    return np.concatenate(out) if out else np.zeros(0, dtype=dtype)
+
+
+def _txlog_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
+    return _read_records(Lib, ctx, "vdl2hip_txlog_read", TX_DTYPE, cap_recs)
 
 
 def _txsearch_enable(Lib, ctx, undecoded_only) -> None:
@@ -446,15 +452,7 @@ def _txsearch_info(Lib, ctx) -> dict:
 
 
 def _txsearch_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
-    """vdl2hip_txsearch_read() until nothing more comes -> the records as one array of TXS_DTYPE (cap_recs: the buffer of one call)"""
-    buf = np.zeros(max(1, cap_recs), dtype=TXS_DTYPE)
-    out = []
-    while True:
-        n = _err(Lib, Lib.vdl2hip_txsearch_read(ctx, buf.ctypes.data, cap_recs), "vdl2hip_txsearch_read")
-        if n == 0:
-            break
-        out.append(buf[:n].copy())
-    return np.concatenate(out) if out else np.zeros(0, dtype=TXS_DTYPE)
+    return _read_records(Lib, ctx, "vdl2hip_txsearch_read", TXS_DTYPE, cap_recs)
 
 
 def live_resources() -> dict:

@@ -32,6 +32,33 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.vdl2hip_abi_version() == 6
 
 
+def test_every_source_of_the_library_is_a_dependency(tmp_path, monkeypatch):
+    """a header, include or source of csrc/ that is newer than the library makes it stale - txsearch.h, once missing from a hand-kept
+    list, among them.  On a stand-in directory with the names of csrc/ and a stand-in library: the tree is not touched."""
+    from dumpvdl2_amd import build
+    names = [f for f in os.listdir(build.CSRC) if f.endswith((".h", ".inc", ".hip"))]
+    assert {"vdl2hip.hip", "txsearch.h", "taps.inc", "hostmem.h", "kernels.h"} <= set(names)
+    csrc, so = tmp_path / "csrc", tmp_path / "libvdl2hip.so"
+    csrc.mkdir()
+    for f in names:
+        (csrc / f).write_text("")
+    so.write_text("")
+    built = os.path.getmtime(os.path.join(ROOT, "include", "vdl2hip.h")) + 1000     # (the public header is a dependency too, where it lies)
+    for f in names:
+        os.utime(csrc / f, (built - 500, built - 500))
+    os.utime(so, (built, built))
+    monkeypatch.setattr(build, "CSRC", str(csrc))
+    monkeypatch.setattr(build, "LIB", str(so))
+    assert not build.needs_build()
+    for f in names:
+        os.utime(csrc / f, (built + 10, built + 10))
+        assert build.needs_build(), f
+        os.utime(csrc / f, (built - 500, built - 500))
+    assert not build.needs_build()
+    so.unlink()
+    assert build.needs_build()
+
+
 def test_struct_layouts_match_header(lib):
     from dumpvdl2_amd import vdl2hip
     # sizes the C compiler gives the structs of the header (checked with a tiny C program)

@@ -47,6 +47,8 @@ def all_taps_on(rx):
     rx.spectrum_enable(1024)
     rx.activity_enable()
     rx.capture_enable()
+    rx.txlog_enable()
+    rx.txsearch_enable()
 
 
 @pytest.mark.parametrize("how", ["standard", "referee off", "resampling"])
@@ -90,11 +92,17 @@ def test_tap_switching_does_not_grow(vh, golden_wav, baseline):
     for _ in range(6):
         settled = feed()
     taps = [
-        ("spectrum", lambda p: rx.spectrum_enable(p), rx.spectrum_disable, [256, 1024]),
-        ("activity", lambda p: rx.activity_enable(bin_samples=p), rx.activity_disable, [105, 210]),
-        ("capture", lambda p: rx.capture_enable(pool_samples=p), rx.capture_disable, [1 << 16, 1 << 18]),
+        ("spectrum", lambda p: rx.spectrum_enable(p), rx.spectrum_disable, [256, 1024], None),
+        ("activity", lambda p: rx.activity_enable(bin_samples=p), rx.activity_disable, [105, 210], None),
+        ("capture", lambda p: rx.capture_enable(pool_samples=p), rx.capture_disable, [1 << 16, 1 << 18], None),
+        # (the log runs beside the activity monitor, which is enabled once more and left on; the search beside the log, likewise)
+        ("log", lambda p: rx.txlog_enable(pool_records=p), rx.txlog_disable, [1024, 4096], rx.activity_enable),
+        ("search", lambda p: rx.txsearch_enable(undecoded_only=p), rx.txsearch_disable, [False, True], rx.txlog_enable),
     ]
-    for name, enable, disable, params in taps:
+    for name, enable, disable, params, first in taps:
+        if first:
+            first()
+            settled = feed()
         enable(params[0])
         on = {params[0]: feed()}
         assert on[params[0]]["device"] > settled["device"], name

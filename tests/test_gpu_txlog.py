@@ -253,6 +253,41 @@ def test_room(vh):
         assert np.array_equal(tight["act"][k], full["act"][k])
 
 
+# ---------------------------------------------------------------- 4b. as many records as come with the header, and one more
+MAIL_N = 1050 * tm.MAIL_BINS + 13
+
+
+@functools.lru_cache(maxsize=2)
+def mail_stream(nrec):
+    """tm.mail_keys(nrec) keyed onto 11 channels: 32 or 33 transmissions that all close within the stream -> (raw, freqs)"""
+    freqs = plan(tm.MAIL_CHANS)
+    return build_stream(freqs, MAIL_N, 41, tm.mail_keys(nrec)), freqs
+
+
+@functools.lru_cache(maxsize=2)
+def mail_run(vh, nrec):
+    """the stream as ONE feed, so that every record closes in that feed: 32 come with the header, 33 are fetched through the staging buffer"""
+    raw, freqs = mail_stream(nrec)
+    return run(vh, raw, freqs, [MAIL_N], 105, 0, max_block_bytes=4 * MAIL_N)
+
+
+@pytest.mark.parametrize("nrec", [tm.MAIL_RECS, tm.MAIL_RECS + 1])
+def test_mail_boundary(vh, nrec):
+    res = mail_run(vh, nrec)
+    print(f"nrec={nrec}: {len(res['per_feed'][0])} records in the feed, dropped {res['info']['dropped']}")
+    assert len(res["per_feed"]) == 1 and len(res["per_feed"][0]) == nrec
+    assert check_model(res, 105, 0, f"mail {nrec}") == nrec
+    assert res["info"]["dropped"] == 0
+    # the staged copy brings what the mail would have: channel by channel the two runs' records are the same bytes wherever the keying
+    # is the same - every channel but the last, whose third transmission only one of the streams has, alone in its bins (the noise is
+    # the same seed's in both)
+    a, b = mail_run(vh, tm.MAIL_RECS)["recs"], mail_run(vh, tm.MAIL_RECS + 1)["recs"]
+    assert b[:tm.MAIL_RECS].tobytes() == a.tobytes()             # (records are ordered by channel: the odd one is the last of all)
+    for c in range(tm.MAIL_CHANS - 1):
+        assert a[a["chan"] == c].tobytes() == b[b["chan"] == c].tobytes() and np.count_nonzero(a["chan"] == c) == 3, c
+    assert np.count_nonzero(a["chan"] == tm.MAIL_CHANS - 1) == 2 and np.count_nonzero(b["chan"] == tm.MAIL_CHANS - 1) == 3
+
+
 # ---------------------------------------------------------------- 5. partial records
 def test_partial(vh):
     raw, freqs, keys = make_stream(2, N, 44, step=200000)

@@ -339,6 +339,22 @@ def test_undecoded_only(vh, golden_wav):
     assert len(res["txs"]) == 9 == res["info"]["records"] and np.all(res["txs"]["frames_ok"] == 0)
 
 
+@pytest.mark.parametrize("nrec", [32, 33])
+def test_mail_boundary(vh, nrec):
+    """the streams of test_gpu_txlog.py's boundary case in one feed: as many search records as come with the header, and one more (the
+    staged copy) - index for index beside the log's, each held to the model"""
+    import test_gpu_txlog as tl
+    raw, freqs = tl.mail_stream(nrec)
+    res = run(vh, raw, freqs, [tl.MAIL_N])
+    tx, txs = res["tx"], res["txs"]
+    print(f"nrec={nrec}: {len(tx)} log records, {len(txs)} search records, {len(res['per_feed'][0])} of them behind the one feed")
+    assert len(res["per_feed"][0]) == nrec == len(txs) == len(tx)
+    assert np.array_equal(tx["chan"], txs["chan"]) and np.array_equal(tx["first_bin"], txs["first_bin"])
+    # (a search record states the transmission's last bin as the last sample of its range: the last sample of that bin, bins of 105)
+    assert np.array_equal(txs["search_last"], 105 * (tx["last_bin"].astype(np.int64) + 1) - 1) and np.all(txs["flags"] == 0)
+    assert check_model(res, label=f"mail {nrec}") == nrec and res["loginfo"]["dropped"] == 0
+
+
 def test_read_one_at_a_time(vh):
     n = 400000
     raw = keyed(n, 7)

@@ -156,6 +156,24 @@ def test_partial_records(lib, H):
                     assert got[0]["peak_power"] == 0 and got[0]["mean_power"] == 0 and got[0]["peak_bin"] == first
 
 
+@pytest.mark.parametrize("nrec", [tm.MAIL_RECS, tm.MAIL_RECS + 1])
+def test_mail_keys_on_a_clean_series(nrec):
+    """the keying of the GPU tests' mailbox boundary (test_gpu_txlog.py, test_gpu_txsearch.py): on a clean series - a keyed bin busy,
+    every other idle - and H = 0 every transmission is a record of its own, and all of them close within the stream"""
+    keys = tm.mail_keys(nrec)
+    total = 0
+    for k in keys:
+        p = np.full(tm.MAIL_BINS, 1e-7, dtype=np.float32)
+        for s, e in k:
+            assert e + 1 < tm.MAIL_BINS
+            p[s:e + 1] = 0.01
+        st = tm.new_state()
+        recs = tm.log(p, 1e-4, 0, st)                            # (the GPU tests' threshold, -40 dBFS)
+        assert [(r["first_bin"], r["last_bin"]) for r in recs] == k and not st["open"]
+        total += len(recs)
+    assert total == nrec and len(keys) == tm.MAIL_CHANS
+
+
 def test_arguments(lib):
     p = np.full(4, 0.5, dtype=np.float32)
     out = np.zeros(4, dtype=np.uint64)

@@ -47,6 +47,22 @@ def log(p, thr, H, state, B=105, k_on=0):
     return out
 
 
+MAIL_RECS = 32                  # hostmem.h, kMailRecs: the records of a feed that come to the host with its header
+MAIL_CHANS, MAIL_BINS = 11, 30
+
+
+def mail_keys(nrec):
+    """Per channel [(first busy bin, last busy bin)] for the mailbox boundary: MAIL_CHANS channels of three short transmissions with 3
+    idle bins between them, all closed within MAIL_BINS bins at H = 0 - 33 records, one more than the mail holds; nrec 32: the last
+    channel has two.  The last channel's third comes when every other channel is idle, so the two streams are the same up to it and
+    whatever the one transmission leaks into its neighbours reaches no record.  (test_txlog_host.py holds this to log() on a clean series.)"""
+    assert nrec in (MAIL_RECS, MAIL_RECS + 1)
+    keys = [[(3, 6), (10, 13), (17, 20)] for _ in range(MAIL_CHANS - 1)] + [[(3, 6), (10, 13), (24, 27)]]
+    if nrec == MAIL_RECS:
+        keys[-1] = keys[-1][:2]
+    return keys
+
+
 def assert_records(got, want, label=""):
     """got: an array of TX_DTYPE (or a list of dicts); want: log()'s records.  Integer fields and peak_power exactly, mean_power to MEAN_RTOL"""
     assert len(got) == len(want), (label, len(got), len(want))
