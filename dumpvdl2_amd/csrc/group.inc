@@ -172,7 +172,7 @@ static int group_feed(vdl2hip_group *g, const void *buf, size_t nbytes, bool wai
 	if(g->failed) return VDL2HIP_E_DEVICE;
 	if(nbytes == 0) return VDL2HIP_OK;
 	if(nbytes > g->in_cap) return VDL2HIP_E_TOOBIG;
-	nbytes -= nbytes % sample_bytes(g->fmt);
+	nbytes -= nbytes % raw_bytes(g->fmt);
 	DeviceGuard guard;
 	{ int r = group_wait_pinned(g); if(r != VDL2HIP_OK) return r; }
 	const int k = (int)(g->feed_no % kSlots), n = g->n;

@@ -15,6 +15,7 @@
 // There is no stored phase stream: atan2 in double (demod.c:232,256) is evaluated where a decision reads a phase - the exact tier
 // of K3, the walker, K5 - and K3's screening tier uses a single-precision phase of its own (vdl2_core.h: ChanView::Phi, phase_fast).
 #pragma once
+#include "rawfmt.h"
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "vdl2_core.h"
@@ -78,26 +79,15 @@ struct RefChan {
 	uint32_t *stats;                       // [0] scans run, [1] requests answered from the list, [2] requests refused (input no longer held), [3] scans with a shortened run-up, [4 + kind] scans by who asked, [7] channels walked again
 };
 
-// CF32 input (VDL2HIP_FMT_CF32: interleaved I, Q as float32, 8 bytes per complex sample): process_buf_short() / process_buf_uchar() do
-// nothing but fill the float array sbuf[] (src/demod.c:349-365) that every later stage reads, so a CF32 sample IS the reference's
-// sbuf[] value - unscaled, unclipped.  This is the one conversion of the format, and every reader of raw input calls it: a negative
-// zero is read as a positive one.  The integer conversions never produce -0; the scan's shortcut for channels that are not mixed
-// (k_ref_scan_multi: q_dphi) multiplies by (sin, cos) = (0, 1) and would turn (+0, -0) into (+0, +0) where the reference leaves it,
-// and atan2 of a silent sample would land on the other side of its branch cut.
-__device__ __forceinline__ float cf32_level(float x) { return x + 0.0f; }
-// S8 input (VDL2HIP_FMT_S8, internal code 3: interleaved I, Q as signed bytes, 2 bytes per complex sample): (float)b / 128.0f, the float
-// process_buf_short() makes of the int16 256 b.  The one conversion of the format, a 16-bit word at a time (defined beside u8_level below)
-__device__ __forceinline__ float2 s8_level(uint32_t w);
-
 // one raw sample as process_buf_short() / process_buf_uchar() convert it (src/demod.c:349-365)
 __device__ __forceinline__ bool ref_raw_sample(const RefChan &r, int64_t s, float &re, float &im) {
 	for(int j = r.npiece - 1; j >= 0; j--) {
 		const RefPiece &pc = r.piece[j];
 		if(s >= pc.s0 && s < pc.s0 + pc.n) {
-			if(r.fmt == 2) { const float2 w = ((const float2 *)pc.p)[s - pc.s0]; re = cf32_level(w.x); im = cf32_level(w.y); }
-			else if(r.fmt == 1) { const uint32_t w = ((const uint32_t *)pc.p)[s - pc.s0]; re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
-			else if(r.fmt == 3) { const float2 v = s8_level(((const uint16_t *)pc.p)[s - pc.s0]); re = v.x; im = v.y; }
-			else { const uint16_t w = ((const uint16_t *)pc.p)[s - pc.s0]; re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)(w >> 8) - 127.5f) / 127.5f; }
+			if(r.fmt == kFmtCF32) raw_ref_sample<kFmtCF32>(pc.p, s - pc.s0, re, im);
+			else if(r.fmt == kFmtS16) raw_ref_sample<kFmtS16>(pc.p, s - pc.s0, re, im);
+			else if(r.fmt == kFmtS8) raw_ref_sample<kFmtS8>(pc.p, s - pc.s0, re, im);
+			else raw_ref_sample<kFmtU8>(pc.p, s - pc.s0, re, im);
 			return true;
 		}
 	}
@@ -116,6 +106,12 @@ typedef __attribute__((address_space(1))) const uint16_t ref_gu16;
 typedef uint32_t ref_v2u __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const ref_v2u ref_gu64;       // a CF32 sample: the bits of I and of Q
 typedef __attribute__((address_space(1))) const v4f ref_gf4;
+// sample i of the raw samples at p as the scans hold it: a 32-bit word w (CF32: two, the bits of I in w and of Q in w2)
+template<int FMT>
+__device__ __forceinline__ void ref_raw_bits(const void *p, int64_t i, uint32_t &w, uint32_t &w2) {
+	if constexpr(FMT == kFmtCF32) { const ref_v2u v = ((ref_gu64 *)p)[i]; w = v.x; w2 = v.y; }
+	else w = ((__attribute__((address_space(1))) const typename RawFmt<FMT>::word *)p)[i];
+}
 __device__ __forceinline__ float ref_lane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 // the list of stretches of a channel made exact: (lo / 256 : 32 bits, length / 256 : 16, launch : 16).
 // WHOSE entries may a kernel believe?  The entry is an agent-scope atomic, the samples behind it are plain stores that may still sit
@@ -232,8 +228,8 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 		#pragma unroll
 		for(int j = 0; j < kRefPieces; j++) {
 			if(j < npiece && s >= ps0[j] && s < ps0[j] + pn[j] && s < s_end) {
-				if(fmt == 2) { const ref_v2u v = ((ref_gu64 *)pp[j])[s - ps0[j]]; w = v.x; w2 = v.y; }
-				else if(fmt == 1) w = ((ref_gu32 *)pp[j])[s - ps0[j]];
+				if(fmt == kFmtCF32) { const ref_v2u v = ((ref_gu64 *)pp[j])[s - ps0[j]]; w = v.x; w2 = v.y; }
+				else if(fmt == kFmtS16) w = ((ref_gu32 *)pp[j])[s - ps0[j]];
 				else w = ((ref_gu16 *)pp[j])[s - ps0[j]];                 // (U8 and S8: a 16-bit word)
 			}
 		}
@@ -262,9 +258,11 @@ __device__ __forceinline__ bool ref_exact_window_dev(const ChanView &v, int64_t 
 		fetch(sb + (int64_t)kRefAhead * blk, w_q[SLOT], w2_q[SLOT], e_q[SLOT]);    // in flight during the next blocks' recursions
 		// ---- this lane's sample: conversion (demod.c:349-365), NCO (:58-72), mixer (:200-203) ----
 		float re, im;
-		if(fmt == 2) { re = cf32_level(__builtin_bit_cast(float, w)); im = cf32_level(__builtin_bit_cast(float, w2)); }
-		else if(fmt == 1) { re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
-		else if(fmt == 3) { const float2 v = s8_level(w); re = v.x; im = v.y; }
+		// (RawFmt<>::ref_level(), written out: called here it swaps the operands of the mixer's add in every kernel that holds this
+		// scan - profiles/rawfmt_ab.txt, 1c.  k_ref_scan_multi's produce() calls it; tests/test_rawfmt_host.py holds both to numpy's)
+		if(fmt == kFmtCF32) { re = cf32_level(__builtin_bit_cast(float, w)); im = cf32_level(__builtin_bit_cast(float, w2)); }
+		else if(fmt == kFmtS16) { re = (float)(int16_t)(w & 0xffff) / 32768.0f; im = (float)(int16_t)(w >> 16) / 32768.0f; }
+		else if(fmt == kFmtS8) { const float2 v = s8_level(w); re = v.x; im = v.y; }
 		else { re = ((float)(w & 0xff) - 127.5f) / 127.5f; im = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
 		if(mix) {
 			const uint32_t phi = ((uint32_t)(sb + lane) * dphi) & 0xffffffu;
@@ -431,32 +429,21 @@ struct K1Args {
 	uint32_t cap, mask, nseg_cap;
 };
 
-// (CF32: the float32 builds of the channeliser - they see no other format, and the other builds never see this one: vdl2hip.hip, launch_chanfir)
-// (S8, internal code 3: 0 - a build that never sees it (the s16 and u8 builds where S8 has a build of its own: they stay the code they
-// were), 1 - told from a.fmt at run time, 2 - the S8 build, which sees nothing else)
-template<bool CF32 = false, int S8 = 1>
+// one sample of the feed's logical stream (the carry, then the block), whatever its place: the generic staging path
+template<int FMT>
+__device__ __forceinline__ void load_sample_as(const K1Args &a, int64_t s, float &re, float &im) {
+	typedef typename RawFmt<FMT>::word W;
+	const W *p = (s < (int64_t)a.ncarry) ? (const W *)a.carry + s : (const W *)a.in + (s - a.ncarry);
+	raw_ref_sample<FMT>(p, 0, re, im);
+}
+// MAY: the formats this build of the channeliser can meet (k_chanfir: kMay) - a build that meets one has no branch here
+template<unsigned MAY = kFmtAny>
 __device__ __forceinline__ void load_sample(const K1Args &a, int64_t s, float &re, float &im) {
-	if(!CF32 && (S8 == 2 || (S8 == 1 && a.fmt == 3))) {   // S8: (float)b / 128.0f (s8_level)
-		const uint16_t *p = (s < (int64_t)a.ncarry) ? (const uint16_t *)a.carry + s : (const uint16_t *)a.in + (s - a.ncarry);
-		const float2 v = s8_level(*p);
-		re = v.x;
-		im = v.y;
-	} else if(CF32) {         // the value itself (cf32_level)
-		const float2 *p = (s < (int64_t)a.ncarry) ? (const float2 *)a.carry + s : (const float2 *)a.in + (s - a.ncarry);
-		const float2 w = *p;
-		re = cf32_level(w.x);
-		im = cf32_level(w.y);
-	} else if(a.fmt == 1) {   // S16_LE: (float)v / 32768.0f  (demod.c:362-363)
-		const uint32_t *p = (s < (int64_t)a.ncarry) ? (const uint32_t *)a.carry + s : (const uint32_t *)a.in + (s - a.ncarry);
-		uint32_t w = *p;
-		re = (float)(int16_t)(w & 0xffff) / 32768.0f;
-		im = (float)(int16_t)(w >> 16) / 32768.0f;
-	} else {           // U8: (i - 127.5f) / 127.5f     (demod.c:349-354)
-		const uint16_t *p = (s < (int64_t)a.ncarry) ? (const uint16_t *)a.carry + s : (const uint16_t *)a.in + (s - a.ncarry);
-		uint16_t w = *p;
-		re = ((float)(w & 0xff) - 127.5f) / 127.5f;
-		im = ((float)(w >> 8) - 127.5f) / 127.5f;
-	}
+	constexpr bool one = (MAY & (MAY - 1)) == 0;
+	if((MAY & fmt_bit(kFmtS8)) && (one || a.fmt == kFmtS8)) load_sample_as<kFmtS8>(a, s, re, im);
+	else if((MAY & fmt_bit(kFmtCF32)) && (one || a.fmt == kFmtCF32)) load_sample_as<kFmtCF32>(a, s, re, im);
+	else if((MAY & fmt_bit(kFmtS16)) && a.fmt == kFmtS16) load_sample_as<kFmtS16>(a, s, re, im);
+	else load_sample_as<kFmtU8>(a, s, re, im);
 }
 
 // Cross-lane moves on the VALU's data-parallel-primitive path (GFX9 DPP controls; checked on the device by
@@ -527,23 +514,8 @@ __device__ unsigned long long vdl2_k1_prof[64][16];
 #define K1_END() do {} while(0)
 #endif
 
-// (i - 127.5f) / 127.5f of an unsigned byte (demod.c:349-354) without the division: d = i - 127.5 is exact, q = d * fl(1 / 127.5) is within an
-// ulp, one Newton step on the residual d - 127.5 q makes it the correctly rounded quotient - for all 256 values (checked on the device
-// against the division: tests/test_gpu_parity.py::test_uint8_conversion_without_the_division)
-__device__ __forceinline__ float u8_level(uint32_t i) {
-	const float d = (float)i - 127.5f, r = 1.0f / 127.5f;
-	const float q = d * r;
-	return __builtin_fmaf(__builtin_fmaf(-127.5f, q, d), r, q);
-}
+// the conversions of rawfmt.h on the device, beside the plain way (tests/test_gpu_parity.py, tests/test_gpu_s8.py)
 __global__ void k_u8_level_probe(float *out) { const uint32_t i = threadIdx.x; out[i] = u8_level(i); out[256 + i] = ((float)i - 127.5f) / 127.5f; }
-// (float)b / 128.0f of the two signed bytes of a 16-bit word (I in the low byte): one XOR per word turns both bytes into u = b + 128, an
-// unsigned byte converts with a byte-select v_cvt_f32_ubyte*, and fma(u, 2^-7, -1) is exact (u 2^-7 is, and so is the difference: a
-// multiple of 2^-7 in [-1, 1)) - two VALU operations per component where u8_level needs four, and never a negative zero (u = 128 gives
-// 1 - 1 = +0).  Checked on the device for all 256 values: tests/test_gpu_s8.py::test_conversion_is_exact
-__device__ __forceinline__ float2 s8_level(uint32_t w) {
-	const uint32_t u = w ^ 0x8080u;
-	return make_float2(__builtin_fmaf((float)(u & 0xffu), 0.0078125f, -1.0f), __builtin_fmaf((float)((u >> 8) & 0xffu), 0.0078125f, -1.0f));
-}
 // (even patterns through the low byte of the word, odd ones through the high byte)
 __global__ void k_s8_level_probe(float *out) { const uint32_t i = threadIdx.x; out[i] = i & 1 ? s8_level(i << 8).y : s8_level(i).x; out[256 + i] = (float)(int8_t)i / 128.0f; }
 
@@ -590,23 +562,34 @@ __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, u
 	}
 }
 
-// U8: the build for unsigned-byte input (the reference's default for --iq-file and what an RTL-SDR delivers): its tiles are fetched a tile
-// ahead and converted without per-sample range checks or divisions, as the s16 tiles of the other build are (round 6c: the generic
-// staging path cost a 256-channel receiver 18 % of its channeliser: 4.46 against 3.77 ms per 16 s).  Only instantiated where the tile
-// prefetch is (kPrefetch below); U8 = false is the code as it was.
-// CF32: the builds for complex-float32 input, beside the ones above - a build of its own for every shape, so that the other formats'
-// builds are the code they were, register for register.  Where the tile prefetch exists its tiles too are fetched a tile ahead and staged
-// without per-sample range checks - and without arithmetic but cf32_level(): the staging is data movement; elsewhere it is the generic
-// staging path (load_sample).  A sample is two words, so at oversample 20 the look-ahead is 20 registers where the s16 build's is 10, and
-// that build already sits at the 128-register cap of four resident workgroups.  Measured at 256 channels x 16 s (profiles/cf32_rate.txt;
-// the s16 build: 3.78 ms per launch): the whole tile ahead under the same cap, at the price of 37 spilled registers (the s16 build: 28), 3.89 ms; the
-// first half of the tile ahead and the second asked for at the top of the staging (3 spills) 3.97; the generic path 4.02; the whole
-// tile ahead with three resident workgroups (148 registers, no spills) 4.08.  Hence the first, which is also the other builds' scheme.
-// S8: the build for signed-byte input (VDL2HIP_FMT_S8: a HackRF's format, the 8-bit wire format of wider radios), where the U8 build is and
-// by its scheme - 16-bit words a tile ahead in pre[], staged without range checks - with s8_level() for u8_level(): a flag beside U8, so
-// that every other instantiation is the code it was.  Everywhere else S8 goes through the generic staging path (load_sample).
-// After the staging the code is the shared code: the tile is float2 whatever the format.
-template<int OS, int R, int CR, bool U8 = false, bool CF32 = false, bool S8 = false>
+// FMT: the one raw format (rawfmt.h) this build stages without per-sample range checks; a tile of any other format, or one that
+// reaches into the carry or past the block, takes the generic staging path (load_sample).  After the staging the code is the
+// shared code: the tile is float2 whatever the format.
+//   S16   every shape.  Where the tile prefetch exists (kPrefetch below) its tiles are fetched a tile ahead.
+//   U8    (the reference's default for --iq-file and what an RTL-SDR delivers) only where the tile prefetch is: fetched a tile ahead
+//         and converted without range checks or divisions (u8_level), as the s16 tiles are (round 6c: the generic staging path cost
+//         a 256-channel receiver 18 % of its channeliser: 4.46 against 3.77 ms per 16 s).
+//   S8    (VDL2HIP_FMT_S8: a HackRF's format, the 8-bit wire format of wider radios) where the U8 build is and by its scheme - 16-bit
+//         words a tile ahead, staged without range checks - with s8_level() for u8_level().  Everywhere else U8 and S8 go through the
+//         S16 build's generic staging path.
+//   CF32  a build for every shape (the float32 builds see no other format, and the other builds never see this one).  Where the tile
+//         prefetch exists its tiles too are fetched a tile ahead and staged without range checks - and without arithmetic but
+//         cf32_level(): the staging is data movement; elsewhere it is the generic staging path.  A sample is two words, so at
+//         oversample 20 the look-ahead is 20 registers where the s16 build's is 10, and that build already sits at the 128-register
+//         cap of four resident workgroups.  Measured at 256 channels x 16 s (profiles/cf32_rate.txt; the s16 build: 3.78 ms per
+//         launch): the whole tile ahead under the same cap, at the price of 37 spilled registers (the s16 build: 28), 3.89 ms; the
+//         first half of the tile ahead and the second asked for at the top of the staging (3 spills) 3.97; the generic path 4.02; the
+//         whole tile ahead with three resident workgroups (148 registers, no spills) 4.08.  Hence the first, the other builds' scheme.
+// The look-ahead (pre[], and pre2[] for the two-word samples), its fetch loops and the three prefetch staging branches are written
+// out per word size: merged into one over RawFmt<FMT>::word they compute the same with other instructions (profiles/rawfmt_ab.txt,
+// 1b).
+// has_fast_build() is that rule, for the kernel's assert and for the launcher (vdl2hip.hip, launch_chanfir): a format without a build
+// of its own for a shape goes to the shape's S16 build.
+// The raw samples of a tile are fetched into registers one tile ahead of their use only where four channels per wave leave that
+// room and the tile is a whole number of at most ten 256-sample rows (see kPrefetch in the kernel for what it buys and costs)
+constexpr bool k1_prefetch(int OS, int R, int CR) { return OS != 0 && CR >= 4 && (64 * R * OS + 255) / 256 <= 10 && (64 * R * OS) % 256 == 0; }
+constexpr bool has_fast_build(int FMT, int OS, int R, int CR) { return FMT == kFmtS16 || FMT == kFmtCF32 || k1_prefetch(OS, R, CR); }
+template<int OS, int R, int CR, int FMT = kFmtS16>
 __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MIN_BLOCKS)) void k_chanfir(K1Args a) {
 	static_assert(64 * R == kFixW || R == 1, "the fused fix-up assumes the fix window is the segment's first tile");
 	static_assert(R >= 1 && R <= 2, "the run's outputs are held in two register pairs");
@@ -641,14 +624,13 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 	// staging never sits between two tiles: 6.8 % of K1 at 256 channels, 8.3 % at 32 (profiles/r03_k1_tile_prefetch.txt).  Costs ten
 	// registers (114 -> 128, a few loop-invariant values spilled outside the loops): only where four channels per wave leave that room
 	// and the tile is a whole number of 256-sample rows.
-	constexpr bool kPrefetch = OS != 0 && CR >= 4 && (64 * R * OS + 255) / 256 <= 10 && (64 * R * OS) % 256 == 0;
-	static_assert(!U8 || kPrefetch, "the unsigned-byte build exists where the tile prefetch does");
-	static_assert(!CF32 || !U8, "one format per build");
-	static_assert(!S8 || (kPrefetch && !U8 && !CF32), "the signed-byte build exists where the unsigned-byte build does, one format per build");
-	constexpr bool kByte = U8 || S8;                          // two bytes per sample: 16-bit words in pre[]
-	constexpr int kFmt = CF32 ? 2 : S8 ? 3 : U8 ? 0 : 1;      // the sample format this build stages without range checks
-	// (S8 reaches a build of oversample 20 or 10 with the tile prefetch only as its own: vdl2hip.hip, launch_chanfir)
-	constexpr int kLoadS8 = S8 ? 2 : (kPrefetch && (OS == 20 || OS == 10)) ? 0 : 1;
+	constexpr bool kPrefetch = k1_prefetch(OS, R, CR);
+	static_assert(has_fast_build(FMT, OS, R, CR), "a byte format has a build of its own only where the tile prefetch is");
+	constexpr bool CF32 = FMT == kFmtCF32, kByte = raw_bytes(FMT) == 2;      // (kByte: 16-bit words in pre[])
+	// The formats the generic staging path of this build can meet.  The float32 and the signed-byte build see nothing else; S8 reaches
+	// another build only where it has no build of its own (vdl2hip.hip, launch_chanfir) - the S16 build at oversample 20 or 10
+	// with four channels per wave never sees it and does not contain that branch: it stays the code it was before S8 existed
+	constexpr unsigned kMay = (FMT == kFmtCF32 || FMT == kFmtS8) ? fmt_bit(FMT) : fmt_bit(kFmtU8) | fmt_bit(kFmtS16) | (has_fast_build(kFmtS8, OS, R, CR) ? 0u : fmt_bit(kFmtS8));
 	constexpr int kPre = kPrefetch ? (64 * R * OS) / 256 : 1;
 	constexpr bool kPipeGather = kPrefetch;
 	uint32_t pre[kPre]; bool have_pre = false;
@@ -659,7 +641,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 	for(int k = 0; k < (CF32 ? kPre : 1); k++) pre2[k] = make_float2(0.f, 0.f);
 	if(kPrefetch) {
 		const int64_t s0 = (int64_t)seg * a.tiles * (64 * R * (OS ? OS : 1));      // first sample of the segment's first tile
-		have_pre = a.fmt == kFmt && s0 >= (int64_t)a.ncarry && s0 + 64 * R * (OS ? OS : 1) <= (int64_t)a.nlogical && (int64_t)seg * a.tiles * (64 * R) < a.D;
+		have_pre = a.fmt == FMT && s0 >= (int64_t)a.ncarry && s0 + 64 * R * (OS ? OS : 1) <= (int64_t)a.nlogical && (int64_t)seg * a.tiles * (64 * R) < a.D;
 		if(have_pre) {
 			if constexpr(CF32) {
 				const float2 *sn = (const float2 *)a.in + (s0 - a.ncarry);
@@ -719,7 +701,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		K1_MARK(ts ? 4 : 0);                                     // 0: prologue (tables, first prefetch); 4: scan, outputs, carry of the previous tile
 		if(ts) __syncthreads();                                  // everyone is done with the previous tile
 		K1_MARK(5);                                              // 5: waiting for the workgroup's other waves before the tile is overwritten
-		const bool fast_now = a.fmt == kFmt && sbase >= (int64_t)a.ncarry && sbase + tile_n <= (int64_t)a.nlogical;
+		const bool fast_now = a.fmt == FMT && sbase >= (int64_t)a.ncarry && sbase + tile_n <= (int64_t)a.nlogical;
 		if(CF32 && kPrefetch && fast_now) {
 			// (the float32 build: the same, eight bytes per sample and nothing to convert)
 			const float2 *src = (const float2 *)a.in + (sbase - a.ncarry);
@@ -728,7 +710,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				const int t = tid + 256 * k;
 				const float2 w = have_pre ? pre2[CF32 ? k : 0] : src[t];
 				const int l = t / run, m = t - l * run;
-				tile[m * 65 + l] = make_float2(cf32_level(w.x), cf32_level(w.y));
+				tile[m * 65 + l] = RawFmt<kFmtCF32>::level(w);
 			}
 			const int64_t snext = sbase + tile_n;
 			have_pre = ts + 1 < a.tiles && (tix + 1) * L < a.D && snext + tile_n <= (int64_t)a.nlogical;
@@ -745,8 +727,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				const int t = tid + 256 * k;
 				const uint32_t w = have_pre ? pre[k] : (uint32_t)src[t];
 				const int l = t / run, m = t - l * run;
-				if constexpr(S8) tile[m * 65 + l] = s8_level(w);
-				else tile[m * 65 + l] = make_float2(u8_level(w & 0xffu), u8_level((w >> 8) & 0xffu));
+				tile[m * 65 + l] = RawFmt<kByte ? FMT : kFmtU8>::level(w);
 			}
 			const int64_t snext = sbase + tile_n;
 			have_pre = ts + 1 < a.tiles && (tix + 1) * L < a.D && snext + tile_n <= (int64_t)a.nlogical;
@@ -770,7 +751,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 				const int t = tid + 256 * k;
 				const uint32_t w = pre[k];
 				const int l = t / run, m = t - l * run;
-				tile[m * 65 + l] = make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f);
+				tile[m * 65 + l] = RawFmt<kFmtS16>::level(w);
 			}
 			const int64_t snext = sbase + tile_n;
 			have_pre = ts + 1 < a.tiles && (tix + 1) * L < a.D && snext + tile_n <= (int64_t)a.nlogical;
@@ -785,7 +766,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 			for(int t = tid; t < tile_n; t += 256) {
 				const uint32_t w = src[t];
 				const int l = t / run, m = t - l * run;
-				tile[m * 65 + l] = make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f);
+				tile[m * 65 + l] = RawFmt<kFmtS16>::level(w);
 			}
 		} else {
 			// (the tile's first sample is made opaque: the compiler otherwise carries this path's four load addresses from tile to tile,
@@ -795,7 +776,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 			for(int t = tid; t < tile_n; t += 256) {
 				const int64_t sidx = sb + t;
 				float re = 0.f, im = 0.f;
-				if(sidx < (int64_t)a.nlogical) load_sample<CF32, kLoadS8>(a, sidx, re, im);
+				if(sidx < (int64_t)a.nlogical) load_sample<kMay>(a, sidx, re, im);
 				const int l = t / run, m = t - l * run;
 				tile[m * 65 + l] = make_float2(re, im);
 			}
@@ -1040,7 +1021,7 @@ __global__ __launch_bounds__(256, (CR >= 4 ? VDL2_K1_MIN_BLOCKS_CR4 : VDL2_K1_MI
 		for(int t = tid; t < tile_n; t += 256) {
 			const int64_t sidx = sbase + t;
 			float re = 0.f, im = 0.f;
-			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample<CF32, kLoadS8>(a, sidx, re, im);
+			if(sidx >= 0 && sidx < (int64_t)a.nlogical) load_sample<kMay>(a, sidx, re, im);
 			const int l = t / run, m = t - l * run;
 			tile[m * 65 + l] = make_float2(re, im);
 		}
@@ -1160,20 +1141,20 @@ __global__ __launch_bounds__(256) void k_fixup(K2Args a) {
 }
 
 // keep the input samples that did not fill a whole decimation block (process_samples()' cnt, demod.c:322)
+template<int FMT>
+__device__ __forceinline__ void carry_word(const K1Args &a, int64_t s, void *carry_out, uint32_t i) {
+	typedef typename RawFmt<FMT>::word W;
+	const W *p = (s < (int64_t)a.ncarry) ? (const W *)a.carry + s : (const W *)a.in + (s - a.ncarry);
+	((W *)carry_out)[i] = *p;
+}
 __global__ void k_carry(K1Args a, void *carry_out, uint32_t nrem) {
 	const uint32_t i = threadIdx.x;
 	if(i >= nrem) return;
 	const int64_t s = (int64_t)(a.nlogical - nrem) + i;
-	if(a.fmt == 2) {
-		const uint2 *p = (s < (int64_t)a.ncarry) ? (const uint2 *)a.carry + s : (const uint2 *)a.in + (s - a.ncarry);
-		((uint2 *)carry_out)[i] = *p;                                  // (the bits as they are: every reader converts)
-	} else if(a.fmt == 1) {
-		const uint32_t *p = (s < (int64_t)a.ncarry) ? (const uint32_t *)a.carry + s : (const uint32_t *)a.in + (s - a.ncarry);
-		((uint32_t *)carry_out)[i] = *p;
-	} else {                                                           // (U8 and S8: two bytes)
-		const uint16_t *p = (s < (int64_t)a.ncarry) ? (const uint16_t *)a.carry + s : (const uint16_t *)a.in + (s - a.ncarry);
-		((uint16_t *)carry_out)[i] = *p;
-	}
+	// (the bits as they are: every reader converts; U8 and S8: two bytes)
+	if(a.fmt == kFmtCF32) carry_word<kFmtCF32>(a, s, carry_out, i);
+	else if(a.fmt == kFmtS16) carry_word<kFmtS16>(a, s, carry_out, i);
+	else carry_word<kFmtU8>(a, s, carry_out, i);
 }
 
 // the per-feed counters of the output control block start at zero - the record and octet counters behind the shares the burst
@@ -2070,7 +2051,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		constexpr int PF = 4;
 		// (a CF32 sample is two words - the bits of I in wq, of Q in wq2; the other formats leave wq2 alone and it costs them nothing)
 		uint32_t wq[PF][NQ], wq2[PF][NQ];
-		constexpr int SB = FMT == 2 ? 8 : FMT == 1 ? 4 : 2;           // bytes per raw sample (U8 and S8: 2)
+		constexpr int SB = raw_bytes(FMT);
 		#pragma unroll
 		for(int q = 0; q < NQ; q++) {
 			const int r = pidx + q * kScanProd;
@@ -2097,9 +2078,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 		};
 		// sample p of request q out of the stretch it lies in
 		auto raw = [&](int q, uint32_t p, uint32_t &w, uint32_t &w2) {
-			const uint8_t *at = q_ptr[q] + (size_t)p * SB;
-			if constexpr(FMT == 2) { const ref_v2u v = *(ref_gu64 *)at; w = v.x; w2 = v.y; }
-			else w = FMT == 1 ? *(ref_gu32 *)at : (uint32_t)*(ref_gu16 *)at;
+			ref_raw_bits<FMT>(q_ptr[q] + (size_t)p * SB, 0, w, w2);
 		};
 		// the raw sample of request q and block b for this lane (0 past the request's end)
 		auto fetch = [&](int q, uint32_t b, uint32_t &w2) -> uint32_t {
@@ -2141,11 +2120,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void k_ref_scan_multi(RefChan *rp,
 			float re[NQ], im[NQ];
 			#pragma unroll
 			for(int q = 0; q < NQ; q++) {
-				const uint32_t w = wc[q];
-				if(FMT == 2) { re[q] = cf32_level(__builtin_bit_cast(float, w)); im[q] = cf32_level(__builtin_bit_cast(float, wc2[q])); }
-				else if(FMT == 1) { re[q] = (float)(int16_t)(w & 0xffff) / 32768.0f; im[q] = (float)(int16_t)(w >> 16) / 32768.0f; }
-				else if(FMT == 3) { const float2 v = s8_level(w); re[q] = v.x; im[q] = v.y; }
-				else { re[q] = ((float)(w & 0xff) - 127.5f) / 127.5f; im[q] = ((float)((w >> 8) & 0xff) - 127.5f) / 127.5f; }
+				RawFmt<FMT>::ref_level(wc[q], wc2[q], re[q], im[q]);
 				const float F = (float)(phq[q] & 0xffffu);
 				const float sn = eq[q].x + eq[q].z * F, cs = eq[q].y + eq[q].w * F;
 				const float mr = re[q] * cs - im[q] * sn, mi = im[q] * cs + re[q] * sn;

@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "rawfmt.h"
 
 namespace vdl2 {
 
@@ -38,26 +39,13 @@ struct K0Args {
 	uint32_t nin, nout, L, M, T, span_cap;
 };
 
-// U8: the correctly rounded (b - 127.5f) / 127.5f without the division, as the channeliser's u8 build converts (kernels.h)
-__device__ __forceinline__ float res_u8_level(uint32_t i) {
-	const float d = (float)i - 127.5f, r = 1.0f / 127.5f;
-	const float q = d * r;
-	return __builtin_fmaf(__builtin_fmaf(-127.5f, q, d), r, q);
-}
-
-// S8 (FMT 3): (float)b / 128.0f of both bytes of a word, the channeliser's own conversion (kernels.h, included before this file)
-__device__ __forceinline__ float2 s8_level(uint32_t w);
-
-// sample `rel` of the stream relative to the block's first: the tail before it, the block, nothing after it
+// sample `rel` of the stream relative to the block's first: the tail before it, the block (the format's conversion: rawfmt.h),
+// nothing after it
 template<int FMT>
 __device__ __forceinline__ float2 res_sample(const K0Args &a, int64_t rel) {
 	if(rel < 0) return rel >= -(int64_t)(a.T - 1) ? a.tail_in[rel + (int64_t)(a.T - 1)] : make_float2(0.f, 0.f);
 	if(rel >= (int64_t)a.nin) return make_float2(0.f, 0.f);
-	if(FMT == 2) { const float2 w = ((const float2 *)a.in)[rel]; return make_float2(w.x + 0.0f, w.y + 0.0f); }      // cf32_level
-	if(FMT == 1) { const uint32_t w = ((const uint32_t *)a.in)[rel]; return make_float2((float)(int16_t)(w & 0xffff) / 32768.0f, (float)(int16_t)(w >> 16) / 32768.0f); }
-	const uint32_t w = ((const uint16_t *)a.in)[rel];
-	if(FMT == 3) return s8_level(w);
-	return make_float2(res_u8_level(w & 0xff), res_u8_level(w >> 8));
+	return RawFmt<FMT>::level(((const typename RawFmt<FMT>::word *)a.in)[rel]);
 }
 
 template<int FMT, bool TAPS_LDS>

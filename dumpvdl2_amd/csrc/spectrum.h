@@ -77,19 +77,7 @@ template<int FMT>
 __device__ __forceinline__ float2 spec_sample(const SpecArgs &a, int64_t rel) {
 	if(rel < 0) { const int64_t i = rel + (int64_t)a.ncarry; return i >= 0 ? a.carry_in[i] : make_float2(0.f, 0.f); }
 	if(rel >= (int64_t)a.nin) return make_float2(0.f, 0.f);                  // (never: the host lists complete segments only)
-	if(FMT == 2) { const float2 v = ((const float2 *)a.in)[rel]; return make_float2(v.x + 0.0f, v.y + 0.0f); }
-	if(FMT == 1) { const uint32_t v = ((const uint32_t *)a.in)[rel]; return make_float2((float)(int16_t)(v & 0xffff) / 32768.0f, (float)(int16_t)(v >> 16) / 32768.0f); }
-	const uint32_t v = ((const uint16_t *)a.in)[rel];
-	if(FMT == 3) return s8_level(v);
-	return make_float2(res_u8_level(v & 0xff), res_u8_level(v >> 8));
-}
-// a component at the rail, stated on the float value (vdl2hip.h)
-template<int FMT>
-__device__ __forceinline__ bool spec_at_rail(float v) {
-	if(FMT == 2) return __builtin_fabsf(v) >= 1.0f;                          // (false for a NaN)
-	if(FMT == 1) return v == -1.0f || v == 32767.0f / 32768.0f;
-	if(FMT == 3) return v == -1.0f || v == 127.0f / 128.0f;                  // (bytes -128 and 127)
-	return __builtin_fabsf(v) == 1.0f;
+	return RawFmt<FMT>::level(((const typename RawFmt<FMT>::word *)a.in)[rel]);
 }
 
 // PER = N / T: the samples (and bins) a lane holds - 1 at N = 64, 4 from 256 to 1024, 16 at 4096: a build per value, so that the
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) 
 				const float2 v = spec_sample<FMT>(a, rel + (int64_t)i);
 				sp += (double)v.x * (double)v.x + (double)v.y * (double)v.y; si += (double)v.x; sq += (double)v.y;
 				peak = __builtin_fmaxf(peak, __builtin_fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)));
-				nclip += (spec_at_rail<FMT>(v.x) || spec_at_rail<FMT>(v.y)) ? 1u : 0u;
+				nclip += (RawFmt<FMT>::at_rail(v.x) || RawFmt<FMT>::at_rail(v.y)) ? 1u : 0u;       // (at the converter's rail, stated on the float value: vdl2hip.h)
 				const float wn = a.w[i];
 				bufa[spec_pad(i)] = make_float2(v.x * wn, v.y * wn);
 			}

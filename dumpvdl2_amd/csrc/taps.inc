@@ -33,7 +33,7 @@ static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hi
 }
 static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	auto &m = c->mon;
-	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
+	const uint64_t nin = nbytes / raw_bytes(c->in_fmt);
 	if(nin == 0) return VDL2HIP_OK;
 	if(nin >= (1ull << 32)) return VDL2HIP_E_TOOBIG;
 	const uint64_t N = m.nfft, pos0 = m.pos, pos1 = pos0 + nin;
@@ -55,10 +55,7 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
 	KernelTimes &t = sl.mon_t;
 	t.arm(c->profiling >= 2);
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_spectrum<2>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_spectrum<1>(c, a, grid, t.e(0), t.e(1));
-	else if(c->in_fmt == kFmtS8) launch_spectrum<3>(c, a, grid, t.e(0), t.e(1));
-	else launch_spectrum<0>(c, a, grid, t.e(0), t.e(1));
+	with_fmt(c->in_fmt, [&](auto F) { launch_spectrum<F()>(c, a, grid, t.e(0), t.e(1)); });
 	if(nseg) {
 		const uint32_t W = m.nfft + kSpecLevels;
 		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), t.e(3), 0,

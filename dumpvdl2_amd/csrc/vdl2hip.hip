@@ -292,18 +292,17 @@ struct vdl2hip_ctx {
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) { \
 	fprintf(stderr, "vdl2hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return VDL2HIP_E_DEVICE; } } while(0)
 
-// The format inside the library (vdl2hip_ctx.fmt / in_fmt, K1Args.fmt, RefChan.fmt, the kernels' template FMT) is a small code: the
-// public value for U8, S16LE and CF32 (0, 1, 2), and 3 for VDL2HIP_FMT_S8, whose public value is 4 (the public 3 is unassigned and
-// refused).  This is the one place that maps one to the other; -1: not a format.
-constexpr int kFmtS8 = 3;
+// The format inside the library is a small code (rawfmt.h); this is the one place that maps a public value to it (the public 3 is
+// unassigned and refused); -1: not a format.
 static int fmt_code(uint32_t sample_fmt) {
 	switch(sample_fmt) {
-		case VDL2HIP_FMT_U8: case VDL2HIP_FMT_S16LE: case VDL2HIP_FMT_CF32: return (int)sample_fmt;
+		case VDL2HIP_FMT_U8: return kFmtU8;
+		case VDL2HIP_FMT_S16LE: return kFmtS16;
+		case VDL2HIP_FMT_CF32: return kFmtCF32;
 		case VDL2HIP_FMT_S8: return kFmtS8;
 		default: return -1;
 	}
 }
-static size_t sample_bytes(int fmt) { return fmt == VDL2HIP_FMT_CF32 ? 8 : fmt == VDL2HIP_FMT_S16LE ? 4 : 2; }   // (of a format's code; U8 and S8: 2)
 
 // Every entry point works on the context's own device whatever the calling thread's current device is (a process may hold
 // receivers on several GPUs), and leaves the thread's device as it found it.
@@ -327,32 +326,25 @@ static void launch_chanfir(vdl2hip_ctx *c, const K1Args &a, int cr, size_t lds, 
 	dim3 grid((unsigned)(nseg8 * b.gy)), block(256);
 	// e0/e1 (profiling only, else null): the runtime stamps them with the kernel's own start and stop, so the roofline figure is
 	// the kernel's duration and not the time the launch spent queued behind other streams' work
-	// (float32 input: builds of its own, so that the integer formats' builds stay the code they were; with four channels per wavefront at
-	// oversample 20 and 10 the one that fetches its tiles ahead and stages them as they are)
-	if(c->fmt == VDL2HIP_FMT_CF32) {
+	// a format that has no build of its own for this shape goes to the shape's S16 build (kernels.h: has_fast_build)
+	with_fmt(c->fmt, [&](auto F) {
+		auto go = [&](auto CR) {
+			constexpr int B = has_fast_build(F(), OS, R, CR()) ? F() : kFmtS16;
+			hipExtLaunchKernelGGL((k_chanfir<OS, R, CR(), B>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b);
+		};
 		switch(cr) {
-			case 4: hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
-			case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
-			default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
+			case 4: go(std::integral_constant<int, 4>{}); break;
+			case 2: go(std::integral_constant<int, 2>{}); break;
+			default: go(std::integral_constant<int, 1>{}); break;
 		}
-		return;
-	}
-	switch(cr) {
-		case 4:
-			// (unsigned-byte input where the tile prefetch exists: the build that fetches and converts its tiles the way the s16 build does)
-			if constexpr(OS == 20 || OS == 10) { if(c->fmt == VDL2HIP_FMT_U8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break; } }
-			// (signed-byte input: the same, with a build of its own; everywhere else it takes the generic staging path of the builds below)
-			if constexpr(OS == 20 || OS == 10) { if(c->fmt == kFmtS8) { hipExtLaunchKernelGGL((k_chanfir<OS, R, 4, false, false, true>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break; } }
-			hipExtLaunchKernelGGL((k_chanfir<OS, R, 4>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
-		case 2: hipExtLaunchKernelGGL((k_chanfir<OS, R, 2>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
-		default: hipExtLaunchKernelGGL((k_chanfir<OS, R, 1>), grid, block, (uint32_t)lds, c->streams.front, e0, e1, 0, b); break;
-	}
+	});
 }
 
-// The front's picks among the builds of its kernel templates (channeliser, exact sync tier, resampler).  They stand here, ahead of
-// taps.inc, for ONE reason: the compiler emits the builds of kernel templates in the order the host code first names them, and the
-// input monitor's k_spectrum, named in taps.inc, must come out behind these as it always did - the device assembly stays the same
-// file, diffable against any earlier build.  Nothing else depends on the three launchers; the order of the names inside them counts too.
+// The front's picks among the builds of its kernel templates (channeliser, exact sync tier, resampler).  The compiler emits the
+// builds of kernel templates in the order the host code first names them; with the launchers here, ahead of taps.inc, the input
+// monitor's k_spectrum comes out behind the front's kernels as it always did.  Within k_chanfir the order is with_fmt's order of
+// formats, which is not that of builds before rawfmt.h: the device assembly is compared with an earlier build's kernel by kernel,
+// sorted by symbol (profiles/rawfmt_ab.txt).  Nothing else depends on the three launchers.
 static void launch_k1(vdl2hip_ctx *c, const K1Args &a, size_t lds, hipEvent_t e0, hipEvent_t e1) {
 	if(c->specialised && c->os == 20) launch_chanfir<20, kRun>(c, a, c->cr, lds, e0, e1);
 	else if(c->specialised && c->os == 13) launch_chanfir<13, kRun>(c, a, c->cr, lds, e0, e1);
@@ -371,10 +363,7 @@ static void launch_resample(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipE
 	else hipExtLaunchKernelGGL((k_resample<FMT, false>), dim3(grid), dim3(kResTile), (uint32_t)c->rs.lds, c->streams.front, e0, e1, 0, a);
 }
 static void launch_k0(vdl2hip_ctx *c, const K0Args &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
-	if(c->in_fmt == VDL2HIP_FMT_CF32) launch_resample<2>(c, a, grid, e0, e1);
-	else if(c->in_fmt == VDL2HIP_FMT_S16LE) launch_resample<1>(c, a, grid, e0, e1);
-	else if(c->in_fmt == kFmtS8) launch_resample<3>(c, a, grid, e0, e1);
-	else launch_resample<0>(c, a, grid, e0, e1);
+	with_fmt(c->in_fmt, [&](auto F) { launch_resample<F()>(c, a, grid, e0, e1); });
 }
 
 static int launch_back(vdl2hip_ctx *c, OutSlot &sl);
@@ -471,7 +460,7 @@ static int collect_pending(vdl2hip_ctx *c, int keep) {
 }
 
 static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in_parts = false) {
-	const size_t sb = sample_bytes(c->fmt);
+	const size_t sb = raw_bytes(c->fmt);
 	const uint64_t nnew = nbytes / sb;
 	const uint64_t nlogical = c->ncarry + nnew;
 	const int64_t D = (int64_t)(nlogical / (uint64_t)c->os);
@@ -635,7 +624,7 @@ static int feed_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool in
 	const int k = (int)(c->feed_no % kSlots);
 	OutSlot &sl = c->slot[k];
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // the slot's block of r[] is about to be overwritten
-	const uint64_t nin = nbytes / sample_bytes(c->in_fmt);
+	const uint64_t nin = nbytes / raw_bytes(c->in_fmt);
 	// outputs n with b_n = floor(n M / L) <= N - 1 exist after N input samples: ceil(N L / M) of them (64 bits: 2^50 samples)
 	const uint64_t N0 = rs.n_in, N1 = N0 + nin, n0 = rs.n_out, n1 = (N1 * rs.L + rs.M - 1) / rs.M, nout = n1 - n0;
 	if(nout > rs.cap) return VDL2HIP_E_TOOBIG;
@@ -668,11 +657,9 @@ static bool feed_is_small(const vdl2hip_ctx *c, int64_t D) {
 	const int nseg = (int)std::min<int64_t>(c->seg_max, D / c->seg_min);
 	return D > 0 && D < 2 * c->seg_min && nseg < 2;
 }
-#define LAUNCH_SCAN_MULTI(how, ...) do { \
-	if(c->fmt == 2) { if(c->os == 20) how((k_ref_scan_multi<2, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<2, 10>), __VA_ARGS__); else how((k_ref_scan_multi<2, 0>), __VA_ARGS__); } \
-	else if(c->fmt == 1) { if(c->os == 20) how((k_ref_scan_multi<1, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<1, 10>), __VA_ARGS__); else how((k_ref_scan_multi<1, 0>), __VA_ARGS__); } \
-	else if(c->fmt == 3) { if(c->os == 20) how((k_ref_scan_multi<3, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<3, 10>), __VA_ARGS__); else how((k_ref_scan_multi<3, 0>), __VA_ARGS__); } \
-	else { if(c->os == 20) how((k_ref_scan_multi<0, 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<0, 10>), __VA_ARGS__); else how((k_ref_scan_multi<0, 0>), __VA_ARGS__); } } while(0)
+// (the kernel is compiled per sample format and for the oversampling factors 20 and 10; 0: any)
+#define LAUNCH_SCAN_MULTI(how, ...) with_fmt(c->fmt, [&](auto F) { \
+	if(c->os == 20) how((k_ref_scan_multi<F(), 20>), __VA_ARGS__); else if(c->os == 10) how((k_ref_scan_multi<F(), 10>), __VA_ARGS__); else how((k_ref_scan_multi<F(), 0>), __VA_ARGS__); })
 // Referee: the listed stretches (`sq`, or the decisions `rq` whose stretches they are; *n of them, at most cap) are made the reference's own,
 // many side by side, and those of them that had not met their witness - a few in ten thousand - are listed in `retry` and scanned again
 // from ref_retry_mul times further back (no list, or ref_retry_mul 0: they are published as they are, counted).  e0 / e1: the first
@@ -985,7 +972,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	uint64_t rs_max_out = 0;
 	if(resample) {
 		if(!design_resampler(cfg->input_rate, (uint32_t)kSymbolRate * kSps * cfg->oversample, rd, false)) return VDL2HIP_E_INVAL;
-		const uint64_t max_in = (cfg->max_block_bytes ? cfg->max_block_bytes : 320000u) / sample_bytes(fmt);
+		const uint64_t max_in = (cfg->max_block_bytes ? cfg->max_block_bytes : 320000u) / raw_bytes(fmt);
 		rs_max_out = (max_in * rd.L + rd.M - 1) / rd.M + 1;
 		if(rs_max_out >= (1ull << 31)) return VDL2HIP_E_INVAL;
 	}
@@ -1003,7 +990,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	c->cfg = *cfg; c->cfg.freqs = nullptr;
 	c->C = (int)count; c->chan_first = (int)first; c->os = (int)cfg->oversample; c->fmt = fmt;
 	c->in_fmt = c->fmt;
-	if(resample) { c->rs.on = true; c->fmt = VDL2HIP_FMT_CF32; }    // what the channeliser and the referee read is r[]
+	if(resample) { c->rs.on = true; c->fmt = kFmtCF32; }    // what the channeliser and the referee read is r[]
 	c->freqs.assign(cfg->freqs + first, cfg->freqs + first + count);
 	c->all_freqs.assign(cfg->freqs, cfg->freqs + cfg->nchan);
 	const uint32_t fs = (uint32_t)kSymbolRate * kSps * cfg->oversample;
@@ -1016,7 +1003,7 @@ int vdl2hip_create(const vdl2hip_cfg *cfg_in, vdl2hip_ctx **out) {
 	for(uint32_t i = 0; i < count; i++) c->dphi[i] = nco_step(cfg->centerfreq, c->freqs[i], fs) & 0xffffffu;
 
 	const uint32_t max_bytes = cfg->max_block_bytes ? cfg->max_block_bytes : 320000u;
-	const size_t sb = sample_bytes(c->fmt);
+	const size_t sb = raw_bytes(c->fmt);
 	const uint64_t max_samples = (resample ? rs_max_out : max_bytes / sb) + c->os;
 	const uint64_t dmax = max_samples / c->os + 1;
 	c->dmax = dmax;
@@ -1211,7 +1198,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	if(nbytes == 0) return VDL2HIP_OK;                             // process_buf_*: len == 0 is a no-op (demod.c:341,358)
 	if(nbytes > c->in_cap) return VDL2HIP_E_TOOBIG;
-	nbytes -= nbytes % sample_bytes(c->in_fmt);
+	nbytes -= nbytes % raw_bytes(c->in_fmt);
 	if(c->pinned_pending) { HIPCHK(hipEventSynchronize(c->pinned_pending)); c->pinned_pending = nullptr; }
 	const int k = (int)(c->feed_no % kSlots);
 	{ int r = collect_slot(c, c->slot[k]); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }
@@ -1231,7 +1218,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 	if(parts) {
 		const size_t piece = (nbytes / kColdParts) & ~(size_t)4095;
 		static_assert(4096 % 8 == 0 && 4096 % 4 == 0, "a piece of a cold-start block ends on a sample boundary in every format");
-		if(piece % sample_bytes(c->fmt)) return VDL2HIP_E_INVAL;
+		if(piece % raw_bytes(c->fmt)) return VDL2HIP_E_INVAL;
 		size_t off = 0;
 		for(int p = 0; p < kColdParts; p++) {
 			const size_t len = p == kColdParts - 1 ? nbytes - off : piece;
@@ -1239,7 +1226,7 @@ static int feed_host(vdl2hip_ctx *c, const void *buf, size_t nbytes, bool wait_c
 			HIPCHK(hipMemcpyAsync(c->d_in[k] + off, (const uint8_t *)buf + off, len, hipMemcpyHostToDevice, c->streams.copy));
 			HIPCHK(hipEventRecord(c->cold.ev[p], c->streams.copy));
 			off += len;
-			c->cold.samples[p] = off / sample_bytes(c->fmt);
+			c->cold.samples[p] = off / raw_bytes(c->fmt);
 		}
 		c->cold.n = kColdParts;
 	} else if(wait_copy) {
@@ -1273,8 +1260,8 @@ int vdl2hip_feed_device(vdl2hip_ctx *c, const void *dev_buf, size_t nbytes) {
 	OnDevice dev_guard(c);
 	if(nbytes == 0) return VDL2HIP_OK;
 	if(nbytes > c->in_cap) return VDL2HIP_E_TOOBIG;
-	if(((uintptr_t)dev_buf) % sample_bytes(c->in_fmt)) return VDL2HIP_E_INVAL;
-	nbytes -= nbytes % sample_bytes(c->in_fmt);
+	if(((uintptr_t)dev_buf) % raw_bytes(c->in_fmt)) return VDL2HIP_E_INVAL;
+	nbytes -= nbytes % raw_bytes(c->in_fmt);
 	if(c->failed) return VDL2HIP_E_DEVICE;
 	int r = feed_block(c, dev_buf, nbytes);
 	if(r == VDL2HIP_E_DEVICE) c->failed = true;

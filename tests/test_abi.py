@@ -37,7 +37,7 @@ def test_every_source_of_the_library_is_a_dependency(tmp_path, monkeypatch):
     list, among them.  On a stand-in directory with the names of csrc/ and a stand-in library: the tree is not touched."""
     from dumpvdl2_amd import build
     names = [f for f in os.listdir(build.CSRC) if f.endswith((".h", ".inc", ".hip"))]
-    assert {"vdl2hip.hip", "txsearch.h", "taps.inc", "hostmem.h", "kernels.h"} <= set(names)
+    assert {"vdl2hip.hip", "txsearch.h", "taps.inc", "hostmem.h", "kernels.h", "rawfmt.h"} <= set(names)
     csrc, so = tmp_path / "csrc", tmp_path / "libvdl2hip.so"
     csrc.mkdir()
     for f in names:

@@ -5,7 +5,8 @@ fed INTEGER bytes: a float32 that equals k / 32768 exactly goes through the same
 computed in float32 (src/demod.c:352) through the same value as the byte b.  A CF32 rendering of an S16 or U8 capture must therefore
 give the oracle's frames, integer metadata, timing and counters exactly, the floats within tests/util.py's tolerances; and where the
 arithmetic is the same source (everything after the channeliser's staging), the same bits as an FMT_S16LE receiver.
-Pieces are always whole samples (multiples of 8 bytes); this file brings its own feeder and conversions."""
+Pieces are always whole samples (multiples of 8 bytes); this file brings its own feeder; the conversions shared with other tests are in
+tests/rawfmt_cases.py, and the referee's scans of a CF32 capture are rows of tests/test_gpu_referee.py's scan tests."""
 import os
 import sys
 
@@ -13,7 +14,8 @@ import numpy as np
 import pytest
 
 import cases
-from util import assert_frames_equal
+from rawfmt_cases import cf32_of_s16
+from util import assert_frames_equal, all_counters
 
 pytestmark = pytest.mark.gpu
 CF = 136975000
@@ -29,12 +31,6 @@ def vh():
     from dumpvdl2_amd import vdl2hip
     vdl2hip.load_library()
     return vdl2hip
-
-
-def cf32_of_s16(raw):
-    """int16 I, Q -> float32 I, Q: k / 32768, exact (process_buf_short(), src/demod.c:362-363)"""
-    k = np.ascontiguousarray(raw).view(np.uint8).reshape(-1).view("<i2")
-    return k.astype(np.float32) / np.float32(32768.0)
 
 
 def cf32_of_u8(raw):
@@ -54,10 +50,6 @@ def feed_cf32(rx, f32, samples=None, rng=None):
     while k < b.size:
         m = 8 * (samples if isinstance(samples, int) else int(rng.integers(*samples)))
         rx.feed(b[k:k + m]); k += m
-
-
-def all_counters(x, nch):
-    return [list(x.counters(c).values()) for c in range(nch)]
 
 
 # ---------------------------------------------------------------- 1. accepted and rejected values
@@ -225,84 +217,7 @@ def test_power_of_two_scaling_is_exact(vh, hot):
     assert held >= D, held                              # (the tuned channel alone carries signal or its filter's tail all along)
 
 
-# ---------------------------------------------------------------- 6. the referee reads CF32
-@pytest.fixture(scope="module")
-def config2(oracle_mod):
-    cfg, iq, _, _ = cases.load("config2_1s")
-    raw = iq.view(np.uint8)
-    D = raw.size // 4 // cfg.oversample
-    o = oracle_mod.Oracle(cfg.centerfreq, list(cfg.freqs), oversample=cfg.oversample, sample_fmt=1, max_ppm=cfg.rx_max_ppm)
-    tr = o.trace_all(D + 4)
-    o.process(raw, block_bytes=1 << 24, nthreads=8)
-    tr = tr[:, :D, :].copy()
-    o.close()
-    return cfg, cf32_of_s16(raw).view(np.uint8), D, tr
-
-
-def _fed_without_referee(vh, cfg, f32b, block):
-    rx = vh.Receiver(cfg.centerfreq, list(cfg.freqs), cfg.oversample, vh.FMT_CF32, cfg.rx_max_ppm, max_block_bytes=f32b.size)
-    rx.debug_option("referee", 0)
-    step = block or f32b.size
-    for k in range(0, f32b.size, step):
-        rx.feed(f32b[k:k + step])
-    rx.drain()
-    return rx
-
-
-@pytest.mark.parametrize("block", [None, 640000])
-def test_scan_is_bit_exact(vh, config2, block):
-    """tests/test_gpu_referee.py::test_scan_is_bit_exact on the capture as CF32: a stretch the single-wavefront scan has been over is the
-    oracle's S16 trace bit for bit - fed as one block, and in blocks of 640 000 bytes so that the run-up comes out of the history ring"""
-    cfg, f32b, D, tr = config2
-    rx = _fed_without_referee(vh, cfg, f32b, block)
-    nch = len(cfg.freqs)
-    rng = np.random.default_rng(5)
-    checked = differed = 0
-    for c in range(nch):
-        for lo in ((0, 17, int(rng.integers(20000, D - 6000)), D - 400) if not block else (int(rng.integers(D - 40000, D - 6000)), D - 3000, D - 400)):
-            hi = min(D - 1, lo + int(rng.integers(40, 700)) + (9000 if c % 3 == 1 else 0))
-            before = rx.read_decimated(c, lo, hi - lo + 1)
-            assert rx.exact_window(c, lo, hi), f"scan refused for channel {c} [{lo}, {hi}]"
-            after = rx.read_decimated(c, lo, hi - lo + 1)
-            want = tr[c, lo:hi + 1]
-            assert after.tobytes() == want.tobytes(), f"channel {c} [{lo}, {hi}]: scan differs from the oracle's stream (max {np.abs(after - want).max():.3e})"
-            differed += before.tobytes() != want.tobytes()
-            checked += 1
-    assert checked >= 2 * nch
-    assert differed >= nch, "the channeliser's own samples were bit-identical to the oracle's: this test shows nothing"
-    s = rx.stats()
-    assert s["referee_scans"] + s["referee_cached"] == checked and s["referee_scans"] >= nch and s["referee_refused"] == 0, s
-    rx.close()
-
-
-@pytest.mark.parametrize("block", [None, 640000])
-def test_many_scans_side_by_side_are_bit_exact(vh, config2, block):
-    """... ::test_many_scans_side_by_side_are_bit_exact likewise: k_ref_scan_multi<2, 20>, whose producers fetch two words per sample"""
-    cfg, f32b, D, tr = config2
-    rx = _fed_without_referee(vh, cfg, f32b, block)
-    nch = len(cfg.freqs)
-    rng = np.random.default_rng(11)
-    n = 75
-    lo_min = 0 if not block else D - 30000
-    chans = rng.integers(0, nch, n); los = rng.integers(lo_min, D - 6000, n); his = los + rng.integers(20, 900, n)
-    his[::7] += 5000
-    chans[40], los[40], his[40] = chans[39], los[39], his[39]
-    if not block:
-        los[3], his[3] = 0, 300
-    his = np.minimum(his, D - 1)
-    before = [rx.read_decimated(int(c), int(a), int(b - a + 1)) for c, a, b in zip(chans, los, his)]
-    ran, _ = rx.scan_multi(chans, los, his)
-    assert 0 < ran <= n - 1, ran
-    differed = 0
-    for c, a, b, bf in zip(chans, los, his, before):
-        got = rx.read_decimated(int(c), int(a), int(b - a + 1)); want = tr[int(c), int(a):int(b) + 1]
-        assert got.tobytes() == want.tobytes(), f"channel {c} [{a}, {b}]: differs from the oracle's stream (max {np.abs(got - want).max():.3e})"
-        differed += bf.tobytes() != want.tobytes()
-    assert differed >= n // 2
-    assert rx.stats()["referee_refused"] == 0
-    rx.close()
-
-
+# ---------------------------------------------------------------- 6. the referee reads CF32 (the scans: tests/test_gpu_referee.py, the cf32 rows)
 @pytest.mark.parametrize("seed,profile", [(175, "plain"), (274, "plain"), (1014, "extreme")])
 def test_decisions_that_hang_on_the_references_rounding(vh, oracle_mod, seed, profile):
     """The captures that differ from the oracle without the referee (tests/test_gpu_referee.py), as CF32: strictly the oracle's with it"""

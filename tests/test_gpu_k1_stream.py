@@ -137,7 +137,7 @@ def dense(os_, freqs, loud, fmt, nsamples, seed, period=None):
     return np.tile(base, nsamples // period + 1)[:nsamples * sb]
 
 
-# ---- builds: k_chanfir<OS, R, CR, U8> over OS in {20, 13, 10, generic}, CR in {1, 2, 4}, the unsigned-byte prefetch build (OS 20 / 10 with CR 4)
+# ---- builds: k_chanfir<OS, R, CR, FMT> over OS in {20, 13, 10, generic}, CR in {1, 2, 4}, the unsigned-byte prefetch build (FMT = kFmtU8: OS 20 / 10 with CR 4)
 # and the staging path everywhere else.  3, 9 and 21 channels = CR 1, 2, 4, each with a partly filled last group; 21 leaves a wave inactive.
 
 @pytest.mark.parametrize("fmt", ["s16", "u8"])

@@ -2,8 +2,8 @@
 reference's own samples, which one wavefront recomputes from the raw input by running the reference's arithmetic sequentially
 (kernels.h: ref_exact_window_dev; src/demod.c:302-329).
 
-1. the scan itself: a stretch made exact on the device is BIT-identical to the oracle's decimated stream - s16 and u8, offset-tuned and
-   on-centre channels, whole-block and 320 000-byte feeds (the run-up then comes out of the history ring), at the stream's start
+1. the scan itself: a stretch made exact on the device is BIT-identical to the oracle's decimated stream - every raw format (s16, u8, cf32, s8:
+   tests/rawfmt_cases.py), offset-tuned and on-centre channels, whole-block and short feeds (the run-up then comes out of the history ring), at the stream's start
    (zero state, exactly) and far into it (run-up from a zero state 2^17 samples back), one at a time and 75 side by side;
 2. the decisions: random captures that differ from the oracle in a frame or a counter without the referee (tests/fuzz_gpu.py's seeds
    175, 274, 1014: a symbol at a slicer boundary, a header bit, a preamble whose metric hangs on atan2()'s branch cut) are identical to
@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import cases
-from util import assert_frames_equal
+import rawfmt_cases
+from util import assert_frames_equal, fed_without_referee
 
 pytestmark = pytest.mark.gpu
 
@@ -33,19 +34,22 @@ def _oracle_trace(oracle_mod, cfg, raw, fmt, D):
     return o, tr[:, :D, :]
 
 
-@pytest.mark.parametrize("fmt,block", [(1, None), (1, 320000), (0, 262144)])
+# the capture in every raw format (tests/rawfmt_cases.py), as one block and in blocks so short that the run-up comes out of the history
+# ring.  u8 whole: k_ref_scan_multi<u8, 20> and the single-wavefront scan's 16-bit words from the stream's own start
+# (fmt: the public value, so that the rows this file always had keep their ids - 1 s16, 0 u8, 2 cf32, 4 s8)
+FMT_NAME = {1: "s16", 0: "u8", 2: "cf32", 4: "s8"}
+SCAN_CASES = [(1, None), (1, 320000), (0, None), (0, 262144), (2, None), (2, 640000), (4, None), (4, 640000)]
+MULTI_CASES = [(1, None), (0, None), (0, 262144), (2, None), (2, 640000), (4, None), (4, 640000)]
+
+
+@pytest.mark.parametrize("fmt,block", SCAN_CASES)
 def test_scan_is_bit_exact(vh, oracle_mod, fmt, block):
-    cfg, iq, _, _ = cases.load("config2_1s")
-    raw = iq.view(np.uint8) if fmt == 1 else np.clip(np.rint(iq.astype(np.float64) / 256.0 + 127.5), 0, 255).astype(np.uint8)
-    sb = 4 if fmt == 1 else 2
-    D = raw.size // sb // cfg.oversample
-    o, tr = _oracle_trace(oracle_mod, cfg, raw, fmt, D)
-    rx = vh.Receiver(cfg.centerfreq, list(cfg.freqs), cfg.oversample, fmt, cfg.rx_max_ppm, max_block_bytes=raw.size)
-    rx.debug_option("referee", 0)                    # the stream as the channeliser leaves it ...
-    step = block or raw.size
-    for k in range(0, raw.size, step):
-        rx.feed(raw[k:k + step])
-    rx.drain()
+    """a stretch the single-wavefront scan has been over is the oracle's stream bit for bit, whatever the format of the raw input"""
+    name = FMT_NAME[fmt]
+    assert rawfmt_cases.receiver_fmt(vh, name) == fmt
+    case = rawfmt_cases.config2(oracle_mod, name)
+    cfg, D, tr = case["cfg"], case["D"], case["tr"]
+    rx = fed_without_referee(vh, cfg, fmt, case["raw"], block)   # the stream as the channeliser leaves it ...
     nch = len(cfg.freqs)
     rng = np.random.default_rng(5)
     # ... is close to the oracle's but not it; the stretches the scan has been over are it, bit for bit
@@ -65,23 +69,18 @@ def test_scan_is_bit_exact(vh, oracle_mod, fmt, block):
     assert differed >= nch, "the channeliser's own samples were bit-identical to the oracle's: this test shows nothing"
     s = rx.stats()
     assert s["referee_scans"] + s["referee_cached"] == checked and s["referee_scans"] >= nch and s["referee_refused"] == 0, s   # (a scan covers whole blocks of 256 samples: some stretches had been done)
-    rx.close(); o.close()
+    rx.close()
 
 
-@pytest.mark.parametrize("fmt,block", [(1, None), (0, 262144)])
+@pytest.mark.parametrize("fmt,block", MULTI_CASES)
 def test_many_scans_side_by_side_are_bit_exact(vh, oracle_mod, fmt, block):
-    """k_ref_scan_multi: a workgroup runs 32 recursions at once (lane = request), two wavefronts feed it - the same arithmetic"""
-    cfg, iq, _, _ = cases.load("config2_1s")
-    raw = iq.view(np.uint8) if fmt == 1 else np.clip(np.rint(iq.astype(np.float64) / 256.0 + 127.5), 0, 255).astype(np.uint8)
-    sb = 4 if fmt == 1 else 2
-    D = raw.size // sb // cfg.oversample
-    o, tr = _oracle_trace(oracle_mod, cfg, raw, fmt, D)
-    rx = vh.Receiver(cfg.centerfreq, list(cfg.freqs), cfg.oversample, fmt, cfg.rx_max_ppm, max_block_bytes=raw.size)
-    rx.debug_option("referee", 0)
-    step = block or raw.size
-    for k in range(0, raw.size, step):
-        rx.feed(raw[k:k + step])
-    rx.drain()
+    """k_ref_scan_multi: a workgroup runs 32 recursions at once (lane = request), two wavefronts feed it - the same arithmetic; its
+    producers fetch 16-bit words (u8, s8), 32-bit words (s16) or two words per sample (cf32)"""
+    name = FMT_NAME[fmt]
+    assert rawfmt_cases.receiver_fmt(vh, name) == fmt
+    case = rawfmt_cases.config2(oracle_mod, name)
+    cfg, D, tr = case["cfg"], case["D"], case["tr"]
+    rx = fed_without_referee(vh, cfg, fmt, case["raw"], block)
     nch = len(cfg.freqs)
     rng = np.random.default_rng(11)
     n = 75                                           # three workgroups, the last one partly filled
@@ -102,7 +101,7 @@ def test_many_scans_side_by_side_are_bit_exact(vh, oracle_mod, fmt, block):
         differed += bf.tobytes() != want.tobytes()
     assert differed >= n // 2
     assert rx.stats()["referee_refused"] == 0
-    rx.close(); o.close()
+    rx.close()
 
 
 def test_witness_tells_a_run_up_that_was_too_short(vh, oracle_mod):

@@ -4,7 +4,8 @@ A byte b counts (float)b / 128.0f, which is bit for bit the float process_buf_sh
 an S8 receiver is an FMT_S16LE receiver fed b << 8, and the reference for every test here is the oracle fed those int16 bytes: the
 oracle's frames, integer metadata, timing and counters exactly, the floats within tests/util.py's tolerances; and where the arithmetic
 is the same source on the same values (everything after the staging), the same bits as an FMT_S16LE receiver fed b << 8.
-Pieces are always whole samples (2 bytes); this file brings its own feeder and conversions."""
+Pieces are always whole samples (2 bytes); the feeder is tests/util.py's, the conversions tests/rawfmt_cases.py's, and the referee's
+scans of an S8 capture are rows of tests/test_gpu_referee.py's scan tests."""
 import os
 import sys
 
@@ -12,7 +13,9 @@ import numpy as np
 import pytest
 
 import cases
-from util import assert_frames_equal
+import rawfmt_cases
+from rawfmt_cases import s8_of_s16, s16_of_s8
+from util import assert_frames_equal, feed_pieces, all_counters
 
 pytestmark = pytest.mark.gpu
 CF = 136975000
@@ -30,39 +33,9 @@ def vh():
     return vdl2hip
 
 
-def s8_of_s16(raw):
-    """int16 I, Q -> int8 I, Q: the nearest byte, saturated"""
-    k = np.ascontiguousarray(raw).view(np.uint8).reshape(-1).view("<i2")
-    return np.clip(np.rint(k / 256), -128, 127).astype(np.int8)
-
-
-def s16_of_s8(b):
-    """the oracle's input: b << 8 as little-endian int16, as bytes"""
-    return (np.ascontiguousarray(b).view(np.int8).reshape(-1).astype("<i2") * 256).view(np.uint8)
-
-
-def feed_pieces(rx, data, sample_bytes, samples=None, rng=None):
-    """data: any array, fed as its bytes.  samples: None - one block; an int - blocks of that many complex samples; (lo, hi) - random
-    pieces of lo..hi-1 samples; a list - pieces of those sizes, in turn"""
-    b = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-    assert b.size % sample_bytes == 0
-    if samples is None:
-        rx.feed(b)
-        return
-    k = i = 0
-    while k < b.size:
-        n = samples if isinstance(samples, int) else samples[i % len(samples)] if isinstance(samples, list) else int(rng.integers(*samples))
-        m = sample_bytes * n
-        rx.feed(b[k:k + m]); k += m; i += 1
-
-
 def feed_s8(rx, b, samples=None, rng=None):
     assert b.dtype == np.int8
     feed_pieces(rx, b, 2, samples, rng)
-
-
-def all_counters(x, nch):
-    return [list(x.counters(c).values()) for c in range(nch)]
 
 
 def oracle_answer(oracle_mod, cf, freqs, os_, b, max_ppm=0.0):
@@ -242,88 +215,12 @@ def test_hot_build_cold_start(vh, oracle_mod, hot):
     rx.close()
 
 
-# ---------------------------------------------------------------- 8. the scans read S8
+# ---------------------------------------------------------------- 8. the capture of the scan tests
 @pytest.fixture(scope="module")
 def config2(oracle_mod):
-    cfg, iq, _, _ = cases.load("config2_1s")
-    b = s8_of_s16(iq)
-    assert int(b.min()) == -37 and int(b.max()) == 37                         # (the low-amplitude case too: a quarter of the range)
-    raw = s16_of_s8(b)
-    D = raw.size // 4 // cfg.oversample
-    o = oracle_mod.Oracle(cfg.centerfreq, list(cfg.freqs), oversample=cfg.oversample, sample_fmt=1, max_ppm=cfg.rx_max_ppm)
-    tr = o.trace_all(D + 4)
-    o.process(raw, block_bytes=1 << 24, nthreads=8)
-    tr = tr[:, :D, :].copy()
-    fo = o.frames()
-    co = [list(o.counters(c).values())[:18] for c in range(len(cfg.freqs))]
-    o.close()
-    assert len(fo) == 41
-    return dict(cfg=cfg, b=b, D=D, tr=tr, frames=fo, counters18=co)
-
-
-def _fed_without_referee(vh, cfg, b, block):
-    b8 = b.view(np.uint8)
-    rx = vh.Receiver(cfg.centerfreq, list(cfg.freqs), cfg.oversample, vh.FMT_S8, cfg.rx_max_ppm, max_block_bytes=b8.size)
-    rx.debug_option("referee", 0)
-    step = block or b8.size
-    for k in range(0, b8.size, step):
-        rx.feed(b8[k:k + step])
-    rx.drain()
-    return rx
-
-
-@pytest.mark.parametrize("block", [None, 640000])
-def test_scan_is_bit_exact(vh, config2, block):
-    """tests/test_gpu_referee.py::test_scan_is_bit_exact on the capture as S8: a stretch the single-wavefront scan has been over is the
-    oracle's trace of b << 8 bit for bit - fed as one block, and in blocks of 640 000 bytes so that the run-up comes out of the history ring"""
-    cfg, D, tr = config2["cfg"], config2["D"], config2["tr"]
-    rx = _fed_without_referee(vh, cfg, config2["b"], block)
-    nch = len(cfg.freqs)
-    rng = np.random.default_rng(5)
-    checked = differed = 0
-    for c in range(nch):
-        for lo in ((0, 17, int(rng.integers(20000, D - 6000)), D - 400) if not block else (int(rng.integers(D - 40000, D - 6000)), D - 3000, D - 400)):
-            hi = min(D - 1, lo + int(rng.integers(40, 700)) + (9000 if c % 3 == 1 else 0))
-            before = rx.read_decimated(c, lo, hi - lo + 1)
-            assert rx.exact_window(c, lo, hi), f"scan refused for channel {c} [{lo}, {hi}]"
-            after = rx.read_decimated(c, lo, hi - lo + 1)
-            want = tr[c, lo:hi + 1]
-            assert after.tobytes() == want.tobytes(), f"channel {c} [{lo}, {hi}]: scan differs from the oracle's stream (max {np.abs(after - want).max():.3e})"
-            differed += before.tobytes() != want.tobytes()
-            checked += 1
-    assert checked >= 2 * nch
-    assert differed >= nch, "the channeliser's own samples were bit-identical to the oracle's: this test shows nothing"
-    s = rx.stats()
-    assert s["referee_scans"] + s["referee_cached"] == checked and s["referee_scans"] >= nch and s["referee_refused"] == 0, s
-    rx.close()
-
-
-@pytest.mark.parametrize("block", [None, 640000])
-def test_many_scans_side_by_side_are_bit_exact(vh, config2, block):
-    """... ::test_many_scans_side_by_side_are_bit_exact likewise: k_ref_scan_multi<3, 20>, whose producers fetch 16-bit words"""
-    cfg, D, tr = config2["cfg"], config2["D"], config2["tr"]
-    rx = _fed_without_referee(vh, cfg, config2["b"], block)
-    nch = len(cfg.freqs)
-    rng = np.random.default_rng(11)
-    n = 75
-    lo_min = 0 if not block else D - 30000
-    chans = rng.integers(0, nch, n); los = rng.integers(lo_min, D - 6000, n); his = los + rng.integers(20, 900, n)
-    his[::7] += 5000
-    chans[40], los[40], his[40] = chans[39], los[39], his[39]
-    if not block:
-        los[3], his[3] = 0, 300
-    his = np.minimum(his, D - 1)
-    before = [rx.read_decimated(int(c), int(a), int(b - a + 1)) for c, a, b in zip(chans, los, his)]
-    ran, _ = rx.scan_multi(chans, los, his)
-    assert 0 < ran <= n - 1, ran
-    differed = 0
-    for c, a, b, bf in zip(chans, los, his, before):
-        got = rx.read_decimated(int(c), int(a), int(b - a + 1)); want = tr[int(c), int(a):int(b) + 1]
-        assert got.tobytes() == want.tobytes(), f"channel {c} [{a}, {b}]: differs from the oracle's stream (max {np.abs(got - want).max():.3e})"
-        differed += bf.tobytes() != want.tobytes()
-    assert differed >= n // 2
-    assert rx.stats()["referee_refused"] == 0
-    rx.close()
+    """(the scans on this capture: tests/test_gpu_referee.py, the s8 rows)"""
+    case = rawfmt_cases.config2(oracle_mod, "s8")
+    return dict(cfg=case["cfg"], b=case["raw"].view(np.int8), frames=case["frames"], counters18=case["counters18"])
 
 
 # ---------------------------------------------------------------- 9. referee on

@@ -135,3 +135,34 @@ def run_oracle(po, cfg, raw, nthreads=4, trace=False):
     o.process(np.ascontiguousarray(raw).view(np.uint8), block_bytes=1 << 24, nthreads=nthreads)
     fr = o.frames()
     return o, fr, tr
+
+
+def feed_pieces(rx, data, sample_bytes, samples=None, rng=None):
+    """data: any array, fed as its bytes.  samples: None - one block; an int - blocks of that many complex samples; (lo, hi) - random
+    pieces of lo..hi-1 samples; a list - pieces of those sizes, in turn"""
+    b = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    assert b.size % sample_bytes == 0
+    if samples is None:
+        rx.feed(b)
+        return
+    k = i = 0
+    while k < b.size:
+        n = samples if isinstance(samples, int) else samples[i % len(samples)] if isinstance(samples, list) else int(rng.integers(*samples))
+        m = sample_bytes * n
+        rx.feed(b[k:k + m]); k += m; i += 1
+
+
+def all_counters(x, nch):
+    return [list(x.counters(c).values()) for c in range(nch)]
+
+
+def fed_without_referee(vh, cfg, fmt, raw, block):
+    """a receiver of format `fmt` that has been fed the bytes `raw` (whole, or in blocks of `block` bytes) with the referee off: its
+    decimated stream is the channeliser's own"""
+    rx = vh.Receiver(cfg.centerfreq, list(cfg.freqs), cfg.oversample, fmt, cfg.rx_max_ppm, max_block_bytes=raw.size)
+    rx.debug_option("referee", 0)
+    step = block or raw.size
+    for k in range(0, raw.size, step):
+        rx.feed(raw[k:k + step])
+    rx.drain()
+    return rx
