@@ -18,10 +18,18 @@
 // which spreads them over all of them; the later passes write runs of s consecutive elements.
 // The samples a feed leaves in an incomplete segment that will be analysed are carried as float2 (the format no longer matters),
 // in two buffers that alternate like the resampler's tail; workgroup 0 writes the next feed's.
+//
+// The spectrogram tap (vdl2hip.h, "Spectrogram") is a second build of the same kernel, k_spectrum_lines: beside the run's float64 sums
+// a lane keeps, per bin it owns, the float32 maximum and the float64 sum of the line under way, and flushes them where the run crosses
+// a line boundary (specgram_plan.h: head, whole lines, tail).  A whole line goes straight to the ring; head and tail are left as pieces
+// - float64 sums, float32 maxima; their line and segment count follow from the plan - with the run's maximum per bin and the smallest
+// mean of its whole lines.  k_specgram_combine, a lane per bin, starts from the carried partial line, adds the pieces in workgroup
+// order, writes the lines that become complete, stores the new carry and updates the holds.  Plain coalesced stores, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "resample.h"
+#include "specgram_plan.h"
 
 namespace vdl2 {
 
@@ -42,6 +50,20 @@ struct SpecArgs {
 	uint64_t seg_step;         // stride N
 	uint32_t nin, ncarry, ncarry_out, nseg, run, N, log2n;
 };
+
+// what the spectrogram build of the kernel and the combine kernel share.  piece_*: [rows][2][N], head then tail; run_max: [rows][N] the
+// largest |X|^2 of the run; run_floor: [rows][N] the smallest line mean among the run's whole lines (+inf: none); ring_*: [ring_lines][N];
+// carry_*: [N] the line under way between feeds; hold: [2][N] max_hold, then floor_hold (+inf while no line has been completed)
+struct SpgArgs {
+	double *piece_sum; float *piece_max, *run_max, *run_floor;
+	float *ring_mean, *ring_max;
+	double *carry_sum; float *carry_max, *hold;
+	double norm;               // 1 / (sum w)^2
+	SpgFeed f;
+};
+// a line's values as the ring receives them
+__host__ __device__ __forceinline__ float spg_mean(double sum, double norm, uint32_t R) { return (float)(sum * norm / (double)R); }
+__host__ __device__ __forceinline__ float spg_peak(float mx, double norm) { return (float)((double)mx * norm); }
 
 __host__ __device__ __forceinline__ uint32_t spec_pad(uint32_t i) { return i + (i >> 5); }
 __host__ __device__ __forceinline__ float2 spec_cmul(float2 a, float2 w) {
@@ -82,8 +104,9 @@ __device__ __forceinline__ float2 spec_sample(const SpecArgs &a, int64_t rel) {
 
 // PER = N / T: the samples (and bins) a lane holds - 1 at N = 64, 4 from 256 to 1024, 16 at 4096: a build per value, so that the
 // loops over them have no idle iterations and a small transform does not pay for the registers of a large one
-template<int FMT, int PER>
-__global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) {
+// SPG: the spectrogram build (sg: its arguments; unused otherwise)
+template<int FMT, int PER, bool SPG>
+__device__ __forceinline__ void spectrum_run(const SpecArgs &a, const SpgArgs &sg) {
 	extern __shared__ float2 spec_lds[];
 	const uint32_t N = a.N, T = blockDim.x, lane = threadIdx.x, half = spec_pad(N) + 1;
 	float2 *bufa = spec_lds, *bufb = spec_lds + half;
@@ -94,6 +117,15 @@ __global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) 
 	double sp = 0.0, si = 0.0, sq = 0.0;
 	uint32_t nclip = 0;
 	float peak = 0.f;
+	// the line under way in this run: its sum and maximum per bin; the run's maximum; the smallest mean of the run's whole lines
+	double lsum[SPG ? PER : 1]; float lmax[SPG ? PER : 1], gmax[SPG ? PER : 1], wmin[SPG ? PER : 1];
+	SpgRun rn{}; uint32_t cnt = 0, until = 0; uint64_t line = 0; bool inside = false;
+	if constexpr(SPG) {
+		#pragma unroll
+		for(int r = 0; r < PER; r++) { lsum[r] = 0.0; lmax[r] = 0.f; gmax[r] = 0.f; wmin[r] = __builtin_inff(); }
+		rn = spg_run(sg.f, blockIdx.x);
+		inside = rn.to_boundary == 0; until = inside ? sg.f.R : rn.to_boundary; line = inside ? rn.whole_first : rn.head_line;
+	}
 	const uint32_t m0 = blockIdx.x * a.run;
 	for(uint32_t m = m0; m < m0 + a.run && m < a.nseg; m++) {              // (uniform)
 		const int64_t rel = a.rel0 + (int64_t)((uint64_t)m * a.seg_step);
@@ -127,10 +159,44 @@ __global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) 
 			const uint32_t i = lane + (uint32_t)r * T;
 			if(i < N) {
 				const float2 X = x[spec_pad((i + (N >> 1)) & (N - 1))];         // bin i of the ascending-frequency order is X[(i + N / 2) mod N]
-				acc[r] += (double)(X.x * X.x + X.y * X.y);
+				const float q = X.x * X.x + X.y * X.y;
+				acc[r] += (double)q;
+				if constexpr(SPG) { lsum[r] += (double)q; lmax[r] = __builtin_fmaxf(lmax[r], q); gmax[r] = __builtin_fmaxf(gmax[r], q); }
+			}
+		}
+		if constexpr(SPG) {
+			if(++cnt == until) {                                            // (uniform) a line ends with this segment
+				#pragma unroll
+				for(int r = 0; r < PER; r++) {
+					const uint32_t i = lane + (uint32_t)r * T;
+					if(i < N) {
+						if(inside) {                                            // it began in this run: to the ring
+							const size_t o = (size_t)(line & sg.f.ring_mask) * N + i;
+							const float mean = spg_mean(lsum[r], sg.norm, sg.f.R);
+							sg.ring_mean[o] = mean; sg.ring_max[o] = spg_peak(lmax[r], sg.norm);
+							wmin[r] = __builtin_fminf(wmin[r], mean);
+						} else {                                                // it began earlier: the head piece
+							const size_t o = (size_t)blockIdx.x * 2 * N + i;
+							sg.piece_sum[o] = lsum[r]; sg.piece_max[o] = lmax[r];
+						}
+					}
+					lsum[r] = 0.0; lmax[r] = 0.f;
+				}
+				inside = true; cnt = 0; until = sg.f.R; line++;
 			}
 		}
 		__syncthreads();                                                    // the next segment overwrites both buffers
+	}
+	if constexpr(SPG) {
+		// what is left of a line: the tail piece, or the head where the run never reached a boundary
+		#pragma unroll
+		for(int r = 0; r < PER; r++) {
+			const uint32_t i = lane + (uint32_t)r * T;
+			if(i < N) {
+				if(cnt) { const size_t o = ((size_t)blockIdx.x * 2 + (inside ? 1 : 0)) * N + i; sg.piece_sum[o] = lsum[r]; sg.piece_max[o] = lmax[r]; }
+				sg.run_max[(size_t)blockIdx.x * N + i] = gmax[r]; sg.run_floor[(size_t)blockIdx.x * N + i] = wmin[r];
+			}
+		}
 	}
 	double *row = a.rows + (size_t)blockIdx.x * (N + kSpecLevels);
 	#pragma unroll
@@ -151,6 +217,43 @@ __global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) 
 		__syncthreads();
 	}
 	if(lane < (uint32_t)kSpecLevels) row[N + lane] = red[lane * T];
+}
+template<int FMT, int PER>
+__global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum(const SpecArgs a) { spectrum_run<FMT, PER, false>(a, SpgArgs{}); }
+template<int FMT, int PER>
+__global__ __launch_bounds__(kSpecMaxThreads) void k_spectrum_lines(const SpecArgs a, const SpgArgs sg) { spectrum_run<FMT, PER, true>(a, sg); }
+
+// One lane per bin: the carried partial line, then this feed's pieces in workgroup order.  Every line that becomes complete goes to
+// the ring; max_hold takes every run's maximum (x -> (float)((double)x norm) is monotone: the maximum of the rounded values is the
+// rounded maximum), floor_hold every completed line's mean, exactly as the ring received it.  carry_n: the segments the carry holds
+__global__ __launch_bounds__(256) void k_specgram_combine(const SpgArgs sg, uint32_t N, uint32_t carry_n) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if(i >= N) return;
+	const SpgFeed &f = sg.f;
+	double csum = carry_n ? sg.carry_sum[i] : 0.0;
+	float cmax = carry_n ? sg.carry_max[i] : 0.f;
+	float hold = sg.hold[i], floor = sg.hold[N + i];
+	uint32_t cnt = carry_n;
+	for(uint32_t g = 0; g < f.grid; g++) {
+		const SpgRun rn = spg_run(f, g);                                    // (uniform)
+		if(rn.m0 >= rn.m1) break;
+		hold = __builtin_fmaxf(hold, spg_peak(sg.run_max[(size_t)g * N + i], sg.norm));
+		if(rn.head_n) {
+			const size_t o = (size_t)g * 2 * N + i;
+			csum += sg.piece_sum[o]; cmax = __builtin_fmaxf(cmax, sg.piece_max[o]); cnt += rn.head_n;
+			if(cnt == f.R) {
+				const size_t w = (size_t)(rn.head_line & f.ring_mask) * N + i;
+				const float mean = spg_mean(csum, sg.norm, f.R);
+				sg.ring_mean[w] = mean; sg.ring_max[w] = spg_peak(cmax, sg.norm);
+				floor = __builtin_fminf(floor, mean);
+				csum = 0.0; cmax = 0.f; cnt = 0;
+			}
+		}
+		if(rn.whole_n) floor = __builtin_fminf(floor, sg.run_floor[(size_t)g * N + i]);
+		if(rn.tail_n) { const size_t o = ((size_t)g * 2 + 1) * N + i; csum = sg.piece_sum[o]; cmax = sg.piece_max[o]; cnt = rn.tail_n; }
+	}
+	sg.carry_sum[i] = csum; sg.carry_max[i] = cmax;
+	sg.hold[i] = hold; sg.hold[N + i] = floor;
 }
 
 // acc[i] += rows[0][i] + rows[1][i] + ...: one lane per bin and per level figure, the rows in index order (the peak: their maximum)

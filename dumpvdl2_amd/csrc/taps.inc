@@ -1,7 +1,8 @@
-// taps.inc - the receiver's five optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h,
-// capture.h, txsearch.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
+// taps.inc - the receiver's six optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
+// input monitor's and the spectrogram's - capture.h, txsearch.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
 // (collect), what gives its buffers back (free), then its entry points of vdl2hip.h.  A tap stands behind those it calls into: the
-// log hands its records to the search, the activity monitor launches the log and switches it off.
+// log hands its records to the search, the activity monitor launches the log and switches it off, the input monitor does both
+// with the spectrogram.
 // Three of them deliver records - capture, search, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
 // (hostmem.h), per context the totals, a queue of collected records and the staging buffer of a feed with more records than come
 // with the header.  Their enable is: validate, collect what is in flight, free the old, allocate per slot, zero the totals, on.
@@ -15,6 +16,165 @@ static int pop_records(std::deque<R> &q, R *recs, size_t cap_recs) {
 	return (int)n;
 }
 
+// ---- the spectrogram (vdl2hip.h, "Spectrogram"; kernels: spectrum.h; the plan of a feed: specgram_plan.h) ----
+// A tap on top of the input monitor, which launches it and switches it off (so it stands ahead of it here): max-hold, floor and the
+// last ring_lines lines of R analysed segments each.  It has no event, stream or landing place of its own: the monitor's serve.
+static_assert(sizeof(vdl2hip_specgram_cfg) == 16 && sizeof(vdl2hip_specgram_info) == 72, "vdl2hip.h states these sizes");
+// Its share of a feed that analyses nseg >= 1 segments (monitor_block): the arguments of k_spectrum_lines, which takes k_spectrum's
+// place in that feed, and of k_specgram_combine behind the monitor's reduction.  The host's counts move on here.
+static bool specgram_plan(vdl2hip_ctx *c, uint64_t nseg, SpgArgs &sg) {
+	auto &s = c->spg; auto &b = s.buf;
+	sg.piece_sum = b.d_piece_sum; sg.piece_max = b.d_piece_max; sg.run_max = b.d_run_max; sg.run_floor = b.d_run_floor;
+	sg.ring_mean = b.d_ring_mean; sg.ring_max = b.d_ring_max; sg.carry_sum = b.d_carry_sum; sg.carry_max = b.d_carry_max; sg.hold = b.d_hold;
+	sg.norm = 1.0 / (c->mon.sum_w * c->mon.sum_w);
+	sg.f = spg_feed(s.seen, nseg, s.R, s.ring, kSpecMaxRows);
+	// (never: a feed is at most max_block_bytes) the pieces have a row per workgroup, the ring a slot per line of one feed
+	return sg.f.grid <= s.rows && spg_lines_after(sg.f) - spg_lines_before(sg.f) < s.ring;
+}
+static void specgram_launch_combine(vdl2hip_ctx *c, const SpgArgs &sg, hipEvent_t e1) {
+	auto &s = c->spg;
+	hipExtLaunchKernelGGL(k_specgram_combine, dim3((c->mon.nfft + 255) / 256), dim3(256), 0u, c->streams.front, (hipEvent_t) nullptr, e1, 0,
+	                      sg, c->mon.nfft, (uint32_t)(sg.f.t0 % s.R));
+	const uint64_t l0 = spg_lines_before(sg.f), l1 = spg_lines_after(sg.f);
+	s.seen += sg.f.nseg; s.hold_segments += sg.f.nseg; s.hold_lines += l1 - l0;
+}
+// give its buffers back (the monitor's launches carry it: whoever calls has waited for them, or nothing was queued since the enable)
+static void specgram_free(vdl2hip_ctx *c) {
+	c->spg.buf = {};
+	c->spg.on = false;
+}
+static int specgram_wait(vdl2hip_ctx *c) {
+	auto &m = c->mon;
+	if(m.tap.queued && hipEventSynchronize(m.tap.last) != hipSuccess) { (void)hipGetLastError(); return VDL2HIP_E_DEVICE; }
+	return VDL2HIP_OK;
+}
+// the holds as they stand once everything the monitor has queued is done: [nfft] max_hold, [nfft] floor_hold (zero while no line)
+static int specgram_fetch_hold(vdl2hip_ctx *c, std::vector<float> &hold) {
+	auto &m = c->mon; auto &s = c->spg;
+	const size_t N = m.nfft;
+	hold.assign(2 * N, 0.f);
+	if(s.hold_segments == 0) return VDL2HIP_OK;                      // nothing has touched them since they were zeroed
+	HIPCHK(m.tap.fetch(m.tap.land, s.buf.d_hold, s.buf.d_hold.bytes()));
+	memcpy(hold.data(), m.tap.land, 2 * N * sizeof(float));
+	if(s.hold_lines == 0) std::fill(hold.begin() + (ptrdiff_t)N, hold.end(), 0.f);
+	return VDL2HIP_OK;
+}
+// the holds' start: max_hold 0, floor_hold +inf (the host reports 0 while no line is complete), on the front stream
+static hipError_t specgram_clear_hold(vdl2hip_ctx *c) {
+	auto &s = c->spg;
+	const size_t N = c->mon.nfft;
+	hipError_t e = hipMemsetAsync(s.buf.d_hold, 0, N * sizeof(float), c->streams.front);
+	if(e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)(s.buf.d_hold.get() + N), 0x7f800000, N, c->streams.front);
+	return e;
+}
+int vdl2hip_specgram_enable(vdl2hip_ctx *c, const vdl2hip_specgram_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_specgram_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(!c->mon.on || cfg->line_segments > kSpgMaxLineSegments || (cfg->ring_lines & (cfg->ring_lines - 1)) != 0) return VDL2HIP_E_INVAL;
+	auto &m = c->mon; auto &s = c->spg;
+	const uint32_t R = cfg->line_segments ? cfg->line_segments : kSpgDefLineSegments;
+	const uint64_t N = m.nfft, feed_segs = spg_feed_segments(c->in_cap / raw_bytes(c->in_fmt), m.nfft, m.stride);
+	const uint64_t ring = std::max<uint64_t>(cfg->ring_lines, spg_ring_min(feed_segs, R));
+	if(ring * N > kSpgMaxRingFloats) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = specgram_wait(c); if(r != VDL2HIP_OK) return r; }      // nothing of an earlier tap is in flight any more
+	specgram_free(c);
+	const size_t rows = (size_t)std::min<uint64_t>(kSpecMaxRows, std::max<uint64_t>(1, feed_segs));
+	auto &b = s.buf;
+	for(hipError_t e : { b.d_piece_sum.alloc(rows * 2 * N), b.d_piece_max.alloc(rows * 2 * N), b.d_run_max.alloc(rows * N), b.d_run_floor.alloc(rows * N),
+	                     b.d_ring_mean.alloc(ring * N, true), b.d_ring_max.alloc(ring * N, true), b.d_carry_sum.alloc(N, true), b.d_carry_max.alloc(N, true), b.d_hold.alloc(2 * N) })
+		if(e != hipSuccess) { specgram_free(c); return e == hipErrorOutOfMemory ? VDL2HIP_E_NOMEM : VDL2HIP_E_DEVICE; }
+	if(specgram_clear_hold(c) != hipSuccess || hipStreamSynchronize(c->streams.front) != hipSuccess) { (void)hipGetLastError(); specgram_free(c); return VDL2HIP_E_DEVICE; }
+	s.R = R; s.ring = (uint32_t)ring; s.rows = (uint32_t)rows; s.a0 = m.ordinal; s.seen = 0; s.hold_segments = s.hold_lines = 0;
+	s.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_specgram_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->spg.on) (void)specgram_wait(c);
+	specgram_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_specgram_read(vdl2hip_ctx *c, vdl2hip_specgram_info *info, float *max_hold, float *floor_hold, size_t cap, int reset) {
+	if(!c || !c->spg.on || !c->mon.on || (info && info->struct_size != sizeof(vdl2hip_specgram_info))) return VDL2HIP_E_INVAL;
+	auto &m = c->mon; auto &s = c->spg;
+	const uint32_t N = m.nfft;
+	if((max_hold || floor_hold) && cap < N) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	if(max_hold || floor_hold) {
+		std::vector<float> hold;
+		{ int r = specgram_fetch_hold(c, hold); if(r != VDL2HIP_OK) return r; }
+		if(max_hold) memcpy(max_hold, hold.data(), (size_t)N * sizeof(float));
+		if(floor_hold) memcpy(floor_hold, hold.data() + N, (size_t)N * sizeof(float));
+	}
+	if(info) {
+		memset(info, 0, sizeof *info);
+		info->struct_size = sizeof *info; info->nfft = N; info->window = m.window; info->stride = m.stride; info->line_segments = s.R; info->ring_lines = s.ring;
+		info->sample_rate = c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample;
+		info->centerfreq = c->cfg.centerfreq;
+		info->first_segment = s.a0; info->first_sample = s.a0 * m.stride * N;
+		info->lines = s.seen / s.R; info->hold_segments = s.hold_segments; info->hold_lines = s.hold_lines;
+	}
+	if(reset) {
+		// (on the front stream: behind the launches that are queued, ahead of the next feed's; the ring and the line under way stay)
+		HIPCHK(specgram_clear_hold(c));
+		HIPCHK(m.tap.mark(c->streams.front));
+		s.hold_segments = s.hold_lines = 0;
+	}
+	return (int)N;
+}
+int vdl2hip_specgram_lines(vdl2hip_ctx *c, int64_t first_line, float *mean, float *max, size_t cap_lines) {
+	if(!c || !c->spg.on || !c->mon.on) return VDL2HIP_E_INVAL;
+	auto &m = c->mon; auto &s = c->spg;
+	const uint64_t lines = s.seen / s.R;
+	if(first_line < 0 || (uint64_t)first_line > lines || lines - (uint64_t)first_line > s.ring) return VDL2HIP_E_INVAL;
+	const size_t n = std::min<size_t>(std::min<size_t>(cap_lines, (size_t)(lines - (uint64_t)first_line)), 0x7fffffffu);
+	if(n == 0 || (!mean && !max)) return (int)n;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	const size_t N = m.nfft, p0 = (size_t)((uint64_t)first_line & (s.ring - 1)), n0 = std::min<size_t>(n, s.ring - p0);
+	for(int k = 0; k < 2; k++) {
+		float *dst = k ? max : mean;
+		const float *plane = k ? s.buf.d_ring_max : s.buf.d_ring_mean;
+		if(!dst) continue;
+		HIPCHK(m.tap.fetch(dst, plane + p0 * N, n0 * N * sizeof(float)));
+		if(n0 < n) HIPCHK(m.tap.fetch(dst + n0 * N, plane, (n - n0) * N * sizeof(float)));
+	}
+	return (int)n;
+}
+// the bins of channel f: those within 12.5 kHz, or the nearest one (vdl2hip_spectrum_channels)
+template<typename F>
+static void channel_bins(const vdl2hip_ctx *c, double f, F take) {
+	const uint32_t N = c->mon.nfft;
+	const double fs = (double)(c->cfg.input_rate ? c->cfg.input_rate : (uint32_t)kSymbolRate * kSps * c->cfg.oversample), cf = (double)c->cfg.centerfreq;
+	double best = 0.0; bool any = false; uint32_t nearest = 0;
+	for(uint32_t i = 0; i < N; i++) {
+		const double d = std::fabs(cf + ((double)i - (double)(N / 2)) * fs / (double)N - f);
+		if(d <= 12500.0) { take(i); any = true; }
+		if(i == 0 || d < best) { best = d; nearest = i; }
+	}
+	if(!any) take(nearest);
+}
+int vdl2hip_specgram_channels(vdl2hip_ctx *c, float *peak_dbfs, float *floor_dbfs, size_t cap) {
+	if(!c || !c->spg.on || !c->mon.on) return VDL2HIP_E_INVAL;
+	const size_t nchan = c->all_freqs.size();
+	if((peak_dbfs || floor_dbfs) && cap < nchan) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	std::vector<float> hold;
+	{ int r = specgram_fetch_hold(c, hold); if(r != VDL2HIP_OK) return r; }
+	const uint32_t N = c->mon.nfft;
+	for(size_t ch = 0; ch < nchan; ch++) {
+		double peak = 0.0, sum = 0.0;
+		channel_bins(c, (double)c->all_freqs[ch], [&](uint32_t i) { peak = std::max(peak, (double)hold[i]); sum += (double)hold[N + i]; });
+		if(peak_dbfs) peak_dbfs[ch] = peak > 0.0 ? (float)(10.0 * std::log10(peak)) : -INFINITY;
+		if(floor_dbfs) floor_dbfs[ch] = sum > 0.0 ? (float)(10.0 * std::log10(sum / c->mon.enbw)) : -INFINITY;
+	}
+	return (int)nchan;
+}
+
 // ---- the input monitor (vdl2hip.h, "Input monitor"; kernels: spectrum.h) ----
 // Its share of a feed: on the front stream ahead of everything else that reads the block, so it is ordered with the copy into
 // d_in[k], with that buffer's reuse and with a caller's device buffer exactly as the channeliser is.
@@ -23,6 +183,19 @@ template<int FMT>
 static void launch_spectrum(vdl2hip_ctx *c, const SpecArgs &a, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
 	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->streams.front, e0, e1, 0, a)
 	switch(c->mon.nfft / c->mon.threads) {                           // samples per lane (spec_threads(): 1, 2, 4 up to N = 1024, 8, 16)
+		case 1: SPEC_LAUNCH(1); break;
+		case 2: SPEC_LAUNCH(2); break;
+		case 4: SPEC_LAUNCH(4); break;
+		case 8: SPEC_LAUNCH(8); break;
+		default: SPEC_LAUNCH(16); break;
+	}
+	#undef SPEC_LAUNCH
+}
+// the spectrogram's build of the same launch (specgram_plan)
+template<int FMT>
+static void launch_spectrum_lines(vdl2hip_ctx *c, const SpecArgs &a, const SpgArgs &sg, unsigned grid, hipEvent_t e0, hipEvent_t e1) {
+	#define SPEC_LAUNCH(PER) hipExtLaunchKernelGGL((k_spectrum_lines<FMT, PER>), dim3(grid), dim3(c->mon.threads), (uint32_t)c->mon.lds, c->streams.front, e0, e1, 0, a, sg)
+	switch(c->mon.nfft / c->mon.threads) {
 		case 1: SPEC_LAUNCH(1); break;
 		case 2: SPEC_LAUNCH(2); break;
 		case 4: SPEC_LAUNCH(4); break;
@@ -48,23 +221,30 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 	a.in = dev_in; a.carry_in = m.buf.d_carry[m.carry_sel]; a.carry_out = m.buf.d_carry[m.carry_sel ^ 1]; a.w = m.buf.d_w; a.tw = m.buf.d_tw; a.rows = m.buf.d_rows;
 	a.rel0 = (int64_t)(ja * N) - (int64_t)pos0; a.carry_rel = (int64_t)(j1 * N) - (int64_t)pos0; a.seg_step = (uint64_t)m.stride * N;
 	a.nin = (uint32_t)nin; a.ncarry = m.ncarry; a.ncarry_out = ncarry_out; a.nseg = (uint32_t)nseg;
-	a.run = (uint32_t)std::max<uint64_t>(1, (nseg + kSpecMaxRows - 1) / kSpecMaxRows); a.N = m.nfft; a.log2n = m.log2n;
-	const unsigned grid = (unsigned)std::max<uint64_t>(1, (nseg + a.run - 1) / a.run);      // (no segment: workgroup 0 still moves the carry on)
+	a.N = m.nfft; a.log2n = m.log2n;
+	uint32_t grid = 1;
+	spg_split(nseg, kSpecMaxRows, a.run, grid);                                             // (no segment: workgroup 0 still moves the carry on)
 	if(grid > kSpecMaxRows || (int64_t)a.ncarry + a.rel0 < 0) return VDL2HIP_E_INVAL;       // (never)
+	// the spectrogram, where it is on and the feed analyses a segment: its build of the kernel, and its combine kernel behind the reduction
+	const bool lines = c->spg.on && nseg != 0;
+	SpgArgs sg{};
+	if(lines && !specgram_plan(c, nseg, sg)) return VDL2HIP_E_INVAL;                        // (never)
 	OutSlot &sl = c->slot[c->feed_no % kSlots];
 	{ int r = collect_slot(c, sl); if(r != VDL2HIP_OK && r != VDL2HIP_E_OVERFLOW) return r; }   // (the feed is about to do the same) its events are about to be reused
 	KernelTimes &t = sl.mon_t;
 	t.arm(c->profiling >= 2);
-	with_fmt(c->in_fmt, [&](auto F) { launch_spectrum<F()>(c, a, grid, t.e(0), t.e(1)); });
+	if(lines) with_fmt(c->in_fmt, [&](auto F) { launch_spectrum_lines<F()>(c, a, sg, grid, t.e(0), t.e(1)); });
+	else with_fmt(c->in_fmt, [&](auto F) { launch_spectrum<F()>(c, a, grid, t.e(0), t.e(1)); });
 	if(nseg) {
 		const uint32_t W = m.nfft + kSpecLevels;
-		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), t.e(3), 0,
+		hipExtLaunchKernelGGL(k_spectrum_reduce, dim3((W + 255) / 256), dim3(256), 0u, c->streams.front, t.e(2), lines ? (hipEvent_t) nullptr : t.e(3), 0,
 		                      (const double *)m.buf.d_rows, m.buf.d_acc.get(), (uint32_t)grid, m.nfft);
+		if(lines) specgram_launch_combine(c, sg, t.e(3));                                   // (the second pair of events spans both)
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(m.tap.mark(c->streams.front));
 	t.launched(nseg ? 2 : 1);
-	m.segments += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
+	m.segments += nseg; m.ordinal += nseg; m.carry_sel ^= 1; m.ncarry = ncarry_out;
 	return VDL2HIP_OK;
 }
 // wait for what the monitor has queued and give its buffers back (event, stream and landing place stay with the context: m.tap;
@@ -72,6 +252,7 @@ static int monitor_block(vdl2hip_ctx *c, const void *dev_in, size_t nbytes) {
 static void monitor_free(vdl2hip_ctx *c) {
 	auto &m = c->mon;
 	if(m.tap.queued) (void)hipEventSynchronize(m.tap.last);
+	specgram_free(c);                                                // (a spectrogram's state would no longer mean anything)
 	m.buf = {};
 	for(auto &sl : c->slot) sl.mon_t.n = 0;
 	m.on = false; m.tap.queued = false; m.nfft = 0;
@@ -119,7 +300,7 @@ int vdl2hip_spectrum_enable(vdl2hip_ctx *c, const vdl2hip_spectrum_cfg *cfg) {
 	m.nfft = cfg->nfft; m.window = cfg->window; m.stride = cfg->stride ? cfg->stride : 1; m.log2n = d.log2n;
 	m.threads = spec_threads(m.nfft); m.lds = spec_lds_bytes(m.nfft);
 	m.sum_w = d.sum_w; m.enbw = d.enbw_bins;
-	m.pos = 0; m.segments = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
+	m.pos = 0; m.segments = 0; m.ordinal = 0; m.ncarry = 0; m.carry_sel = 0; m.kernel_ms = 0.0; m.tap.queued = false;
 	m.on = true;
 	return VDL2HIP_OK;
 }

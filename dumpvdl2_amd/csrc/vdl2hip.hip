@@ -149,7 +149,8 @@ struct OutSlot {
 	// has_chk: the walk noted decisions to a list that is checked
 	bool rest_pending = false, has_chk = false; int nseg = 1; int64_t seglen = 0; K4Args k4{}; SpecOut *d_spec_of = nullptr;
 	Event ev_stitch, ev_chk; DevBuf<uint32_t> d_rqflag2;
-	// profiling level 2: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor) /
+	// profiling level 2: this feed's k_resample (resampling receivers) / k_spectrum and k_spectrum_reduce (input monitor; with the
+	// spectrogram on k_spectrum_lines, and k_specgram_combine inside the second pair) /
 	// k_activity_power and k_activity_scan (activity monitor)
 	KernelTimes rs_t, mon_t, act_t;
 	// burst capture (capture.h): the feed's records, windows and totals, the IQ pool.  on: this feed's back end is followed by the
@@ -189,7 +190,15 @@ struct vdl2hip_ctx {
 		double sum_w = 0.0, enbw = 0.0; uint64_t pos = 0, segments = 0; uint32_t ncarry = 0; int carry_sel = 0;
 		struct { DevBuf<float> d_w; DevBuf<float2> d_tw, d_carry[2]; DevBuf<double> d_rows, d_acc; } buf;
 		TapRead tap; double kernel_ms = 0.0;
+		uint64_t ordinal = 0;                                         // analysed segments since enable (segments restarts with a read's reset)
 	} mon;
+	// Spectrogram (spectrum.h, specgram_plan.h, vdl2hip_specgram_*): off unless enabled, and only on top of the input monitor, whose
+	// launches, event, read stream and landing place it shares.  a0: the monitor's ordinal when it was enabled; seen: segments since;
+	// hold_*: what the holds cover; rows: workgroups the piece buffers have room for.  buf: given back as one (specgram_free)
+	struct {
+		bool on = false; uint32_t R = 0, ring = 0, rows = 0; uint64_t a0 = 0, seen = 0, hold_segments = 0, hold_lines = 0;
+		struct { DevBuf<double> d_piece_sum, d_carry_sum; DevBuf<float> d_piece_max, d_run_max, d_run_floor, d_ring_mean, d_ring_max, d_carry_max, d_hold; } buf;
+	} spg;
 	// Activity monitor (activity.h, vdl2hip_activity_*): off unless enabled.  k_on: the decimated samples made before it was enabled;
 	// bins: complete so far; carry: per channel the float32 sum of what the stream holds of the incomplete bin it stands in (two
 	// buffers, alternating); acc / st: the scan's accumulators and the transmission under way, per channel.
@@ -377,7 +386,7 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0);
 // on the way is the drain's to report, not theirs
 static int collect_all(vdl2hip_ctx *c) { const int r = collect_pending(c); return r == VDL2HIP_E_OVERFLOW ? VDL2HIP_OK : r; }
 
-#include "taps.inc"   // the five taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
+#include "taps.inc"   // the six taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
 
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;

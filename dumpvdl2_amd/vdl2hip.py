@@ -50,6 +50,7 @@ EXPORTS = [
     "vdl2hip_capture_enable", "vdl2hip_capture_disable", "vdl2hip_capture_info_get", "vdl2hip_capture_read",
     "vdl2hip_txlog_enable", "vdl2hip_txlog_disable", "vdl2hip_txlog_info_get", "vdl2hip_txlog_read",
     "vdl2hip_txsearch_enable", "vdl2hip_txsearch_disable", "vdl2hip_txsearch_info_get", "vdl2hip_txsearch_read",
+    "vdl2hip_specgram_enable", "vdl2hip_specgram_disable", "vdl2hip_specgram_read", "vdl2hip_specgram_lines", "vdl2hip_specgram_channels",
 ]
 # include/vdl2hip.h: VDL2HIP_TXSEARCH_UNDECODED_ONLY (cfg.flags), VDL2HIP_TXS_CLIPPED (vdl2hip_tx_search.flags, beside TX_PARTIAL), VDL2HIP_TXS_* (why)
 TXSEARCH_UNDECODED_ONLY, TXS_CLIPPED = 1, 2
@@ -99,6 +100,17 @@ class SpectrumInfo(C.Structure):
                 ("segments", C.c_uint64), ("samples", C.c_uint64), ("clipped", C.c_uint64),
                 ("enbw_bins", C.c_double), ("mean_power", C.c_double), ("dc_i", C.c_double), ("dc_q", C.c_double),
                 ("peak", C.c_float), ("kernel_ms", C.c_float)]
+
+
+class SpecgramCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("line_segments", C.c_uint32), ("ring_lines", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SpecgramInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32), ("stride", C.c_uint32),
+                ("line_segments", C.c_uint32), ("ring_lines", C.c_uint32), ("sample_rate", C.c_uint32), ("centerfreq", C.c_uint32),
+                ("first_segment", C.c_uint64), ("first_sample", C.c_uint64), ("lines", C.c_uint64),
+                ("hold_segments", C.c_uint64), ("hold_lines", C.c_uint64)]
 
 
 class ActivityCfg(C.Structure):
@@ -232,6 +244,12 @@ def load_library(path: str = None):
         L.vdl2hip_spectrum_enable.argtypes = [C.c_void_p, C.POINTER(SpectrumCfg)]
         L.vdl2hip_spectrum_read.argtypes = [C.c_void_p, C.POINTER(SpectrumInfo), C.c_void_p, C.c_size_t, C.c_int]
         L.vdl2hip_spectrum_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_specgram_enable"):               # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
+        L.vdl2hip_specgram_enable.argtypes = [C.c_void_p, C.POINTER(SpecgramCfg)]
+        L.vdl2hip_specgram_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_specgram_read.argtypes = [C.c_void_p, C.POINTER(SpecgramInfo), C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.vdl2hip_specgram_lines.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.vdl2hip_specgram_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     if hasattr(L, "vdl2hip_activity_enable"):               # (absent from older builds loaded through VDL2HIP_LIB for comparisons)
         L.vdl2hip_activity_edges.argtypes = [C.c_void_p, C.c_size_t]
         L.vdl2hip_activity_enable.argtypes = [C.c_void_p, C.POINTER(ActivityCfg)]
@@ -337,6 +355,33 @@ def _spectrum_read(Lib, ctx, reset: bool, power: bool) -> dict:
         out["freq_hz"] = info.centerfreq + (np.arange(n, dtype=np.float64) - n // 2) * (info.sample_rate / n)
         out["power"] = p
     return out
+
+
+def _specgram_read(Lib, ctx, reset: bool) -> dict:
+    """vdl2hip_specgram_read() on a context handle -> dict of every info field, plus max_hold, floor_hold (float32 [nfft]) and freq_hz"""
+    info = SpecgramInfo(C.sizeof(SpecgramInfo))
+    mx, fl = np.zeros(4096, dtype=np.float32), np.zeros(4096, dtype=np.float32)      # (the largest nfft: one call)
+    r = Lib.vdl2hip_specgram_read(ctx, C.byref(info), mx.ctypes.data, fl.ctypes.data, mx.size, int(reset))
+    if r < 0:
+        raise Vdl2HipError(f"vdl2hip_specgram_read: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    out = {k: getattr(info, k) for k, _ in SpecgramInfo._fields_ if k != "struct_size"}
+    n = info.nfft
+    out["freq_hz"] = info.centerfreq + (np.arange(n, dtype=np.float64) - n // 2) * (info.sample_rate / n)
+    out["max_hold"], out["floor_hold"] = mx[:n].copy(), fl[:n].copy()
+    return out
+
+
+def _specgram_lines(Lib, ctx, first: int, count: int):
+    """vdl2hip_specgram_lines() on a context handle -> (mean, max), float32 [lines, nfft]"""
+    info = SpecgramInfo(C.sizeof(SpecgramInfo))
+    r = Lib.vdl2hip_specgram_read(ctx, C.byref(info), None, None, 0, 0)
+    if r < 0:
+        raise Vdl2HipError(f"vdl2hip_specgram_read: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    mean, mx = np.zeros((max(0, count), r), dtype=np.float32), np.zeros((max(0, count), r), dtype=np.float32)
+    r = Lib.vdl2hip_specgram_lines(ctx, first, mean.ctypes.data, mx.ctypes.data, mean.shape[0])
+    if r < 0:
+        raise Vdl2HipError(f"vdl2hip_specgram_lines: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return mean[:r], mx[:r]
 
 
 def activity_edges() -> np.ndarray:
@@ -689,6 +734,32 @@ class Receiver:
         out = np.zeros(len(self.freqs), dtype=np.float32)
         self._chk(self.L.vdl2hip_spectrum_channels(self.h, out.ctypes.data, out.size), "vdl2hip_spectrum_channels")
         return out
+
+    def specgram_enable(self, line_segments: int = 16, ring_lines: int = 0) -> None:
+        """switch the spectrogram on from the next feed, on top of the input monitor (vdl2hip.h, "Spectrogram"): per bin the maximum
+        since enable, the quietest line, and the last ring_lines lines of line_segments analysed segments each (mean and maximum;
+        ring_lines a power of two, 0: what one feed can complete, plus one)."""
+        cfg = SpecgramCfg(C.sizeof(SpecgramCfg), line_segments, ring_lines, 0)
+        self._chk(self.L.vdl2hip_specgram_enable(self.h, C.byref(cfg)), "vdl2hip_specgram_enable")
+
+    def specgram_disable(self) -> None:
+        self._chk(self.L.vdl2hip_specgram_disable(self.h), "vdl2hip_specgram_disable")
+
+    def specgram(self, reset: bool = False) -> dict:
+        """every field of vdl2hip_specgram_info, `max_hold` and `floor_hold` (float32 [nfft], ascending frequency, 1.0 = a full-scale
+        tone on a bin) and `freq_hz`.  reset: zero the holds and their counts afterwards (lines and the ring stay)."""
+        return _specgram_read(self.L, self.h, reset)
+
+    def specgram_lines(self, first: int, count: int):
+        """up to `count` lines from line `first` on -> (mean, max), float32 [lines, nfft]"""
+        return _specgram_lines(self.L, self.h, first, count)
+
+    def specgram_channels(self):
+        """(peak_dbfs, floor_dbfs), float32 [nchan]: per channel of the frequency list the strongest max_hold bin and the floor_hold
+        power in +-12.5 kHz (vdl2hip_specgram_channels)"""
+        peak, floor = np.zeros(len(self.freqs), dtype=np.float32), np.zeros(len(self.freqs), dtype=np.float32)
+        self._chk(self.L.vdl2hip_specgram_channels(self.h, peak.ctypes.data, floor.ctypes.data, peak.size), "vdl2hip_specgram_channels")
+        return peak, floor
 
     def activity_enable(self, bin_samples: int = 105, threshold_dbfs: float = -40.0, hang_bins: int = 0, series_bins: int = 0) -> None:
         """switch the activity monitor on from the next feed (vdl2hip.h, "Activity monitor"): the power of every channel's decimated

@@ -52,7 +52,9 @@ extern "C" {
                                  *    vdl2hip_stats.referee_symbol_pieces_ahead / _late (at its end, as resampled_samples was: a caller built against the
                                  *    shorter structure goes through vdl2hip_get_stats_sized() or never reads them), so the version stayed
                                  *    vdl2hip_txsearch_enable() / _disable() / _info_get() / _read() with vdl2hip_txsearch_cfg / _info and
-                                 *    vdl2hip_tx_search: the preamble search, off unless enabled - new entry points and structures only, so the version stayed */
+                                 *    vdl2hip_tx_search: the preamble search, off unless enabled - new entry points and structures only, so the version stayed
+                                 *    vdl2hip_specgram_enable() / _disable() / _read() / _lines() / _channels() with vdl2hip_specgram_cfg / _info: the
+                                 *    spectrogram on top of the input monitor, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -195,6 +197,58 @@ typedef struct {
 	float    peak, kernel_ms;                  /* kernel_ms: summed HIP-event time of the monitor's launches at profiling level 2, else 0
 	                                            * (of the feeds collected so far: after vdl2hip_sync(), all of them) */
 } vdl2hip_spectrum_info;                       /* 88 bytes */
+
+/* Spectrogram (not in the reference): a tap on top of the input monitor that keeps what an average hides - VDL2 is bursts of a few
+ * milliseconds at a duty cycle of a few percent, and a burst in a share d of the segments at a signal-to-floor ratio s lifts the
+ * averaged bin by 10 log10(1 + d s) dB only (0.4 dB for a 20 dB burst at 0.1 %).  Per bin: the maximum since enable (max_hold), the
+ * quietest line (floor_hold) and the last ring_lines time lines of mean and maximum (a waterfall).  Off unless enabled; with it off
+ * nothing of it is launched or allocated and the monitor launches exactly the kernels it always did.  On, frames, counters, the
+ * decimated stream and every other tap are exactly what they were, and the monitor's own results stay inside its determinism clause
+ * (the tap's build of the kernel adds the same values in the same order; nothing but the order of float64 additions could move).
+ *  - Segments.  The monitor's: N = nfft, window w, stride, the analysed segments and their transforms X_s exactly as the monitor
+ *    forms them.  q_s[i] = |X_s[(i + N / 2) mod N]|^2 is the float32 value the monitor adds to its sums (re re + im im, two
+ *    products and a sum in float32); i ascends in frequency like power[].  norm = 1 / (sum_n w[n])^2 in double.
+ *  - Ordinals.  Analysed segments are numbered a = 0, 1, ... from vdl2hip_spectrum_enable() (a reset of vdl2hip_spectrum_read() does
+ *    not restart them).  a0 = the number of them complete when vdl2hip_specgram_enable() is called; the tap sees segment a iff
+ *    a >= a0 - a segment begun before the enable and completed after it counts.  Which segments it sees, and everything below,
+ *    depends on the stream and on a0 alone, not on how the stream was cut into feeds.
+ *  - Lines.  R = line_segments, 1 <= R <= 2^20; 0 means 16.  Line l covers the analysed segments a0 + l R .. a0 + (l + 1) R - 1 and
+ *    exists once the last of them is complete.  line_mean[l][i] = (float)(sum_s q_s[i] norm / R), the sum in float64, narrowed
+ *    once; line_max[l][i] = (float)((double)max_s q_s[i] norm), the maximum a float32 comparison.  A line that straddles feeds is
+ *    finished from state carried on the device: a float64 partial sum and a float32 maximum per bin.  Line l begins at the monitor's
+ *    sample (a0 + l R) stride N and spans R stride N samples.
+ *  - Hold, since enable or the last reset:  max_hold[i] = (float)((double)max q_s[i] norm) over every segment seen, those of a line
+ *    not yet complete included, so that a single segment of burst is caught; all zero while hold_segments == 0.
+ *    floor_hold[i] = min over the lines completed since then of line_mean[l][i], a float32 minimum of exactly the values the ring
+ *    received; all zero while hold_lines == 0.  It is the quietest line: a floor estimate that bursts cannot lift - and, being a
+ *    minimum, biased low: for exponentially distributed |X|^2 some 2.8 dB under the average floor for R = 16 over 62 lines, less
+ *    for a larger R.
+ *  - Ring.  The device keeps the last ring_lines lines, mean and max as float32 planes: a power of two, raised to at least the
+ *    lines one feed of max_block_bytes can complete, plus one; 0 means that minimum.  ring_lines nfft > 2^25 is refused
+ *    (VDL2HIP_E_INVAL) before anything is allocated, as is a ring_lines that is not a power of two.
+ *  - Determinism.  The same sequence of calls gives the same bytes (no floating-point atomics).  The same stream cut differently
+ *    gives line_max, max_hold and all counts exactly, and line_mean - hence floor_hold - equal or adjacent float32 values: only the
+ *    order of the float64 additions moves, below 1e-12 relative before the narrowing.  Within one run floor_hold equals the minimum
+ *    of the delivered line_mean values bit for bit.
+ *  - Accuracy against the float64 definition: per segment the monitor's bound  b_s[i] = (2 e |X[k]| ||X||_2 + e^2 ||X||_2^2 +
+ *    4 2^-24 |X[k]|^2) norm,  e = log2 N 2^-24.  line_mean is within the mean of b_s over the line plus one float32 rounding of the
+ *    result; line_max and max_hold within the largest b_s[i] among the segments covered plus that rounding
+ *    (|max a - max b| <= max |a - b|).
+ *  - Reset (of vdl2hip_specgram_read) zeroes max_hold, floor_hold, hold_segments and hold_lines after the copy.  Line numbering,
+ *    the ring and the line under way are untouched.  A reset of vdl2hip_spectrum_read() does not touch the tap.
+ *  - Switching.  vdl2hip_spectrum_enable() switches a running spectrogram off first, also with nfft 0.  vdl2hip_specgram_enable()
+ *    with the monitor off is VDL2HIP_E_INVAL.  Enabling again restarts at the then-current a0 with zeroed state.
+ *  - Groups get no group call: vdl2hip_group_ctx(g, 0) is the handle.  A resampling receiver's tap sees the caller's stream, as
+ *    its monitor does.  Time spent in the tap's launches is part of vdl2hip_spectrum_info.kernel_ms. */
+typedef struct { uint32_t struct_size, line_segments, ring_lines, reserved; } vdl2hip_specgram_cfg;   /* 16 bytes; 0 = 16 lines, the smallest ring; reserved must be 0 */
+typedef struct {
+	uint32_t struct_size, nfft, window, stride, line_segments, ring_lines;   /* as in force */
+	uint32_t sample_rate, centerfreq;
+	uint64_t first_segment;                    /* a0 */
+	uint64_t first_sample;                     /* a0 * stride * nfft, in the monitor's sample count */
+	uint64_t lines;                            /* complete so far */
+	uint64_t hold_segments, hold_lines;        /* what max_hold / floor_hold cover */
+} vdl2hip_specgram_info;                       /* 72 bytes */
 
 /* Activity monitor (not in the reference, which reports what it decoded and nothing about what else was on a channel): an optional
  * power envelope of every channel's DECIMATED stream in fixed time bins, and from it the share of time a channel is occupied, the
@@ -650,6 +704,25 @@ int  vdl2hip_spectrum_read(vdl2hip_ctx *ctx, vdl2hip_spectrum_info *info, double
  * with B_c = { i : |f_i - freqs[c]| <= 12500 Hz }, or the single nearest bin if that set is empty,
  * dbfs[c] = 10 log10(sum_{B_c} power[i] / enbw_bins), -INFINITY if the sum is 0.  Returns nchan; VDL2HIP_E_TOOBIG if cap < nchan. */
 int  vdl2hip_spectrum_channels(vdl2hip_ctx *ctx, float *dbfs, size_t cap);
+
+/* ---- Spectrogram (see "Spectrogram" above) ----
+ * Switch the tap on.  Allowed between feeds with the input monitor on; takes effect with the next feed.  VDL2HIP_E_INVAL for the
+ * monitor off, a bad struct_size, reserved, line_segments or ring_lines, before anything is allocated or changed: a tap that was on
+ * stays as it was. */
+int  vdl2hip_specgram_enable(vdl2hip_ctx *ctx, const vdl2hip_specgram_cfg *cfg);
+int  vdl2hip_specgram_disable(vdl2hip_ctx *ctx);
+/* The holds.  Waits only for the monitor's own work queued so far (its event and read stream, as vdl2hip_spectrum_read() does) and
+ * delivers no frames.  info->struct_size must be set; info, max_hold and floor_hold may each be NULL; an array given needs
+ * cap >= nfft, else VDL2HIP_E_TOOBIG.  `reset`: see above.  Tap off: VDL2HIP_E_INVAL.  Returns nfft. */
+int  vdl2hip_specgram_read(vdl2hip_ctx *ctx, vdl2hip_specgram_info *info, float *max_hold, float *floor_hold, size_t cap, int reset);
+/* Lines first_line .. of the ring, at most cap_lines of them, row-major [line][nfft]; mean or max may be NULL.  Returns the count
+ * (0 is legal for first_line == lines); VDL2HIP_E_INVAL for a line older than the ring holds or beyond `lines`. */
+int  vdl2hip_specgram_lines(vdl2hip_ctx *ctx, int64_t first_line, float *mean, float *max, size_t cap_lines);
+/* Host arithmetic on the hold arrays, for all nchan channels of cfg.freqs, with vdl2hip_spectrum_channels()'s bin set B_c:
+ * peak_dbfs[c] = 10 log10(max over B_c of max_hold[i])                  - tone-referred: the strongest bin
+ * floor_dbfs[c] = 10 log10(sum over B_c of floor_hold[i] / enbw_bins)   - the channel's floor in its bandwidth
+ * -INFINITY where the argument is 0; either array may be NULL; returns nchan; VDL2HIP_E_TOOBIG if cap < nchan. */
+int  vdl2hip_specgram_channels(vdl2hip_ctx *ctx, float *peak_dbfs, float *floor_dbfs, size_t cap);
 
 /* ---- Activity monitor (see "Activity monitor" above) ----
  * The histogram's 63 edges: returns 63 and writes edges[0 .. 63) if cap >= 63, else VDL2HIP_E_TOOBIG.  Host only, needs no GPU. */

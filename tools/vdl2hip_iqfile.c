@@ -153,6 +153,27 @@ static int drop_tx(vdl2hip_ctx *rx) {
 	for(;;) { const int n = vdl2hip_txlog_read(rx, rec, 256); if(n <= 0) return n; }
 }
 
+/* --waterfall-mean / --waterfall-max: the spectrogram's lines completed since the last call, appended as raw float32, nfft values per
+ * line - after every drain, so that the ring never has to hold the whole file */
+static FILE *wf_mean, *wf_max;
+static int64_t wf_next;
+static int take_lines(vdl2hip_ctx *rx) {
+	static float mean[16 * 4096], max[16 * 4096];
+	vdl2hip_specgram_info gi;
+	memset(&gi, 0, sizeof gi); gi.struct_size = sizeof gi;
+	int n = vdl2hip_specgram_read(rx, &gi, NULL, NULL, 0, 0);
+	if(n < 0) return n;
+	const size_t nfft = (size_t)n, room = sizeof mean / sizeof mean[0] / nfft;
+	while((uint64_t)wf_next < gi.lines) {
+		n = vdl2hip_specgram_lines(rx, wf_next, wf_mean ? mean : NULL, wf_max ? max : NULL, room);
+		if(n <= 0) return n < 0 ? n : VDL2HIP_E_INVAL;
+		if(wf_mean) fwrite(mean, sizeof(float), (size_t)n * nfft, wf_mean);
+		if(wf_max) fwrite(max, sizeof(float), (size_t)n * nfft, wf_max);
+		wf_next += n;
+	}
+	return 0;
+}
+
 static void on_frame(const vdl2hip_frame *f, void *user) {
 	(void)user;
 	nframes++;
@@ -173,6 +194,8 @@ static void on_frame(const vdl2hip_frame *f, void *user) {
 int main(int argc, char **argv) {
 	const char *infile = NULL, *rawpath = NULL, *statsd_path = NULL, *spectrum_path = NULL;
 	uint32_t spectrum_nfft = 1024, spectrum_window = VDL2HIP_WIN_HANN;
+	const char *waterfall_path = NULL, *wf_mean_path = NULL, *wf_max_path = NULL;
+	uint32_t waterfall_segments = 0;
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
 	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL, *tx_search_path = NULL;
@@ -211,6 +234,10 @@ int main(int argc, char **argv) {
 			else if(!strcmp(argv[i], "bh4")) spectrum_window = VDL2HIP_WIN_BH4;
 			else { fprintf(stderr, "Unknown spectrum window\n"); return 1; }
 		}
+		else if(!strcmp(a, "--waterfall-out")) { NEEDARG(); waterfall_path = argv[++i]; }
+		else if(!strcmp(a, "--waterfall-segments")) { NEEDARG(); waterfall_segments = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--waterfall-mean")) { NEEDARG(); wf_mean_path = argv[++i]; }
+		else if(!strcmp(a, "--waterfall-max")) { NEEDARG(); wf_max_path = argv[++i]; }
 		else if(!strcmp(a, "--activity-out")) { NEEDARG(); activity_path = argv[++i]; }
 		else if(!strcmp(a, "--activity-bin")) { NEEDARG(); activity_bin = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--activity-threshold")) { NEEDARG(); activity_thr = strtof(argv[++i], NULL); }
@@ -230,6 +257,7 @@ int main(int argc, char **argv) {
 	if(!infile) { fprintf(stderr, "usage: %s --iq-file <file|-> [--sample-format U8|S16_LE|CF32|S8] [--sample-rate Hz] [--oversample n] [--centerfreq Hz] "
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
+			"[--waterfall-out file] [--waterfall-segments R] [--waterfall-mean file] [--waterfall-max file] "
 			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] "
 			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
@@ -267,11 +295,18 @@ int main(int argc, char **argv) {
 	if(r != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_create: %s\n", vdl2hip_strerror(r)); return 3; }
 
 	if(avlc_filter) vdl2hip_set_avlc_filter(rx, 1);
-	if(spectrum_path) {
+	const int waterfall = waterfall_path || wf_mean_path || wf_max_path;
+	if(spectrum_path || waterfall) {                                           /* (the spectrogram sits on top of the input monitor) */
 		vdl2hip_spectrum_cfg sc = { sizeof sc, spectrum_nfft, spectrum_window, 1 };
 		if(spectrum_nfft == 0 || (r = vdl2hip_spectrum_enable(rx, &sc)) != VDL2HIP_OK) {
 			fprintf(stderr, "vdl2hip_spectrum_enable: %s\n", vdl2hip_strerror(spectrum_nfft ? r : VDL2HIP_E_INVAL)); return 3;
 		}
+	}
+	if(waterfall) {
+		vdl2hip_specgram_cfg gc = { sizeof gc, waterfall_segments, 0, 0 };
+		if((r = vdl2hip_specgram_enable(rx, &gc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_specgram_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(wf_mean_path && !(wf_mean = fopen(wf_mean_path, "w"))) { perror("Could not open waterfall mean output"); return 2; }
+		if(wf_max_path && !(wf_max = fopen(wf_max_path, "w"))) { perror("Could not open waterfall max output"); return 2; }
 	}
 	if(activity_path || tx_path || tx_search_path) {
 		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
@@ -303,6 +338,7 @@ int main(int argc, char **argv) {
 		if(len != FILE_BUFSIZE) vdl2hip_set_drain_lag(rx, 0);                   /* the last feed: every frame out */
 		if((r = vdl2hip_feed(rx, buf, held)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_feed: %s\n", vdl2hip_strerror(r)); return 3; }
 		if((r = vdl2hip_drain(rx, on_frame, NULL)) < 0) { fprintf(stderr, "vdl2hip_drain: %s\n", vdl2hip_strerror(r)); return 3; }
+		if((wf_mean || wf_max) && (r = take_lines(rx)) < 0) { fprintf(stderr, "vdl2hip_specgram_lines: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_search_path && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
@@ -313,6 +349,8 @@ int main(int argc, char **argv) {
 	uint64_t cnt[VDL2HIP_NUM_COUNTERS];
 	static float level[1024];
 	const int have_levels = spectrum_path && vdl2hip_spectrum_channels(rx, level, 1024) == (int)nfreq;
+	static float wf_peak[1024], wf_floor[1024];
+	const int have_holds = waterfall && vdl2hip_specgram_channels(rx, wf_peak, wf_floor, 1024) == (int)nfreq;
 	static vdl2hip_activity_chan act[1024];
 	vdl2hip_activity_info ai;
 	memset(&ai, 0, sizeof ai); ai.struct_size = sizeof ai;
@@ -323,6 +361,7 @@ int main(int argc, char **argv) {
 					freqs[c], cnt[VDL2HIP_CNT_SYNC_GOOD], cnt[VDL2HIP_CNT_CRC_GOOD], cnt[VDL2HIP_CNT_BLOCKS_FEC_OK],
 					cnt[VDL2HIP_CNT_BLOCKS_PROCESSED], cnt[VDL2HIP_CNT_MSG_GOOD], cnt[VDL2HIP_CNT_ERR_FEC_BAD]);
 			if(have_levels) fprintf(stderr, " level=%.2f dBFS", (double)level[c]);
+			if(have_holds) fprintf(stderr, " peak=%.2f dBFS floor=%.2f dBFS", (double)wf_peak[c], (double)wf_floor[c]);
 			if(nact == (int)nfreq) fprintf(stderr, " busy=%.2f%% tx=%" PRIu64, act[c].bins ? 100.0 * (double)act[c].busy_bins / (double)act[c].bins : 0.0, act[c].transmissions);
 			fprintf(stderr, "\n");
 		}
@@ -349,6 +388,26 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "spectrum not written: %s\n", n < 0 ? vdl2hip_strerror(n) : "cannot open file");
+	}
+	if(wf_mean) fclose(wf_mean);
+	if(wf_max) fclose(wf_max);
+	if(waterfall_path) {
+		static float max_hold[4096], floor_hold[4096];
+		vdl2hip_specgram_info gi;
+		memset(&gi, 0, sizeof gi); gi.struct_size = sizeof gi;
+		int n = vdl2hip_specgram_read(rx, &gi, max_hold, floor_hold, 4096, 0);
+		FILE *so = n > 0 ? fopen(waterfall_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# nfft %u\n# window %u\n# stride %u\n# line_segments %u\n# ring_lines %u\n# sample_rate %u\n# centerfreq %u\n", gi.nfft, gi.window, gi.stride,
+					gi.line_segments, gi.ring_lines, gi.sample_rate, gi.centerfreq);
+			fprintf(so, "# first_segment %" PRIu64 "\n# first_sample %" PRIu64 "\n# lines %" PRIu64 "\n# hold_segments %" PRIu64 "\n# hold_lines %" PRIu64 "\n",
+					gi.first_segment, gi.first_sample, gi.lines, gi.hold_segments, gi.hold_lines);
+			for(int i = 0; i < n; i++)                                              /* freq_hz max_dbfs floor_dbfs */
+				fprintf(so, "%.3f %.4f %.4f\n", (double)gi.centerfreq + ((double)i - (double)(n / 2)) * (double)gi.sample_rate / (double)n,
+						dbfs_of((double)max_hold[i]), dbfs_of((double)floor_hold[i]));
+			fclose(so);
+		}
+		else fprintf(stderr, "waterfall not written: %s\n", n < 0 ? vdl2hip_strerror(n) : "cannot open file");
 	}
 	if(activity_path) {
 		FILE *so = nact == (int)nfreq ? fopen(activity_path, "w") : NULL;
