@@ -1450,10 +1450,19 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 // float instructions - then runs with the 7 lanes of 64 that have a sample to evaluate, word after word, in wavefronts that mostly
 // wait: 0.68 ms for what is 0.1 ms of issue (profiles/exact_tier_before.txt).  Here a workgroup does the same work on its
 // 256 * wpl words (wpl up to kK3dRounds: thousands of words, so that its evaluations fill wavefronts) in three steps:
-//   list      256 flag words at a time, a lane each, as above (cand = 0 where there is nothing to do); the busy words go on a list
+//   list      256 flag words a pass, a lane each, as above (cand = 0 where there is nothing to do); the busy words go on a list
 //             in LDS - the word, its work mask `need`, which of the six samples before it are tabulated - together with the running
-//             count of samples to evaluate: one LDS atomic per wavefront and pass, none in global memory.  Once kK3dFlush
-//             evaluations are waiting (and at the end) the list is worked off:
+//             count of samples to evaluate: one LDS atomic per wavefront and pass, none in global memory.  EVERY WAVEFRONT LISTS ITS
+//             QUARTER OF THE PASSES ON ITS OWN - it fetches the flag words of its 64 lanes of kK3dGroup passes (and the two before and
+//             the one after each 64) into its own piece of LDS, and goes from pass to pass without a workgroup barrier: nothing in
+//             the list step reads what another wavefront wrote, the place on the list is the atomic's answer.  A word in a hundred is
+//             busy, so as a rule all wpl passes are on the list behind ONE barrier.  The list is bounded (kK3dList words): a
+//             wavefront whose reservation would run past the end writes nothing, notes where the list therefore ends (s_lim: the
+//             atomic hands out places in one order, so whoever reserves after it fails too, and the records in front of it are
+//             complete), and waits at the barrier with that pass still to do; the workgroup works the list off and the wavefronts
+//             carry on where they stopped - every flagged sample (screen_all, a channel full of bursts) is two passes a round.
+//             The order of the list depends on how the wavefronts interleave; nothing downstream depends on it (below).
+//             Then the list is worked off:
 //   evaluate  in tiles of whole words with at most kK3dEvals evaluations.  ONE LANE PER EVALUATION, 256 at a time, whichever word
 //             it belongs to: the lane loads its sixteen taps (and, for the referee, the three predecessors of each) and runs the
 //             reference's metric on them in the same operation order as above;
@@ -1465,15 +1474,18 @@ __global__ __launch_bounds__(256, 4) void k_sync_exact4(K3Args a) {
 // Every value is the one the word-at-a-time form computes, bit for bit: the arithmetic of an evaluation depends on its sample
 // alone, and the six samples before a word are evaluated for that word again, as there.
 constexpr int kK3dEvals = 320;           // evaluations per tile; a word has at most 64 + 6
-constexpr int kK3dFlush = kK3dEvals - 64;      // evaluations waiting before the list is worked off: the tile is then all but full
-constexpr int kK3dList = kK3dFlush + 256;      // words on the list at most: fewer than kK3dFlush waiting (a word has an evaluation at least) + a pass
-constexpr int kK3dMinGroups = 2048;       // workgroups the chip should have at least: 256 channels x 16 s then take 8 passes (3 328 workgroups), which beat 4, 16 and 32 (profiles/exact_tier_ab.txt)
-constexpr int kK3dGroup = 4;             // passes whose flag words are fetched at once
+constexpr int kK3dList = 512;            // words on the list at most (a wavefront's pass adds up to 64)
+#ifndef VDL2_K3D_MIN_GROUPS
+#define VDL2_K3D_MIN_GROUPS 2048
+#endif
+constexpr int kK3dMinGroups = VDL2_K3D_MIN_GROUPS;   // workgroups the chip should have at least (profiles/exact_tier_passes_ab.txt)
+constexpr int kK3dGroup = 4;             // passes whose flag words a wavefront fetches at once
+constexpr int kK3dSpan = 64 + 3;         // ... per pass: its 64 words, the two before and the one after
 constexpr int kK3dRounds = 32;           // passes of 256 words per workgroup at most (vdl2hip.hip: fewer when that leaves the chip short of workgroups)
-static_assert(kK3dEvals >= 70 && kK3dEvals <= 512 && kK3dList * 70 < (1 << 20) && kK3dList < (1 << 11) && kK3dRounds * 256 <= (1 << 16),
-              "tile map: 9 bits of word, 7 of position; list head: 11 bits of words, 21 of evaluations; 16 bits of word index");
+static_assert(kK3dEvals >= 70 && kK3dEvals <= 512 && (kK3dList + 256) * 70 < (1 << 20) && kK3dList + 256 < (1 << 11) && kK3dList >= 64 && kK3dRounds * 256 <= (1 << 16),
+              "tile map: 9 bits of word, 7 of position; list head: 11 bits of words, 21 of evaluations - the list and, past its end, one refused reservation per wavefront; 16 bits of word index");
 // (a workgroup barrier that orders LDS alone: the kernel's threads hand nothing to each other through global memory, and a barrier
-// that waited for the cand / pf stores in flight would cost every pass of the list a trip to memory - 7 600 clocks a pass, measured)
+// that waited for the cand / pf stores in flight would cost a trip to memory - 7 600 clocks, measured)
 #define K3D_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while(0)
 template<bool FULL>
 __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
@@ -1490,10 +1502,12 @@ __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
 	__shared__ uint16_t s_map[kK3dEvals];
 	__shared__ float s_res[5][kK3dEvals];
 	__shared__ uint8_t s_neg[kK3dEvals];
-	__shared__ uint32_t s_head, s_r1;
-	// the flag words of kK3dGroup passes, and the two before and the one after them: one trip to memory for the group
-	__shared__ uint64_t s_flag[256 * kK3dGroup + 3];
-	const int c = blockIdx.y, tid = threadIdx.x, lane = threadIdx.x & 63;
+	// the list's head (words in the low 11 bits, evaluations above), where it ends if a reservation was refused, whether a
+	// wavefront has passes left
+	__shared__ uint32_t s_head, s_lim, s_more, s_r1;
+	// per wavefront: the flag words of its lanes of kK3dGroup passes, with the two before and the one after: one trip to memory for the group
+	__shared__ uint64_t s_flag[4][kK3dGroup][kK3dSpan];
+	const int c = blockIdx.y, tid = threadIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const cf32 *y = a.y + (size_t)c * a.cap;
 	const uint64_t *flag = a.flag + (size_t)c * (a.cap >> 6);
 	uint64_t *cand = a.cand + (size_t)c * (a.cap >> 6);
@@ -1504,27 +1518,48 @@ __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
 	const int64_t w0 = a.nbase >> 6, w1 = (a.k1 + 63) >> 6;
 	const int64_t wb = w0 + (int64_t)blockIdx.x * (256 * a.wpl);      // first word of this workgroup
 	K3B_BEGIN();
-	if(tid == 0) s_head = 0u;
+	if(tid == 0) { s_head = 0u; s_lim = ~0u; s_more = 0u; }
 	K3D_BARRIER();
-	#pragma unroll 1
-	for(int g = 0; g < a.wpl; g++) {
-		// ---- list ----
-		if(g % kK3dGroup == 0) {
-			// (words before nbase hold the previous feed's flags; none before the stream's first word or after the feed's last)
-			const int ng = a.wpl - g < kK3dGroup ? a.wpl - g : kK3dGroup;
-			for(int i = tid; i < 256 * ng + 3; i += 256) {
-				const int64_t w = wb + 256 * g - 2 + i;
-				s_flag[i] = w >= 0 && w < w1 ? flag[(uint32_t)w & wmask] : 0ull;
+	int gw = 0, gl = -1;      // (uniform in the wavefront) its next pass; the first pass of the group whose flag words it holds
+	for(;;) {
+		// ---- list: this wavefront's lanes of the passes it has left, no workgroup barrier between them ----
+		// (ll: the lane, as a value the compiler takes for new in every round.  What the list step derives from it - addresses, lane
+		// masks - is then worked out here, where registers are free, and not kept alive across the evaluations, which have none to
+		// spare: spilled, each of them cost every pass a scratch load and a wait for ALL memory operations in flight, the cand
+		// stores of the pass before among them - half a dozen trips to memory a pass, 8 000 clocks; profiles/exact_tier_passes.txt.
+		// For the same reason the loop's control is scalar: readfirstlane / readlane, no branch on a vector value.
+		// This leans on the register allocator and nothing in the build holds it to it.  To check after a compiler change: build
+		// with -save-temps and read this kernel's assembly - between the pass loop's header and its back edge there must be no
+		// scratch_load and no s_waitcnt vmcnt (the group's flag fetch, once in four passes, has the only one); section 3 of
+		// profiles/exact_tier_passes.txt has the figures of the build this was measured on.)
+		int ll = lane;
+		asm volatile("" : "+v"(ll));
+		const int tl = 64 * wave + ll;
+		#pragma unroll 1
+		for(; gw < a.wpl; gw++) {
+			const int gb = gw & ~(kK3dGroup - 1);
+			if(gl != gb) {
+				// (words before nbase hold the previous feed's flags; none before the stream's first word or after the feed's last)
+				const int ng = a.wpl - gb < kK3dGroup ? a.wpl - gb : kK3dGroup;
+				uint64_t va[kK3dGroup], vb[kK3dGroup];
+				#pragma unroll
+				for(int ps = 0; ps < kK3dGroup; ps++) {
+					const int64_t w = wb + 256 * (gb + ps) + tl - 2;           // lane l: word - 2 + l of the pass; lanes 0..2 also + 64
+					va[ps] = ps < ng && w >= 0 && w < w1 ? flag[(uint32_t)w & wmask] : 0ull;
+					vb[ps] = ps < ng && ll < kK3dSpan - 64 && w + 64 < w1 ? flag[(uint32_t)(w + 64) & wmask] : 0ull;
+				}
+				WAVE_SYNC();                                                // (the lanes have read the group before)
+				#pragma unroll
+				for(int ps = 0; ps < kK3dGroup; ps++) { s_flag[wave][ps][ll] = va[ps]; if(ll < kK3dSpan - 64) s_flag[wave][ps][64 + ll] = vb[ps]; }
+				WAVE_SYNC();
+				gl = gb;
 			}
-			K3D_BARRIER();
-		}
-		{
-			const int64_t w = wb + 256 * g + tid;
-			const int fi = 256 * (g % kK3dGroup) + tid;                  // s_flag[fi]: word w - 2
+			const int64_t w = wb + 256 * gw + tl;
+			const uint64_t *sf = &s_flag[wave][gw - gb][ll];                 // sf[0]: word w - 2
 			uint64_t need = 0, fprev = 0, fpp = 0, f0 = 0;
 			if(w < w1) {
-				f0 = s_flag[fi + 2]; fprev = s_flag[fi + 1]; fpp = s_flag[fi];
-				const uint64_t fnext = s_flag[fi + 3];
+				f0 = sf[2]; fprev = sf[1]; fpp = sf[0];
+				const uint64_t fnext = sf[3];
 				need = f0 | (f0 << 3) | (f0 >> 3) | (fprev >> 61) | (fnext << 61);
 				const int64_t base = w << 6;
 				if(a.k1 - 3 < base + 64) {                                      // right neighbour n+3 not there yet
@@ -1532,7 +1567,6 @@ __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
 					need |= lo <= 0 ? ~0ull : (~0ull << lo);
 				}
 				if(a.k1 < base + 64) need &= (a.k1 - base <= 0) ? 0ull : (~0ull >> (64 - (a.k1 - base)));   // samples that exist
-				if(need == 0) cand[(uint32_t)w & wmask] = 0;
 			}
 			// which of the six samples before the word have a tabulated metric: the last six bits of the previous word's work mask
 			// (none before the stream's first sample)
@@ -1543,23 +1577,38 @@ __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
 			const uint32_t inc = cnt << 11 | (need != 0 ? 1u : 0u);
 			uint32_t incl = inc;
 			#pragma unroll
-			for(int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)incl, d); if(lane >= d) incl += o; }
-			const uint32_t tot = (uint32_t)__shfl((int)incl, 63);
+			for(int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)incl, d); if(ll >= d) incl += o; }
+			const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 			uint32_t at = 0;
-			if(lane == 0 && tot != 0) at = atomicAdd(&s_head, tot);
-			at = (uint32_t)__shfl((int)at, 0) + incl - inc;
+			if(tot != 0) {
+				if(ll == 0) at = atomicAdd(&s_head, tot);
+				at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+				if((at & 2047u) + (tot & 2047u) > (uint32_t)kK3dList) {
+					// no room: the list ends where this reservation begins (or where an earlier refused one does); the head stays past the
+					// end, so that every later reservation of the round is refused as well.  The pass is done again behind the tiles.
+					if(ll == 0) { atomicMin(&s_lim, at); s_more = 1u; }
+					break;
+				}
+			}
+			if(w < w1 && need == 0) {
+				uint64_t zero = 0ull;                                          // (made here: as a constant it was kept in scratch, see above)
+				asm volatile("" : "+v"(zero));
+				cand[(uint32_t)w & wmask] = zero;
+			}
 			if(need != 0) {
-				const uint32_t r = at & 2047u;
-				s_need[r] = need; s_fprev[r] = (uint8_t)fp6; s_word[r] = (uint16_t)(256 * g + tid); s_end[r] = (at >> 11) + cnt;
+				const uint32_t rr = at + incl - inc, r = rr & 2047u;
+				s_need[r] = need; s_fprev[r] = (uint8_t)fp6; s_word[r] = (uint16_t)(256 * gw + tl); s_end[r] = (rr >> 11) + cnt;
 				s_cbits[r] = 0ull; s_mbits[r] = 0ull;
 			}
 		}
 		K3D_BARRIER();
-		const uint32_t head = s_head;
-		K3D_BARRIER();                                                 // (everyone has read the head before the next pass adds to it)
+		// (a refused reservation is behind every granted one and has left the head where it was or further on: the smaller of the two.
+		// The packed words compare as their fields do: the atomic only ever adds to both - words below, evaluations above - so both
+		// grow along the order of the reservations, and the smallest `at` among the refused is the first refused one's.)
+		const uint32_t head = s_head < s_lim ? s_head : s_lim;
+		const bool more = s_more != 0u;
 		const int nrec = (int)(head & 2047u);
 		K3B_MARK(0);
-		if((int)(head >> 11) < kK3dFlush && g + 1 < a.wpl) continue;
 		K3B_COUNT(0, nrec); K3B_COUNT(1, head >> 11);
 		// ---- tiles ----
 		#pragma unroll 1
@@ -1681,7 +1730,10 @@ __global__ __launch_bounds__(256, 4) void k_sync_dense(K3Args a) {
 			K3B_MARK(5);
 			r0 = r1;
 		}
-		if(tid == 0) s_head = 0u;
+		if(!more) break;
+		// (a round that refused a reservation has granted one - the first of a round always fits - so it had tiles, and their barriers
+		// stand between every thread's reading of the head above and this)
+		if(tid == 0) { s_head = 0u; s_lim = ~0u; s_more = 0u; }
 		K3D_BARRIER();
 	}
 	K3B_END();
