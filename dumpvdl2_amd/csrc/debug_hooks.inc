@@ -122,7 +122,11 @@ int vdl2hip_debug_dpp_probe(const float in[64], float out[256]) {
 // kind 0 phase_of, 1 phase_fast, 2 mag_of: in (re, im), out 1 float; 3 sync_metric: in 16 phases, out (pherr, slope); 4 sync_metric_screen:
 // in 16 phases in turns, out (16 taps, kScreenEarly taps); 5 slice_symbol: in (phi, prev_phi, vdphi), out int32 (index, neg);
 // 6 parabola_vertex: in (y1, y2, y3), out 1 float; 7 in (vdphi, freq as uint32, max_ppm), out (ppm_of, ppm_gate_threshold); 8 header_to_geometry:
-// in a 25-bit header word (uint32), out uint32 (status, syndrome, tl_bits, want_bits).  Needs no receiver
+// in a 25-bit header word (uint32), out uint32 (status, syndrome, tl_bits, want_bits); 9 / 10 sync_metric_ref with `full` / without: in 16 phases and
+// the 16 ref_eps2() figures of their taps, out (pherr, slope, E, alo, ahi); 11 ref_pherr_range x 3 and ref_candidate_verdict: in (p, alo, ahi, E) of n,
+// (p, alo, ahi, E, slope) of n-3, (p, alo, ahi, E) of n-6, max_ppm, the gate's threshold, out (verdict as int32, r0.lo, r0.hi, r3.lo, r3.hi, r6.lo, r6.hi);
+// 12 ref_vertex_marginal: in three (lo, hi), out int32 0/1; 13 in (phi, prev_phi, vdphi, e_sum), out (ref_symbol_dist, ref_symbol_marginal as int32).
+// Needs no receiver
 int vdl2hip_debug_core_probe(int kind, const void *in, size_t n, void *out) {
 	if(kind < 0 || kind >= PROBE_KINDS || !in || !out || n == 0 || n > (size_t)1 << 26) return VDL2HIP_E_INVAL;
 	DevBuf<float> d_in, d_out; DevBuf<Tables> d_tab;

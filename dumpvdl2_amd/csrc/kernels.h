@@ -522,9 +522,29 @@ __global__ void k_s8_level_probe(float *out) { const uint32_t i = threadIdx.x; o
 // debug kernel (tests/test_gpu_core_probe.py): the DEVICE builds of vdl2_core.h's element-wise pieces, each called as the product calls
 // it, one lane per element, plain loads and stores.  in: core_probe_in_words(kind) 32-bit words per element, out: core_probe_out_words(kind)
 // (PROBE_HEADER, tests/test_gpu_burst_probe.py: the walker's header_to_geometry() on a 25-bit word)
-enum { PROBE_PHASE = 0, PROBE_PHASE_FAST, PROBE_MAG, PROBE_METRIC, PROBE_SCREEN, PROBE_SLICE, PROBE_VERTEX, PROBE_PPM, PROBE_HEADER, PROBE_KINDS };
-VDL2_HD int core_probe_in_words(int kind) { return kind == PROBE_HEADER ? 1 : kind <= PROBE_MAG ? 2 : (kind <= PROBE_SCREEN ? kPreamble : 3); }
-VDL2_HD int core_probe_out_words(int kind) { return kind == PROBE_HEADER ? 4 : (kind <= PROBE_MAG || kind == PROBE_VERTEX) ? 1 : 2; }
+// (PROBE_REF_FULL .. PROBE_SYMBOL, tests/test_gpu_referee_probe.py: the referee's margin arithmetic - sync_metric_ref() in both forms on 16
+// phases and the 16 ref_eps2() figures of their taps; ref_pherr_range() x 3 and ref_candidate_verdict() as the exact sync tier's decide step
+// calls them; ref_vertex_marginal() on three boxes; ref_symbol_dist() / ref_symbol_marginal())
+enum { PROBE_PHASE = 0, PROBE_PHASE_FAST, PROBE_MAG, PROBE_METRIC, PROBE_SCREEN, PROBE_SLICE, PROBE_VERTEX, PROBE_PPM, PROBE_HEADER,
+       PROBE_REF_FULL, PROBE_REF_PLAIN, PROBE_VERDICT, PROBE_VERTEX_MARGINAL, PROBE_SYMBOL, PROBE_KINDS };
+VDL2_HD int core_probe_in_words(int kind) {
+	switch(kind) {
+	case PROBE_REF_FULL: case PROBE_REF_PLAIN: return 2 * kPreamble;
+	case PROBE_VERDICT: return 15;
+	case PROBE_VERTEX_MARGINAL: return 6;
+	case PROBE_SYMBOL: return 4;
+	default: return kind == PROBE_HEADER ? 1 : kind <= PROBE_MAG ? 2 : (kind <= PROBE_SCREEN ? kPreamble : 3);
+	}
+}
+VDL2_HD int core_probe_out_words(int kind) {
+	switch(kind) {
+	case PROBE_REF_FULL: case PROBE_REF_PLAIN: return 5;
+	case PROBE_VERDICT: return 7;
+	case PROBE_VERTEX_MARGINAL: return 1;
+	case PROBE_SYMBOL: return 2;
+	default: return kind == PROBE_HEADER ? 4 : (kind <= PROBE_MAG || kind == PROBE_VERTEX) ? 1 : 2;
+	}
+}
 __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, uint32_t n, float *out, const Tables *tab) {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if(i >= n) return;
@@ -558,6 +578,20 @@ __global__ __launch_bounds__(256) void k_core_probe(int kind, const float *in, u
 		const Geometry g = header_to_geometry(__float_as_uint(x[0]), tab->hdr_H, tab->hdr_fix);
 		o[0] = __int_as_float(g.status); o[1] = __uint_as_float(g.syndrome); o[2] = __uint_as_float(g.tl_bits); o[3] = __uint_as_float(g.want_bits);
 	} break;
+	case PROBE_REF_FULL: case PROBE_REF_PLAIN: {
+		float ph[kPreamble], e2[kPreamble];
+		for(int j = 0; j < kPreamble; j++) { ph[j] = x[j]; e2[j] = x[kPreamble + j]; }
+		if(kind == PROBE_REF_FULL) sync_metric_ref(ph, e2, 1, *tab, o[0], o[1], o[2], o[3], o[4], true);
+		else sync_metric_ref(ph, e2, 1, *tab, o[0], o[1], o[2], o[3], o[4], false);
+	} break;
+	case PROBE_VERDICT: {
+		// (p, alo, ahi, E) of n, of n-3 with its slope, of n-6; max_ppm, the gate's threshold
+		const RefRange r0 = ref_pherr_range(x[0], x[1], x[2], x[3]), r3 = ref_pherr_range(x[4], x[5], x[6], x[7]), r6 = ref_pherr_range(x[9], x[10], x[11], x[12]);
+		o[0] = __int_as_float(ref_candidate_verdict(r0, r3, x[8], x[7], r6, x[13], x[14]));
+		o[1] = r0.lo; o[2] = r0.hi; o[3] = r3.lo; o[4] = r3.hi; o[5] = r6.lo; o[6] = r6.hi;
+	} break;
+	case PROBE_VERTEX_MARGINAL: o[0] = __int_as_float(ref_vertex_marginal(RefRange{ x[0], x[1] }, RefRange{ x[2], x[3] }, RefRange{ x[4], x[5] }) ? 1 : 0); break;
+	case PROBE_SYMBOL: o[0] = ref_symbol_dist(x[0], x[1], x[2]); o[1] = __int_as_float(ref_symbol_marginal(x[0], x[1], x[2], x[3]) ? 1 : 0); break;
 	default: break;
 	}
 }

@@ -578,7 +578,10 @@ VDL2_HD Geometry header_to_geometry(uint32_t hdr, const uint32_t *tH, const uint
 // 2^17 in 1.9e-3 of the stretches measured, after 2^18 in 2.2e-5 (kernels.h)) and takes the decision again on those.  A decision is then either robust against the stream's error or taken on
 // samples that are the reference's own with that probability; where they are not yet, they are within its rounding noise of them.
 // ======================================================================
-constexpr float kRefKappa = 3.0e-4f;       // bound used for |y - y_ref| / (largest |y| among the samples a decision reads): 2x the worst seen
+// bound used for |y - y_ref| / (largest |y| among the samples a decision reads).  Held on the channeliser's own output, at every sample of
+// the golden captures and over its builds, feed geometries and look-back paths, by tests/test_gpu_referee_bounds.py (premise 1);
+// profiles/referee_bounds_device.txt keeps the measured shares of it (the kernel's and the float32 model's)
+constexpr float kRefKappa = 3.0e-4f;
 constexpr float kRefBig = 1.0e30f;
 constexpr int   kRefPre = 156, kRefPost = 96;   // a marginal candidate at n: evaluations n-6, n-3, n read n-156..n; sync point + 9 header symbols end before n+96
 
@@ -635,7 +638,9 @@ VDL2_HD float ref_eps2(const ChanView &v, int64_t n) {
 // length E (mean and slope removal are projections), E = kappa A sqrt(sum 1/|y_i|^2), A = the largest tap
 // E sums the taps' WORST-CASE bounds as if all sixteen errors were at their maximum and lined up with the residual; they are
 // independent, and mostly thirty times smaller: over 25 000 preamble-like windows of the fuzz and bench captures the metric moved by
-// at most 0.040 of that figure (rms 0.006), the slope by at most 0.034 (dev/ref_margin_calibration.py).  kRefSum = 2x the worst seen.
+// at most 0.040 of that figure (rms 0.006), the slope by at most 0.034.  kRefSum = 2x the worst seen then; what the channeliser's stream
+// does to the metric and the slope of every window of the golden captures is held to the two margins below by
+// tests/test_gpu_referee_bounds.py (premise 2), the measured shares are in profiles/referee_bounds_device.txt.
 constexpr float kRefSum = 0.085f;
 VDL2_HD float ref_pherr_margin(float p, float E) { const float e = kRefSum * E; return 2.0f * sqrtf(p) * e + e * e + 4e-6f * p + 1e-6f; }
 // ... and the slope: |df| <= E sqrt(sum lrx^2) / lr_den = E / sqrt(340)

@@ -416,6 +416,36 @@ void hostsim_metric_tables(float *pr_phase16, float *lrx16, float *lr_den) {
 	memcpy(pr_phase16, T.pr_phase, sizeof T.pr_phase); memcpy(lrx16, T.lrx, sizeof T.lrx); *lr_den = T.lr_den;
 }
 float hostsim_pi_below() { return kPiBelow; }
+// the referee's constants (vdl2_core.h): kRefKappa, kRefSum, kRefBig, kSyncThr, kPherrBig
+void hostsim_ref_constants(float out[5]) { out[0] = kRefKappa; out[1] = kRefSum; out[2] = kRefBig; out[3] = kSyncThr; out[4] = kPherrBig; }
+// the host builds of the referee's margin arithmetic on n elements, laid out as the device's test hook lays them out (kernels.h:
+// k_core_probe, kinds 9 .. 13): sync_metric_ref with `full` / without - in 16 phases + 16 eps2, out (pherr, slope, E, alo, ahi);
+// ref_pherr_range x 3 + ref_candidate_verdict - in (p, alo, ahi, E) of n, (p, alo, ahi, E, slope) of n-3, (p, alo, ahi, E) of n-6,
+// max_ppm, ppm_thr, out (verdict as int32, r0, r3, r6); ref_vertex_marginal - in three (lo, hi), out int32; ref_symbol_dist /
+// ref_symbol_marginal - in (phi, prev_phi, vdphi, e_sum), out (distance, int32).  Returns 0, or -1 for a kind it does not know
+int hostsim_ref_probe(int kind, const float *in, int64_t n, float *out) {
+	static Tables T; static bool init = false;
+	if(!init) { build_tables(T); init = true; }
+	auto as_float = [](int v) { float f; memcpy(&f, &v, 4); return f; };
+	for(int64_t i = 0; i < n; i++) {
+		switch(kind) {
+		case 9: case 10: {
+			const float *x = in + 32 * i; float *o = out + 5 * i;
+			sync_metric_ref(x, x + 16, 1, T, o[0], o[1], o[2], o[3], o[4], kind == 9);
+		} break;
+		case 11: {
+			const float *x = in + 15 * i; float *o = out + 7 * i;
+			const RefRange r0 = ref_pherr_range(x[0], x[1], x[2], x[3]), r3 = ref_pherr_range(x[4], x[5], x[6], x[7]), r6 = ref_pherr_range(x[9], x[10], x[11], x[12]);
+			o[0] = as_float(ref_candidate_verdict(r0, r3, x[8], x[7], r6, x[13], x[14]));
+			o[1] = r0.lo; o[2] = r0.hi; o[3] = r3.lo; o[4] = r3.hi; o[5] = r6.lo; o[6] = r6.hi;
+		} break;
+		case 12: { const float *x = in + 6 * i; out[i] = as_float(ref_vertex_marginal(RefRange{ x[0], x[1] }, RefRange{ x[2], x[3] }, RefRange{ x[4], x[5] }) ? 1 : 0); } break;
+		case 13: { const float *x = in + 4 * i; out[2 * i] = ref_symbol_dist(x[0], x[1], x[2]); out[2 * i + 1] = as_float(ref_symbol_marginal(x[0], x[1], x[2], x[3]) ? 1 : 0); } break;
+		default: return -1;
+		}
+	}
+	return 0;
+}
 
 // more of tables.h: preamble phases (units of pi/4 are checked by the caller), Gray map, FCS table, first PRBS bits, RS field
 void hostsim_misc_tables(float *pr_phase16, uint8_t *gray8, uint16_t *crc256, uint8_t *prbs64, uint8_t *gf_exp8) {
