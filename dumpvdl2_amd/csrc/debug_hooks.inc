@@ -5,6 +5,7 @@
 // What the hooks below say three times over each: was the call good, a host block to a buffer (all of it, or its first `bytes`), a
 // buffer filled with a byte, a buffer back to the host, the decoder's tables built and sent
 static bool hip_ok(hipError_t e) { return e == hipSuccess; }
+#include <random>
 template<typename T> static bool dbg_up(const DevBuf<T> &d, const void *src, size_t bytes) { return hip_ok(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); }
 template<typename T> static bool dbg_up(const DevBuf<T> &d, const void *src) { return dbg_up(d, src, d.bytes()); }
 template<typename T> static bool dbg_fill(const DevBuf<T> &d, int v) { return hip_ok(hipMemset(d, v, d.bytes())); }
@@ -52,6 +53,75 @@ int vdl2hip_debug_option(vdl2hip_ctx *c, const char *name, long value) {
 	if(strcmp(name, "referee") == 0) { if(value && !c->d_refhist) return VDL2HIP_E_INVAL; c->referee = value != 0; return VDL2HIP_OK; }   // (on only where it was on at create: the history ring)
 	if(strcmp(name, "ref_warm") == 0) { if(value < 0 || value > c->ref_T - 4096) return VDL2HIP_E_INVAL; c->ref_warm = value; return VDL2HIP_OK; }
 	return VDL2HIP_E_INVAL;
+}
+
+// test hook (not declared in vdl2hip.h; tests/test_gpu_position.py; host code only - no kernel and no kernel argument knows of it): a
+// receiver that has not been fed becomes one whose stream BEGINS at input sample n, at rest - not one that was silent before n.  Every
+// position the receiver keeps is an absolute index since the stream began (n_total / K1Args::n0 and the NCO phase taken from it, k_total /
+// k0, the walker's a, e, e0 and intervals, Burst::t_first / sync_sample / end_sample / prev_n, the evaluation log, ScanReq::lo / hi,
+// RefPiece::s0, the cache of finished stretches, nbase, the taps' k_on): the tests start it hours in, past 2^31 and 2^32, this way.
+//   n_total = n, k_total = K = n / os; every channel's WalkState - and every snapshot copy the walk-ahead path keeps (d_ws_snap[], d_ws_tmp) -
+//   is walk_state_init()'s with a = K, e = e0 = K + 2; noise floor, evaluation counts, burst ordinals, counters stay at their initial values.
+//   Taps enabled afterwards take their k_on from k_total, as ever.
+// What lies before n is rest, and the code must see that:
+//   - at position 0 "before the stream" is a negative index (ChanView::Phi, ref_eps2, the walker's history taps, Burst::prev_n == -1,
+//     txs_range, the scans' n_lo < 0 / s_beg < 0); at n none of those branches is taken, the code reads ring slots (K - j) & mask instead.
+//     d_y, d_pf, d_cand and d_flag are zero from vdl2hip_create (DEV_ALLOC(..., true)) and nothing has written them before the first feed,
+//     and phase_of({+0, +0}) is +0.0f in both builds (device: atan2_f64's !(mx > 0) branch, copysign(0.0, +0.0); host: libm's
+//     atan2(+0, +0)), phase_fast({0, 0}) is 0 likewise: the slots read as position 0's "before the stream" does.  The walker's first
+//     evaluation of a run cannot fire and it never reads pf[] before e0 = K + 2, so the zero metric values before K are never looked at.
+//     One difference: ref_eps2() of a zero sample INSIDE the stream is kRefBig where position 0 has 0 - windows whose taps reach before
+//     K are "cannot tell" and go to the referee, which decides them on the reference's own samples: the same frames, more scans in the
+//     first 150 decimated samples.  Burst::prev_n may be K - 1 where position 0 has -1 (the phase there is 0 either way).
+//   - the referee's scans know the start of the stream from s_beg < 0 at position 0: they begin there in the reference's state, zero,
+//     exactly, and k_ref_scan_multi's witness with them.  At n a scan cannot know, so the history ring gets min(n, ref_T) raw samples
+//     registered as the one piece { s0 = n - that, that many }, ref_wp behind them: seeded noise of a few percent of full scale, then
+//     kPosQuiet samples of zeros up to n.  Over the zeros the recursion decays (0.985 per input sample at oversample 20) through the
+//     subnormal range, where it comes to a stop at 1e-41 or less - not at 0 exactly: (B1 + B2) k rounds to k for small k - and a state
+//     of 1e-41 is absorbed by the first addition of a sample's A0 x (1e-9 for one count of S16), so the stretch comes out bit for bit as
+//     from rest (tests/test_gpu_position.py reads the first samples after n back).  Zeros alone would do that too, but the witness
+//     (started from another state wherever s_beg > 0) could not meet a scan that stays at 0 exactly while its own state stops in the
+//     subnormals: every scan whose run-up lies in the zeros was counted as unmet and run again (measured: 24 of 116 scans of an
+//     8-channel capture of 1 s fed whole, none at position 0).  Over the noise the two meet as they do anywhere in a stream and stay
+//     together through the zeros.  That holds for the formats whose all-zero code is the sample 0 (S16, S8, CF32).  FMT_U8 has no such
+//     code ((b - 127.5) / 127.5) and no history of bytes leaves every channel's filter at rest: a U8 receiver takes a position only with
+//     the referee switched off (debug_option "referee" 0) - its channeliser, walker, noise floor and burst decoder are then held at large
+//     indices, its scans are not.
+// Refused (VDL2HIP_E_INVAL): a receiver that has been fed or has anything carried or queued, or whose activity monitor is on already; n
+// not a multiple of the oversampling; a receiver that resamples (cfg.input_rate) - K0's position pair (q0, t0) is not set by this hook; a
+// receiver of unsigned bytes whose referee is on.
+int vdl2hip_debug_set_position(vdl2hip_ctx *c, uint64_t n) {
+	if(!c || c->failed || c->feed_no != 0 || c->ncarry != 0 || c->n_total != 0 || c->k_total != 0 || !c->queue.empty() || !c->ref_pieces.empty()) return VDL2HIP_E_INVAL;
+	if(c->rs.on || c->act.on || n % (uint64_t)c->os != 0 || n > (1ull << 60) || (c->fmt == kFmtU8 && c->referee)) return VDL2HIP_E_INVAL;      // (an activity monitor that is on has taken its k_on already)
+	OnDevice dev_guard(c);
+	const int64_t K = (int64_t)(n / (uint64_t)c->os);
+	std::vector<WalkState> ws((size_t)c->C);
+	for(auto &w : ws) { memset(&w, 0, sizeof w); walk_state_init(w); w.a = K; w.e = w.e0 = K + 2; }
+	const size_t wb = ws.size() * sizeof(WalkState);
+	HIPCHK(hipMemcpy(c->d_ws, ws.data(), wb, hipMemcpyHostToDevice));
+	for(auto *d : { &c->d_ws_snap[0], &c->d_ws_snap[1], &c->d_ws_tmp }) if(d->get()) HIPCHK(hipMemcpy(d->get(), ws.data(), wb, hipMemcpyHostToDevice));
+	if(c->d_refhist && c->referee) {
+		const uint64_t w = std::min<uint64_t>(n, (uint64_t)c->ref_T);      // (ref_T < ref_cap: the piece does not wrap)
+		if(w) {
+			constexpr uint64_t kPosQuiet = 32768;                             // zeros up to n: hundreds of decay times of the filter at any oversampling up to 32
+			const size_t sb = raw_bytes(c->fmt);
+			const uint64_t noisy = w > kPosQuiet ? w - kPosQuiet : 0;
+			std::vector<uint8_t> h((size_t)w * sb, 0);
+			std::mt19937 rng(20950u);
+			for(uint64_t i = 0; i < 2 * noisy; i++) {                        // (I and Q of every sample)
+				const int v = (int)(rng() % 2001u) - 1000;                    // +-1000 counts of S16: 3 % of full scale
+				if(c->fmt == kFmtS16) { const int16_t q = (int16_t)v; memcpy(&h[2 * i], &q, 2); }
+				else if(c->fmt == kFmtS8) h[i] = (uint8_t)(int8_t)(v / 32);
+				else { const float q = (float)v / 32768.0f; memcpy(&h[4 * i], &q, 4); }
+			}
+			HIPCHK(hipMemcpy(c->d_refhist, h.data(), h.size(), hipMemcpyHostToDevice));
+			c->ref_pieces.push_back(vdl2hip_ctx::HistPiece{ (int64_t)(n - w), (int64_t)w, 0 });
+			c->ref_wp = w % c->ref_cap;
+		}
+	}
+	HIPCHK(hipDeviceSynchronize());
+	c->n_total = n; c->k_total = K;
+	return VDL2HIP_OK;
 }
 
 // test hook (not declared in vdl2hip.h): the referee's scan on [n_lo, n_hi] of one channel, with the raw input the most recent feed could

@@ -639,6 +639,14 @@ class Receiver:
         f.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         self._chk(f(self.h, name.encode(), value), "vdl2hip_debug_option")
 
+    def debug_set_position(self, n: int) -> None:
+        """test hook of the library (not part of include/vdl2hip.h): before the first feed, make this a receiver whose stream begins at
+        input sample n (a multiple of the oversampling), at rest - every absolute index it keeps (input and decimated sample numbers,
+        NCO phase, burst timing, the referee's pieces, the taps' k_on) starts there.  Refused for a fed or a resampling receiver."""
+        f = self.L.vdl2hip_debug_set_position
+        f.argtypes = [C.c_void_p, C.c_uint64]
+        self._chk(f(self.h, n), "vdl2hip_debug_set_position")
+
     def exact_window(self, chan: int, n_lo: int, n_hi: int) -> bool:
         """test hook: the referee's scan over decimated samples n_lo..n_hi of one channel (True: done; read them with read_decimated)"""
         f = self.L.vdl2hip_debug_exact_window
@@ -931,6 +939,13 @@ class ReceiverGroup:
             if n >= 0:
                 return buf[:2 * n].reshape(-1, 2)
         raise Vdl2HipError("no member owns that channel")
+
+    def debug_set_position(self, n: int) -> None:
+        """Receiver.debug_set_position() for every member (test hook): the group's stream begins at input sample n"""
+        f = self.L.vdl2hip_debug_set_position
+        f.argtypes = [C.c_void_p, C.c_uint64]
+        for i in range(self.size()):
+            self._chk(f(self.member(i), n), "vdl2hip_debug_set_position")
 
     def member(self, i: int):
         """the context handle of member i (vdl2hip_group_ctx): what the per-context calls take - vdl2hip_spectrum_*, vdl2hip_activity_*, vdl2hip_capture_*, vdl2hip_txlog_*"""

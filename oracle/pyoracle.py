@@ -74,6 +74,8 @@ def _bind(L):
     L.vdl2o_create.restype = C.c_void_p
     L.vdl2o_create.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.c_uint32, C.c_int, C.c_float]
     L.vdl2o_destroy.argtypes = [C.c_void_p]
+    L.vdl2o_set_position.restype = C.c_int
+    L.vdl2o_set_position.argtypes = [C.c_void_p, C.c_uint64]
     L.vdl2o_process.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
     L.vdl2o_num_frames.restype = C.c_size_t
     L.vdl2o_num_frames.argtypes = [C.c_void_p]
@@ -133,6 +135,15 @@ class Oracle:
     def __del__(self):
         self.close()
 
+    def set_position(self, n):
+        """Start the stream at input sample n (a multiple of the oversampling), before the first process()/run(): a stream that
+        begins at n, at rest - per channel the NCO phase the reference holds at sample n, the decimated counter at n / oversample,
+        nothing else.  sync_sample / end_sample of frames() and the sample fields of sync_events() are then absolute; trace(),
+        trace_all(), trace_noise_floor() and the event list index from the start position (entry 0: the first output at n), and
+        decimated_count() counts from it."""
+        if self.L.vdl2o_set_position(self.h, n) != 0:
+            raise ValueError(f"set_position({n}): after the first block, or not a multiple of the oversampling")
+
     def process(self, raw, block_bytes=320000, nthreads=1):
         """Feed raw bytes in block_bytes pieces like process_iq_file() (dumpvdl2.c:353-356)."""
         raw = np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8) if not isinstance(raw, np.ndarray) else raw.view(np.uint8).reshape(-1))
@@ -159,7 +170,8 @@ class Oracle:
         return self._trace
 
     def trace_all(self, cap):
-        """Record (lp_re, lp_im) of every channel: returns array [nchan, cap, 2]."""
+        """Record (lp_re, lp_im) of every channel: returns array [nchan, cap, 2]; entry i is decimated sample
+        (start position / oversample) + i (set_position)."""
         self._trace_all = np.zeros((len(self.freqs), cap, 2), dtype=np.float32)
         self.L.vdl2o_trace_all(self.h, self._trace_all.ctypes.data, cap)
         return self._trace_all

@@ -98,6 +98,8 @@ struct vdl2o_ctx {
 	int nchan, fmt;
 	uint32_t oversample;
 	float max_ppm;
+	int64_t d0;                 /* decimated index of the stream's first output (vdl2o_set_position); the traces index from it */
+	int started;                /* a block has been processed: the position is fixed */
 	float A[3], B[3];
 	float sin_t[257], cos_t[257];
 	float lrx[K_PREAMBLE], lr_den;
@@ -860,8 +862,8 @@ static void chan_scan_block(vdl2o_ctx *c, int k) {
 		if(++v->decim_cnt == (int)v->oversample) {
 			v->decim_cnt = 0;
 			v->dsample++;
-			if(c->trace_all && (size_t)v->dsample < c->trace_all_cap) {
-				float *t = c->trace_all + 2 * ((size_t)k * c->trace_all_cap + (size_t)v->dsample);
+			if(c->trace_all && (uint64_t)(v->dsample - c->d0) < c->trace_all_cap) {
+				float *t = c->trace_all + 2 * ((size_t)k * c->trace_all_cap + (size_t)(v->dsample - c->d0));
 				t[0] = v->yr[0]; t[1] = v->yi[0];
 			}
 			if(tracing && c->trace_n < c->trace_cap) {
@@ -880,8 +882,23 @@ static void *scan_thread(void *arg) {
 	return NULL;
 }
 
+/* A stream that begins at input sample n, at rest: the NCO phase the reference would hold there (it masks the phase to 24 bits
+ * after every sample, demod.c:311-312, so n steps of nco_dphi from 0 are (n * nco_dphi) & 0xffffff) and the decimated-sample
+ * counter; filter state, walker, noise floor and evaluation counts stay as vdl2o_create() left them. */
+int vdl2o_set_position(vdl2o_ctx *c, uint64_t n) {
+	if(c->started || n % c->oversample != 0) return -1;
+	c->d0 = (int64_t)(n / c->oversample);
+	for(int k = 0; k < c->nchan; k++) {
+		chan_t *v = &c->ch[k];
+		v->nco_phi = (uint32_t)((n * (uint64_t)v->nco_dphi) & 0xffffffu);   /* mod 2^64, and 2^24 divides 2^64 */
+		v->dsample = c->d0 - 1;
+	}
+	return 0;
+}
+
 void vdl2o_process(vdl2o_ctx *c, const uint8_t *buf, uint32_t len, int nthreads) {
 	if(len == 0) return;
+	c->started = 1;
 	/* process_buf_uchar()/process_buf_short(), demod.c:339-365 */
 	uint32_t nfl = (c->fmt == VDL2O_FMT_S16LE) ? len / 2 : len;
 	if(nfl + 1 > c->sbuf_cap) { c->sbuf_cap = nfl + 1; c->sbuf = realloc(c->sbuf, (size_t)c->sbuf_cap * sizeof(float)); c->sbuf[nfl] = 0.f; }
@@ -980,6 +997,7 @@ static void *run_queue_thread(void *arg) {
 
 int vdl2o_run(vdl2o_ctx *c, const uint8_t *buf, uint64_t total_len, uint32_t block_bytes, int mode, int nthreads) {
 	if(block_bytes == 0 || (mode != VDL2O_RUN_THREAD_PER_CHANNEL && mode != VDL2O_RUN_WORKQUEUE)) return -1;
+	c->started = 1;
 	run_shared r; memset(&r, 0, sizeof r);
 	r.c = c; r.mode = mode;
 	const int nw = mode == VDL2O_RUN_THREAD_PER_CHANNEL ? c->nchan : (nthreads < 1 ? 1 : nthreads);
@@ -1046,4 +1064,4 @@ void vdl2o_trace_noise_floor(vdl2o_ctx *c, float *dst, size_t cap_per_chan) { c-
 void vdl2o_trace_sync_events(vdl2o_ctx *c, vdl2o_sync_event *dst, size_t cap_per_chan) { c->trace_ev = dst; c->trace_ev_cap = cap_per_chan; }
 size_t vdl2o_sync_event_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].nev; }
 int64_t vdl2o_sync_evals(const vdl2o_ctx *c, int chan) { return 1000 * c->ch[chan].nf_upd + c->ch[chan].nfcnt; }
-int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].dsample + 1; }
+int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan) { return c->ch[chan].dsample + 1 - c->d0; }

@@ -69,6 +69,15 @@ vdl2o_ctx *vdl2o_create(uint32_t centerfreq, const uint32_t *freqs, int nchan,
 		uint32_t oversample, int sample_fmt, float max_ppm);
 void vdl2o_destroy(vdl2o_ctx *c);
 
+/* Start the stream at input sample n instead of 0: a stream that BEGINS at n, at rest - not one that was silent before n.
+ * Legal only before the first vdl2o_process()/vdl2o_run(), n a multiple of the oversampling; returns 0, or -1 if refused.
+ * Per channel nco_phi = (n * nco_dphi) & 0xffffff (the phase the reference holds at sample n) and the decimated-sample counter
+ * starts at n / oversample; nothing else changes.  sync_sample / end_sample of the frames and the sample / end_sample fields of
+ * the sync events then come out as absolute indices.  The trace buffers (vdl2o_trace_decimated, vdl2o_trace_all,
+ * vdl2o_trace_noise_floor, vdl2o_trace_sync_events) and vdl2o_decimated_count() count from the start position: entry 0 is the
+ * first output at or after n, so the buffers stay small. */
+int vdl2o_set_position(vdl2o_ctx *c, uint64_t n);
+
 /* Equivalent of one process_buf_uchar()/process_buf_short() call followed by
  * every channel's process_samples() pass over that block (demod.c:288-365).
  * nthreads <= 1: channels are processed one after another on the caller.
@@ -99,8 +108,9 @@ void vdl2o_get_sincos_lut(const vdl2o_ctx *c, float s[257], float co[257]);
  * channel; cap = number of complex samples the buffer can hold. */
 void vdl2o_trace_decimated(vdl2o_ctx *c, int chan, float *dst, size_t cap);
 size_t vdl2o_trace_count(const vdl2o_ctx *c);
-/* trace every channel: dst[chan][cap_per_chan] complex (re,im) */
+/* trace every channel: dst[chan][cap_per_chan] complex (re,im); entry i is decimated sample (start position / oversample) + i */
 void vdl2o_trace_all(vdl2o_ctx *c, float *dst, size_t cap_per_chan);
+/* decimated samples produced since the start position */
 int64_t vdl2o_decimated_count(const vdl2o_ctx *c, int chan);
 /* Optional trace of the noise floor (off by default; one test per 1000 evaluations when off): dst[chan][cap_per_chan] =
  * v->mag_nf after each of its updates (demod.c:241-243: every 1000th got_sync() evaluation), every channel */

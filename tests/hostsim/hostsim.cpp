@@ -15,21 +15,21 @@
 // The referee's hook of the CPU build: the "reference's own samples" come from a trace the test supplies (the oracle's decimated
 // stream); the device build works them out from the raw input (kernels.h).
 namespace vdl2 {
-struct RefChan { const float *exact; int64_t n_exact; cf32 *y; uint32_t mask; int64_t calls, samples; std::vector<uint8_t> *done; };
+struct RefChan { const float *exact; int64_t n_exact; cf32 *y; uint32_t mask; int64_t calls, samples; std::vector<uint8_t> *done; int64_t base = 0; };   // base: the stream's first sample (hostsim_set_position); exact[0] is that sample
 inline void ref_debug_log(const ChanView &, int tag, int64_t a, float b, float c, float d) { if(getenv("HOSTSIM_REF_LOG")) fprintf(stderr, "reflog %d %lld %.9g %.9g %.9g\n", tag, (long long)a, b, c, d); }
 inline bool ref_exact_window(const ChanView &v, int64_t n_lo, int64_t n_hi, void *, int kind) {
 	RefChan *r = v.ref;
 	if(!r || !r->exact) return false;
 	r->calls++;
 	if(getenv("HOSTSIM_REF_CALLS")) fprintf(stderr, "refcall y=%p kind %d lo %lld hi %lld\n", (void *)r->y, kind, (long long)n_lo, (long long)n_hi);
-	for(int64_t n = n_lo < 0 ? 0 : n_lo; n <= n_hi && n < r->n_exact; n++) { r->y[(uint32_t)n & r->mask] = cf32{ r->exact[2 * n], r->exact[2 * n + 1] }; r->samples++; if(r->done) (*r->done)[n] = 1; }
+	for(int64_t n = n_lo < r->base ? r->base : n_lo; n <= n_hi && n - r->base < r->n_exact; n++) { const int64_t i = n - r->base; r->y[(uint32_t)n & r->mask] = cf32{ r->exact[2 * i], r->exact[2 * i + 1] }; r->samples++; if(r->done) (*r->done)[i] = 1; }
 	return true;
 }
 // (the device: has ANOTHER launch made the stretch exact - here: has anybody)
 inline bool ref_window_done(const ChanView &v, int64_t n_lo, int64_t n_hi) {
 	RefChan *r = v.ref;
 	if(!r || !r->exact || !r->done) return false;
-	for(int64_t n = n_lo < 0 ? 0 : n_lo; n <= n_hi && n < r->n_exact; n++) if(!(*r->done)[n]) return false;
+	for(int64_t n = n_lo < r->base ? r->base : n_lo; n <= n_hi && n - r->base < r->n_exact; n++) if(!(*r->done)[n - r->base]) return false;
 	return true;
 }
 }
@@ -131,6 +131,18 @@ Sim *hostsim_create(int nchan, const uint32_t *freqs, float max_ppm, int cap_log
 
 void hostsim_destroy(Sim *s) { delete s; }
 
+// A stream that begins at decimated sample K, at rest (before the first feed; -1 if refused): k_total and every channel's walker - first
+// interval and first evaluation grid start at K as they start at 0 in walk_state_init(), everything else as it leaves it.  The rings
+// are zero from hostsim_create(), which is what lies before a stream that begins at rest: where the code reads "before the stream"
+// through a negative index at position 0 (ChanView::Phi, ref_eps2, Burst::prev_n == -1) it reads those zero slots here, and
+// phase_of({+0, +0}) is +0.  Call it before hostsim_set_exact(): the exact samples are then indexed from K too.
+int hostsim_set_position(Sim *s, int64_t K) {
+	if(K < 0 || s->k_total != 0 || !s->rc.empty() || !s->all_bursts.empty()) return -1;
+	s->k_total = K;
+	for(auto &w : s->st) { w.a = K; w.e = w.e0 = K + 2; }
+	return 0;
+}
+
 // walk feeds of at least 2*seg_min decimated samples in up to seg_max speculative segments (0 = plain sequential walk)
 void hostsim_set_segments(Sim *s, int64_t seg_min, int seg_max) { s->seg_min = seg_min; s->seg_max = seg_max < 1 ? 1 : seg_max > kMaxSeg ? kMaxSeg : seg_max; }
 void hostsim_set_two_tier(Sim *s, int on) { s->two_tier = on != 0; }
@@ -140,7 +152,7 @@ void hostsim_set_prescan(Sim *s, int on) { s->prescan = on != 0; }
 void hostsim_set_exact(Sim *s, const float *exact, int64_t D) {
 	s->exact.assign(exact, exact + (size_t)s->nchan * D * 2); s->exact_D = D;
 	s->rc.resize(s->nchan); s->rdone.assign(s->nchan, std::vector<uint8_t>((size_t)D, 0));
-	for(int c = 0; c < s->nchan; c++) s->rc[c] = RefChan{ s->exact.data() + (size_t)c * D * 2, D, &s->y[(size_t)c * s->cap], s->mask, 0, 0, &s->rdone[c] };
+	for(int c = 0; c < s->nchan; c++) s->rc[c] = RefChan{ s->exact.data() + (size_t)c * D * 2, D, &s->y[(size_t)c * s->cap], s->mask, 0, 0, &s->rdone[c], s->k_total };
 	s->pe.assign((size_t)s->nchan * s->cap, 0.f); s->pa.assign((size_t)s->nchan * s->cap, 0.f); s->pb.assign((size_t)s->nchan * s->cap, 0.f);
 }
 // [0] candidates K3 marked, [1] candidate bits set, [2] exact windows served, [3] samples replaced, [4] windows asked for by the walkers (one feed)

@@ -58,6 +58,13 @@ class HostSim:
         self.n = len(freqs)
         self.h = self.L.hostsim_create(self.n, (C.c_uint32 * self.n)(*freqs), max_ppm, cap_log2)
 
+    def set_position(self, K):
+        """before the first feed (and before set_exact): the stream begins at decimated sample K, at rest - k_total and the walkers'
+        first interval start there; feed() and set_exact() then take samples K, K + 1, ..."""
+        self.L.hostsim_set_position.argtypes = [C.c_void_p, C.c_int64]
+        if self.L.hostsim_set_position(self.h, K) != 0:
+            raise ValueError(f"set_position({K}): after the first feed or after set_exact")
+
     def feed(self, y):
         """y: float32 [nchan, D, 2]"""
         y = np.ascontiguousarray(y, dtype=np.float32)
