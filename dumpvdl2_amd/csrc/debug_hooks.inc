@@ -561,6 +561,72 @@ int vdl2hip_debug_txsearch_range(const float *y, uint32_t ring_len, int64_t firs
 	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
 }
 
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): the transmission capture's plan (txcap.h) for the nrec records of one
+// feed, as k_txcap_plan takes it - tx: the log's records (first_sample, last_sample, flags, chan, freq, first_bin are read), cfg: as
+// vdl2hip_txcap_enable() takes it (nfft 0, pool_samples 0 and pool_spectra 0 mean their defaults) -> recs: the records as the device
+// writes them (iq_off in pairs of the pool, spec_off in floats of the feed's spectra), poff[nrec + 1]: the offsets of their pieces,
+// out = { pairs of the pool in use, pieces }
+int vdl2hip_debug_txcap_plan(const vdl2hip_tx *tx, uint32_t nrec, const vdl2hip_txcap_cfg *cfg, vdl2hip_tx_capture *recs, uint32_t *poff, uint64_t out[2]) {
+	if((!tx && nrec) || !cfg || (!recs && nrec) || !poff || !out || cfg->struct_size != sizeof(vdl2hip_txcap_cfg)) return VDL2HIP_E_INVAL;
+	const uint32_t N = cfg->nfft ? cfg->nfft : kTxcDefN;
+	if(N < kTxcMinN || N > kTxcMaxN || (N & (N - 1)) || cfg->pre_samples > kTxcMaxPre) return VDL2HIP_E_INVAL;
+	const TxcCfg k{ cfg->pool_samples ? cfg->pool_samples : kTxcDefPool, cfg->flags, cfg->pre_samples, cfg->post_samples, cfg->max_iq_samples, N, cfg->pool_spectra ? cfg->pool_spectra : kTxcDefSpectra };
+	uint64_t off = 0, used = 0; uint32_t pieces = 0;
+	for(uint32_t i = 0; i < nrec; i++) {
+		TxRec t; memcpy(&t, tx + i, sizeof t);
+		TxcRec r; uint32_t cnt, np;
+		txc_plan_rec(t, i, k, r, cnt, np);
+		if(txc_place(r, off, k) && cnt) used = std::max(used, off + cnt);
+		memcpy(recs + i, &r, sizeof r);
+		poff[i] = pieces; off += cnt; pieces += np;
+	}
+	poff[nrec] = pieces; out[0] = used; out[1] = pieces;
+	return VDL2HIP_OK;
+}
+
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): the transmission capture's per-piece steps (txcap.h) for one record,
+// lane by lane, pass by pass and round by round as k_txcap_spectrum and k_txcap_reduce take them - y: the channel's ring of ring_len
+// (re, im) pairs (a power of two), the record's first_sample and last_sample -> power[nfft], *segments.  The staging arrays have a
+// guard zone of NaNs behind each: VDL2HIP_E_DEVICE if a store went beyond the kernel's sizes.
+int vdl2hip_debug_txcap_spectrum(const float *y, uint32_t ring_len, int64_t first, int64_t last, uint32_t nfft, uint32_t window, float *power, uint32_t *segments) {
+	if(!y || !power || !segments || ring_len < 2 || (ring_len & (ring_len - 1)) || first < 0 || last < first) return VDL2HIP_E_INVAL;
+	const uint32_t N = nfft ? nfft : kTxcDefN;
+	SpectrumDesign d;
+	if(N < kTxcMinN || N > kTxcMaxN || !design_spectrum(N, window, d)) return VDL2HIP_E_INVAL;
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	const float2 *tw = reinterpret_cast<const float2 *>(d.tw.data());
+	int64_t ef; uint32_t efl;
+	txs_range(first, last, ef, efl);
+	const uint32_t S = txc_segments(last - ef + 1, N), np = txc_pieces(S, N), G = txc_groups(N), L = N >> 2, npass = txc_passes(d.log2n);
+	*segments = S;
+	constexpr int GZ = 16;
+	const size_t span = txc_span(N), half = txc_half(N);
+	std::vector<float2> smp(span + GZ), buf((size_t)G * 2 * half + GZ);
+	std::vector<double> gacc((size_t)G * N), part((size_t)std::max(1u, np) * N);
+	const float2 nan2 = make_float2(NAN, NAN);
+	bool bad = false;
+	for(uint32_t pc = 0; pc < np; pc++) {
+		uint32_t s0, ns;
+		txc_piece(S, N, pc, s0, ns);
+		std::fill(smp.begin(), smp.end(), nan2); std::fill(buf.begin(), buf.end(), nan2);
+		for(uint32_t l = 0; l < (uint32_t)kTxcThreads; l++) txc_load_step(yc, ring_len - 1, ef + (int64_t)s0 * (int64_t)(N >> 1), (ns + 1) * (N >> 1), l, kTxcThreads, smp.data());
+		std::vector<double> acc((size_t)kTxcThreads * 4, 0.0);
+		for(uint32_t rd = 0; rd < kTxcRounds; rd++) {
+			auto each = [&](auto f) { for(uint32_t lane = 0; lane < (uint32_t)kTxcThreads; lane++) { const uint32_t g = lane / L, l = lane % L, s = rd * G + g; if(s < ns) f(lane, g, l, s); } };
+			each([&](uint32_t, uint32_t g, uint32_t l, uint32_t s) { txc_fill_step(smp.data(), d.w.data(), N, s, l, buf.data() + (size_t)g * 2 * half); });
+			for(uint32_t p = 0; p < npass; p++)
+				each([&](uint32_t, uint32_t g, uint32_t l, uint32_t) { float2 *a = buf.data() + (size_t)g * 2 * half, *b = a + half; txc_pass_step(p & 1 ? b : a, p & 1 ? a : b, tw, N, d.log2n, p, l); });
+			each([&](uint32_t lane, uint32_t g, uint32_t l, uint32_t) { const float2 *a = buf.data() + (size_t)g * 2 * half; txc_power_step(npass & 1 ? a + half : a, N, l, &acc[(size_t)lane * 4]); });
+		}
+		for(uint32_t lane = 0; lane < (uint32_t)kTxcThreads; lane++) for(uint32_t r = 0; r < 4; r++) gacc[(size_t)(lane / L) * N + lane % L + r * L] = acc[(size_t)lane * 4 + r];
+		for(uint32_t b = 0; b < N; b++) part[(size_t)pc * N + b] = txc_group_sum(gacc.data(), G, N, b);
+		for(int i = 0; i < GZ; i++) bad = bad || !std::isnan(smp[span + i].x) || !std::isnan(buf[(size_t)G * 2 * half + i].x);
+	}
+	const double norm = 1.0 / (d.sum_w * d.sum_w);
+	for(uint32_t b = 0; b < N; b++) power[b] = S ? txc_reduce_bin(part.data(), 0, np, N, b, norm, S) : 0.f;
+	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
+}
+
 // test hook (not declared in vdl2hip.h; host only): k_activity_power's own code, lane by lane and barrier by barrier, for one channel of
 // one feed - y: the channel's ring of `cap` (re, im) pairs, the feed its samples k0 .. k0 + D - 1, t0 of them after the monitor was enabled;
 // series: a ring of S values.  Every index into the staging arrays is checked: VDL2HIP_E_DEVICE if one is out of range.

@@ -1,9 +1,9 @@
-// taps.inc - the receiver's six optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
-// input monitor's and the spectrogram's - capture.h, txsearch.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
+// taps.inc - the receiver's seven optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
+// input monitor's and the spectrogram's - capture.h, txsearch.h, txcap.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
 // (collect), what gives its buffers back (free), then its entry points of vdl2hip.h.  A tap stands behind those it calls into: the
-// log hands its records to the search, the activity monitor launches the log and switches it off, the input monitor does both
-// with the spectrogram.
-// Three of them deliver records - capture, search, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
+// log hands its records to the search and to the transmission capture, the activity monitor launches the log and switches it off,
+// the input monitor does both with the spectrogram.
+// Four of them deliver records - capture, search, transmission capture, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
 // (hostmem.h), per context the totals, a queue of collected records and the staging buffer of a feed with more records than come
 // with the header.  Their enable is: validate, collect what is in flight, free the old, allocate per slot, zero the totals, on.
 // (The entry points have C linkage from their declarations in vdl2hip.h.)
@@ -602,6 +602,187 @@ int vdl2hip_txsearch_read(vdl2hip_ctx *c, vdl2hip_tx_search *recs, size_t cap_re
 	return pop_records(c->txs.queue, recs, cap_recs);
 }
 
+// ---- the transmission capture (vdl2hip.h, "Transmission capture"; kernels: txcap.h) ----
+// The ring behind the window and the extent.  Under the preamble search's conditions (above) a record's last_sample >= k0 - kTxsMaxBack;
+// its window begins at or after last_sample - (kTxsSpan - 1) whatever pre is, and so does its extent: nothing is read further back than
+// the search reads.  The window ends at last_sample + post <= last_sample + (H + 1) B, the last sample of the bin whose completion
+// emits the record: inside the feed.  A window is at most kTxsSpan + kTxsMaxBack = 61 440 pairs long, less than the ring.
+static_assert(kTxsMaxBack + (kTxsSpan - 1) < kHistory + 1024 && kTxsSpan + kTxsMaxBack < kHistory, "a window and an extent begin inside what the ring keeps behind a feed");
+static_assert(sizeof(TxcRec) == sizeof(vdl2hip_tx_capture) && sizeof(vdl2hip_tx_capture) == 80 && offsetof(TxcRec, first_bin) == offsetof(vdl2hip_tx_capture, first_bin)
+              && offsetof(TxcRec, win_first) == offsetof(vdl2hip_tx_capture, win_first) && offsetof(TxcRec, iq_off) == offsetof(vdl2hip_tx_capture, iq_off)
+              && offsetof(TxcRec, spec_off) == offsetof(vdl2hip_tx_capture, spec_off) && offsetof(vdl2hip_tx_capture, spec_off) == 40
+              && offsetof(TxcRec, iq_count) == offsetof(vdl2hip_tx_capture, iq_count) && offsetof(vdl2hip_tx_capture, iq_count) == 48
+              && offsetof(TxcRec, flags) == offsetof(vdl2hip_tx_capture, flags) && offsetof(TxcRec, nfft) == offsetof(vdl2hip_tx_capture, nfft)
+              && offsetof(TxcRec, frames) == offsetof(vdl2hip_tx_capture, frames) && offsetof(vdl2hip_tx_capture, frames) == 64, "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_txcap_cfg) == 40 && sizeof(vdl2hip_txcap_info) == 88 && offsetof(vdl2hip_txcap_info, records) == 40 && sizeof(vdl2hip_tx_shape) == 48 && sizeof(TxcHdr) == 16, "vdl2hip.h states these sizes");
+static_assert(VDL2HIP_TXCAP_IQ == kTxcapIq && VDL2HIP_TXCAP_SPECTRUM == kTxcapSpectrum && VDL2HIP_TXCAP_UNDECODED_ONLY == kTxcapUndecodedOnly && VDL2HIP_TXC_CLIPPED == kTxcClipped
+              && VDL2HIP_TXC_TRUNCATED == kTxcTruncated && VDL2HIP_TXC_NO_ROOM == kTxcNoRoom && VDL2HIP_TXC_SHORT == kTxcShort && VDL2HIP_TXC_NO_SPECTRUM == kTxcNoSpectrum
+              && ((kTxcClipped | kTxcTruncated | kTxcNoRoom | kTxcShort | kTxcNoSpectrum) & kTxPartial) == 0 && kTxcMaxPre == kCapMaxPre && kTxcMaxPool == kCapMaxPool, "the flags share a word; the burst capture's limits");
+// The pieces one feed's spectra can have at the most.  A record of extent L has at most L / 4096 + 1 pieces (txc_pieces: S <= 2 L / N
+// segments, 8192 / N to a piece) - 15, the extent being kTxsSpan at the most - and the first pool_spectra records have any; the extents
+// of the transmissions a channel closes in one feed are disjoint and add up to less than dmax + kTxsMaxBack + kTxsSpan.
+static uint64_t txcap_piece_cap(const vdl2hip_ctx *c, uint32_t txpool, uint32_t pool_spectra) {
+	const uint64_t nspec = std::min(txpool, pool_spectra);
+	return std::min<uint64_t>(nspec * (uint64_t)(kTxsSpan / 4096 + 1), (uint64_t)c->C * ((c->dmax + kTxsMaxBack + (uint64_t)kTxsSpan) / 4096 + 1) + nspec);
+}
+// Its share of a feed (launch_rest): behind the frame finisher and the copy of the log's records, which it reads, like the search
+static int txcap_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->txc;
+	TxcArgs a{};
+	a.y = c->d_y; a.txhdr = sl.txl.mail.d_hdr(); a.txrec = sl.txl.mail.d_rec(); a.w = m.buf.d_w; a.tw = m.buf.d_tw;
+	a.poff = sl.txc.d_poff; a.part = sl.txc.d_part; a.rec = sl.txc.mail.d_rec(); a.hdr = sl.txc.mail.d_hdr(); a.pool = sl.txc.d_pool; a.spec = sl.txc.d_spec;
+	a.k = m.k; a.norm = m.norm; a.txpool = c->txl.pool; a.piece_cap = m.piece_cap; a.cap = c->cap; a.mask = c->cap - 1; a.chan_first = (uint32_t)c->chan_first; a.log2n = m.log2n;
+	const bool iq = (m.k.flags & kTxcapIq) != 0, spectrum = (m.k.flags & kTxcapSpectrum) != 0;
+	KernelTimes &t = sl.txc.times;
+	t.arm(c->profiling >= 2);
+	hipExtLaunchKernelGGL(k_txcap_plan, dim3(1), dim3(kTxcThreads), 0u, st, t.e(0), iq ? (hipEvent_t) nullptr : t.e(1), 0, a);
+	// a workgroup per record / per piece, grid-stride: a piece per 4096 channel-samples of the feed would be every sample busy - a quarter of that, 16 .. 2048
+	const unsigned grid = (unsigned)std::min<uint64_t>(2048, std::max<uint64_t>(16, (uint64_t)sl.back_D * (uint64_t)c->C / (4 * 4096)));
+	if(iq) hipExtLaunchKernelGGL(k_txcap_copy, dim3(std::min(512u, grid)), dim3(kTxcThreads), 0u, st, (hipEvent_t) nullptr, t.e(1), 0, a);
+	if(spectrum) {
+		hipExtLaunchKernelGGL(k_txcap_spectrum, dim3(grid), dim3(kTxcThreads), (uint32_t)m.lds, st, t.e(2), (hipEvent_t) nullptr, 0, a);
+		hipExtLaunchKernelGGL(k_txcap_reduce, dim3(std::min(512u, grid)), dim3(kTxcThreads), 0u, st, (hipEvent_t) nullptr, t.e(3), 0, a);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(sl.txc.mail.post(st));
+	t.launched(spectrum ? 2 : 1);
+	sl.txc.on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed's capture records, index for index beside the log's nrec records, with the used part of its IQ pool and its
+// spectra: one staging buffer, one wait
+struct TxcFeed { const TxcRec *rec = nullptr; std::shared_ptr<std::vector<float>> iq, spec; uint64_t pairs = 0; };
+static int txcap_fetch(vdl2hip_ctx *c, OutSlot &sl, uint32_t nrec, TxcFeed &f) {
+	auto &m = c->txc;
+	if(!m.on || !sl.txc.mail) return VDL2HIP_OK;
+	const TxcHdr h = sl.txc.mail.hdr();
+	if(h.nrec != nrec) return VDL2HIP_E_DEVICE;                      // (never: both are the log's header of this feed)
+	f.pairs = std::min<uint64_t>(h.pairs, m.k.pool_samples);
+	const size_t nspec = (m.k.flags & kTxcapSpectrum) ? std::min(nrec, m.k.pool_spectra) : 0u;
+	const size_t rec_bytes = sl.txc.mail.staged(nrec), iq_bytes = (size_t)f.pairs * sizeof(cf32), sp_bytes = nspec * m.k.N * sizeof(float);
+	HIPCHK(sl.txc.mail.fetch(nrec, m.stage, c->streams.out, f.rec, false, iq_bytes + sp_bytes));
+	if(iq_bytes) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.txc.d_pool, iq_bytes, hipMemcpyDeviceToHost, c->streams.out));
+	if(sp_bytes) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes + iq_bytes, sl.txc.d_spec, sp_bytes, hipMemcpyDeviceToHost, c->streams.out));
+	if(rec_bytes + iq_bytes + sp_bytes) HIPCHK(hipStreamSynchronize(c->streams.out));
+	const float *iqp = reinterpret_cast<const float *>(m.stage + rec_bytes), *spp = reinterpret_cast<const float *>(m.stage + rec_bytes + iq_bytes);
+	f.iq = std::make_shared<std::vector<float>>(iqp, iqp + iq_bytes / sizeof(float));
+	f.spec = std::make_shared<std::vector<float>>(spp, spp + sp_bytes / sizeof(float));
+	return VDL2HIP_OK;
+}
+// ... one of them, with the outcome the log has joined to its record
+static void txcap_take(vdl2hip_ctx *c, const TxcFeed &f, uint32_t i, const vdl2hip_tx &tx) {
+	auto &m = c->txc;
+	vdl2hip_tx_capture r;
+	memcpy(&r, f.rec + i, sizeof r);
+	if(r.iq_off + r.iq_count > f.pairs) { r.iq_count = 0; r.iq_off = 0; r.flags |= VDL2HIP_TXC_NO_ROOM; }      // (never)
+	if(r.nfft && !(r.flags & VDL2HIP_TXC_NO_SPECTRUM) && r.spec_off + r.nfft > f.spec->size()) r.flags |= VDL2HIP_TXC_NO_SPECTRUM;      // (never)
+	r.frames = tx.frames; r.frames_ok = tx.frames_ok; r.reserved[0] = r.reserved[1] = 0;
+	m.records++; m.iq_samples += r.iq_count; if(r.flags & VDL2HIP_TXC_NO_ROOM) m.iq_dropped++;
+	if(r.flags & VDL2HIP_TXC_NO_SPECTRUM) m.spectra_dropped++; else if(r.nfft) m.spectra++;
+	if((m.k.flags & VDL2HIP_TXCAP_UNDECODED_ONLY) && r.frames_ok != 0) return;
+	m.queue.push_back(vdl2hip_ctx::TxcItem{ r, f.iq, f.spec });
+}
+// give the capture's buffers back (nothing of it may be in flight: the callers have collected every feed)
+static void txcap_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.txc.reset();
+	c->txc.buf = {};
+	c->txc.queue.clear();
+	c->txc.on = false;
+}
+int vdl2hip_txcap_enable(vdl2hip_ctx *c, const vdl2hip_txcap_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_txcap_cfg) || cfg->reserved != 0) return VDL2HIP_E_INVAL;
+	if(!c->txl.on || !c->act.on || !(cfg->flags & (VDL2HIP_TXCAP_IQ | VDL2HIP_TXCAP_SPECTRUM)) || (cfg->flags & ~(VDL2HIP_TXCAP_IQ | VDL2HIP_TXCAP_SPECTRUM | VDL2HIP_TXCAP_UNDECODED_ONLY))) return VDL2HIP_E_INVAL;
+	const uint64_t back = ((uint64_t)c->act.H + 1) * c->act.B;
+	if(back > kTxsMaxBack || cfg->pre_samples > kTxcMaxPre || cfg->post_samples > back || cfg->pool_samples > kTxcMaxPool) return VDL2HIP_E_INVAL;
+	const uint32_t N = cfg->nfft ? cfg->nfft : kTxcDefN, pool_spectra = cfg->pool_spectra ? cfg->pool_spectra : kTxcDefSpectra;
+	SpectrumDesign d;
+	if(N < kTxcMinN || N > kTxcMaxN || !design_spectrum(N, cfg->window, d) || (uint64_t)pool_spectra * N > kTxcMaxSpecFloats) return VDL2HIP_E_INVAL;
+	const uint64_t piece_cap = txcap_piece_cap(c, c->txl.pool, pool_spectra);
+	if(piece_cap > 0x7fffffffull) return VDL2HIP_E_TOOBIG;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier capture is in flight any more
+	auto &m = c->txc;
+	txcap_free(c);
+	const uint32_t txpool = c->txl.pool, pool = cfg->pool_samples ? cfg->pool_samples : kTxcDefPool;
+	const bool iq = (cfg->flags & VDL2HIP_TXCAP_IQ) != 0, spectrum = (cfg->flags & VDL2HIP_TXCAP_SPECTRUM) != 0;
+	bool ok = true;
+	if(spectrum) ok = m.buf.d_w.alloc(N) == hipSuccess && m.buf.d_tw.alloc(N) == hipSuccess;
+	for(auto &sl : c->slot) {
+		auto &b = sl.txc;
+		ok = ok && b.mail.alloc(txpool) == hipSuccess && b.d_poff.alloc((size_t)txpool + 1) == hipSuccess;
+		if(iq) ok = ok && b.d_pool.alloc(pool) == hipSuccess;
+		if(spectrum) ok = ok && b.d_part.alloc((size_t)std::max<uint64_t>(1, piece_cap) * N) == hipSuccess && b.d_spec.alloc((size_t)std::min(txpool, pool_spectra) * N) == hipSuccess;
+	}
+	if(!ok) { txcap_free(c); return VDL2HIP_E_NOMEM; }
+	if((spectrum && (hipMemcpy(m.buf.d_w, d.w.data(), m.buf.d_w.bytes(), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(m.buf.d_tw, d.tw.data(), m.buf.d_tw.bytes(), hipMemcpyHostToDevice) != hipSuccess))
+	   || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); txcap_free(c); return VDL2HIP_E_DEVICE; }
+	m.k = TxcCfg{ pool, cfg->flags, cfg->pre_samples, cfg->post_samples, cfg->max_iq_samples, N, pool_spectra };
+	m.window = cfg->window; m.log2n = d.log2n; m.norm = 1.0 / (d.sum_w * d.sum_w); m.lds = txc_lds_bytes(N); m.piece_cap = (uint32_t)piece_cap;
+	m.records = m.iq_samples = m.iq_dropped = m.spectra = m.spectra_dropped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_txcap_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->txc.on && !c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	txcap_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_txcap_info_get(vdl2hip_ctx *c, vdl2hip_txcap_info *info) {
+	if(!c || !c->txc.on || !info || info->struct_size != sizeof(vdl2hip_txcap_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->txc;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->flags = m.k.flags; info->pre_samples = m.k.pre; info->post_samples = m.k.post; info->max_iq_samples = m.k.max_iq;
+	info->nfft = m.k.N; info->window = m.window; info->pool_samples = (uint32_t)m.k.pool_samples; info->pool_spectra = m.k.pool_spectra;
+	info->records = m.records; info->iq_samples = m.iq_samples; info->iq_dropped = m.iq_dropped; info->spectra = m.spectra; info->spectra_dropped = m.spectra_dropped;
+	info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+// (its own: a record goes out with its IQ and its spectrum, each packed behind those of the records before it)
+int vdl2hip_txcap_read(vdl2hip_ctx *c, vdl2hip_tx_capture *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used, float *spectra, size_t cap_floats, size_t *floats_used) {
+	if(!c || !c->txc.on || (!recs && cap_recs) || (!iq && cap_pairs) || (!spectra && cap_floats)) return VDL2HIP_E_INVAL;
+	auto &q = c->txc.queue;
+	size_t n = 0, used = 0, fused = 0;
+	while(!q.empty() && n < cap_recs) {
+		const vdl2hip_ctx::TxcItem &it = q.front();
+		const size_t nfl = it.r.nfft && !(it.r.flags & VDL2HIP_TXC_NO_SPECTRUM) ? it.r.nfft : 0;
+		if(used + it.r.iq_count > cap_pairs || fused + nfl > cap_floats) break;
+		recs[n] = it.r;
+		recs[n].iq_off = used; recs[n].spec_off = fused;
+		if(it.r.iq_count) memcpy(iq + 2 * used, it.iq->data() + 2 * it.r.iq_off, (size_t)it.r.iq_count * 2 * sizeof(float));
+		if(nfl) memcpy(spectra + fused, it.spec->data() + it.r.spec_off, nfl * sizeof(float));
+		used += it.r.iq_count; fused += nfl;
+		n++;
+		q.pop_front();
+	}
+	if(pairs_used) *pairs_used = used;
+	if(floats_used) *floats_used = fused;
+	return (int)n;
+}
+int vdl2hip_txcap_measure(const float *power, uint32_t nfft, vdl2hip_tx_shape *out) {
+	if(!power || !out || nfft < kTxcMinN || nfft > kTxcMaxN || (nfft & (nfft - 1)) != 0) return VDL2HIP_E_INVAL;
+	memset(out, 0, sizeof *out);
+	const double step = 105000.0 / (double)nfft;
+	double total = 0.0;
+	for(uint32_t i = 0; i < nfft; i++) total += (double)power[i];
+	if(!(total > 0.0)) return VDL2HIP_OK;
+	uint32_t peak = 0, lo = nfft - 1, hi = nfft - 1; bool have_lo = false, have_hi = false;
+	double moment = 0.0, run = 0.0;
+	for(uint32_t i = 0; i < nfft; i++) {
+		const double p = (double)power[i];
+		if(p > (double)power[peak]) peak = i;
+		moment += ((double)i - (double)(nfft / 2)) * step * p;
+		run += p;
+		if(!have_lo && run >= 0.005 * total) { lo = i; have_lo = true; }
+		if(!have_hi && run >= 0.995 * total) { hi = i; have_hi = true; }
+	}
+	out->total = total; out->peak_bin = peak; out->peak_hz = ((double)peak - (double)(nfft / 2)) * step;
+	out->centroid_hz = moment / total; out->obw_lo = lo; out->obw_hi = hi; out->obw_hz = (double)(hi - lo + 1) * step;
+	return VDL2HIP_OK;
+}
+
 // ---- the transmission log (vdl2hip.h, "Transmission log"; kernels: txlog.h) ----
 static_assert(sizeof(TxRec) == 64 && sizeof(vdl2hip_tx) == 80 && offsetof(vdl2hip_tx, frames) == sizeof(TxRec) && offsetof(vdl2hip_tx, first_burst_ord) == 72
               && offsetof(TxRec, first_bin) == offsetof(vdl2hip_tx, first_bin) && offsetof(TxRec, peak_bin) == offsetof(vdl2hip_tx, peak_bin)
@@ -641,15 +822,17 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 	}
 	if(!sl.txl.on) return VDL2HIP_OK;
 	sl.txl.on = false;
-	if(!sl.txl.mail) { sl.txs.on = false; return VDL2HIP_OK; }
+	if(!sl.txl.mail) { sl.txs.on = sl.txc.on = false; return VDL2HIP_OK; }
 	const TxHdr h = sl.txl.mail.hdr();
 	const uint32_t nrec = std::min(h.nrec, m.pool);
 	m.dropped += h.dropped;
-	if(nrec == 0) { sl.txs.on = false; return VDL2HIP_OK; }
+	if(nrec == 0) { sl.txs.on = sl.txc.on = false; return VDL2HIP_OK; }
 	const TxRec *rec = nullptr;
 	HIPCHK(sl.txl.mail.fetch(nrec, m.stage, c->streams.out, rec));
 	const TxsRec *srec = nullptr;
 	if(sl.txs.on) { sl.txs.on = false; int r = txsearch_fetch(c, sl, nrec, srec); if(r != VDL2HIP_OK) return r; }
+	TxcFeed capf;
+	if(sl.txc.on) { sl.txc.on = false; int r = txcap_fetch(c, sl, nrec, capf); if(r != VDL2HIP_OK) return r; }
 	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
 	for(uint32_t i = 0; i < nrec; i++) {
 		vdl2hip_tx r;
@@ -671,6 +854,7 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 		}
 		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
 		if(srec) txsearch_take(c, srec[i], r);
+		if(capf.rec) txcap_take(c, capf, i, r);
 		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
 		m.queue.push_back(r);
 	}
@@ -689,7 +873,8 @@ static int txlog_off(vdl2hip_ctx *c) {
 	if(!c->txl.on) return VDL2HIP_OK;
 	if(!c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
 	(void)hipStreamSynchronize(c->streams.front);
-	txsearch_free(c);                                                // (a search reads the log's records: it goes first)
+	txsearch_free(c);                                                // (a search and a capture read the log's records: they go first)
+	txcap_free(c);
 	txlog_free(c);
 	return VDL2HIP_OK;
 }
@@ -701,7 +886,8 @@ int vdl2hip_txlog_enable(vdl2hip_ctx *c, const vdl2hip_txlog_cfg *cfg) {
 	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier log is in flight any more
 	(void)hipStreamSynchronize(c->streams.front);
 	auto &m = c->txl;
-	txsearch_free(c);                                                // (a search that was running goes with the log it read)
+	txsearch_free(c);                                                // (a search and a capture that were running go with the log they read)
+	txcap_free(c);
 	txlog_free(c);
 	const uint32_t pool = cfg->pool_records ? cfg->pool_records : kTxDefPool;
 	const size_t C = (size_t)c->C;

@@ -26,6 +26,7 @@
 #include "activity.h"
 #include "txlog.h"
 #include "txsearch.h"
+#include "txcap.h"
 #include "capture.h"
 #include "tables.h"
 #include "hostmem.h"
@@ -165,6 +166,10 @@ struct OutSlot {
 	// followed this feed's frame finisher; times: k_txsearch_plan .. k_txsearch_reduce (one pair round the three)
 	struct TxsBufs { RecordMail<TxsHdr, TxsRec> mail; DevBuf<uint32_t> d_off; DevBuf<TxsPart> d_part; };
 	TapSlot<TxsBufs> txs;
+	// transmission capture (txcap.h): the feed's records, their piece offsets, the pieces' float64 rows, the IQ pool, the spectra.  on:
+	// the capture's launches followed this feed's frame finisher; times: k_txcap_plan + k_txcap_copy, k_txcap_spectrum + k_txcap_reduce
+	struct TxcBufs { RecordMail<TxcHdr, TxcRec> mail; DevBuf<uint32_t> d_poff; DevBuf<double> d_part; DevBuf<cf32> d_pool; DevBuf<float> d_spec; };
+	TapSlot<TxcBufs> txc;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -235,6 +240,17 @@ struct vdl2hip_ctx {
 		uint64_t records = 0, samples = 0, clipped = 0; double kernel_ms = 0.0;
 		PinnedBuf stage; std::deque<vdl2hip_tx_search> queue;
 	} txs;
+	// Transmission capture (txcap.h, vdl2hip_txcap_*): off unless enabled, and only beside the transmission log.  k: the configuration
+	// in force as the kernels take it; buf: the window and the twiddles of its transform, given back as one (txcap_free); queue: the
+	// records of the collected feeds, oldest first, each with the IQ and the spectra of its feed (one allocation each per feed, shared by
+	// its records; iq_off, spec_off: where the record's begin in them)
+	struct TxcItem { vdl2hip_tx_capture r; std::shared_ptr<std::vector<float>> iq, spec; };
+	struct {
+		bool on = false; TxcCfg k{}; uint32_t window = 0, log2n = 0, piece_cap = 0; double norm = 0.0; size_t lds = 0;
+		uint64_t records = 0, iq_samples = 0, iq_dropped = 0, spectra = 0, spectra_dropped = 0; double kernel_ms = 0.0;
+		struct { DevBuf<float> d_w; DevBuf<float2> d_tw; } buf;
+		PinnedBuf stage; std::deque<TxcItem> queue;
+	} txc;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
@@ -399,6 +415,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.cap.times.collect(c->capt.kernel_ms);
 	sl.txl.times.collect(c->txl.kernel_ms);
 	sl.txs.times.collect(c->txs.kernel_ms);
+	sl.txc.times.collect(c->txc.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
 		const Event *ev = sl.ev;
 		float ms = 0.f;
@@ -506,6 +523,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	sl.cap.on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
 	sl.txl.on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
 	sl.txs.on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
+	sl.txc.on = false;                                              // (... and the transmission capture's)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
 		// (a cold-start feed launches the channeliser in pieces that wait for the pieces of the copy: not a kernel duration, not timed)
@@ -896,6 +914,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		if(sl.txl.on) HIPCHK(sl.txl.mail.post(s5_));
 		// the preamble search reads the log's records of this feed (the same ordering) and y here, like the capture
 		if(sl.txl.on && c->txs.on) { int r = txsearch_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		// ... and so does the transmission capture
+		if(sl.txl.on && c->txc.on) { int r = txcap_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 	}
 	// the control block and the first few delivered frames in one copy (collect_slot)
 	HIPCHK(hipMemcpyAsync(sl.h_mail, sl.d_mail, sizeof(OutMail), hipMemcpyDeviceToHost, s5_));

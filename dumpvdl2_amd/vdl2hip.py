@@ -51,7 +51,11 @@ EXPORTS = [
     "vdl2hip_txlog_enable", "vdl2hip_txlog_disable", "vdl2hip_txlog_info_get", "vdl2hip_txlog_read",
     "vdl2hip_txsearch_enable", "vdl2hip_txsearch_disable", "vdl2hip_txsearch_info_get", "vdl2hip_txsearch_read",
     "vdl2hip_specgram_enable", "vdl2hip_specgram_disable", "vdl2hip_specgram_read", "vdl2hip_specgram_lines", "vdl2hip_specgram_channels",
+    "vdl2hip_txcap_enable", "vdl2hip_txcap_disable", "vdl2hip_txcap_info_get", "vdl2hip_txcap_read", "vdl2hip_txcap_measure",
 ]
+# include/vdl2hip.h: VDL2HIP_TXCAP_* (cfg.flags), VDL2HIP_TXC_* (vdl2hip_tx_capture.flags, beside TX_PARTIAL)
+TXCAP_IQ, TXCAP_SPECTRUM, TXCAP_UNDECODED_ONLY = 1, 2, 4
+TXC_CLIPPED, TXC_TRUNCATED, TXC_NO_ROOM, TXC_SHORT, TXC_NO_SPECTRUM = 2, 4, 8, 16, 32
 # include/vdl2hip.h: VDL2HIP_TXSEARCH_UNDECODED_ONLY (cfg.flags), VDL2HIP_TXS_CLIPPED (vdl2hip_tx_search.flags, beside TX_PARTIAL), VDL2HIP_TXS_* (why)
 TXSEARCH_UNDECODED_ONLY, TXS_CLIPPED = 1, 2
 TXS_DECODED, TXS_FRAMES_BAD, TXS_LOCK_NO_FRAME, TXS_NO_PREAMBLE = 0, 1, 2, 3
@@ -185,6 +189,27 @@ TXS_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("
                       ("frames", "<u4"), ("frames_ok", "<u4"), ("why", "<u4"), ("reserved", "<u4"), ("reserved2", "<u4")])     # vdl2hip_tx_search, 96 bytes
 
 
+class TxcapCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("pre_samples", C.c_uint32), ("post_samples", C.c_uint32),
+                ("max_iq_samples", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32), ("pool_samples", C.c_uint32),
+                ("pool_spectra", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TxcapInfo(C.Structure):
+    _fields_ = TxcapCfg._fields_ + [("records", C.c_uint64), ("iq_samples", C.c_uint64), ("iq_dropped", C.c_uint64), ("spectra", C.c_uint64),
+                                    ("spectra_dropped", C.c_uint64), ("kernel_ms", C.c_float), ("reserved2", C.c_uint32)]
+
+
+class TxShape(C.Structure):
+    _fields_ = [("total", C.c_double), ("peak_hz", C.c_double), ("centroid_hz", C.c_double), ("obw_hz", C.c_double),
+                ("peak_bin", C.c_uint32), ("obw_lo", C.c_uint32), ("obw_hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+TXC_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("win_first", "<i8"), ("win_last", "<i8"),
+                      ("iq_off", "<u8"), ("spec_off", "<u8"), ("iq_count", "<u4"), ("flags", "<u4"), ("segments", "<u4"), ("nfft", "<u4"),
+                      ("frames", "<u4"), ("frames_ok", "<u4"), ("reserved", "<u4", (2,))])     # vdl2hip_tx_capture, 80 bytes
+
+
 class PackedFrame(C.Structure):
     _fields_ = [("frame", CFrame), ("octets_off", C.c_uint64)]
 
@@ -271,6 +296,12 @@ def load_library(path: str = None):
         L.vdl2hip_txsearch_disable.argtypes = [C.c_void_p]
         L.vdl2hip_txsearch_info_get.argtypes = [C.c_void_p, C.POINTER(TxsearchInfo)]
         L.vdl2hip_txsearch_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "vdl2hip_txcap_enable"):
+        L.vdl2hip_txcap_enable.argtypes = [C.c_void_p, C.POINTER(TxcapCfg)]
+        L.vdl2hip_txcap_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_txcap_info_get.argtypes = [C.c_void_p, C.POINTER(TxcapInfo)]
+        L.vdl2hip_txcap_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.vdl2hip_txcap_measure.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(TxShape)]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -498,6 +529,53 @@ def _txsearch_info(Lib, ctx) -> dict:
 
 def _txsearch_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
     return _read_records(Lib, ctx, "vdl2hip_txsearch_read", TXS_DTYPE, cap_recs)
+
+
+def _txcap_enable(Lib, ctx, iq, spectrum, pre, post, max_iq_samples, nfft, window, pool_samples, pool_spectra, undecoded_only) -> None:
+    flags = (TXCAP_IQ if iq else 0) | (TXCAP_SPECTRUM if spectrum else 0) | (TXCAP_UNDECODED_ONLY if undecoded_only else 0)
+    cfg = TxcapCfg(C.sizeof(TxcapCfg), flags, pre, post, max_iq_samples, nfft, window, pool_samples, pool_spectra, 0)
+    _err(Lib, Lib.vdl2hip_txcap_enable(ctx, C.byref(cfg)), "vdl2hip_txcap_enable")
+
+
+def _txcap_info(Lib, ctx) -> dict:
+    info = TxcapInfo(C.sizeof(TxcapInfo))
+    _err(Lib, Lib.vdl2hip_txcap_info_get(ctx, C.byref(info)), "vdl2hip_txcap_info_get")
+    return {k: getattr(info, k) for k, _ in TxcapInfo._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+
+
+def _txcap_read(Lib, ctx, cap_recs: int = 4096, cap_pairs: int = 1 << 20, cap_floats: int = 1 << 20):
+    """vdl2hip_txcap_read() until nothing more comes -> (records as one array of TXC_DTYPE, with iq_off and spec_off as the calls
+    gave them; their windows as complex64 arrays; their spectra as float32 arrays, empty where the record has none).  cap_*: the
+    buffers of one call (a window longer than cap_pairs or a spectrum longer than cap_floats would never be delivered: 2^16 pairs
+    and 1024 floats hold any)."""
+    recs = np.zeros(max(1, cap_recs), dtype=TXC_DTYPE)
+    iq = np.zeros((max(1, cap_pairs), 2), dtype=np.float32)
+    sp = np.zeros(max(1, cap_floats), dtype=np.float32)
+    out, wins, spectra = [], [], []
+    while True:
+        used, fused = C.c_size_t(0), C.c_size_t(0)
+        n = _err(Lib, Lib.vdl2hip_txcap_read(ctx, recs.ctypes.data, cap_recs, iq.ctypes.data, cap_pairs, C.byref(used), sp.ctypes.data, cap_floats, C.byref(fused)), "vdl2hip_txcap_read")
+        if n == 0:
+            break
+        out.append(recs[:n].copy())
+        for r in recs[:n]:
+            off, cnt, so = int(r["iq_off"]), int(r["iq_count"]), int(r["spec_off"])
+            nfl = int(r["nfft"]) if not int(r["flags"]) & TXC_NO_SPECTRUM else 0
+            wins.append(iq[off:off + cnt].copy().view(np.complex64).reshape(-1))
+            spectra.append(sp[so:so + nfl].copy())
+    return (np.concatenate(out) if out else np.zeros(0, dtype=TXC_DTYPE)), wins, spectra
+
+
+def txcap_measure(power, nfft: int = None) -> dict:
+    """vdl2hip_txcap_measure(): total, peak_bin / peak_hz, centroid_hz and the 99 % occupied bandwidth obw_hz (obw_lo .. obw_hi) of one
+    power[] of a transmission capture's record.  Needs no GPU."""
+    Lib = load_library()
+    p = np.ascontiguousarray(power, dtype=np.float32)
+    out = TxShape()
+    r = Lib.vdl2hip_txcap_measure(p.ctypes.data, p.size if nfft is None else nfft, C.byref(out))
+    if r != 0:
+        raise Vdl2HipError(f"vdl2hip_txcap_measure: {Lib.vdl2hip_strerror(r).decode()} ({r})")
+    return {k: getattr(out, k) for k, _ in TxShape._fields_ if k != "reserved"}
 
 
 def live_resources() -> dict:
@@ -820,6 +898,25 @@ class Receiver:
         """the records of the feeds collected so far (sync() or a drain first), oldest first, as an array of TXS_DTYPE"""
         return _txsearch_read(self.L, self.h, cap_recs)
 
+    def txcap_enable(self, iq: bool = True, spectrum: bool = True, pre: int = 0, post: int = 0, max_iq_samples: int = 0, nfft: int = 0,
+                     window: int = WIN_HANN, pool_samples: int = 0, pool_spectra: int = 0, undecoded_only: bool = False) -> None:
+        """Switch the transmission capture on (include/vdl2hip.h, "Transmission capture"): it needs the transmission log, takes effect
+        with the next feed, and delivers of every transmission the log closes the decimated IQ (iq) and a power spectrum of nfft bins
+        (spectrum).  0 for nfft, pool_samples and pool_spectra means 256, 2^20 and 1024."""
+        _txcap_enable(self.L, self.h, iq, spectrum, pre, post, max_iq_samples, nfft, window, pool_samples, pool_spectra, undecoded_only)
+
+    def txcap_disable(self) -> None:
+        self._chk(self.L.vdl2hip_txcap_disable(self.h), "vdl2hip_txcap_disable")
+
+    def txcap_info(self) -> dict:
+        """the fields of vdl2hip_txcap_info: the configuration in force and the totals of the feeds collected so far"""
+        return _txcap_info(self.L, self.h)
+
+    def txcap_read(self, cap_recs: int = 4096, cap_pairs: int = 1 << 20, cap_floats: int = 1 << 20):
+        """the records of the feeds collected so far (sync() or a drain first), oldest first: (array of TXC_DTYPE, list of complex64
+        arrays - their IQ windows -, list of float32 arrays - their spectra, empty where a record has none)"""
+        return _txcap_read(self.L, self.h, cap_recs, cap_pairs, cap_floats)
+
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """switch the burst capture on from the next feed (vdl2hip.h, "Burst capture"): of every burst handed to the burst decoder the
         decimated IQ from `pre` samples before its sync to `post` after its last symbol, its timing and a phase-error quality figure.
@@ -1004,6 +1101,23 @@ class ReceiverGroup:
     def txsearch_read(self, member: int, cap_recs: int = 4096) -> np.ndarray:
         """Receiver.txsearch_read() of one member: its own channels' transmissions"""
         return _txsearch_read(self.L, self.member(member), cap_recs)
+
+    def txcap_enable(self, iq: bool = True, spectrum: bool = True, pre: int = 0, post: int = 0, max_iq_samples: int = 0, nfft: int = 0,
+                     window: int = WIN_HANN, pool_samples: int = 0, pool_spectra: int = 0, undecoded_only: bool = False) -> None:
+        """Receiver.txcap_enable() on every member"""
+        for i in range(self.size()):
+            _txcap_enable(self.L, self.member(i), iq, spectrum, pre, post, max_iq_samples, nfft, window, pool_samples, pool_spectra, undecoded_only)
+
+    def txcap_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_txcap_disable(self.member(i)), "vdl2hip_txcap_disable")
+
+    def txcap_info(self, member: int) -> dict:
+        return _txcap_info(self.L, self.member(member))
+
+    def txcap_read(self, member: int, cap_recs: int = 4096, cap_pairs: int = 1 << 20, cap_floats: int = 1 << 20):
+        """Receiver.txcap_read() of one member: its own channels' transmissions"""
+        return _txcap_read(self.L, self.member(member), cap_recs, cap_pairs, cap_floats)
 
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """the burst capture of every member (there is no group call: each member captures its own channels' bursts)"""

@@ -54,7 +54,9 @@ extern "C" {
                                  *    vdl2hip_txsearch_enable() / _disable() / _info_get() / _read() with vdl2hip_txsearch_cfg / _info and
                                  *    vdl2hip_tx_search: the preamble search, off unless enabled - new entry points and structures only, so the version stayed
                                  *    vdl2hip_specgram_enable() / _disable() / _read() / _lines() / _channels() with vdl2hip_specgram_cfg / _info: the
-                                 *    spectrogram on top of the input monitor, off unless enabled - new entry points and structures only, so the version stayed */
+                                 *    spectrogram on top of the input monitor, off unless enabled - new entry points and structures only, so the version stayed
+                                 *    vdl2hip_txcap_enable() / _disable() / _info_get() / _read() / _measure() with vdl2hip_txcap_cfg / _info, vdl2hip_tx_capture
+                                 *    and vdl2hip_tx_shape: the transmission capture, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -474,6 +476,85 @@ typedef struct {
 	uint32_t reserved;
 } vdl2hip_txsearch_info;                       /* 40 bytes */
 
+/* Transmission capture (not in the reference): for every transmission the transmission log closes, the channel's decimated samples
+ * around it and a compact spectral signature of the channel during it - where in the 25 kHz the energy sat and how wide it was.  The
+ * burst capture shows only bursts whose header decoded; this tap is the evidence for the records with frames_ok == 0: a D8PSK burst,
+ * an AM voice carrier, a stuck carrier and a neighbour's splatter look nothing alike in 400 Hz bins.  Off unless enabled; with it off
+ * nothing is launched or allocated and every result is what it was, to the bit.  On, frames, counters, the decimated stream, the
+ * activity monitor, the log, the search and the burst capture are still exactly what they were.
+ *  - Dependencies and switching.  The tap sits on top of the transmission log: vdl2hip_txcap_enable() with the log off is
+ *    VDL2HIP_E_INVAL.  It is independent of the preamble search: either, both or neither may run.  vdl2hip_txlog_enable(),
+ *    vdl2hip_txlog_disable(), vdl2hip_activity_enable() and vdl2hip_activity_disable() switch a running capture off first, as they do
+ *    the search.
+ *  - Placement and records.  The tap runs behind the frame finisher of the feed that closes the transmission: the preamble search's
+ *    placement, with the same caveat about a later feed's referee.  It reads the log's records of that feed and y, and writes buffers
+ *    of its own.  One record per record the log wrote to its pool, in the log's order, feed by feed; (chan, first_bin) is the join
+ *    key with vdl2hip_tx and vdl2hip_tx_search.
+ *  Below, B and H are the monitor's bin_samples and hang_bins; first_sample and last_sample are the log record's.
+ *  - IQ window (with VDL2HIP_TXCAP_IQ).  win_first = max(0, first_sample - pre_samples, last_sample - 57 343), win_last = last_sample
+ *    + post_samples.  pre_samples <= 4096; post_samples <= (H + 1) B, a larger value is refused at enable: the samples up to
+ *    last_sample + (H + 1) B exist when the record is emitted, whatever the cuts, so the window depends on the stream alone.
+ *    VDL2HIP_TXC_CLIPPED is set iff last_sample - 57 343 > max(0, first_sample - pre_samples).  Nothing is read further back than the
+ *    preamble search reads, and like it vdl2hip_txcap_enable() refuses a monitor with (H + 1) B > 4096.
+ *    iq_count = min(win_last - win_first + 1, max_iq_samples), max_iq_samples 0 meaning no limit: the FIRST iq_count samples of the
+ *    window are delivered, so the start of a transmission survives; VDL2HIP_TXC_TRUNCATED is set if the limit bit.  The values are
+ *    y_c[win_first ...] as they stand at that point, bit for bit.  (win_first and win_last are stated without VDL2HIP_TXCAP_IQ too;
+ *    iq_count is 0 then.)
+ *  - IQ pool.  pool_samples pairs per feed in flight (0 means 2^20; above 2^24 is refused).  Offsets are the exclusive prefix sum of
+ *    iq_count in record order; a window that ends beyond the pool gets iq_count = 0 and VDL2HIP_TXC_NO_ROOM, and
+ *    vdl2hip_txcap_info.iq_dropped counts these.  Offsets only grow, so what survives is a prefix.  (The burst capture's rules.)
+ *  - Spectrum (with VDL2HIP_TXCAP_SPECTRUM).  Extent: e_first = max(first_sample, last_sample - 57 343), e_last = last_sample - the
+ *    preamble search's range, without pre or post -, len = e_last - e_first + 1.  N = nfft, one of 64, 128, 256, 512, 1024 (0 means
+ *    256); the hop is N / 2;  S = len >= N ? (len - N) / (N / 2) + 1 : 0;  segment s covers e_first + s N / 2 .. + N - 1.  w[] is what
+ *    vdl2hip_spectrum_window(N, window) returns.
+ *      X_s[k] = sum_n w[n] y[e_first + s N / 2 + n] exp(-2 pi i k n / N)   in float32: the input monitor's transform, its twiddle table
+ *      q_s[i] = |X_s[(i + N / 2) mod N]|^2                                  two products and a sum in float32
+ *      power[i] = (float)((sum_s (double)q_s[i]) norm / S),  norm = 1 / (sum w)^2 in double
+ *    The sum over s is float64 in an order that is a function of S and N alone (no atomics).  Bin i lies at freq + (i - N / 2)
+ *    105000 / N Hz.  S = 0 sets VDL2HIP_TXC_SHORT and segments = 0; power[] is all zero.
+ *  - Spectrum room.  The first pool_spectra records of a feed get a spectrum (0 means 1024; pool_spectra N > 2^24 is refused).  Later
+ *    records get VDL2HIP_TXC_NO_SPECTRUM and no power[]; vdl2hip_txcap_info.spectra_dropped counts them.
+ *  - Determinism.  The same sequence of calls gives the same bytes.  Every integer field - win_*, iq_count before room, segments, the
+ *    flags other than the two room flags - depends on the stream alone, not on the cuts.  For the same y_c, power[] is the same bytes
+ *    however the stream was cut and however the kernel splits the work.
+ *  - Accuracy of power[].  Against the float64 definition on the same y, per segment the monitor's own bound holds ("Spectrogram":
+ *    b_s[i] with e = log2 N 2^-24); power[i] lies within the mean of b_s[i] over the segments plus one float32 rounding.
+ *  - Outcome.  frames and frames_ok are copied from the log's join on the host.  VDL2HIP_TXCAP_UNDECODED_ONLY delivers only the
+ *    records with frames_ok == 0 (filtered on the host, like the log's: the device captures everything and vdl2hip_txcap_info counts
+ *    everything).  A stated limit: on a busy band the pools fill with decoded transmissions; max_iq_samples, the pools and the room
+ *    flags are the control.
+ *  - vdl2hip_txcap_measure() turns a power[] into four figures (below).  No thresholds and no classification are in the library.
+ *  - chan is the index in cfg.freqs.  Groups get no group call: vdl2hip_group_ctx(g, k) is the handle. */
+#define VDL2HIP_TXCAP_IQ             1u        /* vdl2hip_txcap_cfg.flags: at least one of _IQ and _SPECTRUM */
+#define VDL2HIP_TXCAP_SPECTRUM       2u
+#define VDL2HIP_TXCAP_UNDECODED_ONLY 4u
+#define VDL2HIP_TXC_CLIPPED          2u        /* vdl2hip_tx_capture.flags (bit 0 is VDL2HIP_TX_PARTIAL, passed on from the log's record) */
+#define VDL2HIP_TXC_TRUNCATED        4u
+#define VDL2HIP_TXC_NO_ROOM          8u
+#define VDL2HIP_TXC_SHORT            16u
+#define VDL2HIP_TXC_NO_SPECTRUM      32u
+typedef struct {
+	uint32_t struct_size, flags, pre_samples, post_samples, max_iq_samples, nfft, window, pool_samples, pool_spectra, reserved;
+} vdl2hip_txcap_cfg;                           /* 40 bytes; reserved must be 0; window: VDL2HIP_WIN_* */
+typedef struct {
+	uint32_t chan, freq;                  /* as in vdl2hip_tx */
+	uint64_t first_bin;                   /* the join key with vdl2hip_tx and vdl2hip_tx_search */
+	int64_t  win_first, win_last;
+	uint64_t iq_off, spec_off;            /* pairs / floats into the caller's buffers of that vdl2hip_txcap_read() */
+	uint32_t iq_count, flags, segments, nfft;   /* flags: VDL2HIP_TXC_* | VDL2HIP_TX_PARTIAL; nfft: floats of power[], 0 without a spectrum */
+	uint32_t frames, frames_ok, reserved[2];    /* frames, frames_ok: filled in by the host from the log's join */
+} vdl2hip_tx_capture;                          /* 80 bytes */
+typedef struct {
+	uint32_t struct_size, flags, pre_samples, post_samples, max_iq_samples, nfft, window, pool_samples, pool_spectra, reserved;   /* as in force */
+	uint64_t records, iq_samples, iq_dropped, spectra, spectra_dropped;   /* of the feeds collected so far: records, pairs, windows without room, spectra, records beyond pool_spectra */
+	float    kernel_ms;                        /* summed HIP-event time of the tap's launches at profiling level 2, else 0 */
+	uint32_t reserved2;
+} vdl2hip_txcap_info;                          /* 88 bytes */
+typedef struct {
+	double   total, peak_hz, centroid_hz, obw_hz;
+	uint32_t peak_bin, obw_lo, obw_hi, reserved;
+} vdl2hip_tx_shape;                            /* 48 bytes */
+
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
 typedef struct {
@@ -786,6 +867,32 @@ int  vdl2hip_txsearch_info_get(vdl2hip_ctx *ctx, vdl2hip_txsearch_info *info);
 /* Like vdl2hip_txlog_read(): the records of the feeds collected so far, oldest first.  What does not fit stays queued for the next
  * call; the call never waits for the device itself.  Returns the number of records written.  Search off: VDL2HIP_E_INVAL. */
 int  vdl2hip_txsearch_read(vdl2hip_ctx *ctx, vdl2hip_tx_search *recs, size_t cap_recs);
+
+/* ---- Transmission capture (see "Transmission capture" above) ----
+ * Switch the capture on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way, drops
+ * what is queued unread and starts afresh.  VDL2HIP_E_INVAL if the transmission log is off, for a bad struct_size, flags without
+ * VDL2HIP_TXCAP_IQ or _SPECTRUM or with an unknown bit, pre_samples > 4096, post_samples > (hang_bins + 1) * bin_samples, an nfft
+ * other than 0, 64, 128, 256, 512, 1024, an unknown window, pool_samples > 2^24, pool_spectra * nfft > 2^24, a reserved word that is
+ * not 0, or an activity monitor with (hang_bins + 1) * bin_samples > 4096, before anything is allocated or changed: a capture that was
+ * on stays as it was. */
+int  vdl2hip_txcap_enable(vdl2hip_ctx *ctx, const vdl2hip_txcap_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_txcap_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Capture off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txcap_info_get(vdl2hip_ctx *ctx, vdl2hip_txcap_info *info);
+/* Like vdl2hip_capture_read(): the records of the feeds collected so far, oldest first, with their windows in iq[] as (re, im) float
+ * pairs - record i's at pair recs[i].iq_off - and their spectra in spectra[] - record i's recs[i].nfft floats at recs[i].spec_off, none
+ * for a record with VDL2HIP_TXC_NO_SPECTRUM or a capture without VDL2HIP_TXCAP_SPECTRUM.  What does not fit - records, their IQ or
+ * their spectra - stays queued for the next call; the call never waits for the device itself.  Returns the number of records written,
+ * *pairs_used the pairs and *floats_used the floats (either may be NULL).  Capture off: VDL2HIP_E_INVAL. */
+int  vdl2hip_txcap_read(vdl2hip_ctx *ctx, vdl2hip_tx_capture *recs, size_t cap_recs, float *iq, size_t cap_pairs, size_t *pairs_used,
+                        float *spectra, size_t cap_floats, size_t *floats_used);
+/* Four figures of a power[] of nfft bins (host only, needs no GPU, needs no receiver).  All arithmetic is double, in ascending i, with
+ * f_i = (i - nfft / 2) * 105000 / nfft:  total = sum power;  peak_bin = the lowest index of the maximum, peak_hz = f_peak_bin;
+ * centroid_hz = sum f_i p_i / total;  obw_hz = (obw_hi - obw_lo + 1) * 105000 / nfft, obw_lo and obw_hi being the smallest i at which
+ * the running sum reaches 0.005 total and 0.995 total.  Everything is 0 when total is 0.
+ * VDL2HIP_E_INVAL for a NULL pointer or an nfft that is not one of the capture's. */
+int  vdl2hip_txcap_measure(const float *power, uint32_t nfft, vdl2hip_tx_shape *out);
 
 #ifdef __cplusplus
 }

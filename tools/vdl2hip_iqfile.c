@@ -44,6 +44,17 @@
  *                                 transmission the fields of vdl2hip_tx_search in the structure's order - "chan freq first_bin search_first
  *                                 search_last best_sample first_lock best_pherr best_slope best_ppm lock_points below_thr lock_phases
  *                                 flags frames frames_ok why"
+ *   --tx-capture-out <path>       (this library's own) switch the transmission capture on - and with it the transmission log and the activity
+ *                                 monitor, as --tx-out does - and, at exit, write what every transmission looked like: two lines "# key value
+ *                                 ..." with the fields of vdl2hip_txcap_info, then per transmission the fields of vdl2hip_tx_capture in the
+ *                                 structure's order and the four figures of vdl2hip_txcap_measure() - "chan freq first_bin win_first win_last
+ *                                 iq_off spec_off iq_count flags segments nfft frames frames_ok total peak_bin peak_hz centroid_hz obw_hz"
+ *   --tx-iq <path>                the transmissions' IQ windows (256 samples ahead of the first busy bin, a bin behind the last) one after the
+ *                                 other as cf32 at 105 kS/s; iq_off of a line is then the pair in this file its window begins at
+ *   --tx-spectra <path>           their power spectra one after the other as float32, nfft values each, bin i at freq + (i - nfft / 2)
+ *                                 105000 / nfft Hz; spec_off of a line is then the float in this file its spectrum begins at
+ *   --tx-capture-undecoded-only   only the transmissions that produced no frame that passes the AVLC checks
+ *   --tx-capture-nfft <n>         bins of a spectrum: 64, 128, 256, 512 or 1024 (default 256)
  *   --bursts-out <path>           (this library's own) switch the burst capture on and, at exit, write every burst handed to the burst decoder,
  *                                 decoded or not: a "# key value" line per field of vdl2hip_capture_info, then per burst every field of
  *                                 vdl2hip_burst in the structure's order - "chan freq burst_ord sync_sample end_sample first_symbol nsym
@@ -147,6 +158,39 @@ static int take_tx_search(vdl2hip_ctx *rx) {
 		ntxss += (size_t)n;
 	}
 }
+/* transmission capture: the records so far with the four figures of each spectrum (written at exit, behind the totals), the IQ and
+ * the spectra files as they grow - raw float32, record i's at iq_off pairs / spec_off floats */
+typedef struct { vdl2hip_tx_capture r; vdl2hip_tx_shape shape; } tx_cap_row;
+static tx_cap_row *txcs;
+static size_t ntxcs, cap_txcs;
+static FILE *txc_iq, *txc_spectra;
+static uint64_t txc_iq_pairs, txc_spec_floats;
+static int take_tx_capture(vdl2hip_ctx *rx) {
+	enum { RECS = 256, PAIRS = 1 << 18, FLOATS = 1 << 18 };                     /* (a window is shorter than 2^16 pairs, a spectrum 1024 floats at the most) */
+	static vdl2hip_tx_capture rec[RECS];
+	static float iq[2 * PAIRS], sp[FLOATS];
+	for(;;) {
+		size_t used = 0, fused = 0;
+		const int n = vdl2hip_txcap_read(rx, rec, RECS, iq, PAIRS, &used, sp, FLOATS, &fused);
+		if(n <= 0) return n;
+		if(ntxcs + (size_t)n > cap_txcs) {
+			cap_txcs = 2 * (ntxcs + (size_t)n);
+			txcs = realloc(txcs, cap_txcs * sizeof *txcs);
+			if(!txcs) { perror("realloc"); exit(3); }
+		}
+		for(int i = 0; i < n; i++) {
+			tx_cap_row *row = &txcs[ntxcs++];
+			memset(row, 0, sizeof *row);
+			const int has = rec[i].nfft && !(rec[i].flags & VDL2HIP_TXC_NO_SPECTRUM);
+			if(has) (void)vdl2hip_txcap_measure(sp + rec[i].spec_off, rec[i].nfft, &row->shape);
+			rec[i].iq_off = txc_iq ? txc_iq_pairs + rec[i].iq_off : 0;
+			rec[i].spec_off = txc_spectra && has ? txc_spec_floats + rec[i].spec_off : 0;
+			row->r = rec[i];
+		}
+		if(txc_iq) { fwrite(iq, 2 * sizeof(float), used, txc_iq); txc_iq_pairs += used; }
+		if(txc_spectra) { fwrite(sp, sizeof(float), fused, txc_spectra); txc_spec_floats += fused; }
+	}
+}
 /* ... without --tx-out the log's own records are read and let go, so that they do not pile up */
 static int drop_tx(vdl2hip_ctx *rx) {
 	static vdl2hip_tx rec[256];
@@ -199,6 +243,8 @@ int main(int argc, char **argv) {
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
 	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL, *tx_search_path = NULL;
+	const char *tx_capture_path = NULL, *tx_iq_path = NULL, *tx_spectra_path = NULL;
+	uint32_t tx_capture_flags = VDL2HIP_TXCAP_SPECTRUM, tx_capture_nfft = 0;
 	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
@@ -244,6 +290,11 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--tx-out")) { NEEDARG(); tx_path = argv[++i]; }
 		else if(!strcmp(a, "--tx-search-out")) { NEEDARG(); tx_search_path = argv[++i]; }
+		else if(!strcmp(a, "--tx-capture-out")) { NEEDARG(); tx_capture_path = argv[++i]; }
+		else if(!strcmp(a, "--tx-iq")) { NEEDARG(); tx_iq_path = argv[++i]; tx_capture_flags |= VDL2HIP_TXCAP_IQ; }
+		else if(!strcmp(a, "--tx-spectra")) { NEEDARG(); tx_spectra_path = argv[++i]; }
+		else if(!strcmp(a, "--tx-capture-undecoded-only")) tx_capture_flags |= VDL2HIP_TXCAP_UNDECODED_ONLY;
+		else if(!strcmp(a, "--tx-capture-nfft")) { NEEDARG(); tx_capture_nfft = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--bursts-out")) { NEEDARG(); bursts_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-iq")) { NEEDARG(); bursts_iq_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-failed-only")) bursts_flags |= VDL2HIP_CAPTURE_FAILED_ONLY;
@@ -259,6 +310,7 @@ int main(int argc, char **argv) {
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
 			"[--waterfall-out file] [--waterfall-segments R] [--waterfall-mean file] [--waterfall-max file] "
 			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] "
+			"[--tx-capture-out file] [--tx-iq file] [--tx-spectra file] [--tx-capture-undecoded-only] [--tx-capture-nfft n] "
 			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
@@ -278,6 +330,9 @@ int main(int argc, char **argv) {
 	if(rawpath && !(raw_out = fopen(rawpath, "w"))) { perror("Could not open raw frames output"); return 2; }
 	if(bursts_iq_path && !bursts_path) { fprintf(stderr, "--bursts-iq needs --bursts-out\n"); return 1; }
 	if(bursts_iq_path && !(bursts_iq = fopen(bursts_iq_path, "w"))) { perror("Could not open bursts IQ output"); return 2; }
+	if((tx_iq_path || tx_spectra_path) && !tx_capture_path) { fprintf(stderr, "--tx-iq and --tx-spectra need --tx-capture-out\n"); return 1; }
+	if(tx_iq_path && !(txc_iq = fopen(tx_iq_path, "w"))) { perror("Could not open transmission IQ output"); return 2; }
+	if(tx_spectra_path && !(txc_spectra = fopen(tx_spectra_path, "w"))) { perror("Could not open transmission spectra output"); return 2; }
 
 	vdl2hip_cfg cfg;
 	memset(&cfg, 0, sizeof cfg);
@@ -308,19 +363,24 @@ int main(int argc, char **argv) {
 		if(wf_mean_path && !(wf_mean = fopen(wf_mean_path, "w"))) { perror("Could not open waterfall mean output"); return 2; }
 		if(wf_max_path && !(wf_max = fopen(wf_max_path, "w"))) { perror("Could not open waterfall max output"); return 2; }
 	}
-	if(activity_path || tx_path || tx_search_path) {
+	if(activity_path || tx_path || tx_search_path || tx_capture_path) {
 		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
 		if(activity_bin == 0 || (r = vdl2hip_activity_enable(rx, &ac)) != VDL2HIP_OK) {
 			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
-	if(tx_path || tx_search_path) {
+	if(tx_path || tx_search_path || tx_capture_path) {
 		vdl2hip_txlog_cfg tc = { sizeof tc, 0, 0, 0 };
 		if((r = vdl2hip_txlog_enable(rx, &tc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txlog_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
 	if(tx_search_path) {
 		vdl2hip_txsearch_cfg sc = { sizeof sc, 0, { 0, 0 } };
 		if((r = vdl2hip_txsearch_enable(rx, &sc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txsearch_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+	}
+	if(tx_capture_path) {
+		/* (post: a bin's worth behind the last busy bin, which the record's feed always holds) */
+		vdl2hip_txcap_cfg xc = { sizeof xc, tx_capture_flags, 256, activity_bin, 0, tx_capture_nfft, VDL2HIP_WIN_HANN, 0, 0, 0 };
+		if((r = vdl2hip_txcap_enable(rx, &xc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txcap_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
 	if(bursts_path) {
 		vdl2hip_capture_cfg cc = { sizeof cc, bursts_pre, bursts_post, bursts_flags, 0, 0 };
@@ -341,8 +401,9 @@ int main(int argc, char **argv) {
 		if((wf_mean || wf_max) && (r = take_lines(rx)) < 0) { fprintf(stderr, "vdl2hip_specgram_lines: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
-		if(tx_search_path && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if((tx_search_path || tx_capture_path) && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_search_path && (r = take_tx_search(rx)) < 0) { fprintf(stderr, "vdl2hip_txsearch_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(tx_capture_path && (r = take_tx_capture(rx)) < 0) { fprintf(stderr, "vdl2hip_txcap_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		held = 0;
 	} while(len == FILE_BUFSIZE);
 	free(buf);
@@ -487,6 +548,28 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "preamble search not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+	}
+	if(tx_capture_path) {
+		vdl2hip_txcap_info xi;
+		memset(&xi, 0, sizeof xi); xi.struct_size = sizeof xi;
+		r = vdl2hip_txcap_info_get(rx, &xi);
+		FILE *so = r == VDL2HIP_OK ? fopen(tx_capture_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# flags %u pre_samples %u post_samples %u max_iq_samples %u nfft %u window %u pool_samples %u pool_spectra %u\n", xi.flags, xi.pre_samples,
+					xi.post_samples, xi.max_iq_samples, xi.nfft, xi.window, xi.pool_samples, xi.pool_spectra);
+			fprintf(so, "# records %" PRIu64 " iq_samples %" PRIu64 " iq_dropped %" PRIu64 " spectra %" PRIu64 " spectra_dropped %" PRIu64 " kernel_ms %.6g\n", xi.records,
+					xi.iq_samples, xi.iq_dropped, xi.spectra, xi.spectra_dropped, (double)xi.kernel_ms);
+			for(size_t i = 0; i < ntxcs; i++) {                                     /* the record's fields in their order, then total peak_bin peak_hz centroid_hz obw_hz */
+				const vdl2hip_tx_capture *t = &txcs[i].r; const vdl2hip_tx_shape *m = &txcs[i].shape;
+				fprintf(so, "%u %u %" PRIu64 " %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 " %u %u %u %u %u %u %.9g %u %.3f %.3f %.3f\n", t->chan, t->freq, t->first_bin,
+						t->win_first, t->win_last, t->iq_off, t->spec_off, t->iq_count, t->flags, t->segments, t->nfft, t->frames, t->frames_ok,
+						m->total, m->peak_bin, m->peak_hz, m->centroid_hz, m->obw_hz);
+			}
+			fclose(so);
+		}
+		else fprintf(stderr, "transmission capture not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+		if(txc_iq) fclose(txc_iq);
+		if(txc_spectra) fclose(txc_spectra);
 	}
 	if(statsd_path) {
 		static char lines[1 << 20];
