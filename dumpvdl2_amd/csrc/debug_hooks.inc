@@ -743,6 +743,45 @@ int vdl2hip_debug_capture_plan(const void *bursts, const uint32_t *nb_chan, uint
 	return (int)total;
 }
 
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): k_toa's per-burst steps on the CPU, lane by lane and level by level.
+// One burst - its first symbol at first_symbol, its slope dphi - over y, a channel's ring of ring_len (re, im) pairs (a power of two,
+// at least 256), W = max_lag (0: 8): -> the record (chan, freq, burst_ord, sync_sample 0; curve_off 0) and curve[0 .. 2 W + 1).
+int vdl2hip_debug_toa_burst(const float *y, uint32_t ring_len, int64_t first_symbol, float dphi, uint32_t max_lag, vdl2hip_burst_toa *rec, float *curve, size_t cap_floats) {
+	if(!y || !rec || (ring_len & (ring_len - 1)) || ring_len < 256 || max_lag > kToaMaxLag) return VDL2HIP_E_INVAL;
+	const uint32_t W = max_lag ? max_lag : kToaDefLag, nlags = 2 * W + 1, nwin = (uint32_t)kToaTaps + 2 * W;
+	if(curve && cap_floats < nlags) return VDL2HIP_E_TOOBIG;
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	ToaDesign d;
+	design_toa(d);
+	Burst b{};
+	b.t_first = first_symbol; b.vdphi = dphi;
+	const int64_t t0 = b.t_first - kToaLead;
+	cf32 u[kToaTaps], yw[kToaWin], cl[kToaMaxLags], part[64];
+	float P[kToaMaxLags];
+	double dpart[64];
+	auto add = [](cf32 p, cf32 q) { return toa_add(p, q); };
+	auto dadd = [](double p, double q) { return p + q; };
+	auto sum = [&](uint32_t k, uint32_t n0, uint32_t n1) {
+		for(uint32_t l = 0; l < 64; l++) part[l] = toa_lane_sum(u, yw, k, l, n0, n1);
+		for(uint32_t s = 32; s >= 1; s >>= 1) for(uint32_t l = 0; l < 64; l++) toa_tree_step(part, l, s, add);
+		return part[0];
+	};
+	for(uint32_t l = 0; l < (uint32_t)kToaTaps; l++) u[l] = toa_u(cf32{ d.s[2 * l], d.s[2 * l + 1] }, dphi, l);
+	for(uint32_t l = 0; l < nwin; l++) yw[l] = toa_window(yc, ring_len - 1, t0, W, l);
+	for(uint32_t w = 0; w < (uint32_t)kToaWaves; w++) for(uint32_t k = w; k < nlags; k += kToaWaves) { cl[k] = sum(k, 0u, (uint32_t)kToaTaps); P[k] = toa_power(cl[k]); }
+	const uint32_t kp = toa_peak(P, nlags);
+	ToaSums q;
+	q.c = cl[kp]; q.ca = sum(kp, 0u, (uint32_t)kToaHalf); q.cb = sum(kp, (uint32_t)kToaHalf, 2u * kToaHalf);
+	for(uint32_t l = 0; l < 64; l++) dpart[l] = toa_lane_energy(yw, kp, l);
+	for(uint32_t s = 32; s >= 1; s >>= 1) for(uint32_t l = 0; l < 64; l++) toa_tree_step(dpart, l, s, dadd);
+	q.ey = dpart[0];
+	ToaRec r{};
+	toa_record(b, 0u, 0u, W, P, kp, q, d.energy, curve != nullptr, r);
+	memcpy(rec, &r, sizeof r);
+	if(curve) memcpy(curve, P, nlags * sizeof(float));
+	return VDL2HIP_OK;
+}
+
 // test hook (not declared in vdl2hip.h): what the sync kernels left for decimated samples first .. first+count-1 of one channel - the tabulated
 // metric {pherr (its sign: the referee's mark), slope} and the candidate bit, one byte per sample
 int vdl2hip_debug_read_sync(vdl2hip_ctx *c, uint32_t chan, int64_t first, size_t count, float *pf, uint8_t *cand) {

@@ -1,9 +1,9 @@
-// taps.inc - the receiver's seven optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
-// input monitor's and the spectrogram's - capture.h, txsearch.h, txcap.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
+// taps.inc - the receiver's eight optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
+// input monitor's and the spectrogram's - capture.h, toa.h, txsearch.h, txcap.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
 // (collect), what gives its buffers back (free), then its entry points of vdl2hip.h.  A tap stands behind those it calls into: the
 // log hands its records to the search and to the transmission capture, the activity monitor launches the log and switches it off,
 // the input monitor does both with the spectrogram.
-// Four of them deliver records - capture, search, transmission capture, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
+// Five of them deliver records - capture, burst timing, search, transmission capture, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
 // (hostmem.h), per context the totals, a queue of collected records and the staging buffer of a feed with more records than come
 // with the header.  Their enable is: validate, collect what is in flight, free the old, allocate per slot, zero the totals, on.
 // (The entry points have C linkage from their declarations in vdl2hip.h.)
@@ -491,6 +491,148 @@ int vdl2hip_capture_read(vdl2hip_ctx *c, vdl2hip_burst *recs, size_t cap_recs, f
 		q.pop_front();
 	}
 	if(pairs_used) *pairs_used = used;
+	return (int)n;
+}
+
+// ---- burst timing (vdl2hip.h, "Burst timing"; kernel: toa.h; the template: toa_design.h) ----
+// The ring behind the window.  Under the burst capture's conditions (above) a burst's first symbol lies after k0 - 56 320, k0 being the
+// first sample of the feed that decodes it; the window begins a unique word and W samples before that: t0 - W > k0 - 56 320 - 160 - 32
+// > k0 - kHistory - 1024.  It ends at t0 + W + 150 < first_symbol + 32, inside the header the walker has already read.
+static_assert(56320 + kToaLead + kToaMaxLag < kHistory + 1024, "a window begins inside what the ring keeps behind a feed");
+static_assert(sizeof(ToaRec) == sizeof(vdl2hip_burst_toa) && sizeof(vdl2hip_burst_toa) == 96 && offsetof(ToaRec, peak_sample) == offsetof(vdl2hip_burst_toa, peak_sample)
+              && offsetof(ToaRec, peak_lag) == offsetof(vdl2hip_burst_toa, peak_lag) && offsetof(ToaRec, toa_frac) == offsetof(vdl2hip_burst_toa, toa_frac)
+              && offsetof(ToaRec, resid) == offsetof(vdl2hip_burst_toa, resid) && offsetof(ToaRec, flags) == offsetof(vdl2hip_burst_toa, flags)
+              && offsetof(vdl2hip_burst_toa, flags) == 80 && offsetof(ToaRec, curve_off) == offsetof(vdl2hip_burst_toa, curve_off), "the host copies the device's records as they are");
+static_assert(sizeof(vdl2hip_toa_cfg) == 16 && sizeof(vdl2hip_toa_info) == 64 && sizeof(ToaHdr) == 16, "vdl2hip.h states these sizes");
+static_assert(VDL2HIP_TOA_EARLY == kToaEarly && VDL2HIP_TOA_EDGE == kToaEdge && VDL2HIP_TOA_FLAT == kToaFlat && VDL2HIP_TOA_NO_CURVE == kToaNoCurve, "the record's flags");
+static_assert(kCapMaxChan == kK5MaxChan && kToaWin <= kToaThreads, "k_toa keeps every channel's offsets in LDS and stages a window with a lane per sample");
+
+// Its share of a feed (launch_rest): behind the frame finisher on the feed's burst stream, like the capture
+static int toa_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->toa;
+	ToaArgs a{};
+	a.y = c->d_y; a.bursts = sl.d_bursts; a.nb_chan = sl.d_nbchan; a.freq = c->d_freq; a.s = m.d_s;
+	a.rec = sl.toa.mail.d_rec(); a.curve = sl.toa.d_curve; a.hdr = sl.toa.mail.d_hdr();
+	a.e_s = m.e_s; a.cap_bursts_chan = c->cap_bursts_chan; a.nchan = (uint32_t)c->C; a.chan_first = (uint32_t)c->chan_first;
+	a.cap = c->cap; a.mask = c->cap - 1; a.W = m.W; a.pool_curves = m.pool_curves;
+	KernelTimes &t = sl.toa.times;
+	t.arm(c->profiling >= 2);
+	// a workgroup per burst, bounded like the capture's: 8 .. 512
+	const unsigned grid = std::min(512u, std::max(8u, sl.k5_waves / 4));
+	hipExtLaunchKernelGGL(k_toa, dim3(grid), dim3(kToaThreads), 0u, st, t.e(0), t.e(1), 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(sl.toa.mail.post(st));
+	t.launched(1);
+	return VDL2HIP_OK;
+}
+// A collected feed's records and the curves of the first pool_curves of them - one staging buffer, one wait - joined with the feed's
+// frames as the capture's are and appended to the queue.
+static int toa_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+	auto &m = c->toa;
+	if(!m.on || !sl.toa.mail) return VDL2HIP_OK;
+	const uint32_t nrec = (uint32_t)std::min<uint64_t>(sl.toa.mail.hdr().nrec, (uint64_t)c->C * c->cap_bursts_chan);
+	if(nrec == 0) return VDL2HIP_OK;
+	const uint32_t nlags = 2 * m.W + 1, ncurve = std::min(nrec, m.pool_curves);
+	const ToaRec *rec = nullptr;
+	const size_t rec_bytes = sl.toa.mail.staged(nrec), cv_bytes = (size_t)ncurve * nlags * sizeof(float);
+	HIPCHK(sl.toa.mail.fetch(nrec, m.stage, c->streams.out, rec, false, cv_bytes));
+	HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.toa.d_curve, cv_bytes, hipMemcpyDeviceToHost, c->streams.out));
+	HIPCHK(hipStreamSynchronize(c->streams.out));
+	const float *cvp = reinterpret_cast<const float *>(m.stage + rec_bytes);
+	auto curves = std::make_shared<std::vector<float>>(cvp, cvp + (size_t)ncurve * nlags);
+	struct Join { uint32_t frames = 0, ok = 0; };
+	std::map<std::pair<int32_t, int64_t>, Join> join;
+	for(uint32_t i = 0; i < nf; i++) {
+		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
+		Join &j = join[{ fr[i].chan + c->chan_first, fr[i].burst_ord }];
+		j.frames++; if(fr[i].avlc_status == AVLC_OK) j.ok++;
+	}
+	for(uint32_t i = 0; i < nrec; i++) {
+		vdl2hip_burst_toa r;
+		memcpy(&r, rec + i, sizeof r);
+		if(i < ncurve && !(r.flags & VDL2HIP_TOA_NO_CURVE) && r.nlags == nlags) r.curve_off = i * nlags;
+		else { r.flags |= VDL2HIP_TOA_NO_CURVE; r.curve_off = 0; }
+		m.bursts++; if(r.flags & VDL2HIP_TOA_NO_CURVE) m.curves_dropped++; else m.curves++;
+		if(r.flags & VDL2HIP_TOA_EARLY) m.early++;
+		if(r.flags & VDL2HIP_TOA_EDGE) m.edge++;
+		auto it = join.find({ (int32_t)r.chan, r.burst_ord });
+		if(it != join.end()) { r.frames = it->second.frames; r.frames_ok = it->second.ok; }
+		if((m.flags & VDL2HIP_TOA_FAILED_ONLY) && r.frames_ok != 0) continue;
+		m.queue.push_back(vdl2hip_ctx::ToaItem{ r, curves });
+	}
+	return VDL2HIP_OK;
+}
+// give the tap's buffers back (nothing of it may be in flight: the callers have collected every feed)
+static void toa_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.toa.reset();
+	c->toa.d_s.reset();
+	c->toa.queue.clear();
+	c->toa.on = false;
+}
+int vdl2hip_toa_template(float *s, size_t cap_pairs) {
+	if(!s) return VDL2HIP_E_INVAL;
+	if(cap_pairs < (size_t)kToaTaps) return VDL2HIP_E_TOOBIG;
+	ToaDesign d;
+	design_toa(d);
+	memcpy(s, d.s, sizeof d.s);
+	return kToaTaps;
+}
+int vdl2hip_toa_enable(vdl2hip_ctx *c, const vdl2hip_toa_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_toa_cfg)) return VDL2HIP_E_INVAL;
+	if(cfg->max_lag > kToaMaxLag || (cfg->flags & ~VDL2HIP_TOA_FAILED_ONLY)) return VDL2HIP_E_INVAL;
+	const uint32_t W = cfg->max_lag ? cfg->max_lag : kToaDefLag, nlags = 2 * W + 1, pool_curves = cfg->pool_curves ? cfg->pool_curves : kToaDefCurves;
+	if((uint64_t)pool_curves * nlags > kToaMaxPool) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier tap is in flight any more
+	auto &m = c->toa;
+	toa_free(c);
+	ToaDesign d;
+	design_toa(d);
+	const size_t nb = (size_t)c->C * c->cap_bursts_chan;
+	bool ok = m.d_s.alloc(kToaTaps) == hipSuccess;
+	// (a feed has at most nb records: no more curves than that)
+	for(auto &sl : c->slot) ok = ok && sl.toa.mail.alloc(nb) == hipSuccess && sl.toa.d_curve.alloc(std::min<size_t>(nb, pool_curves) * nlags) == hipSuccess;
+	if(!ok) { toa_free(c); return VDL2HIP_E_NOMEM; }
+	if(hipMemcpy(m.d_s, d.s, sizeof d.s, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); toa_free(c); return VDL2HIP_E_DEVICE; }
+	m.W = W; m.flags = cfg->flags; m.pool_curves = pool_curves; m.e_s = d.energy;
+	m.bursts = m.curves = m.curves_dropped = m.early = m.edge = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_toa_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->toa.on && !c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	toa_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_toa_info_get(vdl2hip_ctx *c, vdl2hip_toa_info *info) {
+	if(!c || !c->toa.on || !info || info->struct_size != sizeof(vdl2hip_toa_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->toa;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->max_lag = m.W; info->flags = m.flags; info->pool_curves = m.pool_curves;
+	info->bursts = m.bursts; info->curves = m.curves; info->curves_dropped = m.curves_dropped; info->early = m.early; info->edge = m.edge;
+	info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+// (its own: a record goes out with its curve, packed behind the curves of the records before it)
+int vdl2hip_toa_read(vdl2hip_ctx *c, vdl2hip_burst_toa *recs, size_t cap_recs, float *curves, size_t cap_floats, size_t *floats_used) {
+	if(!c || !c->toa.on || (!recs && cap_recs) || (!curves && cap_floats)) return VDL2HIP_E_INVAL;
+	auto &q = c->toa.queue;
+	size_t n = 0, used = 0;
+	while(!q.empty() && n < cap_recs) {
+		const vdl2hip_ctx::ToaItem &it = q.front();
+		const size_t nfl = (it.r.flags & VDL2HIP_TOA_NO_CURVE) ? 0 : it.r.nlags;
+		if(used + nfl > cap_floats || used + nfl > 0xffffffffull) break;
+		recs[n] = it.r;
+		recs[n].curve_off = (uint32_t)(nfl ? used : 0);
+		if(nfl) memcpy(curves + used, it.curves->data() + it.r.curve_off, nfl * sizeof(float));
+		used += nfl;
+		n++;
+		q.pop_front();
+	}
+	if(floats_used) *floats_used = used;
 	return (int)n;
 }
 

@@ -28,6 +28,7 @@
 #include "txsearch.h"
 #include "txcap.h"
 #include "capture.h"
+#include "toa.h"
 #include "tables.h"
 #include "hostmem.h"
 
@@ -170,6 +171,10 @@ struct OutSlot {
 	// the capture's launches followed this feed's frame finisher; times: k_txcap_plan + k_txcap_copy, k_txcap_spectrum + k_txcap_reduce
 	struct TxcBufs { RecordMail<TxcHdr, TxcRec> mail; DevBuf<uint32_t> d_poff; DevBuf<double> d_part; DevBuf<cf32> d_pool; DevBuf<float> d_spec; };
 	TapSlot<TxcBufs> txc;
+	// burst timing (toa.h): the feed's records and the curves of the first pool_curves of them.  on: this feed's back end is followed by
+	// k_toa; times: k_toa
+	struct ToaBufs { RecordMail<ToaHdr, ToaRec> mail; DevBuf<float> d_curve; };
+	TapSlot<ToaBufs> toa;
 	unsigned k5_waves = 0; bool small = false;   // wavefronts of this feed's burst decoder; short feed: its whole back end runs on the front stream
 };
 
@@ -251,6 +256,16 @@ struct vdl2hip_ctx {
 		struct { DevBuf<float> d_w; DevBuf<float2> d_tw; } buf;
 		PinnedBuf stage; std::deque<TxcItem> queue;
 	} txc;
+	// Burst timing (toa.h, vdl2hip_toa_*): off unless enabled.  W, pool_curves: the configuration in force; e_s: the template's energy;
+	// d_s: the template on the device; queue: the records of the collected feeds, oldest first, each with the curves of its feed (one
+	// allocation per feed, shared by its records; curve_off: where the record's begins in it)
+	struct ToaItem { vdl2hip_burst_toa r; std::shared_ptr<std::vector<float>> curves; };
+	struct {
+		bool on = false; uint32_t W = 0, flags = 0, pool_curves = 0; double e_s = 0.0;
+		uint64_t bursts = 0, curves = 0, curves_dropped = 0, early = 0, edge = 0; double kernel_ms = 0.0;
+		DevBuf<cf32> d_s;
+		PinnedBuf stage; std::deque<ToaItem> queue;
+	} toa;
 	uint64_t dmax = 0;                     // decimated samples one feed can make at the most
 	bool specialised = false;
 	std::vector<uint32_t> freqs, dphi, all_freqs;
@@ -402,7 +417,7 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0);
 // on the way is the drain's to report, not theirs
 static int collect_all(vdl2hip_ctx *c) { const int r = collect_pending(c); return r == VDL2HIP_E_OVERFLOW ? VDL2HIP_OK : r; }
 
-#include "taps.inc"   // the six taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
+#include "taps.inc"   // the taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
 
 static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	if(!sl.pending) return VDL2HIP_OK;
@@ -416,6 +431,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.txl.times.collect(c->txl.kernel_ms);
 	sl.txs.times.collect(c->txs.kernel_ms);
 	sl.txc.times.collect(c->txc.kernel_ms);
+	sl.toa.times.collect(c->toa.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
 		const Event *ev = sl.ev;
 		float ms = 0.f;
@@ -466,6 +482,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 		}
 	}
 	if(sl.cap.on) { sl.cap.on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
+	if(sl.toa.on) { sl.toa.on = false; int r = toa_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	if(c->txl.on) { int r = txlog_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	return ctl.overflow ? VDL2HIP_E_OVERFLOW : VDL2HIP_OK;
 }
@@ -521,6 +538,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 
 	sl.ev_valid = false;
 	sl.cap.on = c->capt.on && D > 0;                                // (the capture takes effect with the feed that follows its enabling)
+	sl.toa.on = c->toa.on && D > 0;                                 // (... and so does burst timing)
 	sl.txl.on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
 	sl.txs.on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
 	sl.txc.on = false;                                              // (... and the transmission capture's)
@@ -910,6 +928,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		                   c->d_acnt, (const float *)c->d_nfring, c->nf_ring - 1, sl.d_frames_out, sl.d_pool_out);
 		// the burst capture reads this feed's burst lists and y here: both passes of the burst decoder and its scans are done
 		if(sl.cap.on) { int r = capture_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		// ... and so does burst timing
+		if(sl.toa.on) { int r = toa_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 		// the transmission log's header and first records of this feed (written on the front stream ahead of the sync kernels: long done)
 		if(sl.txl.on) HIPCHK(sl.txl.mail.post(s5_));
 		// the preamble search reads the log's records of this feed (the same ordering) and y here, like the capture

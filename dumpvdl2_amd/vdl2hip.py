@@ -52,7 +52,12 @@ EXPORTS = [
     "vdl2hip_txsearch_enable", "vdl2hip_txsearch_disable", "vdl2hip_txsearch_info_get", "vdl2hip_txsearch_read",
     "vdl2hip_specgram_enable", "vdl2hip_specgram_disable", "vdl2hip_specgram_read", "vdl2hip_specgram_lines", "vdl2hip_specgram_channels",
     "vdl2hip_txcap_enable", "vdl2hip_txcap_disable", "vdl2hip_txcap_info_get", "vdl2hip_txcap_read", "vdl2hip_txcap_measure",
+    "vdl2hip_toa_template", "vdl2hip_toa_enable", "vdl2hip_toa_disable", "vdl2hip_toa_info_get", "vdl2hip_toa_read",
 ]
+# include/vdl2hip.h: VDL2HIP_TOA_FAILED_ONLY (cfg.flags), VDL2HIP_TOA_* (vdl2hip_burst_toa.flags)
+TOA_FAILED_ONLY = 1
+TOA_EARLY, TOA_EDGE, TOA_FLAT, TOA_NO_CURVE = 1, 2, 4, 8
+TOA_TAPS = 151
 # include/vdl2hip.h: VDL2HIP_TXCAP_* (cfg.flags), VDL2HIP_TXC_* (vdl2hip_tx_capture.flags, beside TX_PARTIAL)
 TXCAP_IQ, TXCAP_SPECTRUM, TXCAP_UNDECODED_ONLY = 1, 2, 4
 TXC_CLIPPED, TXC_TRUNCATED, TXC_NO_ROOM, TXC_SHORT, TXC_NO_SPECTRUM = 2, 4, 8, 16, 32
@@ -210,6 +215,21 @@ TXC_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("
                       ("frames", "<u4"), ("frames_ok", "<u4"), ("reserved", "<u4", (2,))])     # vdl2hip_tx_capture, 80 bytes
 
 
+class ToaCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_lag", C.c_uint32), ("flags", C.c_uint32), ("pool_curves", C.c_uint32)]
+
+
+class ToaInfo(C.Structure):
+    _fields_ = ToaCfg._fields_ + [("bursts", C.c_uint64), ("curves", C.c_uint64), ("curves_dropped", C.c_uint64), ("early", C.c_uint64),
+                                  ("edge", C.c_uint64), ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+BURST_TOA_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("burst_ord", "<i8"), ("sync_sample", "<i8"), ("first_symbol", "<i8"), ("peak_sample", "<i8"),
+                            ("peak_lag", "<i4"), ("nlags", "<u4"), ("toa_frac", "<f4"), ("peak_power", "<f4"), ("energy", "<f4"), ("rho", "<f4"),
+                            ("carrier_phase", "<f4"), ("cfo_hz", "<f4"), ("dphi", "<f4"), ("resid", "<f4"),
+                            ("flags", "<u4"), ("frames", "<u4"), ("frames_ok", "<u4"), ("curve_off", "<u4")])     # vdl2hip_burst_toa, 96 bytes
+
+
 class PackedFrame(C.Structure):
     _fields_ = [("frame", CFrame), ("octets_off", C.c_uint64)]
 
@@ -302,6 +322,12 @@ def load_library(path: str = None):
         L.vdl2hip_txcap_info_get.argtypes = [C.c_void_p, C.POINTER(TxcapInfo)]
         L.vdl2hip_txcap_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.vdl2hip_txcap_measure.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(TxShape)]
+    if hasattr(L, "vdl2hip_toa_enable"):
+        L.vdl2hip_toa_template.argtypes = [C.c_void_p, C.c_size_t]
+        L.vdl2hip_toa_enable.argtypes = [C.c_void_p, C.POINTER(ToaCfg)]
+        L.vdl2hip_toa_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_toa_info_get.argtypes = [C.c_void_p, C.POINTER(ToaInfo)]
+        L.vdl2hip_toa_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -576,6 +602,45 @@ def txcap_measure(power, nfft: int = None) -> dict:
     if r != 0:
         raise Vdl2HipError(f"vdl2hip_txcap_measure: {Lib.vdl2hip_strerror(r).decode()} ({r})")
     return {k: getattr(out, k) for k, _ in TxShape._fields_ if k != "reserved"}
+
+
+def toa_template() -> np.ndarray:
+    """vdl2hip_toa_template(): the unique word's waveform the burst timing tap correlates with, 151 complex64 values at the decimated
+    rate - index 0 the centre of symbol 0, index 150 that of symbol 15.  Needs no GPU."""
+    Lib = load_library()
+    s = np.zeros((TOA_TAPS, 2), dtype=np.float32)
+    _err(Lib, Lib.vdl2hip_toa_template(s.ctypes.data, TOA_TAPS), "vdl2hip_toa_template")
+    return s.view(np.complex64).reshape(-1)
+
+
+def _toa_enable(Lib, ctx, max_lag, failed_only, pool_curves) -> None:
+    cfg = ToaCfg(C.sizeof(ToaCfg), max_lag, TOA_FAILED_ONLY if failed_only else 0, pool_curves)
+    _err(Lib, Lib.vdl2hip_toa_enable(ctx, C.byref(cfg)), "vdl2hip_toa_enable")
+
+
+def _toa_info(Lib, ctx) -> dict:
+    info = ToaInfo(C.sizeof(ToaInfo))
+    _err(Lib, Lib.vdl2hip_toa_info_get(ctx, C.byref(info)), "vdl2hip_toa_info_get")
+    return {k: getattr(info, k) for k, _ in ToaInfo._fields_ if k not in ("struct_size", "reserved")}
+
+
+def _toa_read(Lib, ctx, cap_recs: int = 4096, cap_floats: int = 1 << 20):
+    """vdl2hip_toa_read() until nothing more comes -> (records as one array of BURST_TOA_DTYPE, with curve_off as the calls gave it;
+    their curves P(-W .. W) as float32 arrays, empty where the record has none).  cap_*: the buffers of one call (65 floats hold any
+    curve)."""
+    recs = np.zeros(max(1, cap_recs), dtype=BURST_TOA_DTYPE)
+    cv = np.zeros(max(1, cap_floats), dtype=np.float32)
+    out, curves = [], []
+    while True:
+        used = C.c_size_t(0)
+        n = _err(Lib, Lib.vdl2hip_toa_read(ctx, recs.ctypes.data, cap_recs, cv.ctypes.data, cap_floats, C.byref(used)), "vdl2hip_toa_read")
+        if n == 0:
+            break
+        out.append(recs[:n].copy())
+        for r in recs[:n]:
+            nfl = int(r["nlags"]) if not int(r["flags"]) & TOA_NO_CURVE else 0
+            curves.append(cv[int(r["curve_off"]):int(r["curve_off"]) + nfl].copy())
+    return (np.concatenate(out) if out else np.zeros(0, dtype=BURST_TOA_DTYPE)), curves
 
 
 def live_resources() -> dict:
@@ -917,6 +982,24 @@ class Receiver:
         arrays - their IQ windows -, list of float32 arrays - their spectra, empty where a record has none)"""
         return _txcap_read(self.L, self.h, cap_recs, cap_pairs, cap_floats)
 
+    def toa_enable(self, max_lag: int = 0, failed_only: bool = False, pool_curves: int = 0) -> None:
+        """switch burst timing on from the next feed (vdl2hip.h, "Burst timing"): of every burst handed to the burst decoder the
+        correlation with the unique word's waveform at 2 max_lag + 1 lags (0: 8) round the decoder's symbol clock - arrival time to a
+        fraction of a sample, fit, carrier phase and offset.  failed_only: deliver only bursts without a good frame; pool_curves: the
+        records of a feed that also deliver their curve (0: 4096)."""
+        _toa_enable(self.L, self.h, max_lag, failed_only, pool_curves)
+
+    def toa_disable(self) -> None:
+        self._chk(self.L.vdl2hip_toa_disable(self.h), "vdl2hip_toa_disable")
+
+    def toa_info(self) -> dict:
+        """the configuration in force and the totals of the feeds collected so far (vdl2hip_toa_info)"""
+        return _toa_info(self.L, self.h)
+
+    def toa_read(self, cap_recs: int = 4096, cap_floats: int = 1 << 20):
+        """the records of the feeds collected so far (sync() or a drain collects) -> (array of BURST_TOA_DTYPE, their curves)"""
+        return _toa_read(self.L, self.h, cap_recs, cap_floats)
+
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """switch the burst capture on from the next feed (vdl2hip.h, "Burst capture"): of every burst handed to the burst decoder the
         decimated IQ from `pre` samples before its sync to `post` after its last symbol, its timing and a phase-error quality figure.
@@ -1118,6 +1201,22 @@ class ReceiverGroup:
     def txcap_read(self, member: int, cap_recs: int = 4096, cap_pairs: int = 1 << 20, cap_floats: int = 1 << 20):
         """Receiver.txcap_read() of one member: its own channels' transmissions"""
         return _txcap_read(self.L, self.member(member), cap_recs, cap_pairs, cap_floats)
+
+    def toa_enable(self, max_lag: int = 0, failed_only: bool = False, pool_curves: int = 0) -> None:
+        """burst timing of every member (there is no group call: each member times its own channels' bursts)"""
+        for i in range(self.size()):
+            _toa_enable(self.L, self.member(i), max_lag, failed_only, pool_curves)
+
+    def toa_disable(self) -> None:
+        for i in range(self.size()):
+            self._chk(self.L.vdl2hip_toa_disable(self.member(i)), "vdl2hip_toa_disable")
+
+    def toa_info(self, member: int) -> dict:
+        return _toa_info(self.L, self.member(member))
+
+    def toa_read(self, member: int, cap_recs: int = 4096, cap_floats: int = 1 << 20):
+        """Receiver.toa_read() of one member: its own channels' bursts (chan: the index in the group's frequency list)"""
+        return _toa_read(self.L, self.member(member), cap_recs, cap_floats)
 
     def capture_enable(self, pre: int = 256, post: int = 32, failed_only: bool = False, pool_samples: int = 0) -> None:
         """the burst capture of every member (there is no group call: each member captures its own channels' bursts)"""

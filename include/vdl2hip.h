@@ -56,7 +56,9 @@ extern "C" {
                                  *    vdl2hip_specgram_enable() / _disable() / _read() / _lines() / _channels() with vdl2hip_specgram_cfg / _info: the
                                  *    spectrogram on top of the input monitor, off unless enabled - new entry points and structures only, so the version stayed
                                  *    vdl2hip_txcap_enable() / _disable() / _info_get() / _read() / _measure() with vdl2hip_txcap_cfg / _info, vdl2hip_tx_capture
-                                 *    and vdl2hip_tx_shape: the transmission capture, off unless enabled - new entry points and structures only, so the version stayed */
+                                 *    and vdl2hip_tx_shape: the transmission capture, off unless enabled - new entry points and structures only, so the version stayed
+                                 *    vdl2hip_toa_template() / _enable() / _disable() / _info_get() / _read() with vdl2hip_toa_cfg / _info and vdl2hip_burst_toa:
+                                 *    burst timing, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -555,6 +557,79 @@ typedef struct {
 	uint32_t peak_bin, obw_lo, obw_hi, reserved;
 } vdl2hip_tx_shape;                            /* 48 bytes */
 
+/* Burst timing (not in the reference, whose sync grid evaluates every third decimated sample and rounds a parabola vertex to a whole
+ * one, demod.c:173-183): for every burst handed to the burst decoder, the correlation of the channel's DECIMATED stream with the one
+ * part of the burst whose waveform is known in advance - the 16-symbol unique word - at 2 W + 1 lags round the decoder's own symbol
+ * clock: when symbol 0 arrived to a fraction of a sample, how far the decoder's clock and slope were from the signal's, and how well
+ * the template fits.  Off unless enabled; with it off nothing is launched or allocated and every result is what it was, to the bit.
+ * On, frames, counters, the decimated stream and every other tap are still exactly what they were: a read-only pass behind the frame
+ * finisher of each feed, where the burst capture runs.  It is independent of the burst capture: either, both or neither may run.
+ *  - Which bursts.  Exactly the burst capture's: every burst whose header decoded, in the feed whose burst decoder decodes it.
+ *  - Template.  vdl2hip_toa_template() returns s[0 .. 151) as float32 (re, im) pairs, designed on the host in double and rounded once:
+ *    s[n] = sum_{i = 0 .. 15} exp(j P[i]) p((n - 10 i) / 10), P[] the cumulative preamble phases of demod.c:107-124 and
+ *    p(t) = sinc(t) cos(0.6 pi t) / (1 - (1.2 t)^2) the raised cosine of roll-off 0.6, untruncated (t is a multiple of 0.1, never
+ *    +-1 / 1.2).  Index 0 is the centre of unique-word symbol 0, index 150 that of symbol 15: a template that reaches beyond the outer
+ *    centres correlates with the constant-phase ramp-up symbols and is biased.  E_s = sum |s[n]|^2 in double from the float32 table.
+ *  - Anchor and lags.  t0 = first_symbol - 160 is where the decoder's own symbol clock puts symbol 0; W = max_lag, 1 <= W <= 32, 0
+ *    means 8; nlags = 2 W + 1; dphi is the burst's slope per symbol as the decoder used it.
+ *  - Correlation.  For tau = -W .. W: c(tau) = sum_{n = 0 .. 150} u[n] y_c[t0 + tau + n], u[n] = conj(s[n]) (cos th_n, sin th_n),
+ *    th_n = -(double)dphi n / 10, cosine and sine computed in double and narrowed to float32, the product float32 (a product and a
+ *    fused multiply-add per component).  y_c[m] = 0 for m < 0, and VDL2HIP_TOA_EARLY is set if t0 - W < 0.  Products and sums are
+ *    float32 fused multiply-adds from zero in an order that is a function of nothing but n: the taps l, l + 64, l + 128 in that order
+ *    for l = 0 .. 63, then a tree over l that adds l + 32, then l + 16, ... l + 1.  P(tau) = re^2 + im^2 of c(tau) in float32 (a
+ *    product, a fused multiply-add).  y is taken as it stands when that feed's burst decoder has finished (the burst capture's
+ *    placement and its caveat about a later feed's referee).  The samples up to t0 + W + 150 < first_symbol + 32 always exist by
+ *    then - a header is 9 symbols - so the record depends on the stream and y alone, not on how the stream was cut into feeds.
+ *  - Peak.  peak_lag = the lowest tau among those with the largest P (a float32 >, taken in ascending tau); peak_sample = t0 +
+ *    peak_lag.  With a, b, c = P(peak_lag - 1), P(peak_lag), P(peak_lag + 1) widened to double - a neighbour beyond +-W counts as 0 -
+ *    den = (a - 2.0 b) + c.  VDL2HIP_TOA_EDGE if |peak_lag| == W, VDL2HIP_TOA_FLAT if den >= 0 (an all-zero window has both);
+ *    toa_frac = 0 with either, else (float)(0.5 (a - c) / den).  The arrival of symbol 0's centre is peak_sample + toa_frac on the
+ *    sync_sample clock - decimated samples, 105 000 a second, counted from the stream's start - and includes the channel filter's
+ *    constant delay: 2.30 samples for the reference's filter at oversample 10, measured with the float64 model on synthetic bursts
+ *    (tests/test_toa_definition.py), where the noise-free spread over 28 bursts is 0.014 sample WITH THE SLOPE THE BURST REALLY HAS.
+ *    The unique word's waveform is not symmetric, so a slope that is off moves the peak: -0.0058 sample per Hz of dphi's error on the
+ *    same run, where the decoder's own slope is up to 24 Hz off and the spread is 0.28 sample (standard deviation 0.084).  cfo_hz
+ *    says how far off it was.  peak_lag + toa_frac is the error of the decoder's symbol clock.
+ *  - Strength.  peak_power = P(peak_lag); energy = (float)E_y, E_y the float64 sum - per l in ascending tap order, then the same tree -
+ *    of the float32 re^2 + im^2 (a product, a fused multiply-add) of the 151 samples under the template at peak_lag;
+ *    rho = (float)((double)peak_power / (E_s E_y)), in 0 .. 1: 1 is the template itself; 0 if E_y == 0.
+ *  - Carrier.  carrier_phase = the phase of c(peak_lag) by the decoder's double atan2, narrowed.  c_a, c_b = the same products summed
+ *    over n = 0 .. 74 and 75 .. 149 (each lane's taps of that range, the same tree); resid = (float)(atan2(Im z, Re z) / 75) with
+ *    z = c_b conj(c_a) in double, rad per sample: what the decoder's slope left over; cfo_hz = (float)(((double)dphi / 10 +
+ *    (double)resid) 105000 / (2 pi)), of ppm_error's sign (ppm_error freq 1e-6 is the decoder's own figure for the same offset).
+ *  - Curve.  The first pool_curves records of a feed (0 means 4096; pool_curves * nlags > 2^24 is refused) also deliver P(-W .. W);
+ *    later ones carry VDL2HIP_TOA_NO_CURVE and curve_off 0 - their scalar fields are still valid - and vdl2hip_toa_info.curves_dropped
+ *    counts them.  Records never run out.
+ *  - Determinism and accuracy.  The same y gives the same bytes however the stream was cut; there are no floating-point atomics.
+ *    Against float64 with the same float32 s[]: |c - c64| <= b := (151 + 16) 2^-24 sum_n |s[n]| |y[t0 + tau + n]|, and
+ *    |P - P64| <= 2 |c64| b + b^2 + 2^-22 P64.  Everything from "Peak" down except the two phases is exact arithmetic on the delivered
+ *    float32 P and on E_y (which is within 151 2^-53 relative of any order); carrier_phase is within asin(min(1, b / |c|)) plus a
+ *    float32 ulp, resid within the sum of that for the two halves, over 75.
+ *  - Outcome: frames and frames_ok are joined on the host by (chan, burst_ord) exactly as the burst capture's are;
+ *    VDL2HIP_TOA_FAILED_ONLY delivers only the records with frames_ok == 0 (filtered on the host: vdl2hip_toa_info counts everything).
+ *  - Order: the records of one feed are ordered by (channel, position in the channel's burst list), feeds follow one another in
+ *    feed order.  chan is the index in cfg.freqs.  Groups get no group call: vdl2hip_group_ctx(g, k) is the handle for member k. */
+#define VDL2HIP_TOA_FAILED_ONLY 1u        /* vdl2hip_toa_cfg.flags */
+#define VDL2HIP_TOA_EARLY       1u        /* vdl2hip_burst_toa.flags */
+#define VDL2HIP_TOA_EDGE        2u
+#define VDL2HIP_TOA_FLAT        4u
+#define VDL2HIP_TOA_NO_CURVE    8u
+typedef struct { uint32_t struct_size, max_lag, flags, pool_curves; } vdl2hip_toa_cfg;   /* 16 bytes */
+typedef struct {
+	uint32_t chan, freq;                  /* index in cfg.freqs, Hz */
+	int64_t  burst_ord, sync_sample, first_symbol, peak_sample;
+	int32_t  peak_lag; uint32_t nlags;
+	float    toa_frac, peak_power, energy, rho, carrier_phase, cfo_hz, dphi, resid;
+	uint32_t flags, frames, frames_ok;    /* flags: VDL2HIP_TOA_*; frames, frames_ok: filled in by the host */
+	uint32_t curve_off;                   /* floats into the caller's buffer of that vdl2hip_toa_read(): P(-W) is curves[curve_off] */
+} vdl2hip_burst_toa;                           /* 96 bytes */
+typedef struct {
+	uint32_t struct_size, max_lag, flags, pool_curves;   /* as in force */
+	uint64_t bursts, curves, curves_dropped, early, edge;   /* of the feeds collected so far: records, curves, records beyond pool_curves, with _EARLY, with _EDGE */
+	float    kernel_ms;                        /* summed HIP-event time of k_toa at profiling level 2, else 0 */
+	uint32_t reserved;
+} vdl2hip_toa_info;                            /* 64 bytes */
+
 /* One AVLC frame plus the vdl2_msg_metadata the reference attaches to it
  * (src/output-common.h:31-43).  `octets` is only valid during the callback. */
 typedef struct {
@@ -893,6 +968,24 @@ int  vdl2hip_txcap_read(vdl2hip_ctx *ctx, vdl2hip_tx_capture *recs, size_t cap_r
  * the running sum reaches 0.005 total and 0.995 total.  Everything is 0 when total is 0.
  * VDL2HIP_E_INVAL for a NULL pointer or an nfft that is not one of the capture's. */
 int  vdl2hip_txcap_measure(const float *power, uint32_t nfft, vdl2hip_tx_shape *out);
+
+/* ---- Burst timing (see "Burst timing" above) ----
+ * The template: s[0 .. 151) as (re, im) float pairs.  Host only, needs no GPU, needs no receiver.  Returns 151; VDL2HIP_E_TOOBIG if
+ * cap_pairs is smaller, VDL2HIP_E_INVAL for a NULL pointer. */
+int  vdl2hip_toa_template(float *s, size_t cap_pairs);
+/* Switch the tap on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way, drops
+ * what is queued unread and starts afresh.  VDL2HIP_E_INVAL for a bad struct_size, max_lag > 32, an unknown flag or pool_curves *
+ * nlags > 2^24, before anything is allocated or changed: a tap that was on stays as it was. */
+int  vdl2hip_toa_enable(vdl2hip_ctx *ctx, const vdl2hip_toa_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_toa_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Tap off: VDL2HIP_E_INVAL. */
+int  vdl2hip_toa_info_get(vdl2hip_ctx *ctx, vdl2hip_toa_info *info);
+/* Like vdl2hip_txcap_read(): the records of the feeds collected so far, oldest first, with their curves in curves[] - record i's
+ * recs[i].nlags floats at recs[i].curve_off, none for a record with VDL2HIP_TOA_NO_CURVE.  What does not fit - records or their
+ * curves - stays queued for the next call; the call never waits for the device itself.  Returns the number of records written,
+ * *floats_used the floats (may be NULL).  Tap off: VDL2HIP_E_INVAL. */
+int  vdl2hip_toa_read(vdl2hip_ctx *ctx, vdl2hip_burst_toa *recs, size_t cap_recs, float *curves, size_t cap_floats, size_t *floats_used);
 
 #ifdef __cplusplus
 }

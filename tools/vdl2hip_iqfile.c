@@ -65,6 +65,12 @@
  *   --bursts-failed-only          only the bursts that produced no frame that passes the AVLC checks
  *   --bursts-pre <samples>        decimated samples kept ahead of the sync, 0 .. 4096 (default 256)
  *   --bursts-post <samples>       ... and behind the last symbol, 0 .. 1024 (default 32)
+ *   --toa-out <path>              (this library's own) switch burst timing on and, at exit, write one CSV line per burst handed to the burst
+ *                                 decoder, decoded or not: a "# key value" line per field of vdl2hip_toa_info, a header line, then
+ *                                 "chan,freq,burst_ord,sync_sample,first_symbol,peak_sample,peak_lag,nlags,toa_frac,toa_sample,peak_power,
+ *                                 energy,rho,carrier_phase,cfo_hz,dphi,resid,flags,frames,frames_ok" - toa_sample = peak_sample + toa_frac,
+ *                                 the arrival of unique-word symbol 0's centre in decimated samples (105 000 a second) from the file's start
+ *   --toa-max-lag <n>             lags searched on either side of the decoder's symbol clock, 1 .. 32 (default 8)
  *   freq [freq ...]               channel frequencies in Hz; default: the CSC, 136975000
  * and prints one line per AVLC frame (metadata in the reference's "[S:…] [L:…] [F:…] [#idx]" style + hex octets).
  * Everything after avlc_decoder_queue_push() (AVLC/ACARS/X.25/... decoding, formatters) is out of scope here.
@@ -118,6 +124,25 @@ static int take_bursts(vdl2hip_ctx *rx) {
 			bursts[nbursts++] = rec[i];
 		}
 		if(bursts_iq) { fwrite(iq, 2 * sizeof(float), used, bursts_iq); bursts_iq_pairs += used; }
+	}
+}
+
+/* burst timing: the records so far (written at exit, behind the totals); the curves are not kept */
+static vdl2hip_burst_toa *toas;
+static size_t ntoas, cap_toas;
+static int take_toa(vdl2hip_ctx *rx) {
+	enum { RECS = 256 };
+	static vdl2hip_burst_toa rec[RECS];
+	static float curves[RECS * 65];
+	for(;;) {
+		const int n = vdl2hip_toa_read(rx, rec, RECS, curves, RECS * 65, NULL);
+		if(n <= 0) return n;
+		if(ntoas + (size_t)n > cap_toas) {
+			cap_toas = 2 * (ntoas + (size_t)n);
+			toas = realloc(toas, cap_toas * sizeof *toas);
+			if(!toas) { perror("realloc"); exit(3); }
+		}
+		for(int i = 0; i < n; i++) toas[ntoas++] = rec[i];
 	}
 }
 
@@ -246,6 +271,8 @@ int main(int argc, char **argv) {
 	const char *tx_capture_path = NULL, *tx_iq_path = NULL, *tx_spectra_path = NULL;
 	uint32_t tx_capture_flags = VDL2HIP_TXCAP_SPECTRUM, tx_capture_nfft = 0;
 	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
+	const char *toa_path = NULL;
+	uint32_t toa_max_lag = 0;
 	int avlc_filter = 0;
 	uint32_t per_feed = 0;
 	uint32_t oversample = 0, centerfreq = 0, fmt = VDL2HIP_FMT_U8, freqs[1024], nfreq = 0, input_rate = 0;
@@ -295,6 +322,8 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--tx-spectra")) { NEEDARG(); tx_spectra_path = argv[++i]; }
 		else if(!strcmp(a, "--tx-capture-undecoded-only")) tx_capture_flags |= VDL2HIP_TXCAP_UNDECODED_ONLY;
 		else if(!strcmp(a, "--tx-capture-nfft")) { NEEDARG(); tx_capture_nfft = (uint32_t)strtoul(argv[++i], NULL, 10); }
+		else if(!strcmp(a, "--toa-out")) { NEEDARG(); toa_path = argv[++i]; }
+		else if(!strcmp(a, "--toa-max-lag")) { NEEDARG(); toa_max_lag = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--bursts-out")) { NEEDARG(); bursts_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-iq")) { NEEDARG(); bursts_iq_path = argv[++i]; }
 		else if(!strcmp(a, "--bursts-failed-only")) bursts_flags |= VDL2HIP_CAPTURE_FAILED_ONLY;
@@ -311,7 +340,7 @@ int main(int argc, char **argv) {
 			"[--waterfall-out file] [--waterfall-segments R] [--waterfall-mean file] [--waterfall-max file] "
 			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] "
 			"[--tx-capture-out file] [--tx-iq file] [--tx-spectra file] [--tx-capture-undecoded-only] [--tx-capture-nfft n] "
-			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [freq ...]\n", argv[0]); return 1; }
+			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [--toa-out file] [--toa-max-lag n] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
 		fprintf(stderr, "Warning: frequency not set - using VDL2 Common Signalling Channel as a default (%u Hz)\n", CSC_FREQ);
 		freqs[nfreq++] = CSC_FREQ;
@@ -386,6 +415,10 @@ int main(int argc, char **argv) {
 		vdl2hip_capture_cfg cc = { sizeof cc, bursts_pre, bursts_post, bursts_flags, 0, 0 };
 		if((r = vdl2hip_capture_enable(rx, &cc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_capture_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
+	if(toa_path) {
+		vdl2hip_toa_cfg tc = { sizeof tc, toa_max_lag, 0, 0 };
+		if((r = vdl2hip_toa_enable(rx, &tc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_toa_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+	}
 
 	unsigned char *buf = malloc((size_t)per_feed * FILE_BUFSIZE);
 	if(!buf) { perror("malloc"); return 3; }
@@ -400,6 +433,7 @@ int main(int argc, char **argv) {
 		if((r = vdl2hip_drain(rx, on_frame, NULL)) < 0) { fprintf(stderr, "vdl2hip_drain: %s\n", vdl2hip_strerror(r)); return 3; }
 		if((wf_mean || wf_max) && (r = take_lines(rx)) < 0) { fprintf(stderr, "vdl2hip_specgram_lines: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(toa_path && (r = take_toa(rx)) < 0) { fprintf(stderr, "vdl2hip_toa_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if((tx_search_path || tx_capture_path) && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_search_path && (r = take_tx_search(rx)) < 0) { fprintf(stderr, "vdl2hip_txsearch_read: %s\n", vdl2hip_strerror(r)); return 3; }
@@ -506,6 +540,27 @@ int main(int argc, char **argv) {
 		}
 		else fprintf(stderr, "bursts not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
 		if(bursts_iq) fclose(bursts_iq);
+	}
+	if(toa_path) {
+		vdl2hip_toa_info ti;
+		memset(&ti, 0, sizeof ti); ti.struct_size = sizeof ti;
+		r = vdl2hip_toa_info_get(rx, &ti);
+		FILE *so = r == VDL2HIP_OK ? fopen(toa_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# max_lag %u\n# flags %u\n# pool_curves %u\n", ti.max_lag, ti.flags, ti.pool_curves);
+			fprintf(so, "# bursts %" PRIu64 "\n# curves %" PRIu64 "\n# curves_dropped %" PRIu64 "\n# early %" PRIu64 "\n# edge %" PRIu64 "\n# kernel_ms %.6g\n",
+			        ti.bursts, ti.curves, ti.curves_dropped, ti.early, ti.edge, (double)ti.kernel_ms);
+			fprintf(so, "chan,freq,burst_ord,sync_sample,first_symbol,peak_sample,peak_lag,nlags,toa_frac,toa_sample,peak_power,energy,rho,carrier_phase,cfo_hz,dphi,resid,flags,frames,frames_ok\n");
+			for(size_t i = 0; i < ntoas; i++) {
+				const vdl2hip_burst_toa *b = &toas[i];
+				fprintf(so, "%u,%u,%" PRId64 ",%" PRId64 ",%" PRId64 ",%" PRId64 ",%d,%u,%.9g,%.17g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%u,%u,%u\n",
+				        b->chan, b->freq, b->burst_ord, b->sync_sample, b->first_symbol, b->peak_sample, b->peak_lag, b->nlags, (double)b->toa_frac,
+				        (double)b->peak_sample + (double)b->toa_frac, (double)b->peak_power, (double)b->energy, (double)b->rho, (double)b->carrier_phase,
+				        (double)b->cfo_hz, (double)b->dphi, (double)b->resid, b->flags, b->frames, b->frames_ok);
+			}
+			fclose(so);
+		}
+		else fprintf(stderr, "burst timing not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
 	}
 	if(tx_path) {
 		vdl2hip_txlog_info ti;
