@@ -561,6 +561,92 @@ int vdl2hip_debug_txsearch_range(const float *y, uint32_t ring_len, int64_t firs
 	return bad ? VDL2HIP_E_DEVICE : VDL2HIP_OK;
 }
 
+// test hook (not declared in vdl2hip.h; host only, needs no GPU): the second look's steps (relook.h) for one record, lane by lane as
+// k_relook_anchors, k_relook_select and k_relook_decode take them - y: the channel's ring of ring_len (re, im) pairs (a power of two),
+// the record's first_sample and last_sample, the limit (last_sample + (H + 1) B in the receiver), its frequency, the configuration as
+// vdl2hip_relook_enable() takes it (0: the defaults) -> recs: the attempt records with chan and first_bin 0 and frames_new 0, frames /
+// octets: as vdl2hip_relook_read() packs them, out = { anchors found, attempts, frames, octets }.  Returns the attempts.  The staging
+// arrays have a guard zone of NaNs behind each: VDL2HIP_E_DEVICE if a store went beyond a piece's sizes.
+int vdl2hip_debug_relook_range(const float *y, uint32_t ring_len, int64_t first, int64_t last, int64_t limit, uint32_t freq, float threshold, uint32_t max_anchors, float max_ppm,
+		uint32_t pool_frames, uint32_t pool_octets, vdl2hip_relook *recs, uint32_t cap_recs, vdl2hip_packed_frame *frames, uint32_t cap_frames, uint8_t *octets, uint32_t cap_octets, uint64_t out[4]) {
+	if(!y || !out || ring_len < 2 || (ring_len & (ring_len - 1)) || first < 0 || last < first || limit < last || !freq) return VDL2HIP_E_INVAL;
+	if((!recs && cap_recs) || (!frames && cap_frames) || (!octets && cap_octets)) return VDL2HIP_E_INVAL;
+	if(!(threshold >= 0.f && threshold <= 30.f) || !(max_ppm >= 0.f) || max_anchors > kRlMaxAnchors || pool_frames > kRlMaxFrames || pool_octets > kRlMaxOctets) return VDL2HIP_E_INVAL;
+	const float thr = threshold != 0.f ? threshold : kSyncThr;
+	const uint32_t K = max_anchors ? max_anchors : kRlDefAnchors, pf = pool_frames ? pool_frames : kRlDefFrames, po = pool_octets ? pool_octets : kRlDefOctets;
+	const cf32 *yc = reinterpret_cast<const cf32 *>(y);
+	const uint32_t mask = ring_len - 1;
+	auto tab = std::make_unique<Tables>(); build_tables(*tab);
+	int64_t sf; uint32_t fl;
+	txs_range(first, last, sf, fl);
+	const uint32_t np = txs_pieces(sf, last);
+	if(np == 0 || np > (uint32_t)(kTxsSpan / kTxsPiece)) return VDL2HIP_E_DEVICE;
+	constexpr int G = 16;
+	std::vector<float> phi(kRlPhi + G), p(kRlP + G);
+	std::vector<RlPiece> piece(np);
+	bool bad = false;
+	for(uint32_t g = 0; g < np; g++) {
+		const int64_t n0 = sf + (int64_t)g * (int64_t)kTxsPiece, left = last - n0 + 1;
+		const uint32_t cnt = left < (int64_t)kTxsPiece ? (uint32_t)left : kTxsPiece;
+		int64_t lo; uint32_t E;
+		rl_span(n0, cnt, sf, last, lo, E);
+		std::fill(phi.begin(), phi.end(), NAN); std::fill(p.begin(), p.end(), NAN);
+		for(uint32_t l = 0; l < (uint32_t)kRlThreads; l++) txs_phase_step(yc, mask, lo + kSyncSkip, E - (uint32_t)kSyncSkip, l, kRlThreads, phi.data());
+		for(uint32_t l = 0; l < (uint32_t)kRlThreads; l++) { TxsPart unused = txs_none(); txs_metric_step(phi.data(), *tab, lo + kSyncSkip, E - (uint32_t)kSyncSkip, l, kRlThreads, p.data(), unused); }
+		const uint32_t base = (uint32_t)(n0 - lo);
+		uint32_t idx[kRlPieceAnchors + 1], n = 0;
+		for(uint32_t l = 0; l < (uint32_t)kRlThreads; l++)
+			for(uint32_t k = l; k < cnt; k += kRlThreads)
+				if(rl_is_anchor(p.data(), base + k, E, thr)) { if(n < (uint32_t)kRlPieceAnchors) idx[n] = base + k; n++; }
+		if(n > (uint32_t)kRlPieceAnchors) return VDL2HIP_E_DEVICE;         // (never: they are 161 samples apart)
+		std::sort(idx, idx + n);
+		piece[g].n = n;
+		for(uint32_t x = 0; x < n; x++) piece[g].a[x] = rl_anchor_at(phi.data(), *tab, lo, idx[x]);
+		for(int i = 0; i < G; i++) bad = bad || !std::isnan(phi[kRlPhi + i]) || !std::isnan(p[kRlP + i]);
+	}
+	RlAnchor best[kRlMaxAnchors]; uint32_t nb = 0; uint64_t found = 0;
+	for(uint32_t g = 0; g < np; g++) for(uint32_t x = 0; x < piece[g].n; x++) { rl_keep(best, nb, K, piece[g].a[x]); found++; }
+	rl_sort_by_n(best, nb);
+	if(nb > cap_recs) return VDL2HIP_E_TOOBIG;
+	std::vector<RlRec> rec(nb); std::vector<RlPlan> plan(nb);
+	uint32_t o_fr = 0; unsigned long long o_oc = 0;
+	for(uint32_t k = 0; k < nb; k++) {
+		RlAtt t;
+		rl_plan_attempt(yc, mask, *tab, freq, max_ppm, limit, best[k], t);
+		rl_record(0u, freq, 0ull, 0u, t, o_fr, o_oc, pf, po, rec[k], plan[k]);
+		o_fr += t.claim_f; o_oc += t.claim_p;
+	}
+	std::vector<OutFrame> fr(pf); std::vector<uint8_t> pool((size_t)po + 4);
+	auto sh = std::make_unique<BurstShared>(); auto fs = std::make_unique<FrameShared>();
+	OutCtl ctl{}; ctl.nframes = 0xf0000000u; ctl.pool_used = 0xf0000000u;
+	unsigned long long acnt[kNumAvlcCounters] = {};
+	const float nfring = 0.f;
+	burst_shared_init(*tab, 0u, &ctl, *sh, true);
+	frame_shared_init(*tab, *fs);
+	size_t nfr = 0, used = 0;
+	for(uint32_t k = 0; k < nb; k++) {
+		rl_decode(rec[k], plan[k], 0, yc, mask, *tab, fr.data(), pool.data(), &ctl, rec[k].counters, acnt, &nfring, *sh, *fs);
+		memcpy(recs + k, &rec[k], sizeof(RlRec));
+		recs[k].frame_first = (uint32_t)(rec[k].frames ? nfr : 0);
+		for(uint32_t j = 0; j < rec[k].frames; j++) {
+			const OutFrame &f = fr[rec[k].frame_first + j];
+			if(nfr >= cap_frames || used + f.len > cap_octets) return VDL2HIP_E_TOOBIG;
+			vdl2hip_packed_frame &o = frames[nfr++];
+			memset(&o, 0, sizeof o);
+			o.frame.chan = 0; o.frame.freq = freq; o.frame.idx = f.idx; o.frame.len = f.len; o.frame.octets = nullptr;
+			o.frame.synd_weight = f.synd_weight; o.frame.datalen_octets = f.datalen_octets; o.frame.num_fec_corrections = f.num_fec_corrections;
+			o.frame.frame_pwr_dbfs = f.frame_pwr_dbfs; o.frame.nf_pwr_dbfs = f.nf_pwr_dbfs; o.frame.ppm_error = f.ppm_error;
+			o.frame.burst_ord = f.burst_ord; o.frame.sync_sample = f.sync_sample; o.frame.end_sample = f.end_sample;
+			o.frame.avlc_status = f.avlc_status; o.frame.dst_addr = f.dst_addr; o.frame.src_addr = f.src_addr;
+			o.octets_off = used;
+			memcpy(octets + used, pool.data() + f.pool_off, f.len);
+			used += f.len;
+		}
+	}
+	out[0] = found; out[1] = nb; out[2] = nfr; out[3] = used;
+	return bad || ctl.overflow ? VDL2HIP_E_DEVICE : (int)nb;
+}
+
 // test hook (not declared in vdl2hip.h; host only, needs no GPU): the transmission capture's plan (txcap.h) for the nrec records of one
 // feed, as k_txcap_plan takes it - tx: the log's records (first_sample, last_sample, flags, chan, freq, first_bin are read), cfg: as
 // vdl2hip_txcap_enable() takes it (nfft 0, pool_samples 0 and pool_spectra 0 mean their defaults) -> recs: the records as the device

@@ -1,9 +1,9 @@
-// taps.inc - the receiver's eight optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
-// input monitor's and the spectrogram's - capture.h, toa.h, txsearch.h, txcap.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
+// taps.inc - the receiver's nine optional taps, host side (included by vdl2hip.hip behind the context; kernels: spectrum.h - the
+// input monitor's and the spectrogram's - capture.h, toa.h, relook.h, txsearch.h, txcap.h, txlog.h, activity.h).  Each tap stands in one place: its share of a feed (launch), of a collected feed
 // (collect), what gives its buffers back (free), then its entry points of vdl2hip.h.  A tap stands behind those it calls into: the
 // log hands its records to the search and to the transmission capture, the activity monitor launches the log and switches it off,
 // the input monitor does both with the spectrogram.
-// Five of them deliver records - capture, burst timing, search, transmission capture, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
+// Six of them deliver records - capture, burst timing, second look, search, transmission capture, log - and share one mechanism: per slot a TapSlot with a RecordMail in it
 // (hostmem.h), per context the totals, a queue of collected records and the staging buffer of a feed with more records than come
 // with the header.  Their enable is: validate, collect what is in flight, free the old, allocate per slot, zero the totals, on.
 // (The entry points have C linkage from their declarations in vdl2hip.h.)
@@ -636,6 +636,179 @@ int vdl2hip_toa_read(vdl2hip_ctx *c, vdl2hip_burst_toa *recs, size_t cap_recs, f
 	return (int)n;
 }
 
+// ---- the second look (vdl2hip.h, "Second look"; kernels: relook.h) ----
+// A tap on top of the preamble search, whose plan of the feed it reads and which switches it off (so it stands ahead of it here).  The
+// ring behind an attempt: an anchor lies in the search's range, and every symbol an attempt reads lies at or before limit =
+// last_sample + (H + 1) B, the last sample of the bin whose completion emits the record: inside the feed (the transmission capture's
+// post window ends there too).
+static_assert(sizeof(RlRec) == sizeof(vdl2hip_relook) && sizeof(vdl2hip_relook) == 256 && offsetof(RlRec, first_bin) == offsetof(vdl2hip_relook, first_bin)
+              && offsetof(RlRec, anchor) == offsetof(vdl2hip_relook, anchor) && offsetof(RlRec, end_sample) == offsetof(vdl2hip_relook, end_sample)
+              && offsetof(RlRec, pherr) == offsetof(vdl2hip_relook, pherr) && offsetof(vdl2hip_relook, pherr) == 32 && offsetof(RlRec, prev_phase) == offsetof(vdl2hip_relook, prev_phase)
+              && offsetof(RlRec, tl_bits) == offsetof(vdl2hip_relook, tl_bits) && offsetof(RlRec, stop) == offsetof(vdl2hip_relook, stop) && offsetof(vdl2hip_relook, stop) == 60
+              && offsetof(RlRec, frames) == offsetof(vdl2hip_relook, frames) && offsetof(RlRec, fec_corrections) == offsetof(vdl2hip_relook, fec_corrections)
+              && offsetof(RlRec, frame_first) == offsetof(vdl2hip_relook, frame_first) && offsetof(RlRec, flags) == offsetof(vdl2hip_relook, flags) && offsetof(vdl2hip_relook, flags) == 84
+              && offsetof(RlRec, counters) == offsetof(vdl2hip_relook, counters) && offsetof(vdl2hip_relook, counters) == 96, "the host copies the device's records as they are and fills in the rest");
+static_assert(sizeof(vdl2hip_relook_cfg) == 32 && sizeof(vdl2hip_relook_info) == 96 && sizeof(RlHdr) == 32 && sizeof(RlPiece) == 128 && sizeof(RlPlan) == 32 && sizeof(RlAnchor) == 16, "vdl2hip.h states these sizes");
+static_assert(VDL2HIP_RELOOK_PPM_REJECT == kRlPpmReject && VDL2HIP_RELOOK_TRUNCATED == kRlTruncated && VDL2HIP_RELOOK_NO_ROOM == kRlNoRoom
+              && ((kRlPpmReject | kRlTruncated | kRlNoRoom) & kTxPartial) == 0, "the flags share a word");
+constexpr unsigned kRlDecodeGrid = 256;       // wavefronts of k_relook_decode, an attempt each at a time
+constexpr size_t kRlDecodeLds = ((sizeof(BurstShared) + 15) & ~(size_t)15) + sizeof(FrameShared);
+static_assert(kRlDecodeLds + sizeof(OutCtl) + kNumCounters * 8 <= 65536, "k_relook_decode's wavefront has its BurstShared and FrameShared in LDS");
+// FNV-1a, 64 bits: what the join compares beside the length
+static uint64_t relook_hash(const uint8_t *p, uint32_t n) {
+	uint64_t h = 0xcbf29ce484222325ull;
+	for(uint32_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
+	return h;
+}
+// Its share of a feed (launch_rest): directly behind the search's launches, whose plan it reads
+static int relook_launch(vdl2hip_ctx *c, OutSlot &sl, hipStream_t st) {
+	auto &m = c->rl;
+	RlArgs a{};
+	a.y = c->d_y; a.tab = c->d_tab; a.txhdr = sl.txl.mail.d_hdr(); a.txrec = sl.txl.mail.d_rec(); a.off = sl.txs.d_off; a.shdr = sl.txs.mail.d_hdr();
+	a.piece = sl.rl.d_piece; a.rec = sl.rl.mail.d_rec(); a.plan = sl.rl.d_plan; a.hdr = sl.rl.mail.d_hdr(); a.frames = sl.rl.d_frames; a.pool = sl.rl.d_pool;
+	a.acnt = sl.rl.d_acnt; a.nfring = c->d_nfring; a.frames_out = sl.rl.d_frames_out; a.pool_out = sl.rl.d_pool_out;
+	a.thr = m.thr; a.max_ppm = m.max_ppm; a.max_anchors = m.max_anchors; a.pool_frames = m.pool_frames; a.pool_octets = m.pool_octets; a.rec_cap = m.rec_cap;
+	a.piece_cap = c->txs.piece_cap; a.cap = c->cap; a.mask = c->cap - 1; a.chan_first = (uint32_t)c->chan_first; a.back = (c->act.H + 1) * c->act.B;
+	KernelTimes &t = sl.rl.times;
+	t.arm(c->profiling >= 2);
+	// a workgroup per piece, grid-stride, sized as the search's
+	const unsigned grid = (unsigned)std::min<uint64_t>(2048, std::max<uint64_t>(16, (uint64_t)sl.back_D * (uint64_t)c->C / (4 * kTxsPiece)));
+	hipExtLaunchKernelGGL(k_relook_anchors, dim3(grid), dim3(kRlThreads), 0u, st, t.e(0), (hipEvent_t) nullptr, 0, a);
+	hipLaunchKernelGGL(k_relook_select, dim3(1), dim3(kRlThreads), 0, st, a);
+	hipLaunchKernelGGL(k_relook_decode, dim3(kRlDecodeGrid), dim3(64), (uint32_t)kRlDecodeLds, st, a);
+	// what the attempts produced, packed: the host copies that, not the claims
+	hipLaunchKernelGGL(k_relook_pack_plan, dim3(1), dim3(kRlThreads), 0, st, a);
+	hipExtLaunchKernelGGL(k_relook_pack_copy, dim3(kRlDecodeGrid), dim3(64), 0u, st, (hipEvent_t) nullptr, t.e(1), 0, a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(sl.rl.mail.post(st));
+	t.launched(1);
+	sl.rl.on = true;
+	return VDL2HIP_OK;
+}
+// A collected feed's attempt records - in the order of the log's nrec records, a run of them per record - with the claimed part of
+// its frame pool: one staging buffer, one wait
+struct RlFeed { const RlRec *rec = nullptr; uint32_t natt = 0, cur = 0; std::shared_ptr<std::vector<OutFrame>> fr; std::shared_ptr<std::vector<uint8_t>> pool; };
+static int relook_fetch(vdl2hip_ctx *c, OutSlot &sl, uint32_t nrec, RlFeed &f) {
+	auto &m = c->rl;
+	if(!m.on || !sl.rl.mail) return VDL2HIP_OK;
+	const RlHdr h = sl.rl.mail.hdr();
+	if(h.ntx != nrec) return VDL2HIP_E_DEVICE;                       // (never: both are the log's header of this feed)
+	f.natt = std::min(h.nrec, m.rec_cap);
+	const size_t nfr = std::min(h.frames_used, m.pool_frames), noct = std::min(h.octets_used, m.pool_octets);      // (what was produced, packed: not what was claimed)
+	const size_t rec_bytes = sl.rl.mail.staged(f.natt), fr_bytes = nfr * sizeof(OutFrame);
+	HIPCHK(sl.rl.mail.fetch(f.natt, m.stage, c->streams.out, f.rec, false, fr_bytes + noct));
+	if(fr_bytes) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes, sl.rl.d_frames_out, fr_bytes, hipMemcpyDeviceToHost, c->streams.out));
+	if(noct) HIPCHK(hipMemcpyAsync(m.stage + rec_bytes + fr_bytes, sl.rl.d_pool_out, noct, hipMemcpyDeviceToHost, c->streams.out));
+	if(rec_bytes + fr_bytes + noct) HIPCHK(hipStreamSynchronize(c->streams.out));
+	const OutFrame *frp = reinterpret_cast<const OutFrame *>(m.stage + rec_bytes);
+	f.fr = nfr ? std::make_shared<std::vector<OutFrame>>(frp, frp + nfr) : std::make_shared<std::vector<OutFrame>>();
+	f.pool = noct ? std::make_shared<std::vector<uint8_t>>(m.stage + rec_bytes + fr_bytes, m.stage + rec_bytes + fr_bytes + noct) : std::make_shared<std::vector<uint8_t>>();
+	m.records += nrec; m.anchors_found += h.anchors_found; m.dropped += h.dropped;
+	return VDL2HIP_OK;
+}
+// ... the attempts of one log record, with what the log has joined to it: seen - (len, hash) of the main-path frames of the record
+static void relook_take(vdl2hip_ctx *c, RlFeed &f, const vdl2hip_tx &tx, const std::vector<std::pair<uint32_t, uint64_t>> &seen) {
+	auto &m = c->rl;
+	for(; f.cur < f.natt && f.rec[f.cur].chan == tx.chan && f.rec[f.cur].first_bin == tx.first_bin; f.cur++) {
+		vdl2hip_relook r;
+		memcpy(&r, f.rec + f.cur, sizeof r);
+		r.frames_new = 0; r.new_mask = 0; r.reserved = 0;
+		if((size_t)r.frame_first + r.frames > f.fr->size()) { r.frames = r.frames_ok = 0; r.frame_first = 0; r.flags |= VDL2HIP_RELOOK_NO_ROOM; }      // (never)
+		for(uint32_t k = 0; k < r.frames; k++) {
+			const OutFrame &fr = (*f.fr)[r.frame_first + k];
+			if((size_t)fr.pool_off + fr.len > f.pool->size() || fr.avlc_status != AVLC_OK) continue;
+			const std::pair<uint32_t, uint64_t> key{ fr.len, relook_hash(f.pool->data() + fr.pool_off, fr.len) };
+			if(std::find(seen.begin(), seen.end(), key) == seen.end()) { r.frames_new++; if(k < 32) r.new_mask |= 1u << k; }
+		}
+		m.attempts++; m.frames += r.frames; m.frames_ok += r.frames_ok; m.frames_new += r.frames_new; if(r.flags & VDL2HIP_RELOOK_NO_ROOM) m.dropped++;
+		if((m.flags & VDL2HIP_RELOOK_NEW_ONLY) && r.frames_new == 0) continue;
+		m.queue.push_back(vdl2hip_ctx::RlItem{ r, f.fr, f.pool });
+	}
+}
+// give the second look's buffers back (nothing of it may be in flight: the callers have collected every feed)
+static void relook_free(vdl2hip_ctx *c) {
+	for(auto &sl : c->slot) sl.rl.reset();
+	c->rl.queue.clear();
+	c->rl.stage.reset();
+	c->rl.on = false;
+}
+int vdl2hip_relook_enable(vdl2hip_ctx *c, const vdl2hip_relook_cfg *cfg) {
+	if(!c || !cfg || cfg->struct_size != sizeof(vdl2hip_relook_cfg) || cfg->reserved != 0 || (cfg->flags & ~VDL2HIP_RELOOK_NEW_ONLY)) return VDL2HIP_E_INVAL;
+	if(!c->txs.on || !c->txl.on || !c->act.on) return VDL2HIP_E_INVAL;
+	if(!(cfg->threshold >= 0.f && cfg->threshold <= 30.f) || !(cfg->max_ppm >= 0.f) || std::isinf(cfg->max_ppm)) return VDL2HIP_E_INVAL;      // (a NaN fails both)
+	if(cfg->max_anchors > kRlMaxAnchors || cfg->pool_frames > kRlMaxFrames || cfg->pool_octets > kRlMaxOctets) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->failed) return VDL2HIP_E_DEVICE;
+	{ int r = collect_all(c); if(r != VDL2HIP_OK) return r; }        // nothing of an earlier second look is in flight any more
+	auto &m = c->rl;
+	relook_free(c);
+	const uint32_t K = cfg->max_anchors ? cfg->max_anchors : kRlDefAnchors;
+	// (the defaults grow with the receiver: 256 records and 8192 octets a channel, at least 4096 and 2^20)
+	const uint32_t pool_frames = cfg->pool_frames ? cfg->pool_frames : std::max<uint32_t>(kRlDefFrames, 256u * (uint32_t)c->C);
+	const uint32_t pool_octets = cfg->pool_octets ? cfg->pool_octets : std::max<uint32_t>(kRlDefOctets, 8192u * (uint32_t)c->C);
+	// the attempts one feed's records can have at the most: K a record, and - anchors lie 161 samples apart - what the pieces can hold
+	const uint32_t rec_cap = (uint32_t)std::min<uint64_t>(kRlMaxRecs, std::min<uint64_t>((uint64_t)c->txl.pool * K, (uint64_t)c->txs.piece_cap * kRlPieceAnchors));
+	for(auto &sl : c->slot) {
+		auto &b = sl.rl;
+		const bool ok = b.mail.alloc(rec_cap) == hipSuccess && b.d_piece.alloc(c->txs.piece_cap) == hipSuccess && b.d_plan.alloc(rec_cap) == hipSuccess
+		                && b.d_frames.alloc(pool_frames) == hipSuccess && b.d_pool.alloc((size_t)pool_octets + 4) == hipSuccess
+		                && b.d_frames_out.alloc(pool_frames) == hipSuccess && b.d_pool_out.alloc((size_t)pool_octets + 4) == hipSuccess && b.d_acnt.alloc((size_t)kRlDecodeGrid * kNumAvlcCounters, true) == hipSuccess;
+		if(!ok) { relook_free(c); return VDL2HIP_E_NOMEM; }
+	}
+	if(hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); relook_free(c); return VDL2HIP_E_DEVICE; }
+	m.flags = cfg->flags; m.thr = cfg->threshold != 0.f ? cfg->threshold : kSyncThr; m.max_ppm = cfg->max_ppm; m.max_anchors = K;
+	m.pool_frames = pool_frames; m.pool_octets = pool_octets; m.rec_cap = rec_cap;
+	m.records = m.anchors_found = m.attempts = m.frames = m.frames_ok = m.frames_new = m.dropped = 0; m.kernel_ms = 0.0;
+	m.on = true;
+	return VDL2HIP_OK;
+}
+int vdl2hip_relook_disable(vdl2hip_ctx *c) {
+	if(!c) return VDL2HIP_E_INVAL;
+	OnDevice dev_guard(c);
+	if(c->rl.on && !c->failed) { int r = collect_all(c); if(r != VDL2HIP_OK) return r; }
+	relook_free(c);
+	return VDL2HIP_OK;
+}
+int vdl2hip_relook_info_get(vdl2hip_ctx *c, vdl2hip_relook_info *info) {
+	if(!c || !c->rl.on || !info || info->struct_size != sizeof(vdl2hip_relook_info)) return VDL2HIP_E_INVAL;
+	const auto &m = c->rl;
+	memset(info, 0, sizeof *info);
+	info->struct_size = sizeof *info; info->flags = m.flags; info->threshold = m.thr; info->max_ppm = m.max_ppm;
+	info->max_anchors = m.max_anchors; info->pool_frames = m.pool_frames; info->pool_octets = m.pool_octets;
+	info->records = m.records; info->anchors_found = m.anchors_found; info->attempts = m.attempts;
+	info->frames = m.frames; info->frames_ok = m.frames_ok; info->frames_new = m.frames_new; info->dropped = m.dropped; info->kernel_ms = (float)m.kernel_ms;
+	return VDL2HIP_OK;
+}
+// (its own: a record goes out with its frames and their octets, each packed behind those of the records before it)
+int vdl2hip_relook_read(vdl2hip_ctx *c, vdl2hip_relook *recs, size_t cap_recs, vdl2hip_packed_frame *frames, size_t cap_frames, uint8_t *octets, size_t cap_octets, size_t *octets_used) {
+	if(!c || !c->rl.on || (!recs && cap_recs) || (!frames && cap_frames) || (!octets && cap_octets)) return VDL2HIP_E_INVAL;
+	auto &q = c->rl.queue;
+	size_t n = 0, nfr = 0, used = 0;
+	while(!q.empty() && n < cap_recs) {
+		const vdl2hip_ctx::RlItem &it = q.front();
+		size_t need = 0;
+		for(uint32_t k = 0; k < it.r.frames; k++) need += (*it.fr)[it.r.frame_first + k].len;
+		if(nfr + it.r.frames > cap_frames || used + need > cap_octets || nfr + it.r.frames > 0xffffffffull) break;
+		recs[n] = it.r;
+		recs[n].frame_first = (uint32_t)(it.r.frames ? nfr : 0);
+		for(uint32_t k = 0; k < it.r.frames; k++) {
+			HostFrame h{ (*it.fr)[it.r.frame_first + k], nullptr };
+			h.f.chan = (int32_t)(it.r.chan - (uint32_t)c->chan_first);
+			vdl2hip_packed_frame &o = frames[nfr++];
+			fill_frame(c, h, o.frame);
+			o.frame.octets = nullptr; o.octets_off = used;
+			const uint32_t len = h.f.len;
+			if(len && (size_t)h.f.pool_off + len <= it.pool->size()) memcpy(octets + used, it.pool->data() + h.f.pool_off, len);
+			else if(len) memset(octets + used, 0, len);                // (never)
+			used += len;
+		}
+		n++;
+		q.pop_front();
+	}
+	if(octets_used) *octets_used = used;
+	return (int)n;
+}
+
 // ---- the preamble search (vdl2hip.h, "Preamble search"; kernels: txsearch.h) ----
 // The ring behind the range.  The search of feed i reads y from search_first - 153 on (the taps of p(search_first - 3)), under the
 // burst capture's conditions (above): what the ring keeps behind feed i's first sample k0 is kHistory + 1024 samples.  A record is
@@ -697,6 +870,7 @@ static void txsearch_take(vdl2hip_ctx *c, const TxsRec &s, const vdl2hip_tx &tx)
 }
 // give the search's buffers back (nothing of it may be in flight: the callers have collected every feed)
 static void txsearch_free(vdl2hip_ctx *c) {
+	relook_free(c);                                                  // (a second look reads the search's plan: it goes first)
 	for(auto &sl : c->slot) sl.txs.reset();
 	c->txs.queue.clear();
 	c->txs.on = false;
@@ -954,27 +1128,32 @@ static int txlog_launch(vdl2hip_ctx *c, OutSlot &sl, uint64_t m0, uint32_t nb) {
 // A collected feed and the log.  The feed's frames first - all of them, whatever the AVLC filter lets through: they wait, per channel,
 // for the record whose window holds their sync_sample.  Then the feed's records: each takes the waiting frames of its window; those
 // before the window are counted as unmatched and dropped (vdl2hip.h, "Transmission log": Outcome).
-static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf) {
+static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32_t nf, const uint8_t *po, uint32_t pool_n) {
 	auto &m = c->txl;
 	for(uint32_t i = 0; i < nf; i++) {
 		if(fr[i].chan < 0 || fr[i].chan >= c->C) continue;
 		auto &w = m.wait[(size_t)fr[i].chan];
 		if(w.size() >= kTxMaxWait) { w.pop_front(); m.unmatched++; }
-		w.push_back(vdl2hip_ctx::TxFrame{ fr[i].sync_sample, fr[i].burst_ord, fr[i].avlc_status == AVLC_OK });
+		// (the second look's join compares a frame's length and a hash of its octets: taken here, while the feed's octets are at hand, whether
+		// that tap is on or not - a frame that waits for its record may see it enabled before the record comes)
+		const bool hashed = po && (uint64_t)fr[i].pool_off + fr[i].len <= pool_n;
+		w.push_back(vdl2hip_ctx::TxFrame{ fr[i].sync_sample, fr[i].burst_ord, fr[i].avlc_status == AVLC_OK, hashed ? fr[i].len : 0u, hashed ? relook_hash(po + fr[i].pool_off, fr[i].len) : 0ull });
 	}
 	if(!sl.txl.on) return VDL2HIP_OK;
 	sl.txl.on = false;
-	if(!sl.txl.mail) { sl.txs.on = sl.txc.on = false; return VDL2HIP_OK; }
+	if(!sl.txl.mail) { sl.txs.on = sl.txc.on = sl.rl.on = false; return VDL2HIP_OK; }
 	const TxHdr h = sl.txl.mail.hdr();
 	const uint32_t nrec = std::min(h.nrec, m.pool);
 	m.dropped += h.dropped;
-	if(nrec == 0) { sl.txs.on = sl.txc.on = false; return VDL2HIP_OK; }
+	if(nrec == 0) { sl.txs.on = sl.txc.on = sl.rl.on = false; return VDL2HIP_OK; }
 	const TxRec *rec = nullptr;
 	HIPCHK(sl.txl.mail.fetch(nrec, m.stage, c->streams.out, rec));
 	const TxsRec *srec = nullptr;
 	if(sl.txs.on) { sl.txs.on = false; int r = txsearch_fetch(c, sl, nrec, srec); if(r != VDL2HIP_OK) return r; }
 	TxcFeed capf;
 	if(sl.txc.on) { sl.txc.on = false; int r = txcap_fetch(c, sl, nrec, capf); if(r != VDL2HIP_OK) return r; }
+	RlFeed rlf; std::vector<std::pair<uint32_t, uint64_t>> seen;
+	if(sl.rl.on) { sl.rl.on = false; int r = relook_fetch(c, sl, nrec, rlf); if(r != VDL2HIP_OK) return r; }
 	const int64_t close_bins = (int64_t)c->act.H + 2, B = c->act.B;
 	for(uint32_t i = 0; i < nrec; i++) {
 		vdl2hip_tx r;
@@ -990,6 +1169,7 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 				else if(f.sync_sample < close_sample) {
 					if(!r.frames || f.sync_sample < first_sync) { first_sync = f.sync_sample; r.first_burst_ord = f.burst_ord; }
 					r.frames++; if(f.ok) r.frames_ok++;
+					if(rlf.rec && f.len) seen.emplace_back(f.len, f.hash);
 				} else w[keep++] = f;
 			}
 			w.resize(keep);
@@ -997,6 +1177,7 @@ static int txlog_collect(vdl2hip_ctx *c, OutSlot &sl, const OutFrame *fr, uint32
 		m.transmissions++; m.matched += r.frames; if(r.frames_ok) m.decoded++;
 		if(srec) txsearch_take(c, srec[i], r);
 		if(capf.rec) txcap_take(c, capf, i, r);
+		if(rlf.rec) { relook_take(c, rlf, r, seen); seen.clear(); }
 		if((m.flags & VDL2HIP_TXLOG_UNDECODED_ONLY) && r.frames_ok != 0) continue;
 		m.queue.push_back(r);
 	}

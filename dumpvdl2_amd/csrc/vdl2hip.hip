@@ -29,6 +29,7 @@
 #include "txcap.h"
 #include "capture.h"
 #include "toa.h"
+#include "relook.h"
 #include "tables.h"
 #include "hostmem.h"
 
@@ -167,6 +168,11 @@ struct OutSlot {
 	// followed this feed's frame finisher; times: k_txsearch_plan .. k_txsearch_reduce (one pair round the three)
 	struct TxsBufs { RecordMail<TxsHdr, TxsRec> mail; DevBuf<uint32_t> d_off; DevBuf<TxsPart> d_part; };
 	TapSlot<TxsBufs> txs;
+	// second look (relook.h): the feed's attempt records, the pieces' anchors, the attempts' plans, the frame pool of the attempts and
+	// the frame finisher's counters nobody reads.  on: its launches followed this feed's search; times: k_relook_anchors .. k_relook_decode
+	// (one pair round the three)
+	struct RlBufs { RecordMail<RlHdr, RlRec> mail; DevBuf<RlPiece> d_piece; DevBuf<RlPlan> d_plan; DevBuf<OutFrame> d_frames, d_frames_out; DevBuf<uint8_t> d_pool, d_pool_out; DevBuf<unsigned long long> d_acnt; };
+	TapSlot<RlBufs> rl;
 	// transmission capture (txcap.h): the feed's records, their piece offsets, the pieces' float64 rows, the IQ pool, the spectra.  on:
 	// the capture's launches followed this feed's frame finisher; times: k_txcap_plan + k_txcap_copy, k_txcap_spectrum + k_txcap_reduce
 	struct TxcBufs { RecordMail<TxcHdr, TxcRec> mail; DevBuf<uint32_t> d_poff; DevBuf<double> d_part; DevBuf<cf32> d_pool; DevBuf<float> d_spec; };
@@ -231,7 +237,7 @@ struct vdl2hip_ctx {
 	// Transmission log (txlog.h, vdl2hip_txlog_*): off unless enabled, and only beside the activity monitor.  buf: its per-channel state
 	// and counts, given back as one (txlog_free).  queue: the records of the collected feeds, oldest first; wait: per channel the frames
 	// no record has claimed yet (txlog_collect)
-	struct TxFrame { int64_t sync_sample, burst_ord; bool ok; };
+	struct TxFrame { int64_t sync_sample, burst_ord; bool ok; uint32_t len; uint64_t hash; };      // len, hash: of its octets, for the second look's join
 	struct {
 		bool on = false; uint32_t pool = 0, flags = 0;
 		uint64_t transmissions = 0, decoded = 0, dropped = 0, matched = 0, unmatched = 0; double kernel_ms = 0.0;
@@ -245,6 +251,15 @@ struct vdl2hip_ctx {
 		uint64_t records = 0, samples = 0, clipped = 0; double kernel_ms = 0.0;
 		PinnedBuf stage; std::deque<vdl2hip_tx_search> queue;
 	} txs;
+	// Second look (relook.h, vdl2hip_relook_*): off unless enabled, and only on top of the preamble search.  k: the configuration in
+	// force; rec_cap: the attempts one feed can have at the most; queue: the attempt records of the collected feeds, oldest first, each
+	// with the frame records and the octets of its feed (one allocation each per feed, shared by its records)
+	struct RlItem { vdl2hip_relook r; std::shared_ptr<std::vector<OutFrame>> fr; std::shared_ptr<std::vector<uint8_t>> pool; };
+	struct {
+		bool on = false; uint32_t flags = 0, max_anchors = 0, pool_frames = 0, pool_octets = 0, rec_cap = 0; float thr = 0.f, max_ppm = 0.f;
+		uint64_t records = 0, anchors_found = 0, attempts = 0, frames = 0, frames_ok = 0, frames_new = 0, dropped = 0; double kernel_ms = 0.0;
+		PinnedBuf stage; std::deque<RlItem> queue;
+	} rl;
 	// Transmission capture (txcap.h, vdl2hip_txcap_*): off unless enabled, and only beside the transmission log.  k: the configuration
 	// in force as the kernels take it; buf: the window and the twiddles of its transform, given back as one (txcap_free); queue: the
 	// records of the collected feeds, oldest first, each with the IQ and the spectra of its feed (one allocation each per feed, shared by
@@ -416,6 +431,7 @@ static int collect_pending(vdl2hip_ctx *c, int keep = 0);
 // what is in flight is collected, as a tap's enable and disable need it before they touch its buffers: an output buffer that ran over
 // on the way is the drain's to report, not theirs
 static int collect_all(vdl2hip_ctx *c) { const int r = collect_pending(c); return r == VDL2HIP_E_OVERFLOW ? VDL2HIP_OK : r; }
+static void fill_frame(const vdl2hip_ctx *c, const HostFrame &h, vdl2hip_frame &f);
 
 #include "taps.inc"   // the taps, each in one place: its share of a feed, its collect, its vdl2hip_<tap>_* entry points
 
@@ -430,6 +446,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	sl.cap.times.collect(c->capt.kernel_ms);
 	sl.txl.times.collect(c->txl.kernel_ms);
 	sl.txs.times.collect(c->txs.kernel_ms);
+	sl.rl.times.collect(c->rl.kernel_ms);
 	sl.txc.times.collect(c->txc.kernel_ms);
 	sl.toa.times.collect(c->toa.kernel_ms);
 	if(c->profiling && sl.ev_valid) {
@@ -456,9 +473,9 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	c->stats.bursts += std::min(ctl.nbursts, ctl.cap_bursts);
 	const uint32_t nf = std::min(ctl.nvalid, ctl.cap_frames);
 	const OutFrame *fr = nullptr;
+	const uint8_t *po = nullptr; uint32_t pool_n = 0;
 	if(nf) {
-		const uint32_t pool_n = std::min(ctl.pool_out_used, ctl.cap_pool);
-		const uint8_t *po;
+		pool_n = std::min(ctl.pool_out_used, ctl.cap_pool);
 		if(nf <= (uint32_t)kMailFrames && pool_n <= (uint32_t)kMailPool) {
 			// a handful of frames (the usual case for a block of a live receiver): they have come with the control block
 			fr = mail->frames; po = mail->pool;
@@ -483,7 +500,7 @@ static int collect_slot(vdl2hip_ctx *c, OutSlot &sl) {
 	}
 	if(sl.cap.on) { sl.cap.on = false; int r = capture_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
 	if(sl.toa.on) { sl.toa.on = false; int r = toa_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
-	if(c->txl.on) { int r = txlog_collect(c, sl, fr, nf); if(r != VDL2HIP_OK) return r; }
+	if(c->txl.on) { int r = txlog_collect(c, sl, fr, nf, po, pool_n); if(r != VDL2HIP_OK) return r; }
 	return ctl.overflow ? VDL2HIP_E_OVERFLOW : VDL2HIP_OK;
 }
 
@@ -541,6 +558,7 @@ static int feed_common(vdl2hip_ctx *c, const void *dev_in, size_t nbytes, bool i
 	sl.toa.on = c->toa.on && D > 0;                                 // (... and so does burst timing)
 	sl.txl.on = false;                                              // (set by activity_feed if the log's kernels follow this feed's scan)
 	sl.txs.on = false;                                              // (set by launch_rest if the search's kernels follow this feed's frame finisher)
+	sl.rl.on = false;                                               // (... and the second look's, behind them)
 	sl.txc.on = false;                                              // (... and the transmission capture's)
 	if(D > 0) {
 		const size_t lds = (size_t)c->run * c->os * 65 * sizeof(float2);   // the tile; the tables are static LDS
@@ -934,6 +952,8 @@ static int launch_rest(vdl2hip_ctx *c, OutSlot &sl, OutSlot *succ) {
 		if(sl.txl.on) HIPCHK(sl.txl.mail.post(s5_));
 		// the preamble search reads the log's records of this feed (the same ordering) and y here, like the capture
 		if(sl.txl.on && c->txs.on) { int r = txsearch_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
+		// the second look reads the search's plan of this feed, the log's records and y behind it
+		if(sl.txs.on && c->rl.on) { int r = relook_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 		// ... and so does the transmission capture
 		if(sl.txl.on && c->txc.on) { int r = txcap_launch(c, sl, s5_); if(r != VDL2HIP_OK) return r; }
 	}

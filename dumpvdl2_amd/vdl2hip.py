@@ -53,7 +53,11 @@ EXPORTS = [
     "vdl2hip_specgram_enable", "vdl2hip_specgram_disable", "vdl2hip_specgram_read", "vdl2hip_specgram_lines", "vdl2hip_specgram_channels",
     "vdl2hip_txcap_enable", "vdl2hip_txcap_disable", "vdl2hip_txcap_info_get", "vdl2hip_txcap_read", "vdl2hip_txcap_measure",
     "vdl2hip_toa_template", "vdl2hip_toa_enable", "vdl2hip_toa_disable", "vdl2hip_toa_info_get", "vdl2hip_toa_read",
+    "vdl2hip_relook_enable", "vdl2hip_relook_disable", "vdl2hip_relook_info_get", "vdl2hip_relook_read",
 ]
+# include/vdl2hip.h: VDL2HIP_RELOOK_NEW_ONLY (cfg.flags), VDL2HIP_RELOOK_* (vdl2hip_relook.flags, beside TX_PARTIAL)
+RELOOK_NEW_ONLY = 1
+RELOOK_PPM_REJECT, RELOOK_TRUNCATED, RELOOK_NO_ROOM = 2, 4, 8
 # include/vdl2hip.h: VDL2HIP_TOA_FAILED_ONLY (cfg.flags), VDL2HIP_TOA_* (vdl2hip_burst_toa.flags)
 TOA_FAILED_ONLY = 1
 TOA_EARLY, TOA_EDGE, TOA_FLAT, TOA_NO_CURVE = 1, 2, 4, 8
@@ -194,6 +198,25 @@ TXS_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("
                       ("frames", "<u4"), ("frames_ok", "<u4"), ("why", "<u4"), ("reserved", "<u4"), ("reserved2", "<u4")])     # vdl2hip_tx_search, 96 bytes
 
 
+class RelookCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("max_ppm", C.c_float),
+                ("max_anchors", C.c_uint32), ("pool_frames", C.c_uint32), ("pool_octets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RelookInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("max_ppm", C.c_float),
+                ("max_anchors", C.c_uint32), ("pool_frames", C.c_uint32), ("pool_octets", C.c_uint32), ("reserved", C.c_uint32),
+                ("records", C.c_uint64), ("anchors_found", C.c_uint64), ("attempts", C.c_uint64), ("frames", C.c_uint64),
+                ("frames_ok", C.c_uint64), ("frames_new", C.c_uint64), ("dropped", C.c_uint64), ("kernel_ms", C.c_float), ("reserved2", C.c_uint32)]
+
+
+RELOOK_DTYPE = np.dtype([("chan", "<u4"), ("freq", "<u4"), ("first_bin", "<u8"), ("anchor", "<i8"), ("end_sample", "<i8"),
+                         ("pherr", "<f4"), ("slope", "<f4"), ("ppm_error", "<f4"), ("prev_phase", "<f4"),
+                         ("tl_bits", "<u4"), ("nsym", "<u4"), ("synd_weight", "<u4"), ("stop", "<i4"),
+                         ("frames", "<u4"), ("frames_ok", "<u4"), ("frames_new", "<u4"), ("fec_corrections", "<i4"),
+                         ("frame_first", "<u4"), ("flags", "<u4"), ("new_mask", "<u4"), ("reserved", "<u4"), ("counters", "<u8", (20,))])     # vdl2hip_relook, 256 bytes
+
+
 class TxcapCfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("pre_samples", C.c_uint32), ("post_samples", C.c_uint32),
                 ("max_iq_samples", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32), ("pool_samples", C.c_uint32),
@@ -328,6 +351,11 @@ def load_library(path: str = None):
         L.vdl2hip_toa_disable.argtypes = [C.c_void_p]
         L.vdl2hip_toa_info_get.argtypes = [C.c_void_p, C.POINTER(ToaInfo)]
         L.vdl2hip_toa_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "vdl2hip_relook_enable"):
+        L.vdl2hip_relook_enable.argtypes = [C.c_void_p, C.POINTER(RelookCfg)]
+        L.vdl2hip_relook_disable.argtypes = [C.c_void_p]
+        L.vdl2hip_relook_info_get.argtypes = [C.c_void_p, C.POINTER(RelookInfo)]
+        L.vdl2hip_relook_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PackedFrame), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vdl2hip_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
     L.vdl2hip_group_destroy.argtypes = [C.c_void_p]
     L.vdl2hip_group_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -555,6 +583,51 @@ def _txsearch_info(Lib, ctx) -> dict:
 
 def _txsearch_read(Lib, ctx, cap_recs: int = 4096) -> np.ndarray:
     return _read_records(Lib, ctx, "vdl2hip_txsearch_read", TXS_DTYPE, cap_recs)
+
+
+def _relook_enable(Lib, ctx, threshold, max_anchors, max_ppm, pool_frames, pool_octets, new_only) -> None:
+    cfg = RelookCfg(C.sizeof(RelookCfg), RELOOK_NEW_ONLY if new_only else 0, threshold, max_ppm, max_anchors, pool_frames, pool_octets, 0)
+    _err(Lib, Lib.vdl2hip_relook_enable(ctx, C.byref(cfg)), "vdl2hip_relook_enable")
+
+
+def _relook_info(Lib, ctx) -> dict:
+    info = RelookInfo(C.sizeof(RelookInfo))
+    _err(Lib, Lib.vdl2hip_relook_info_get(ctx, C.byref(info)), "vdl2hip_relook_info_get")
+    return {k: getattr(info, k) for k, _ in RelookInfo._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+
+
+def unpack_frames(n, recs, octets) -> List[dict]:
+    """n vdl2hip_packed_frame records and their octets -> one dict per frame"""
+    out = []
+    for i in range(n):
+        f = recs[i].frame; off = recs[i].octets_off
+        out.append(dict(chan=f.chan, freq=f.freq, idx=f.idx, octets=bytes(octets[off:off + f.len]),
+                        synd_weight=f.synd_weight, datalen_octets=f.datalen_octets,
+                        num_fec_corrections=f.num_fec_corrections, frame_pwr_dbfs=f.frame_pwr_dbfs,
+                        nf_pwr_dbfs=f.nf_pwr_dbfs, ppm_error=f.ppm_error, burst_ord=f.burst_ord,
+                        sync_sample=f.sync_sample, end_sample=f.end_sample,
+                        avlc_status=f.avlc_status, dst_addr=f.dst_addr, src_addr=f.src_addr))
+    return out
+
+
+def _relook_read(Lib, ctx, cap_recs: int = 1024, cap_frames: int = 4096, cap_octets: int = 1 << 20):
+    """vdl2hip_relook_read until nothing more comes -> (records as an array of RELOOK_DTYPE, frames as a list of dicts): record i's
+    frames are frames[rec["frame_first"] : rec["frame_first"] + rec["frames"]]"""
+    buf = np.zeros(max(1, cap_recs), dtype=RELOOK_DTYPE)
+    pk = (PackedFrame * max(1, cap_frames))()
+    po = (C.c_uint8 * max(1, cap_octets))()
+    recs, frames = [], []
+    while True:
+        used = C.c_size_t(0)
+        n = _err(Lib, Lib.vdl2hip_relook_read(ctx, buf.ctypes.data, cap_recs, pk, cap_frames, po, cap_octets, C.byref(used)), "vdl2hip_relook_read")
+        if n == 0:
+            break
+        r = buf[:n].copy()
+        nfr = int(r["frames"].sum())
+        r["frame_first"] = np.where(r["frames"] > 0, r["frame_first"] + len(frames), 0)
+        frames += unpack_frames(nfr, pk, memoryview(po)[:used.value])
+        recs.append(r)
+    return (np.concatenate(recs) if recs else np.zeros(0, dtype=RELOOK_DTYPE)), frames
 
 
 def _txcap_enable(Lib, ctx, iq, spectrum, pre, post, max_iq_samples, nfft, window, pool_samples, pool_spectra, undecoded_only) -> None:
@@ -962,6 +1035,24 @@ class Receiver:
     def txsearch_read(self, cap_recs: int = 4096) -> np.ndarray:
         """the records of the feeds collected so far (sync() or a drain first), oldest first, as an array of TXS_DTYPE"""
         return _txsearch_read(self.L, self.h, cap_recs)
+
+    def relook_enable(self, threshold: float = 0.0, max_anchors: int = 0, max_ppm: float = 0.0, pool_frames: int = 0, pool_octets: int = 0,
+                      new_only: bool = False) -> None:
+        """Switch the second look on (include/vdl2hip.h, "Second look"): for every transmission the log closes, a decode attempt anchored
+        on every preamble in it.  Needs the preamble search enabled.  0: the defaults (threshold 4, 4 anchors, no ppm gate)."""
+        _relook_enable(self.L, self.h, threshold, max_anchors, max_ppm, pool_frames, pool_octets, new_only)
+
+    def relook_disable(self) -> None:
+        self._chk(self.L.vdl2hip_relook_disable(self.h), "vdl2hip_relook_disable")
+
+    def relook_info(self) -> dict:
+        """the fields of vdl2hip_relook_info: the configuration in force and the totals of the feeds collected so far"""
+        return _relook_info(self.L, self.h)
+
+    def relook_read(self, cap_recs: int = 1024, cap_frames: int = 4096, cap_octets: int = 1 << 20):
+        """the attempt records of the feeds collected so far (sync() or a drain first), oldest first, as an array of RELOOK_DTYPE, and
+        their frames as a list of dicts (record i's: frames[frame_first : frame_first + frames])"""
+        return _relook_read(self.L, self.h, cap_recs, cap_frames, cap_octets)
 
     def txcap_enable(self, iq: bool = True, spectrum: bool = True, pre: int = 0, post: int = 0, max_iq_samples: int = 0, nfft: int = 0,
                      window: int = WIN_HANN, pool_samples: int = 0, pool_spectra: int = 0, undecoded_only: bool = False) -> None:

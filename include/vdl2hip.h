@@ -58,7 +58,9 @@ extern "C" {
                                  *    vdl2hip_txcap_enable() / _disable() / _info_get() / _read() / _measure() with vdl2hip_txcap_cfg / _info, vdl2hip_tx_capture
                                  *    and vdl2hip_tx_shape: the transmission capture, off unless enabled - new entry points and structures only, so the version stayed
                                  *    vdl2hip_toa_template() / _enable() / _disable() / _info_get() / _read() with vdl2hip_toa_cfg / _info and vdl2hip_burst_toa:
-                                 *    burst timing, off unless enabled - new entry points and structures only, so the version stayed */
+                                 *    burst timing, off unless enabled - new entry points and structures only, so the version stayed
+                                 *    vdl2hip_relook_enable() / _disable() / _info_get() / _read() with vdl2hip_relook_cfg / _info and vdl2hip_relook:
+                                 *    the second look, off unless enabled - new entry points and structures only, so the version stayed */
 
 /* enum sample_formats, src/dumpvdl2.h:319 */
 #define VDL2HIP_FMT_U8     0
@@ -477,6 +479,98 @@ typedef struct {
 	float    kernel_ms;                        /* summed HIP-event time of the search's launches at profiling level 2, else 0 */
 	uint32_t reserved;
 } vdl2hip_txsearch_info;                       /* 40 bytes */
+
+/* Second look (not in the reference): for every transmission the transmission log closes, a decode attempt anchored on every preamble
+ * in it, whatever state the sequential walk was in when it passed by.  The reference's per-channel FSM looks for a preamble only while
+ * it is idle: from a lock to the end of the length the header announced it evaluates nothing (src/demod.c:251-284), so a burst that
+ * begins while an earlier lock - a weaker burst, or a false lock with a long garbage header - is still being sliced is never seen.  The
+ * second look invents no decoding rule: it runs the reference's own slicer and burst decoder from the sync state the reference would
+ * have reached had it been looking, and delivers what comes out on a tap of its own.  The main path stays the reference's, to the bit.
+ *  - Dependencies and placement.  It sits on top of the preamble search: vdl2hip_relook_enable() with the search off is
+ *    VDL2HIP_E_INVAL, and whatever switches a running search off (vdl2hip_txsearch_enable() / _disable(), vdl2hip_txlog_enable() /
+ *    _disable(), vdl2hip_activity_enable() / _disable()) switches a running second look off first.  It runs behind the search of the
+ *    feed that closes the transmission and reads y_c as it stands there: the search's placement, with the same caveat about a later
+ *    feed's referee.  It writes only buffers of its own.  Off unless enabled; with it off nothing is launched or allocated and every
+ *    result is what it was.  On, frames, counters, the decimated stream and every other tap are still exactly what they were.
+ *    Groups get no group call: vdl2hip_group_ctx(g, k) is the handle.
+ *  - Metric and range.  Phi(n), p(n), s(n), search_first and search_last are exactly those of "Preamble search".  R = 160 (16 symbols
+ *    of 10 samples: two preambles cannot lie closer).
+ *  - Anchors.  thr = cfg.threshold; 0 means 4.0f; a value outside (0, 30] or a NaN is refused.  n in [search_first, search_last] is
+ *    an anchor iff  p(n) < thr (a float32 <),  p(n) < p(m) for every m in [n - R, n) inside the range,  and  p(n) <= p(m) for every
+ *    m in (n, n + R] inside the range.  A NaN is never an anchor and never beats one.  Of a transmission's anchors the max_anchors
+ *    best are kept, by (p ascending, n ascending); 0 means 4, above 16 is refused.  The kept anchors are reported in ascending n;
+ *    vdl2hip_relook_info.anchors_found counts all of them.  The set depends on y_c alone: not on the cuts, not on how a kernel splits
+ *    the range.
+ *  - Attempt at anchor a.  The reference's DM_SYNC from a channel reset with prev_phi = Phi(a), dphi = s(a) and ppm_error =
+ *    ppm_of(s(a), freq).  Symbol m is taken at a + 10 (m + 1), as the walker places them behind its sync point, and sliced with the
+ *    decoder's own arithmetic (src/demod.c:256-264); the bits go to decode_vdl2_burst(): header state, then data state.  The
+ *    frames' frame_pwr_dbfs is that of the mean of |y|^2 over the attempt's symbols, header included (the reference's running mean of
+ *    the same terms, up to rounding).  With cfg.max_ppm set (not 0) and |ppm_error| above it the attempt is not made: flag
+ *    VDL2HIP_RELOOK_PPM_REJECT, every other field of the outcome 0.  The slope is taken at the dense minimum itself, where the
+ *    reference takes it at its grid's minimum (v->prev_dphi, src/demod.c:184) and moves its sampling point by a parabola's vertex:
+ *    the dense metric has the minimum to the sample, so no parabola is needed.
+ *  - Limit.  limit = last_sample + (hang_bins + 1) * bin_samples is the last sample that exists when the log emits the record,
+ *    whatever the cuts.  A header whose length needs a symbol beyond limit gives VDL2HIP_RELOOK_TRUNCATED and decodes nothing (the
+ *    header's tl_bits, nsym and synd_weight are reported, the counters stay 0); an attempt whose nine header symbols themselves pass
+ *    limit gives the same.  So every field depends on the stream alone.
+ *  - Room.  The frames of a feed's attempts go to a pool of pool_frames records and pool_octets octets per feed in flight (0: 256
+ *    records and 8192 octets per channel of the receiver, at least 4096 and 2^20; above 2^20 and 2^26: refused).  What goes to the
+ *    host is what the attempts produced, whatever the pools' sizes.  An attempt claims, from its header, what it can need at the
+ *    most: a frame is at least
+ *    one octet behind an eight-bit flag, so with O = ceil(tl_bits / 8) it claims O / 2 + 1 records and (O + 3 (O / 2 + 1) + 3) & ~3
+ *    octets (a frame's octets begin at a multiple of 4).  The claims' places are their exclusive prefix sums in record order, whether
+ *    they fit or not.  An attempt whose claim does not fit gets VDL2HIP_RELOOK_NO_ROOM, keeps its header fields, decodes nothing and is
+ *    counted in vdl2hip_relook_info.dropped - as are the attempts beyond 32 768 in one feed, which get no record.
+ *  - Attempt record.  One vdl2hip_relook per kept anchor, in (log record order, anchor) order, feed by feed.  chan, freq, first_bin:
+ *    the join key with vdl2hip_tx / vdl2hip_tx_search.  anchor, pherr = p(a), slope = s(a), ppm_error, prev_phase = Phi(a).  tl_bits,
+ *    nsym (symbols behind the unique word, header included), synd_weight: of a header that decoded, else 0.  end_sample: the last
+ *    symbol the attempt reads or would need (a + 90 while there is no header).  stop: the VDL2HIP_CNT_* index of the error counter
+ *    that ended the attempt (crc.bad, errors.too_long, errors.no_fec, errors.fec_bad, errors.unstuff, errors.truncated_octets), -1
+ *    if none did.  counters: a row private to the attempt - what the reference's counters would have gained from it, sync.good aside.
+ *    frames, frames_ok (avlc_status OK), frames_new, fec_corrections (of the burst; -1 without a frame), frame_first (index of its
+ *    first frame among the frames of the same vdl2hip_relook_read()).  flags: VDL2HIP_RELOOK_PPM_REJECT, _TRUNCATED, _NO_ROOM, and
+ *    VDL2HIP_TX_PARTIAL passed on from the log's record.
+ *  - Frames.  Delivered as vdl2hip_packed_frame plus octets by vdl2hip_relook_read(), with the frame finisher's avlc_status and
+ *    addresses; sync_sample = anchor, burst_ord = -1.  nf_pwr_dbfs = NaN: the reference's figure is a state of its walk, which the
+ *    attempt is not part of - the log's record (mean_power, peak_power) and the activity monitor have the levels.  Second-look
+ *    frames never enter vdl2hip_drain*(), the counters or the statsd lines.
+ *  - New or seen.  A host-side join, done where the log's join is done: a second-look frame is SEEN iff the log attributed to the same
+ *    record a main-path frame with the same len and the same octets (compared as len plus a 64-bit FNV-1a hash taken when the feed's
+ *    frames are collected); otherwise it is NEW, and frames_new counts the NEW ones with avlc_status OK; new_mask says which of the
+ *    attempt's first 32 frames they are.  The join inherits the log's
+ *    one stated dependence on the cuts: a frame delivered after its transmission's record was emitted is not attributed to it.
+ *    VDL2HIP_RELOOK_NEW_ONLY delivers only the attempts with frames_new > 0 (filtered on the host, like its neighbours). */
+#define VDL2HIP_RELOOK_NEW_ONLY     1u         /* vdl2hip_relook_cfg.flags */
+#define VDL2HIP_RELOOK_PPM_REJECT   2u         /* vdl2hip_relook.flags (bit 0 is VDL2HIP_TX_PARTIAL) */
+#define VDL2HIP_RELOOK_TRUNCATED    4u
+#define VDL2HIP_RELOOK_NO_ROOM      8u
+typedef struct {
+	uint32_t struct_size, flags;               /* flags: VDL2HIP_RELOOK_NEW_ONLY */
+	float    threshold, max_ppm;               /* 0: 4.0f; 0: no gate */
+	uint32_t max_anchors, pool_frames, pool_octets, reserved;      /* 0: 4, and the pools' defaults ("Room"); reserved must be 0 */
+} vdl2hip_relook_cfg;                          /* 32 bytes */
+typedef struct {
+	uint32_t chan, freq;                  /* as in vdl2hip_tx */
+	uint64_t first_bin;                   /* the join key with vdl2hip_tx and vdl2hip_tx_search */
+	int64_t  anchor, end_sample;
+	float    pherr, slope, ppm_error, prev_phase;
+	uint32_t tl_bits, nsym, synd_weight;
+	int32_t  stop;
+	uint32_t frames, frames_ok, frames_new;    /* frames_new: filled in by the host from the log's join */
+	int32_t  fec_corrections;
+	uint32_t frame_first, flags;
+	uint32_t new_mask, reserved;          /* new_mask: bit k set iff frame k of the attempt (k < 32) is NEW and passes the AVLC front door; filled in by the host */
+	uint64_t counters[VDL2HIP_NUM_COUNTERS];
+} vdl2hip_relook;                              /* 256 bytes */
+typedef struct {
+	uint32_t struct_size, flags;               /* as in force */
+	float    threshold, max_ppm;
+	uint32_t max_anchors, pool_frames, pool_octets, reserved;
+	uint64_t records, anchors_found, attempts; /* of the feeds collected so far: log records looked at, anchors, attempt records */
+	uint64_t frames, frames_ok, frames_new, dropped;
+	float    kernel_ms;                        /* summed HIP-event time of the second look's launches at profiling level 2, else 0 */
+	uint32_t reserved2;
+} vdl2hip_relook_info;                         /* 96 bytes */
 
 /* Transmission capture (not in the reference): for every transmission the transmission log closes, the channel's decimated samples
  * around it and a compact spectral signature of the channel during it - where in the 25 kHz the energy sat and how wide it was.  The
@@ -942,6 +1036,25 @@ int  vdl2hip_txsearch_info_get(vdl2hip_ctx *ctx, vdl2hip_txsearch_info *info);
 /* Like vdl2hip_txlog_read(): the records of the feeds collected so far, oldest first.  What does not fit stays queued for the next
  * call; the call never waits for the device itself.  Returns the number of records written.  Search off: VDL2HIP_E_INVAL. */
 int  vdl2hip_txsearch_read(vdl2hip_ctx *ctx, vdl2hip_tx_search *recs, size_t cap_recs);
+
+/* ---- Second look (see "Second look" above) ----
+ * Switch the second look on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way,
+ * drops what is queued unread and starts afresh.  VDL2HIP_E_INVAL if the preamble search is off, for a bad struct_size, an unknown
+ * flag, a threshold that is a NaN or outside (0, 30] (0: 4.0f), a max_ppm that is negative or a NaN, max_anchors > 16, pool_frames >
+ * 2^20, pool_octets > 2^26 or a reserved word that is not 0, before anything is allocated or changed: a second look that was on stays
+ * as it was. */
+int  vdl2hip_relook_enable(vdl2hip_ctx *ctx, const vdl2hip_relook_cfg *cfg);
+/* Switch it off: the feeds under way are collected, its buffers and what is queued unread are freed, later feeds launch nothing. */
+int  vdl2hip_relook_disable(vdl2hip_ctx *ctx);
+/* The configuration in force and the totals so far; info->struct_size must be set.  Second look off: VDL2HIP_E_INVAL. */
+int  vdl2hip_relook_info_get(vdl2hip_ctx *ctx, vdl2hip_relook_info *info);
+/* The attempt records of the feeds collected so far, oldest first, with their frames: record i's recs[i].frames frames are
+ * frames[recs[i].frame_first ...], in the burst's order, each frame's len octets at octets[frames[j].octets_off] (frame.octets is
+ * NULL).  What does not fit - records, their frames or their octets - stays queued for the next call; the call never waits for the
+ * device itself.  Returns the number of records written, *octets_used the octets (may be NULL); the frames written are the sum of
+ * recs[i].frames.  Second look off: VDL2HIP_E_INVAL. */
+int  vdl2hip_relook_read(vdl2hip_ctx *ctx, vdl2hip_relook *recs, size_t cap_recs, vdl2hip_packed_frame *frames, size_t cap_frames,
+                         uint8_t *octets, size_t cap_octets, size_t *octets_used);
 
 /* ---- Transmission capture (see "Transmission capture" above) ----
  * Switch the capture on.  Allowed between feeds; takes effect with the next feed.  Enabling again collects the feeds under way, drops

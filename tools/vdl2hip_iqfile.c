@@ -44,6 +44,15 @@
  *                                 transmission the fields of vdl2hip_tx_search in the structure's order - "chan freq first_bin search_first
  *                                 search_last best_sample first_lock best_pherr best_slope best_ppm lock_points below_thr lock_phases
  *                                 flags frames frames_ok why"
+ *   --relook-out <path>           (this library's own) switch the second look on - and with it the preamble search, the transmission log
+ *                                 and the activity monitor - and, at exit, write to a file of its own one line "# flags <f> threshold <x>
+ *                                 max_anchors <n> records <n> anchors_found <n> attempts <n> frames <n> frames_ok <n> frames_new <n>
+ *                                 dropped <n> kernel_ms <x>", then per attempt "chan freq first_bin anchor end_sample pherr slope ppm_error
+ *                                 prev_phase tl_bits nsym synd_weight stop frames frames_ok frames_new fec_corrections flags"
+ *   --relook-frames <path>        ... and write the NEW frames that pass the AVLC front door (frames of attempts the main path did not
+ *                                 deliver) to a file of their own, in the raw-frame archive format of --output raw:binary:file.  They are
+ *                                 never mixed into the main output: dumpvdl2, given the same IQ, does not deliver them
+ *   --relook-threshold <x>        the anchors' threshold on the preamble metric (default 4, at most 30)
  *   --tx-capture-out <path>       (this library's own) switch the transmission capture on - and with it the transmission log and the activity
  *                                 monitor, as --tx-out does - and, at exit, write what every transmission looked like: two lines "# key value
  *                                 ..." with the fields of vdl2hip_txcap_info, then per transmission the fields of vdl2hip_tx_capture in the
@@ -183,6 +192,44 @@ static int take_tx_search(vdl2hip_ctx *rx) {
 		ntxss += (size_t)n;
 	}
 }
+/* second look: the attempt records so far (written at exit, behind the totals); the NEW good frames go to their own archive as they come */
+static vdl2hip_relook *rls;
+static size_t nrls, cap_rls;
+static FILE *relook_frames;
+static int take_relook(vdl2hip_ctx *rx) {
+	enum { RECS = 64, FRAMES = 1024, OCTETS = 1 << 20 };
+	static vdl2hip_relook rec[RECS];
+	static vdl2hip_packed_frame fr[FRAMES];
+	static uint8_t oct[OCTETS];
+	for(;;) {
+		size_t used = 0;
+		const int n = vdl2hip_relook_read(rx, rec, RECS, fr, FRAMES, oct, OCTETS, &used);
+		if(n <= 0) return n;
+		if(nrls + (size_t)n > cap_rls) {
+			cap_rls = 2 * (nrls + (size_t)n);
+			rls = realloc(rls, cap_rls * sizeof *rls);
+			if(!rls) { perror("realloc"); exit(3); }
+		}
+		memcpy(rls + nrls, rec, (size_t)n * sizeof *rec);
+		nrls += (size_t)n;
+		for(int i = 0; relook_frames && i < n; i++) {
+			if(rec[i].frames_new == 0) continue;
+			/* (new_mask names the NEW good frames among an attempt's first 32; beyond that only an attempt all of whose good frames are new is taken) */
+			for(uint32_t k = 0; k < rec[i].frames; k++) {
+				vdl2hip_frame f = fr[rec[i].frame_first + k].frame;
+				const int is_new = k < 32 ? (int)((rec[i].new_mask >> k) & 1u) : rec[i].frames_new == rec[i].frames_ok;
+				if(f.avlc_status != VDL2HIP_AVLC_OK || !is_new) continue;
+				f.octets = oct + fr[rec[i].frame_first + k].octets_off;
+				f.nf_pwr_dbfs = f.frame_pwr_dbfs;                        /* (the archive has no way to say "unknown": SNR 0) */
+				static uint8_t out[70000];
+				struct timeval tv; gettimeofday(&tv, NULL);
+				const int m = vdl2hip_pack_raw_frame(&f, station_id, tv.tv_sec, tv.tv_usec, out, sizeof out);
+				if(m > 0) fwrite(out, 1, (size_t)m, relook_frames);
+				else fprintf(stderr, "second-look frame not archived: %s\n", vdl2hip_strerror(m));
+			}
+		}
+	}
+}
 /* transmission capture: the records so far with the four figures of each spectrum (written at exit, behind the totals), the IQ and
  * the spectra files as they grow - raw float32, record i's at iq_off pairs / spec_off floats */
 typedef struct { vdl2hip_tx_capture r; vdl2hip_tx_shape shape; } tx_cap_row;
@@ -268,6 +315,7 @@ int main(int argc, char **argv) {
 	const char *activity_path = NULL;
 	uint32_t activity_bin = 105, activity_hang = 0; float activity_thr = -40.f;
 	const char *bursts_path = NULL, *bursts_iq_path = NULL, *tx_path = NULL, *tx_search_path = NULL;
+	const char *relook_path = NULL, *relook_frames_path = NULL; float relook_thr = 0.f;
 	const char *tx_capture_path = NULL, *tx_iq_path = NULL, *tx_spectra_path = NULL;
 	uint32_t tx_capture_flags = VDL2HIP_TXCAP_SPECTRUM, tx_capture_nfft = 0;
 	uint32_t bursts_pre = 256, bursts_post = 32, bursts_flags = 0;
@@ -317,6 +365,9 @@ int main(int argc, char **argv) {
 		else if(!strcmp(a, "--activity-hang")) { NEEDARG(); activity_hang = (uint32_t)strtoul(argv[++i], NULL, 10); }
 		else if(!strcmp(a, "--tx-out")) { NEEDARG(); tx_path = argv[++i]; }
 		else if(!strcmp(a, "--tx-search-out")) { NEEDARG(); tx_search_path = argv[++i]; }
+		else if(!strcmp(a, "--relook-out")) { NEEDARG(); relook_path = argv[++i]; }
+		else if(!strcmp(a, "--relook-frames")) { NEEDARG(); relook_frames_path = argv[++i]; }
+		else if(!strcmp(a, "--relook-threshold")) { NEEDARG(); relook_thr = (float)atof(argv[++i]); }
 		else if(!strcmp(a, "--tx-capture-out")) { NEEDARG(); tx_capture_path = argv[++i]; }
 		else if(!strcmp(a, "--tx-iq")) { NEEDARG(); tx_iq_path = argv[++i]; tx_capture_flags |= VDL2HIP_TXCAP_IQ; }
 		else if(!strcmp(a, "--tx-spectra")) { NEEDARG(); tx_spectra_path = argv[++i]; }
@@ -338,7 +389,7 @@ int main(int argc, char **argv) {
 			"[--max-ppm x] [--station-id s] [--raw-frames-out file] [--avlc-filter] [--statsd-out file] [--blocks-per-feed n] "
 			"[--spectrum-out file] [--spectrum-nfft n] [--spectrum-window rect|hann|bh4] "
 			"[--waterfall-out file] [--waterfall-segments R] [--waterfall-mean file] [--waterfall-max file] "
-			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] "
+			"[--activity-out file] [--activity-bin samples] [--activity-threshold dBFS] [--activity-hang bins] [--tx-out file] [--tx-search-out file] [--relook-out file] [--relook-frames file] [--relook-threshold x] "
 			"[--tx-capture-out file] [--tx-iq file] [--tx-spectra file] [--tx-capture-undecoded-only] [--tx-capture-nfft n] "
 			"[--bursts-out file] [--bursts-iq file] [--bursts-failed-only] [--bursts-pre samples] [--bursts-post samples] [--toa-out file] [--toa-max-lag n] [freq ...]\n", argv[0]); return 1; }
 	if(nfreq == 0) {
@@ -392,19 +443,25 @@ int main(int argc, char **argv) {
 		if(wf_mean_path && !(wf_mean = fopen(wf_mean_path, "w"))) { perror("Could not open waterfall mean output"); return 2; }
 		if(wf_max_path && !(wf_max = fopen(wf_max_path, "w"))) { perror("Could not open waterfall max output"); return 2; }
 	}
-	if(activity_path || tx_path || tx_search_path || tx_capture_path) {
+	const int relook = relook_path || relook_frames_path, search = tx_search_path || relook;
+	if(activity_path || tx_path || search || tx_capture_path) {
 		vdl2hip_activity_cfg ac = { sizeof ac, activity_bin, activity_hang, 0, activity_thr, 0 };
 		if(activity_bin == 0 || (r = vdl2hip_activity_enable(rx, &ac)) != VDL2HIP_OK) {
 			fprintf(stderr, "vdl2hip_activity_enable: %s\n", vdl2hip_strerror(activity_bin ? r : VDL2HIP_E_INVAL)); return 3;
 		}
 	}
-	if(tx_path || tx_search_path || tx_capture_path) {
+	if(tx_path || search || tx_capture_path) {
 		vdl2hip_txlog_cfg tc = { sizeof tc, 0, 0, 0 };
 		if((r = vdl2hip_txlog_enable(rx, &tc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txlog_enable: %s\n", vdl2hip_strerror(r)); return 3; }
 	}
-	if(tx_search_path) {
+	if(search) {
 		vdl2hip_txsearch_cfg sc = { sizeof sc, 0, { 0, 0 } };
 		if((r = vdl2hip_txsearch_enable(rx, &sc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_txsearch_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+	}
+	if(relook) {
+		vdl2hip_relook_cfg lc = { sizeof lc, 0, relook_thr, 0.f, 0, 0, 0, 0 };
+		if((r = vdl2hip_relook_enable(rx, &lc)) != VDL2HIP_OK) { fprintf(stderr, "vdl2hip_relook_enable: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(relook_frames_path && !(relook_frames = fopen(relook_frames_path, "wb"))) { perror("Could not open second-look frames output"); return 2; }
 	}
 	if(tx_capture_path) {
 		/* (post: a bin's worth behind the last busy bin, which the record's feed always holds) */
@@ -435,8 +492,9 @@ int main(int argc, char **argv) {
 		if(bursts_path && (r = take_bursts(rx)) < 0) { fprintf(stderr, "vdl2hip_capture_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(toa_path && (r = take_toa(rx)) < 0) { fprintf(stderr, "vdl2hip_toa_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_path && (r = take_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
-		if((tx_search_path || tx_capture_path) && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
-		if(tx_search_path && (r = take_tx_search(rx)) < 0) { fprintf(stderr, "vdl2hip_txsearch_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if((search || tx_capture_path) && !tx_path && (r = drop_tx(rx)) < 0) { fprintf(stderr, "vdl2hip_txlog_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(search && (r = take_tx_search(rx)) < 0) { fprintf(stderr, "vdl2hip_txsearch_read: %s\n", vdl2hip_strerror(r)); return 3; }
+		if(relook && (r = take_relook(rx)) < 0) { fprintf(stderr, "vdl2hip_relook_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		if(tx_capture_path && (r = take_tx_capture(rx)) < 0) { fprintf(stderr, "vdl2hip_txcap_read: %s\n", vdl2hip_strerror(r)); return 3; }
 		held = 0;
 	} while(len == FILE_BUFSIZE);
@@ -603,6 +661,26 @@ int main(int argc, char **argv) {
 			fclose(so);
 		}
 		else fprintf(stderr, "preamble search not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+	}
+	if(relook) {
+		vdl2hip_relook_info li;
+		memset(&li, 0, sizeof li); li.struct_size = sizeof li;
+		r = vdl2hip_relook_info_get(rx, &li);
+		FILE *so = r == VDL2HIP_OK && relook_path ? fopen(relook_path, "w") : NULL;
+		if(so) {
+			fprintf(so, "# flags %u threshold %.9g max_anchors %u records %" PRIu64 " anchors_found %" PRIu64 " attempts %" PRIu64 " frames %" PRIu64 " frames_ok %" PRIu64
+					" frames_new %" PRIu64 " dropped %" PRIu64 " kernel_ms %.6g\n", li.flags, (double)li.threshold, li.max_anchors, li.records, li.anchors_found, li.attempts,
+					li.frames, li.frames_ok, li.frames_new, li.dropped, (double)li.kernel_ms);
+			for(size_t i = 0; i < nrls; i++) {
+				const vdl2hip_relook *t = &rls[i];
+				fprintf(so, "%u %u %" PRIu64 " %" PRId64 " %" PRId64 " %.9g %.9g %.9g %.9g %u %u %u %d %u %u %u %d %u\n", t->chan, t->freq, t->first_bin, t->anchor, t->end_sample,
+						(double)t->pherr, (double)t->slope, (double)t->ppm_error, (double)t->prev_phase, t->tl_bits, t->nsym, t->synd_weight, t->stop, t->frames, t->frames_ok,
+						t->frames_new, t->fec_corrections, t->flags);
+			}
+			fclose(so);
+		}
+		else if(relook_path) fprintf(stderr, "second look not written: %s\n", r != VDL2HIP_OK ? vdl2hip_strerror(r) : "cannot open file");
+		if(relook_frames) fclose(relook_frames);
 	}
 	if(tx_capture_path) {
 		vdl2hip_txcap_info xi;
