@@ -33,17 +33,23 @@ def _place(acc, chan, start, wave, amp):
     acc[start:start + wave.size] += (amp * wave * np.exp(1j * w * idx)).astype(np.complex64)
 
 
-@functools.lru_cache(maxsize=1)
-def scenario():
-    """-> (raw int16 [N, 2], frames: {"A", "B", "C"} -> the AVLC frame of the burst)"""
+@functools.lru_cache(maxsize=3)
+def scenario(b_at=120000, cut_at=0):
+    """-> (raw int16 [N, 2], frames: {"A", "B", "C"} -> the AVLC frame of the burst); b_at: the input sample at which B begins;
+    cut_at: a fourth burst begins there on channel 1 whose transmitter stops halfway through it (0: none)"""
     rng = np.random.default_rng(20261021)
     fr = {k: synth.make_avlc_frame(rng.integers(0, 256, size=n, dtype=np.uint8).tobytes()) for k, n in (("A", 700), ("B", 40), ("C", 60))}
     wave = {k: synth.modulate(synth.build_burst([f]).symbols, 10 * OS, start_phase=float(rng.uniform(0, 6.28))) for k, f in fr.items()}
     acc = np.zeros(N, dtype=np.complex64)
     _place(acc, 0, 40000, wave["A"], 0.008)
-    _place(acc, 0, 120000, wave["B"], 0.09)                     # begins and ends inside A (A: 1.9e5 input samples, B: 1.9e4)
+    _place(acc, 0, b_at, wave["B"], 0.09)                       # begins and ends inside A (A: 1.9e5 input samples, B: 1.9e4)
     _place(acc, 1, 60000, wave["C"], 0.05)
-    assert 40000 + wave["A"].size > 120000 + wave["B"].size
+    assert 40000 + wave["A"].size > b_at + wave["B"].size and b_at > 40000
+    if cut_at:
+        r2 = np.random.default_rng(20261022)                     # (its own generator: A, B, C and the noise are those of scenario())
+        w = synth.modulate(synth.build_burst([synth.make_avlc_frame(r2.integers(0, 256, size=300, dtype=np.uint8).tobytes())]).symbols, 10 * OS)
+        _place(acc, 1, cut_at, w[:w.size // 2], 0.05)
+        assert cut_at > 60000 + wave["C"].size + 10 * OS * ACT[0] * (ACT[2] + 2) and cut_at + w.size // 2 < N - 10000
     iq = np.stack([acc.real, acc.imag], axis=1) + rng.standard_normal((N, 2)).astype(np.float32) * np.float32(0.0004)
     return np.clip(np.rint(iq * 32768.0), -32768, 32767).astype(np.int16), fr
 
@@ -65,10 +71,17 @@ def cut_sizes(n, sizes):
     return out
 
 
-def run(vh, sizes, relook=None, search=True, chan_first=0, chan_count=0, reenable_at=None):
-    """the capture fed in pieces of `sizes` samples; relook: the arguments of relook_enable (None: off) -> dict"""
-    raw, _ = scenario()
-    rx = vh.Receiver(CF, FREQS, OS, vh.FMT_S16LE, 0.0, max_block_bytes=4 * max(sizes), chan_first=chan_first, chan_count=chan_count)
+def run(vh, sizes, relook=None, search=True, chan_first=0, chan_count=0, reenable_at=None, capture=None, base=0, per_feed=False):
+    """the capture fed in pieces of `sizes` samples; relook: the arguments of relook_enable (None: off); capture: (raw int16 [n, 2],
+    freqs, oversample) in place of scenario()'s; base: the input sample the stream begins at (debug_set_position on the fresh receiver,
+    ahead of every tap); per_feed: a sync() behind every feed, so that every read holds the records of that feed alone - feeds_tx, by
+    which model() shares a feed's room - and the new decimated samples are read back behind every feed (a short ring keeps no more)
+    -> dict; y[c][i] is decimated sample K + i, K = base / oversample"""
+    raw, freqs, os_ = capture if capture is not None else (scenario()[0], FREQS, OS)
+    n, K = raw.shape[0], base // os_
+    rx = vh.Receiver(CF, freqs, os_, vh.FMT_S16LE, 0.0, max_block_bytes=4 * max(sizes), chan_first=chan_first, chan_count=chan_count)
+    if base:
+        rx.debug_set_position(base)
     rx.debug_option("referee", 0)
     rx.activity_enable(*ACT, 0)
     rx.txlog_enable()
@@ -76,7 +89,8 @@ def run(vh, sizes, relook=None, search=True, chan_first=0, chan_count=0, reenabl
         rx.txsearch_enable()
     if relook is not None:
         rx.relook_enable(**relook)
-    frames, tx, txs, recs, rlf = [], [], [], [], []
+    chans = range(rx.chan_first, rx.chan_first + rx.chan_count)
+    frames, tx, txs, recs, rlf, y = [], [], [], [], [], {c: [] for c in chans}
 
     def collect():
         frames.extend(rx.drain())
@@ -87,23 +101,48 @@ def run(vh, sizes, relook=None, search=True, chan_first=0, chan_count=0, reenabl
             r, f = rx.relook_read()
             r["frame_first"] = np.where(r["frames"] > 0, r["frame_first"] + len(rlf), 0)
             recs.append(r); rlf.extend(f)
-    k = 0
+    k = made = 0
     for i, d in enumerate(sizes):
         if reenable_at == i:
             rx.sync(); collect()
             rx.relook_enable(**relook)
         rx.feed(raw[k:k + d])
         k += d
+        if per_feed:
+            rx.sync()
         collect()
+        if per_feed and k // os_ > made:
+            for c in chans:
+                y[c].append(rx.read_decimated(c, K + made, k // os_ - made))
+            made = k // os_
+    assert k == n
     rx.sync()
     collect()
-    chans = range(rx.chan_first, rx.chan_first + rx.chan_count)
+    for c in chans:
+        y[c].append(rx.read_decimated(c, K + made, n // os_ - made))
     out = dict(frames=frames, tx=np.concatenate(tx), txs=np.concatenate(txs) if search else None,
                recs=np.concatenate(recs) if relook is not None else None, rlf=rlf, info=rx.relook_info() if relook is not None else None,
+               loginfo=rx.txlog_info(), feeds_tx=[len(t) for t in tx] if per_feed else None, feeds_recs=[len(r) for r in recs], K=K,
                counters=[[list(rx.counters(c).values()), list(rx.avlc_counters(c).values())] for c in chans],
-               y={c: rx.read_decimated(c, 0, N // OS).view(np.complex64).reshape(-1) for c in chans})
+               y={c: np.concatenate(v).view(np.complex64).reshape(-1) for c, v in y.items()})
     rx.close()
+    assert all(v.size == n // os_ for v in out["y"].values())
     return out
+
+
+def getter(res, c):
+    """channel c's stream of a run as the model reads it: absolute sample n; ahead of the run's first sample K lies rest"""
+    v, K = res["y"][c], res["K"]
+    if K == 0:
+        return tm.stream_get(v)
+
+    def get(n):
+        n = np.asarray(n, dtype=np.int64)
+        out = np.zeros(n.shape, dtype=np.complex64)
+        ok = n >= K
+        out[ok] = v[n[ok] - K]
+        return out
+    return get
 
 
 @pytest.fixture(scope="module")
@@ -113,18 +152,20 @@ def single(vh):
 
 def model(res, feeds_tx=None, **cfg):
     """the model on the run's own stream: the attempts of every log record in the log's order; the room of a feed is shared by the
-    records of that feed (feeds_tx: the number of log records of each feed; None: one feed)"""
+    records of that feed (feeds_tx: the number of log records of each feed; None: one feed) -> ([(log record, attempt, frames)], anchors found)"""
     want, found = [], 0
     bounds = np.cumsum(feeds_tx if feeds_tx is not None else [len(res["tx"])])
-    pf, pc = cfg.get("pool_frames", 0) or rm.DEF_FRAMES, cfg.get("pool_octets", 0) or rm.DEF_OCTETS
+    # (vdl2hip.h, "Room": the defaults are 256 records and 8192 octets per channel of the receiver, at least 4096 and 2^20)
+    pf, pc = cfg.get("pool_frames", 0) or max(rm.DEF_FRAMES, 256 * len(res["y"])), cfg.get("pool_octets", 0) or max(rm.DEF_OCTETS, 8192 * len(res["y"]))
     off = [0, 0]
     for i, t in enumerate(res["tx"]):
         if i in bounds:
             off = [0, 0]
-        att, nf = rm.second_look(tm.stream_get(res["y"][int(t["chan"])]), int(t["first_sample"]), int(t["last_sample"]), int(t["last_sample"]) + BACK,
+        att, nf = rm.second_look(getter(res, int(t["chan"])), int(t["first_sample"]), int(t["last_sample"]), int(t["last_sample"]) + BACK,
                                  int(t["freq"]), cfg.get("threshold", 0.0), cfg.get("max_anchors", 0), cfg.get("max_ppm", 0.0), 1 << 30, 1 << 30, int(t["flags"]))
         found += nf
         for r, frames in att:
+            r["found"] = nf                                      # (the anchors found in its record, of which max_anchors are kept)
             cf, cp = rm.claim(r["tl_bits"]) if r["tl_bits"] and not r["flags"] & (rm.TRUNCATED | rm.PPM_REJECT) else (0, 0)
             if cf and (off[0] + cf > pf or off[1] + cp > pc):
                 r.update(flags=r["flags"] | rm.NO_ROOM, stop=-1, counters=[0] * 20, frames=0, frames_ok=0, fec_corrections=-1)
@@ -180,17 +221,19 @@ def stable(res):
     """records and frames in an order and a form that does not depend on the cut: by (chan, first_bin, anchor); frame_first is an index
     of the read and frames_new the host's join (vdl2hip.h, "Second look": New or seen), both left out.  Per record: the bytes of its
     integer fields and of its frames' octets and integer fields; the bytes of its float fields and of its frames' frame_pwr_dbfs; the
-    samples it read"""
-    out = []
+    samples it read.  Samples are counted from the run's first, K (first_bin is: the log counts its bins from where it was enabled),
+    so that a run hours into a stream gives what the run at 0 gives"""
+    out, K = [], res["K"]
     for g in np.sort(res["recs"], order=["chan", "first_bin", "anchor"]):
         ff = int(g["frame_first"])
         h = g.copy(); h["frame_first"] = 0; h["frames_new"] = 0; h["new_mask"] = 0
-        fr = res["rlf"][ff:ff + int(g["frames"])]
+        h["anchor"] -= K; h["end_sample"] -= K
+        fr = [dict(f, sync_sample=f["sync_sample"] - K, end_sample=f["end_sample"] - K) for f in res["rlf"][ff:ff + int(g["frames"])]]
         floats = b"".join(h[k].tobytes() for k in rm.FLOAT_FIELDS) + b"".join(np.float32(f["frame_pwr_dbfs"]).tobytes() + np.float32(f["ppm_error"]).tobytes() for f in fr)
         for k in rm.FLOAT_FIELDS:
             h[k] = 0
         ints = h.tobytes() + b"".join(f["octets"] + bytes(str((f["idx"], f["avlc_status"], f["num_fec_corrections"], f["sync_sample"], f["end_sample"])), "ascii") for f in fr)
-        out.append((ints, floats, (int(g["chan"]), max(0, int(g["anchor"]) - 150), int(g["end_sample"]) + 1)))
+        out.append((ints, floats, (int(g["chan"]), max(0, int(h["anchor"]) - 150), int(h["end_sample"]) + 1)))
     return out
 
 
